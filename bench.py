@@ -6,6 +6,12 @@ metric (BASELINE.json): images/sec generator@256^2 + descriptors/sec GeM-R101@10
 A "step" is one pass of the hot path over one batch already resident in HBM.  One process per GPU; N>1 is launched by
 torch.distributed.run (RCCL); every rank processes its own batch (weak scaling), the only collective is the descriptor
 all-gather of the secondary workload.
+
+A plain run measures the primary alone: set-up, --warmup steps, --steps timed steps, the generator output of the last timed step
+written with --dump-outputs DIR (seeded inputs: identical from run to run for the same arguments), one JSON line.  --full adds
+everything else -- roofline, clocks and the MFMA-only rate, the fast (f16) and exact (f16x3) modes, the secondary, the CPU baselines
+and the parity measured against them -- with its `roofline`, `fast_mode`, `exact_mode`, `secondary`, `cpu_baseline` and
+`parity_measured` fields, which are null (or absent) in a plain run.
 """
 import argparse
 import json
@@ -96,6 +102,7 @@ LAST_EVENT_MS = [None]
 
 
 def timed(fn, steps, warmup, dev, distributed):
+    """(wall seconds of `steps` calls of fn, what the last of them returned)"""
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize(dev)
@@ -103,10 +110,11 @@ def timed(fn, steps, warmup, dev, distributed):
         dist.barrier()
     torch.cuda.synchronize(dev)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    last = None
     t0 = time.perf_counter()
     e0.record()                      # (the library launches on torch's current stream: the events bracket exactly the timed launches)
     for _ in range(steps):
-        fn()
+        last = fn()
     e1.record()
     torch.cuda.synchronize(dev)
     if distributed:
@@ -118,7 +126,24 @@ def timed(fn, steps, warmup, dev, distributed):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    return dt
+    return dt, last
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, name, t):
+    """`t` (the timed path's output of its last step, first dimension = images) -> out_dir/<name>.npy in float32.  Above DUMP_MAX_BYTES a fixed,
+    seeded sample of whole images is written instead, and the sampled image indices beside it as out_dir/<name>_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = t.detach().float().cpu().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        k = max(1, DUMP_MAX_BYTES // (a.nbytes // a.shape[0]))
+        idx = np.sort(np.random.default_rng(0).choice(a.shape[0], size=k, replace=False))
+        a = a[idx]
+        np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def kernel_name(variant):
@@ -362,6 +387,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--gen-batch", type=int, default=64)
     ap.add_argument("--r101-batch", type=int, default=32)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, clocks, the fast / exact modes, the GeM-R101 secondary, CPU baselines "
+                         "with measured parity (the --no-* options below take parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the generator output of the last timed step to DIR/generator_output.npy (float32; rank 0's batch)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fast", action="store_true", help="skip the single-pass fp16 (fast_mode) generator measurement")
     ap.add_argument("--no-exact", action="store_true", help="skip the f16x3 (three-pass split) generator measurement")
@@ -400,19 +430,24 @@ def main():
     gsd = synth.generator_state(0, "instance", gain=0.02)
     gen = engine.build_generator(gsd, dev, precision="f16c")
     xg = synth.synth_input(1000 + rank, (a.gen_batch, 3, 256, 256), 1.0)
-    want_parity = rank == 0 and world == 1 and not a.no_cpu_baseline and a.gen_batch >= CPU_SAMPLE_GEN[1][0]
-    if want_parity:                 # the CPU baseline's four images ride inside the timed batch: what the HIP path makes of them is compared with the oracle below
+    # the CPU baseline's four images ride inside rank 0's timed batch whether or not the baseline runs (the batch is the same with and without
+    # --full): under --full, what the HIP path makes of them is compared with the oracle below
+    if rank == 0 and world == 1 and a.gen_batch >= CPU_SAMPLE_GEN[1][0]:
         xg[:CPU_SAMPLE_GEN[1][0]] = synth.synth_input(CPU_SAMPLE_GEN[0], CPU_SAMPLE_GEN[1], 1.0)
+    want_parity = a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.gen_batch >= CPU_SAMPLE_GEN[1][0]
     xg = xg.to(dev)
-    sampler = ClockSampler(dev) if rank == 0 else None
+    sampler = ClockSampler(dev) if (a.full and rank == 0) else None
     if sampler is not None:
         with sampler:
-            dt = timed(lambda: gen.forward(xg), a.steps, a.warmup, dev, distributed)
+            dt, last = timed(lambda: gen.forward(xg), a.steps, a.warmup, dev, distributed)
     else:
-        dt = timed(lambda: gen.forward(xg), a.steps, a.warmup, dev, distributed)
+        dt, last = timed(lambda: gen.forward(xg), a.steps, a.warmup, dev, distributed)
     gen_event_ms = LAST_EVENT_MS[0]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, "generator_output", last[gen.out_slot])
+    del last
     mfma_only = None
-    if rank == 0:          # sustained rate of the fp16 matrix pipe alone on this very device, measured right after the timed region
+    if a.full and rank == 0:          # sustained rate of the fp16 matrix pipe alone on this very device, measured right after the timed region
         try:
             import ctypes
             from gandtr_amd import _hip
@@ -423,7 +458,7 @@ def main():
             print("mfma-only measurement failed: %r" % (exc,), file=sys.stderr)
     gen_ips = a.gen_batch * world * a.steps / dt
     gen_ms = dt / a.steps * 1e3
-    roof = conv_roofline(gen, xg, traffic_key="r05_pmc_traffic.json" if a.gen_batch == 64 else None) if rank == 0 else None
+    roof = conv_roofline(gen, xg, traffic_key="r05_pmc_traffic.json" if a.gen_batch == 64 else None) if (a.full and rank == 0) else None
     if roof is not None:
         # the kernel issues 1.5 MFMA-slots per algorithmic fp16 one (1 fp16 + 1/2 block-scaled): its matrix pipe work is 1.5 x `achieved`
         roof["mfma_work_factor"] = 1.5
@@ -455,7 +490,7 @@ def main():
 
     def side_mode(precision, label, parity, ksteps):
         net = engine.build_generator(gsd, dev, precision=precision)
-        dtx = timed(lambda: net.forward(xg), ksteps, 2, dev, distributed)
+        dtx, _ = timed(lambda: net.forward(xg), ksteps, 2, dev, distributed)
         roofx = conv_roofline(net, xg, steps=2, traffic_key="r01_pmc_traffic.json" if (precision == "f16" and a.gen_batch == 64) else None) if rank == 0 else None
         rec = {"precision": label, "value": round(a.gen_batch * world * ksteps / dtx, 2), "unit": "images/s", "steps": ksteps,
                "ms_per_step": round(dtx / ksteps * 1e3, 3), "parity_gate_of_mode": parity, "roofline": roofx}
@@ -464,16 +499,16 @@ def main():
         return rec
 
     # NOT the headline: single-pass fp16 (fastest, generator taps only within 3.5e-3) and the three-pass split (f16x3, exact to 3e-6)
-    fast = None if a.no_fast else side_mode(
+    fast = None if (a.no_fast or not a.full) else side_mode(
         "f16", "f16: fp16 NHWC activations, single fp16 MFMA pass, fp32 accumulate",
         "OUTSIDE north_star's generator tolerance by design (tests assert an envelope of 3.5e-3 pre-tanh: *_f16_envelope); not the headline", a.steps)
-    exact = None if a.no_exact else side_mode(
+    exact = None if (a.no_exact or not a.full) else side_mode(
         "f16x3", "f16x3: fp32 NHWC activations, a_hi*w_hi + a_lo*w_hi + a_hi*w_lo on fp16 MFMA, fp32 accumulate",
         "tests assert max|d|/max|ref| <= 1e-5 at every tap", max(2, a.steps // 4))
 
     # ---------------------------------------------------------------- secondary: GeM-R101 descriptors/s @1024^2
     secondary = None
-    if not a.no_secondary:
+    if a.full and not a.no_secondary:
         rsd = synth.resnet101_state(0)
         emb = engine.build_embedder(rsd, dev)
         xe = synth.synth_input(2000 + rank, (a.r101_batch, 3, 1024, 1024))
@@ -487,7 +522,7 @@ def main():
             if distributed:
                 d = sharding.all_gather_descriptors(d, n_total)     # D x N on every rank (RCCL all-gather)
             return d
-        dt2 = timed(step, a.steps, a.warmup, dev, distributed)
+        dt2, _ = timed(step, a.steps, a.warmup, dev, distributed)
         r_dps = n_total * a.steps / dt2
         hip_desc0 = emb.forward(xe)[emb.out_slot][0].float().cpu() if want_parity else None
         roof2 = conv_roofline(emb, xe, traffic_key="r05_pmc_traffic_r101.json" if a.r101_batch == 32 else None) if rank == 0 else None
@@ -536,8 +571,9 @@ def main():
                 # measured in THIS run when the CPU baseline runs (N = 1): HIP output of the baseline's own images, taken from inside the timed batch, against the
                 # fp32 CPU oracle; null otherwise.  The asserting tests: tests/test_hip_models.py, test_hip_fullsize_properties.py, test_hip_golden.py
                 "parity_measured": None,
-                "roofline": roof, "fast_mode": fast, "exact_mode": exact, "secondary": secondary}
-        if not a.no_cpu_baseline and world == 1:
+                # null without --full (and for the parts a --no-* option took out)
+                "full": a.full, "roofline": roof, "fast_mode": fast, "exact_mode": exact, "secondary": secondary}
+        if a.full and not a.no_cpu_baseline and world == 1:
             line["cpu_baseline"], line["parity_measured"] = cpu_baseline_generator(hip_pre_tanh=hip_pre_tanh)
             if secondary is not None:
                 secondary["cpu_baseline"], secondary["parity_measured"] = cpu_baseline_r101(hip_descriptor=hip_desc0)

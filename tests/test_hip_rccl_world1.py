@@ -63,7 +63,7 @@ def test_bench_line_through_one_rccl_rank(cuda_device):
     timing and the descriptor all-gather of the secondary workload inside the timed step"""
     env = _env(GANDTR_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--gen-batch", "8", "--r101-batch", "2",
-                           "--no-fast", "--no-exact", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, check=False)
+                           "--full", "--no-fast", "--no-exact", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, check=False)
     assert proc.returncode == 0, proc.stderr.decode(errors="replace")[-2000:]
     lines = [ln for ln in proc.stdout.decode(errors="replace").splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                   # exactly one JSON line on stdout (RCCL's banner goes to stderr)

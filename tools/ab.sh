@@ -7,7 +7,7 @@ LIBS=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do LIBS+=("$1"); shift; done
 ARGS=${@:---no-cpu-baseline --no-secondary --no-fast --no-exact}
 for r in $(seq 1 $R); do
   for L in "${LIBS[@]}"; do
-    GANDTR_HIP_LIB=$PWD/$L python bench.py $ARGS 2>/dev/null | python -c "
+    GANDTR_HIP_LIB=$PWD/$L python bench.py --full $ARGS 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1])
 k=d['roofline']['all_conv_kernels']

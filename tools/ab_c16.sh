@@ -2,7 +2,7 @@
 # dev: conv3x3_halo_c16 (16 x 16 MFMA shapes) against conv3x3_halo_c inside one gpurun call: layer tests, bench A/B, stamps
 mkdir -p gpurun_out
 timeout -k 10 300 python -m pytest tests/test_hip_f16c.py -x -q -m gpu -k "halo_c_conv3x3" 2>&1 | tail -3
-B="python bench.py --steps 50 --warmup 10 --no-fast --no-exact --no-secondary --no-cpu-baseline"
+B="python bench.py --full --steps 50 --warmup 10 --no-fast --no-exact --no-secondary --no-cpu-baseline"
 run() {   # name, lib, c16 on/off
   if [ -n "$2" ]; then export GANDTR_HIP_LIB=$PWD/tmpbin/lib_$2.so; else unset GANDTR_HIP_LIB; fi
   GDT_CONV_HALO_C16=$3 timeout -k 10 300 $B > gpurun_out/ab_$1.log 2> gpurun_out/ab_$1.err
@@ -20,4 +20,4 @@ for rep in 1 2; do
   for v in "$@"; do run ${v}_$rep $v 1; done
 done
 unset GANDTR_HIP_LIB
-if [ -f tmpbin/lib_stamp16.so ]; then GANDTR_HIP_LIB=$PWD/tmpbin/lib_stamp16.so timeout -k 10 200 python bench.py --steps 30 --warmup 5 --no-fast --no-exact --no-secondary --no-cpu-baseline 2>&1 >/dev/null | python tools/stamp_summary.py; fi
+if [ -f tmpbin/lib_stamp16.so ]; then GANDTR_HIP_LIB=$PWD/tmpbin/lib_stamp16.so timeout -k 10 200 python bench.py --full --steps 30 --warmup 5 --no-fast --no-exact --no-secondary --no-cpu-baseline 2>&1 >/dev/null | python tools/stamp_summary.py; fi

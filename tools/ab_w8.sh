@@ -1,7 +1,7 @@
 #!/bin/bash
 # dev: A/B of the 1 x 8 (two waves per SIMD) layout of conv3x3_halo_c against the shipped 1 x 4 one and of build variants (tmpbin/lib_*.so), inside one gpurun call
 mkdir -p gpurun_out
-B="python bench.py --steps 50 --warmup 10 --no-fast --no-exact --no-secondary --no-cpu-baseline"
+B="python bench.py --full --steps 50 --warmup 10 --no-fast --no-exact --no-secondary --no-cpu-baseline"
 run() {   # name, lib, waves
   if [ -n "$2" ]; then export GANDTR_HIP_LIB=$PWD/tmpbin/lib_$2.so; else unset GANDTR_HIP_LIB; fi
   GDT_C_WAVES=$3 timeout -k 10 300 $B > gpurun_out/ab_$1.log 2> gpurun_out/ab_$1.err

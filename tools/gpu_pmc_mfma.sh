@@ -9,7 +9,7 @@ R=$(pwd)
 export TMPDIR=/tmp
 OUT=$R/gpurun_out/pmc_mfma_$TAG
 mkdir -p $OUT
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-fast --no-exact"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-fast --no-exact"
 if [ -z "$GROUPS_FILE" ]; then
   GROUPS_FILE=$OUT/groups.txt
   cat > $GROUPS_FILE <<'EOG'

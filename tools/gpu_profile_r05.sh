@@ -8,10 +8,10 @@ export TMPDIR=/tmp
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 echo "== kernel stats"
-(cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_under_rocprof.json 2> $O/stats.err) || exit 1
+(cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_under_rocprof.json 2> $O/stats.err) || exit 1
 cp $(ls $O/stats/*/*kernel_stats.csv | head -1) $O/${TAG}_kernel_stats.csv
 echo "== traffic passes (generator)"
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-fast --no-exact"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-fast --no-exact"
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fg --output-format csv -- python3 $R/bench.py $ARGS > $O/fg.log 2>&1) || exit 1
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/wg --output-format csv -- python3 $R/bench.py $ARGS > $O/wg.log 2>&1) || exit 1
 python3 profiles/summarise_pmc.py $(ls $O/fg/*/*counter_collection.csv | head -1) $(ls $O/wg/*/*counter_collection.csv | head -1) $O/${TAG}_pmc_traffic.json "bench.py $ARGS (f16c generator, 64x3x256x256), round-5 build"
