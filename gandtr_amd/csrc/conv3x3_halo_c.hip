@@ -94,9 +94,11 @@ constexpr int A_BYTES = HALO_ROWS_PAD * ROWB;              // 41984
 constexpr int Q_BYTES = HALO_ROWS_PAD * QROWB;             // 20992
 constexpr int STAGE_BYTES = A_BYTES + Q_BYTES;             // 62976
 constexpr int NORM_BYTES = 4096 + 64;                      // (scale, shift): two slots of up to 256 input channels + a zero entry
+constexpr int E_OFF = 2 * STAGE_BYTES + NORM_BYTES;        // scale bytes of the fp4 plane: one per halo row and stage (gdt_c_pixel_exp)
+constexpr int E_BYTES = 2 * HALO_ROWS_PAD;
 constexpr int BM = PH * 16;
 // + epilogue patches: two 4 KB patches per wave with four waves (pipelined body), one with eight (all 160 KB are taken then)
-constexpr size_t lds_bytes(int waves) { return 2 * (size_t)STAGE_BYTES + NORM_BYTES + (waves > 4 ? waves * 4096 : 4 * 8192); }
+constexpr size_t lds_bytes(int waves) { return 2 * (size_t)STAGE_BYTES + NORM_BYTES + E_BYTES + (waves > 4 ? waves * 4096 : 4 * 8192); }
 
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -181,7 +183,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
     // ---- halo loader: through registers, branch-free (see conv3x3_halo_rb.hip for why)
     const int lrow = tid >> 3;
     const bool refl = d.pad_reflect != 0;
-    const float lo_scale = __builtin_ldexpf(1.f, -d.c_lo_exp), hi_scale = __builtin_ldexpf(1.f, d.c_hi_exp);   // cvt divides by the scale
     struct Pend { float4 r0, r1, s0, s1; unsigned goff; bool ok; };
     auto load_piece = [&](const TileAt& ta, int chunk, int r) -> Pend {
         const int tl = tid_now();
@@ -275,7 +276,10 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] = p.ok ? a[e] : 0.f;
         // split: o = fp16(a) (round to nearest even, two per instruction), a_lo = a - o in ONE v_fma_mix_f32 each (fp16 source read
-        // in place), both planes quantised to fp4 by the scaled converts (the convert divides by its scale operand)
+        // in place), both planes quantised to fp4 by the scaled converts (the convert divides by its scale operand) at the pixel's own
+        // scale (gdt_c_pixel_exp)
+        const int ex = gdt_c_pixel_exp(a);
+        const float lo_scale = gdt_exp2i(ex - 13), hi_scale = gdt_exp2i(ex - 2);
         unsigned ou[4], qlo = 0, qhi = 0;
 #define GDT_Q4(k)                                                                                                                    \
         {                                                                                                                            \
@@ -299,6 +303,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
         const int qo = stage_off + A_BYTES + row * QROWB + ((((q >> 2) << 1) ^ key) << 4) + ((q & 3) << 2);
         *(unsigned*)(smem + qo) = qlo;
         *(unsigned*)(smem + (qo ^ 16)) = qhi;
+        smem[E_OFF + (stage_off ? HALO_ROWS_PAD : 0) + row] = (char)(127 + ex - 13);      // (the row's 8 lanes store the same byte)
     };
 
     // ---- weights, streamed L2 -> registers in MFMA fragment order.  Grouped layouts (net.hip pack_mx): the four 32-channel
@@ -365,7 +370,9 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
             vq[t] = A_BYTES + ((wm * (WTM / 16) + (fr >> 4)) * HW_ + (fr & 15)) * QROWB + ((fh ^ key) << 4);
         }
     }
-    // (the stage offset `so` is folded into vt / vq when the stage flips: STAGE_BYTES is a multiple of 128, the XORs below touch bits 5-6)
+    // scale byte of the fp4 fragment's pixel (one per halo row and stage, same row arithmetic)
+    int ve = E_OFF + (wm * (WTM / 16) + (fr >> 4)) * HW_ + (fr & 15);
+    // (the stage offset `so` is folded into vt / vq / ve when the stage flips: STAGE_BYTES is a multiple of 128, the XORs below touch bits 5-6)
     auto a_frag = [&](int i, int ty, int tx, int kk) -> f16x8 {
         return *(const f16x8*)(smem + (vt[tx] ^ (kk << 5)) + (i * 2 * HW_ + ty * HW_ + tx) * ROWB);
     };
@@ -373,14 +380,18 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
         const int base = SHIFT ? vq[ty * 2 + tx] : vq[tx];
         return *(const v4i*)(smem + (base ^ (ms << 5) ^ (SHIFT ? ((i & 1) << 5) : 0)) + (i * 2 * HW_ + ty * HW_ + tx) * QROWB);
     };
+    auto a_efrag = [&](int i, int ty, int tx) -> int {
+        return *(const unsigned char*)(smem + ve + i * 2 * HW_ + ty * HW_ + tx);
+    };
     auto flip_stage = [&](int delta) {
+        ve += delta > 0 ? HALO_ROWS_PAD : -HALO_ROWS_PAD;
 #pragma unroll
         for (int k = 0; k < 3; ++k) vt[k] += delta;
 #pragma unroll
         for (int k = 0; k < (SHIFT ? 4 : 3); ++k) vq[k] += delta;
     };
-    // E8M0 scales of the activation side: lanes 0-31 carry a_lo (stored * 2^c_lo_exp), lanes 32-63 a_hi (stored * 2^-c_hi_exp)
-    const int a_scale = fh ? 127 + d.c_hi_exp : 127 - d.c_lo_exp;
+    // E8M0 scales of the activation side: lanes 0-31 carry a_lo, lanes 32-63 a_hi, of their pixel (scale byte + this)
+    const int a_scale_off = fh ? GDT_C_HI_SCALE_OFF : 0;
 
     const int nchunks = d.Cin >> 6;
     // ---- prologue
@@ -404,6 +415,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
 
     f16x8 afr[AW];
     v4i aq[AW];
+    int ae[AW];             // the fp4 fragments' scale bytes
 #pragma unroll
     for (int i = 0; i < AW; ++i) afr[i] = a_frag(i, 0, 0, 0);
 
@@ -507,7 +519,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
                         else if (kk < 3) { if (s2_ld(t)) afr[i % AW] = a_frag(i + AW - TM, ty, tx, kk + 1); }
                         else if (t < NTAP - 1) { if (s2_ld(t + 1)) afr[i % AW] = a_frag(i + AW - TM, nty, ntx, 0); }
                         if (cu == 0) {             // (the MX weights were last read at the end of substep u - 1; all columns are re-loaded
-                            if (!(GDT_C_ABL & 64) && i < AW && s2_ld(t)) aq[i] = a_qfrag(i, ty, tx, kk >> 1);      //  behind the first rows: >= 24 MFMAs before their first use)
+                            if (!(GDT_C_ABL & 64) && i < AW && s2_ld(t)) { aq[i] = a_qfrag(i, ty, tx, kk >> 1); ae[i] = a_efrag(i, ty, tx); }      //  behind the first rows: >= 24 MFMAs before their first use)
                             if (!(GDT_C_ABL & (2 | 128)) && 2 * i < TN && s2_ld(t)) {
                                 if (ct_on(t_of(u), 2 * i)) load_bq(2 * i, tn_of(u), ks_of(u));
                                 if (2 * i + 1 < TN && ct_on(t_of(u), 2 * i + 1)) load_bq(2 * i + 1, tn_of(u), ks_of(u));
@@ -518,6 +530,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
 #pragma unroll
                         for (int i = 0; i < TM; ++i) {
                             const v8i av = __builtin_shufflevector(aq[i % AW], aq[i % AW], 0, 1, 2, 3, -1, -1, -1, -1);
+                            const int a_scale = ae[i % AW] + a_scale_off;
 #pragma unroll
                             for (int j = 0; j < TN; ++j)
                                 if (ct_on(t, j) && s2_on(t)) {
@@ -534,7 +547,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
                                     acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(__builtin_shufflevector(bq[j], bq[j], 0, 1, 2, 3, 4, 5, -1, -1), av, acc[i][j], 2, 4, 0, bqs[j], 0, a_scale);
 #endif
                                 }
-                            if (!(GDT_C_ABL & 64) && i + AW < TM && s2_ld(t)) aq[i % AW] = a_qfrag(i + AW, ty, tx, kk >> 1);      // (AW < TM)
+                            if (!(GDT_C_ABL & 64) && i + AW < TM && s2_ld(t)) { aq[i % AW] = a_qfrag(i + AW, ty, tx, kk >> 1); ae[i % AW] = a_efrag(i + AW, ty, tx); }      // (AW < TM)
                         }
                     }
                     // in-order issue: lay the substep out as MFMA, a few VALU (the halo staging), MFMA, ... with the memory operations
@@ -629,7 +642,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
         if (!(d.dbg & 4)) {
             float* __restrict__ outp = (float*)d.out;
             const float* __restrict__ resp = (const float*)d.res;
-            float* patch = (float*)(smem + 2 * STAGE_BYTES + NORM_BYTES) + wave * (PIPE2 ? 2048 : 1024);
+            float* patch = (float*)(smem + 2 * STAGE_BYTES + NORM_BYTES + E_BYTES) + wave * (PIPE2 ? 2048 : 1024);
             int lane_e = lane_now();
             asm volatile("" : "+v"(lane_e));             // (opaque copy: keeps the epilogue's addresses out of the loop's invariant set)
             const int fr_e = lane_e & 31, fh_e = lane_e >> 5, pl = lane_e >> 3, q = lane_e & 7;

@@ -60,7 +60,8 @@ constexpr int A_BYTES = HROWS_PAD * ROWB;                  // 41984
 constexpr int Q_BYTES = HROWS_PAD * QROWB;                 // 20992
 constexpr int STAGE_BYTES = A_BYTES + Q_BYTES;             // 62976
 constexpr int NORM_BYTES = 4096 + 64;
-constexpr size_t LDS_BYTES = 2 * (size_t)STAGE_BYTES + NORM_BYTES;
+constexpr int E_OFF = 2 * STAGE_BYTES + NORM_BYTES;        // scale bytes of the fp4 plane: one per halo row and stage (gdt_c_pixel_exp)
+constexpr size_t LDS_BYTES = 2 * (size_t)STAGE_BYTES + NORM_BYTES + 2 * HROWS_PAD;
 constexpr int NT = 256, RPR = NT / 8, NR = (HROWS_PAD + RPR - 1) / RPR;      // threads, halo rows per loader round, rounds per chunk (11)
 constexpr int NTAP = 9, SLOTS = NTAP * 3;      // per tap: two fp16 half-steps + the MX run
 constexpr int SPR = 2;                         // loader round r: loaded at slot SPR * r, written to LDS at slot SPR * (r + SDIST)
@@ -124,7 +125,6 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     // ---- halo loader: through registers, branch-free (conv3x3_halo_c.hip)
     const int lrow = tid >> 3;
     const bool refl = d.pad_reflect != 0;
-    const float lo_scale = __builtin_ldexpf(1.f, -d.c_lo_exp), hi_scale = __builtin_ldexpf(1.f, d.c_hi_exp);   // the converts divide by their scale
     struct Pend { float4 r0, r1, s0, s1; unsigned goff; bool ok; };
     auto load_piece = [&](const TileAt& ta, int chunk, int r) -> Pend {
         int lr = lrow;
@@ -204,6 +204,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] = p.ok ? a[e] : 0.f;
+        const int ex = gdt_c_pixel_exp(a);                       // the pixel's scale: the converts divide by it
+        const float lo_scale = gdt_exp2i(ex - 13), hi_scale = gdt_exp2i(ex - 2);
         unsigned ou[4], qlo = 0, qhi = 0;
 #define GDT_Q4(k)                                                                                                                    \
         {                                                                                                                            \
@@ -227,6 +229,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
         const int qo = stage_off + A_BYTES + row * QROWB + ((((q >> 2) << 1) ^ key2) << 4) + ((q & 3) << 2);
         *(unsigned*)(smem + qo) = qlo;
         *(unsigned*)(smem + (qo ^ 16)) = qhi;
+        smem[E_OFF + (stage_off ? HROWS_PAD : 0) + row] = (char)(127 + ex - 13);      // (the row's 8 lanes store the same byte)
     };
 
     // The same work in PHASES for the main loop: the MFMAs there are inline asm, which the compiler neither schedules around nor sees as long
@@ -235,6 +238,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     // fenced by sched_barrier; a round's store (phases 0-9) and the next round's load (10, 11) share a slot of 16 patch rows.
     float sa[8];
     unsigned sou[4], sqlo = 0, sqhi = 0;
+    int sex = 0;                      // the pixel's scale exponent (gdt_c_pixel_exp) and the converts' scales
+    float slo_scale = 1.f, shi_scale = 1.f;
     auto stage_phase = [&](const TileAt& ta, int chunk, int stage_off, int sl, int ph) {
         if ((GDT_C16_ABL & 1) || sl % SPR != 0) return;
         const int r = sl / SPR;
@@ -270,6 +275,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
 #pragma unroll
             for (int e = 0; e < 8; ++e) sa[e] = pend.ok ? sa[e] : 0.f;
             sqlo = 0; sqhi = 0;
+            sex = gdt_c_pixel_exp(sa);
+            slo_scale = gdt_exp2i(sex - 13); shi_scale = gdt_exp2i(sex - 2);
         }
 #define GDT_Q4P(k)                                                                                                                   \
         if (st && ph == 5 + k) {                                                                                                     \
@@ -277,8 +284,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
             float l0, l1;                                                                                                            \
             asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(sou[k]), "v"(sa[2 * k]));         \
             asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(sou[k]), "v"(sa[2 * k + 1]));     \
-            sqlo = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(sqlo, l0, l1, lo_scale, k);                                              \
-            sqhi = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(sqhi, __builtin_bit_cast(f16x2, sou[k]), hi_scale, k);                   \
+            sqlo = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(sqlo, l0, l1, slo_scale, k);                                             \
+            sqhi = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(sqhi, __builtin_bit_cast(f16x2, sou[k]), shi_scale, k);                  \
         }
         GDT_Q4P(0) GDT_Q4P(1) GDT_Q4P(2) GDT_Q4P(3)
 #undef GDT_Q4P
@@ -293,6 +300,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
             const int qo = stage_off + A_BYTES + row * QROWB + ((((q >> 2) << 1) ^ key2) << 4) + ((q & 3) << 2);
             *(unsigned*)(smem + qo) = sqlo;
             *(unsigned*)(smem + (qo ^ 16)) = sqhi;
+            smem[E_OFF + (stage_off ? HROWS_PAD : 0) + row] = (char)(127 + sex - 13);
         }
         if (ld && ph >= 10 && ph <= 13) load_piece_part(ta, chunk, r, ph - 10);
 #undef GDT_PIN4
@@ -359,12 +367,17 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     auto a_qfrag = [&](int pb, int ty, int tx) -> v4i {
         return *(const v4i*)(smem + vq[tx] + ((pb + ty) * HW_ + tx) * QROWB);
     };
+    int ve = E_OFF + px;                 // scale byte of the fp4 fragment's pixel
+    auto a_efrag = [&](int pb, int ty, int tx) -> int {
+        return *(const unsigned char*)(smem + ve + (pb + ty) * HW_ + tx);
+    };
     auto flip_stage = [&](int delta) {
+        ve += delta > 0 ? HROWS_PAD : -HROWS_PAD;
 #pragma unroll
         for (int k = 0; k < 3; ++k) { vt[k] += delta; vq[k] += delta; }
     };
-    // E8M0 scales of the activation side: blocks 0 / 2 carry a_lo (stored * 2^c_lo_exp), 1 / 3 a_hi (stored * 2^-c_hi_exp)
-    const int a_scale = (fg & 1) ? 127 + d.c_hi_exp : 127 - d.c_lo_exp;
+    // E8M0 scales of the activation side: blocks 0 / 2 carry a_lo, 1 / 3 a_hi, of their pixel (scale byte + this)
+    const int a_scale_off = (fg & 1) ? GDT_C_HI_SCALE_OFF : 0;
 
     const int nchunks = d.Cin >> 6;
     // ---- prologue
@@ -385,7 +398,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
 
     f16x8 afr[AW];
     v4i aq[QW];
-    if (GDT_C16_ABL & 8) { for (int i = 0; i < QW; ++i) aq[i] = a_qfrag(i, 0, 0); }
+    int ae[QW];                   // their scale bytes
+    if (GDT_C16_ABL & 8) { for (int i = 0; i < QW; ++i) { aq[i] = a_qfrag(i, 0, 0); ae[i] = a_efrag(i, 0, 0); } }
     if (GDT_C16_ABL & (16 | 64)) { for (int st = 0; st < BQS + ((GDT_C16_ABL & 64) ? 1 : 0); ++st) for (int part = 0; part < 9; ++part) load_bq_part(st, part, cur.tile_n, 0); }
 #pragma unroll
     for (int i = 0; i < AW; ++i) afr[i] = a_frag(i, 0, 0, 0);
@@ -449,7 +463,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
                         // (one set: behind the previous tap's MX run, one part per second patch row of the first half-step, the scales in the second)
                         if (!(GDT_C16_ABL & (2 | 16)) && BQS == 1 && (pb & 1) == 1 && (s == 0 || pb == 1)) load_bq_part(0, s == 0 ? pb >> 1 : 8, cur.tile_n, (long)(t * cin64 + c));
                         // the first fp4 fragments of the MX run
-                        if (!(GDT_C16_ABL & (2 | 8)) && s == 1 && pb >= 16 - QW) aq[pb - (16 - QW)] = a_qfrag(pb - (16 - QW), ty, tx);
+                        if (!(GDT_C16_ABL & (2 | 8)) && s == 1 && pb >= 16 - QW) { aq[pb - (16 - QW)] = a_qfrag(pb - (16 - QW), ty, tx); ae[pb - (16 - QW)] = a_efrag(pb - (16 - QW), ty, tx); }
                         stage_phase(sta, sc, STAGE_BYTES - so, 3 * t + s, pb);
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -459,8 +473,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
                 for (int pb = 0; pb < 16; ++pb) {
                     if (!(GDT_C16_ABL & 2)) {
 #pragma unroll
-                        for (int cb = 0; cb < 4; ++cb) mfma16_mx(acc[pb][cb], bq[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], aq[pb % QW], bqs[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], a_scale);
-                        if (!(GDT_C16_ABL & 8) && pb + QW < 16) aq[pb % QW] = a_qfrag(pb + QW, ty, tx);
+                        for (int cb = 0; cb < 4; ++cb) mfma16_mx(acc[pb][cb], bq[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], aq[pb % QW], bqs[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], ae[pb % QW] + a_scale_off);
+                        if (!(GDT_C16_ABL & 8) && pb + QW < 16) { aq[pb % QW] = a_qfrag(pb + QW, ty, tx); ae[pb % QW] = a_efrag(pb + QW, ty, tx); }
                         if (!(GDT_C16_ABL & 16) && BQS == 2 && t + 1 < NTAP && pb == 1) load_bq_part((t + 1) & 1, 8, cur.tile_n, (long)((t + 1) * cin64 + c));
                     }
                     stage_phase(sta, sc, STAGE_BYTES - so, 3 * t + 2, pb);

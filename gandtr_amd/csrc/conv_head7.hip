@@ -35,6 +35,7 @@ constexpr int MROWS = PH * HWD;                  // 304 partial-sum pixels
 constexpr int LOAD_ROWS8 = (HPIX + 7) / 8;       // 67 wave-wide 1 KB loads per tile
 constexpr int LROWS = 552;                       // LDS rows of the halo buffer: >= NBLK * 32 - 1 + 6 * HWD + 1 = 548
 constexpr int HBYTES = LROWS * 128;              // 70,656 B: two workgroups per CU
+constexpr int E_BYTES = (LROWS + 15) / 16 * 16;  // MX form: the activation scale byte of each halo pixel behind the halo (gdt_c_pixel_exp)
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int ROUNDS = (HPIX + NT / 8 - 1) / (NT / 8);      // 17 staging rounds of 32 halo pixels (F32IN form)
 constexpr int PSTRIDE = 33;                      // floats per partial-sum pixel (odd: the 7-tap combine is conflict free)
@@ -82,6 +83,8 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
     const int span_lo = xcd * per_xcd, span_hi = min(span_lo + per_xcd, ntiles);
     int tile = span_lo + slot;
     if (tile >= span_hi) return;
+    // (MX) scale bytes of the LDS rows beyond the staged pixels (read for the discarded partial-sum rows only): a finite scale
+    if (MX && tid < E_BYTES - ROUNDS * (NT / 8)) smem[HBYTES + ROUNDS * (NT / 8) + tid] = (char)114;
 
     // Blocks of 32 partial-sum pixels per wave: 10 blocks over 4 waves is 3,3,2,2.  The two workgroups that share a CU sit
     // on the same four SIMDs; rotating the assignment by two waves in every other workgroup makes it 5,5,5,5 per SIMD.
@@ -150,7 +153,6 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
             constexpr int RING = 4;
             float4 ring[RING][2];
             unsigned okmask = 0;
-            const float lo_scale = __builtin_ldexpf(1.f, -d.c_lo_exp), hi_scale = __builtin_ldexpf(1.f, d.c_hi_exp);   // the converts divide by their scale
             auto issue = [&](int j, float4 (&rg)[2]) {
                 const int hp = t8 + j * (NT / 8);
                 const int hy = (hp * 1725) >> 16, hx = hp - hy * HWD;
@@ -166,13 +168,23 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
             auto finish = [&](int j, const float4 (&rg)[2]) {
                 const bool ok = (okmask >> j) & 1u;
                 const float a[8] = {rg[0].x, rg[0].y, rg[0].z, rg[0].w, rg[1].x, rg[1].y, rg[1].z, rg[1].w};
+                float pv[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) pv[k] = fmaxf(fmaf(a[k], sc[k], sh[k]), lo);
                 u32x4 o;
                 unsigned qlo = 0, qhi = 0;
+                // (MX) the pixel's own scale: the converts divide by it; its byte goes behind the halo at once (the fp4 words wait in registers)
+                float lo_scale = 1.f, hi_scale = 1.f;
+                if (MX) {
+                    const int ex = gdt_c_pixel_exp(pv);
+                    lo_scale = gdt_exp2i(ex - 13); hi_scale = gdt_exp2i(ex - 2);
+                    smem[HBYTES + t8 + j * (NT / 8)] = (char)(127 + ex - 13);
+                }
                 // per channel pair k: normalise, round to fp16 (two per instruction); (MX) residuals p - fp16(p) in one v_fma_mix each, both
                 // planes to fp4 by the scaled converts (the byte select must be a literal: hence the macro; see conv3x3_halo_c.hip)
 #define GDT_H7_PAIR(k)                                                                                                                     \
                 {                                                                                                                          \
-                    const float p0 = fmaxf(fmaf(a[2 * k], sc[2 * k], sh[2 * k]), lo), p1 = fmaxf(fmaf(a[2 * k + 1], sc[2 * k + 1], sh[2 * k + 1]), lo); \
+                    const float p0 = pv[2 * k], p1 = pv[2 * k + 1];                                                                        \
                     unsigned w;                                                                                                            \
                     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(w) : "v"(p0), "v"(p1));                                                       \
                     if (MX) {                                                                                                              \
@@ -338,7 +350,7 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
             };
             load_wq(0, 0);
             lds_barrier();
-            const int a_scale = fh_t ? 127 + d.c_hi_exp : 127 - d.c_lo_exp;       // lanes 0-31 carry a_lo * 2^c_lo_exp, lanes 32-63 a_hi * 2^-c_hi_exp
+            const int a_scale_off = fh_t ? GDT_C_HI_SCALE_OFF : 0;       // lanes 0-31 carry a_lo, lanes 32-63 a_hi, at their pixel's scale
             const int qrow0 = wrot * 32 + fr_t;
 #pragma unroll
             for (int ms = 0; ms < 2 * KT; ++ms) {
@@ -349,6 +361,7 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
 #pragma unroll
                 for (int b = 0; b < 3; ++b) {
                         const v4i av4 = *(const v4i*)(smem + off + (b == 2 ? b2 : b) * (NWAVE * 32 * 64));
+                        const int a_scale = *(const unsigned char*)(smem + HBYTES + row + (b == 2 ? b2 : b) * (NWAVE * 32)) + a_scale_off;
                         const v8i av = __builtin_shufflevector(av4, av4, 0, 1, 2, 3, -1, -1, -1, -1);
                         acc[b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, wv, acc[b], 4, 2, 0, a_scale, 0, wqs[ms & 1]);
                     }
@@ -417,13 +430,13 @@ bool gdt_conv_head7_eligible(const ConvLaunch& d) {
 int gdt_launch_conv_head7(const ConvLaunch& d, hipStream_t stream) {
     static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
     int cus = 0;
-    constexpr int lds = HBYTES;
+    constexpr int lds = HBYTES, lds_mx = HBYTES + E_BYTES;
     {
         const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
             v = ncu / 8 * 8;
             GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_head7_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_head7_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_head7_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_head7_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_mx));
             GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_head7_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             return GDT_OK;
         });
@@ -436,7 +449,7 @@ int gdt_launch_conv_head7(const ConvLaunch& d, hipStream_t stream) {
     ConvLaunch dd = d;
     dd.dbg = dbg;
     if (d.in_f32 && d.w_frag2) hipLaunchKernelGGL((conv_head7_kernel<true, false, true>), dim3(grid), dim3(NT), lds, stream, dd, ntiles);       // f16x3: w_frag2 = the lo parts
-    else if (d.in_f32 && d.wmx_a && d.wmx_b && d.wmx_s) hipLaunchKernelGGL((conv_head7_kernel<true, true>), dim3(grid), dim3(NT), lds, stream, dd, ntiles);
+    else if (d.in_f32 && d.wmx_a && d.wmx_b && d.wmx_s) hipLaunchKernelGGL((conv_head7_kernel<true, true>), dim3(grid), dim3(NT), lds_mx, stream, dd, ntiles);
     else if (d.in_f32) hipLaunchKernelGGL(conv_head7_kernel<true>, dim3(grid), dim3(NT), lds, stream, dd, ntiles);
     else hipLaunchKernelGGL(conv_head7_kernel<false>, dim3(grid), dim3(NT), lds, stream, dd, ntiles);
     GDT_CHECK_HIP(hipGetLastError());

@@ -104,7 +104,8 @@ struct ConvLaunch {
     int pool2;                    // 1: MaxPool2d(2, 2) fused into the epilogue of the patch kernels; `out` is the pooled [N][H/2][W/2][Cout] tensor
     // "f16c" precision mode (conv3x3_halo_c.hip): block-scaled correction operands of the weights in MFMA fragment order --
     // wmx_a [CoutPad/128][Kpad/32][4][64 lanes][16 B] + wmx_b [..][64][8 B]: per lane 32 e2m3 values (24 bytes); wmx_s [..][64] dwords: its E8M0
-    // block scale (lanes 0-31: fp16(w) of output channel lane, lanes 32-63: w - fp16(w), same 32 k-values).  Activation side: a_lo is stored as fp4(a_lo * 2^c_lo_exp), a_hi as fp4(a_hi * 2^-c_hi_exp).
+    // block scale (lanes 0-31: fp16(w) of output channel lane, lanes 32-63: w - fp16(w), same 32 k-values).  Activation side: one E8M0 scale per
+    // (pixel, 64-channel chunk), staged in LDS beside the fp4 plane (gdt_c_pixel_exp).
     const f16* w_frag2;           // conv_stem.hip, f16c form: the weight residuals W2 = [w - fp16(w), 0 ..] in the stem fragment order
     const void* w_cfrag;          // fp16 weights grouped per 128 output channels: [CoutPad/128][Kpad/16][4][64 lanes][8 halves] (wmx_* grouped alike)
     const void* wmx_a; const void* wmx_b; const void* wmx_s;
@@ -113,7 +114,6 @@ struct ConvLaunch {
     // k = 8 g ..+7][the same of k 32-63][correction operands, first 16 bytes per lane: 4 blocks x 64 lanes][their last 8 bytes][E8M0 scales: 64 lanes x
     // 4 blocks]; lane (n, blk) of a correction operand = 32 e2m3 values of fp16(w) (blk 0, 2) / w - fp16(w) (blk 1, 3) of k 0-31 (blk 0, 1) / 32-63 (blk 2, 3)
     const void* w_c16;
-    int c_lo_exp, c_hi_exp;
     int pair_cout, ooy2, oox2;    // conv3x3_halo_x3.hip FORM 1: > 0 = the 128 GEMM columns are TWO sub-pixel phases of a transposed conv with pair_cout (64) output channels each;
                                   //      the second half writes output pixel (oy * osy + ooy2, ox * osx + oox2) and its statistics one record set (M / 128 records) further on
     int x3_form;                  // conv3x3_halo_x3.hip: 2 = Conv2d(k3,s2,p1) as 2 x 2 shifts over the virtual space-to-depth view (Cin counts the 4 parities); else 0
@@ -149,6 +149,24 @@ struct ConvLaunch {
 // the levels' tile lists one after the other with the whole grid -- measured 10.1 ms (the level-by-level sum).  The streams stay the default
 // (GANDTR_HIP_JOINT_LEVELS=1 selects this path).
 constexpr int GDT_MAX_LEVELS = 4;
+
+// ---- "f16c" correction operands, activation side (conv3x3_halo_c.hip, conv3x3_halo_c16.hip, conv_head7.hip) ----
+// A staged halo pixel's 64 channels are held 8 per lane by 8 consecutive lanes.  Its scale exponent e is the exponent of max|a| over them,
+// clamped to the fp16 normal range: a_hi is stored as fp4(a_hi * 2^(2 - e)) (|a_hi| <= 2^(e + 1): the e2m1 range, 6 saturating),
+// a_lo = a - fp16(a) as fp4(a_lo * 2^(13 - e)) (|a_lo| <= 2^(e - 11): <= 4).  The scale follows the data, so the correction holds at
+// any activation magnitude and scaling the input by 2^s scales the result by exactly 2^s.  The byte kept per pixel is the E8M0 scale
+// of the a_lo operand, 127 + e - 13; the a_hi operand's is 11 more.
+constexpr int GDT_C_HI_SCALE_OFF = 11;
+__device__ __forceinline__ int gdt_c_pixel_exp(const float (&a)[8]) {
+    const float m = fmaxf(fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))),
+                          fmaxf(fmaxf(fabsf(a[4]), fabsf(a[5])), fmaxf(fabsf(a[6]), fabsf(a[7]))));
+    int b = __float_as_int(m);                                             // (non-negative: orders as an integer)
+    b = max(b, __builtin_amdgcn_mov_dpp(b, 0xB1, 0xF, 0xF, false));     // quad_perm [1, 0, 3, 2]
+    b = max(b, __builtin_amdgcn_mov_dpp(b, 0x4E, 0xF, 0xF, false));     // quad_perm [2, 3, 0, 1]
+    b = max(b, __builtin_amdgcn_mov_dpp(b, 0x141, 0xF, 0xF, false));    // row_half_mirror: the other quad of the 8 lanes
+    return min(max((b >> 23) - 127, -14), 15);
+}
+__device__ __forceinline__ float gdt_exp2i(int e) { return __int_as_float((e + 127) << 23); }      // 2^e, -126 <= e <= 127
 struct MultiConv {
     int nlev;
     int prefix[GDT_MAX_LEVELS + 1];      // first workgroup of each level; prefix[nlev] = grid size

@@ -1713,7 +1713,6 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                     int variant = 960256;
                     if (net->precision == 2) {
                         d.w_cfrag = net->dev_blob + o.ctf.wc_off; d.wmx_a = net->dev_blob + o.ctf.wmx_a_off; d.wmx_b = net->dev_blob + o.ctf.wmx_b_off; d.wmx_s = net->dev_blob + o.ctf.wmx_s_off;
-                        d.c_lo_exp = 12; d.c_hi_exp = 0;
                         variant = 980256;
                         rc = gdt_launch_conv_halo_c_ct(d, st);
                     } else
@@ -1734,7 +1733,6 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                         break;
                     }
                     d.w_cfrag = net->dev_blob + o.s2.wc_off; d.wmx_a = net->dev_blob + o.s2.wmx_a_off; d.wmx_b = net->dev_blob + o.s2.wmx_b_off; d.wmx_s = net->dev_blob + o.s2.wmx_s_off;
-                    d.c_lo_exp = 12; d.c_hi_exp = 0;
                     d.stats_tile_base = 0;
                     rc = gdt_launch_conv_halo_c_s2(d, st);
                     if (net->profiling) net->last_variant[stp.op] = 990256;
@@ -1770,7 +1768,6 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                     d.w_frag = ph.has_frag ? (const f16*)(net->dev_blob + ph.w_frag_off) : nullptr;
                     if (ph.has_mx) {
                         d.w_cfrag = net->dev_blob + ph.wc_off; d.wmx_a = net->dev_blob + ph.wmx_a_off; d.wmx_b = net->dev_blob + ph.wmx_b_off; d.wmx_s = net->dev_blob + ph.wmx_s_off;
-                        d.c_lo_exp = 12; d.c_hi_exp = 0;
                     }
                     if (ph.has_mx16) {
                         d.w_c16 = net->dev_blob + ph.w16_off;

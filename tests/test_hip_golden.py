@@ -53,11 +53,13 @@ def test_hub_generator_on_gpu(cuda_device, name):
     # range is 3.5e-2 / ~0.3 in front of the tanh and outputs near a zero crossing move by that much while the image as a whole agrees to
     # < 5e-4 in the mean.  All three statistics are gated, each with its measured value next to it (tools/parity_report.py, round 3):
     #   cyclegan  mean 2.97e-4   p99.9 7.5e-3   max 9.6e-3        hedngan  mean 4.93e-4   p99.9 0.100   max 0.259
+    # and with the per-pixel scale of the correction product (tests/test_hip_f16c_range.py), same box:
+    #   cyclegan  mean 2.81e-4   p99.9 7.1e-3   max 9.7e-3        hedngan  mean 1.72e-4   p99.9 3.6e-2  max 7.1e-2
     # (single-pass fp16 mode: mean 1.8e-3; the unsaturated absolute gate, max|d image| <= 1e-3, is test_hip_models.py::test_generator_image_absolute_gate)
     diff = (y[:, :, ::8, ::8] - torch.from_numpy(g["out_sub"])).abs().flatten()
     mean, p999, mx = float(diff.mean()), float(torch.quantile(diff, 0.999)), float(diff.max())
     print("hub %s vs the reference's output: mean %.2e, p99.9 %.2e, max %.2e" % (name, mean, p999, mx))
-    gate = {"cyclegan": (5e-4, 1.5e-2, 3.5e-2), "hedngan": (1e-3, 0.2, 0.5)}[name]
+    gate = {"cyclegan": (5e-4, 1.5e-2, 3.5e-2), "hedngan": (3e-4, 6e-2, 0.12)}[name]
     assert mean < gate[0] and p999 < gate[1] and mx < gate[2], (mean, p999, mx)
 
 
