@@ -107,6 +107,143 @@ __global__ __launch_bounds__(64) void select_negatives_kernel(const int* __restr
     }
 }
 
+// Average precision / precision@k from ranks (mdir/external/cirtorch/utils/evaluate.py:3-118).  A unit is one (setup, query) pair.
+//   1. inv[q][ranks[q][r]] = r (the inverse permutation; a value out of range or a slot left unfilled flags status bit 0);
+//   2. per unit, the positive / junk ids are flagged in POSITION space: one bit per rank in two bitmasks (set semantics for free);
+//   3. per unit one workgroup scans the bitmasks in rank order: a positive at position p is the j-th positive and has k = popcount of the
+//      junk bits below p (the reference's strict pos[ip] > junk[ij]); its trapezoid goes to terms[j], its adjusted rank p - k to adj[j];
+//   4. one lane adds the terms in rank order (the reference's `ap +=` loop: the same doubles in the same order) and reads precision@k
+//      off the adjusted ranks, which never decrease.
+// No cap below ndb: terms / adj live in the workspace at the unit's CSR offset, so a query may have every database image as a positive.
+constexpr int AP_MAX_KAPPAS = 16;
+constexpr int AP_THREADS = 256;
+struct Kappas { int k[AP_MAX_KAPPAS]; };
+
+struct ApLayout { size_t inv, pmask, jmask, terms, adj, total; int nwords; };
+
+int ap_plan(int ndb, int nq, int nsetups, long n_ok, ApLayout& L) {
+    GDT_REQUIRE(ndb >= 1 && nq >= 1 && nsetups >= 1, "average precision needs ndb, nq, nsetups >= 1");
+    GDT_REQUIRE((long)ndb * nq < (1l << 31), "ndb * nq must stay below 2^31");
+    GDT_REQUIRE((long)nsetups * nq < (1l << 31), "nsetups * nq must stay below 2^31");
+    GDT_REQUIRE(n_ok >= 0, "n_ok >= 0");
+    const size_t units = (size_t)nsetups * nq;
+    L.nwords = (ndb + 31) / 32;
+    size_t off = 0;
+    L.inv = off; off += align_up((size_t)nq * ndb * sizeof(int));
+    L.pmask = off; off += align_up(units * L.nwords * sizeof(unsigned));
+    L.jmask = off; off += align_up(units * L.nwords * sizeof(unsigned));
+    L.terms = off; off += align_up((size_t)std::max<long>(n_ok, 1) * sizeof(double));
+    L.adj = off; off += align_up((size_t)std::max<long>(n_ok, 1) * sizeof(int));
+    L.total = off + ALIGN;
+    return GDT_OK;
+}
+
+__global__ __launch_bounds__(256) void ap_inverse_kernel(const int* __restrict__ ranks_t, int* __restrict__ inv, int* __restrict__ status, int ndb,
+                                                         long total) {
+    bool bad = false;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long q = i / ndb;
+        const int v = ranks_t[i];
+        if (v >= 0 && v < ndb) inv[q * ndb + v] = (int)(i - q * ndb);
+        else bad = true;
+    }
+    if (bad) atomicOr(status, 1);
+}
+
+__global__ __launch_bounds__(256) void ap_check_kernel(const int* __restrict__ inv, int* __restrict__ status, long total) {
+    bool bad = false;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) bad |= inv[i] < 0;
+    if (bad) atomicOr(status, 1);           // ndb values in range and every slot filled: a permutation
+}
+
+__device__ inline void ap_mark(const int* __restrict__ inv_q, const int* __restrict__ ids, int lo, int hi, unsigned* __restrict__ mask, int ndb) {
+    for (int i = lo + (int)threadIdx.x; i < hi; i += AP_THREADS) {
+        const int id = ids[i];
+        if (id < 0 || id >= ndb) continue;                       // np.in1d: an id outside the database matches nothing
+        const int p = inv_q[id];
+        if (p >= 0) atomicOr(mask + (p >> 5), 1u << (p & 31));
+    }
+}
+
+__global__ __launch_bounds__(AP_THREADS) void ap_mark_kernel(const int* __restrict__ inv, const int* __restrict__ ok_off, const int* __restrict__ ok_ids,
+                                                             const int* __restrict__ junk_off, const int* __restrict__ junk_ids,
+                                                             unsigned* __restrict__ pmask, unsigned* __restrict__ jmask, int ndb, int nq, int nwords) {
+    const int u = blockIdx.x;
+    const int* inv_q = inv + (size_t)(u % nq) * ndb;
+    ap_mark(inv_q, ok_ids, ok_off[u], ok_off[u + 1], pmask + (size_t)u * nwords, ndb);
+    ap_mark(inv_q, junk_ids, junk_off[u], junk_off[u + 1], jmask + (size_t)u * nwords, ndb);
+}
+
+__global__ __launch_bounds__(AP_THREADS) void ap_terms_kernel(const unsigned* __restrict__ pmask, const unsigned* __restrict__ jmask,
+                                                              const int* __restrict__ ok_off, double* __restrict__ terms, int* __restrict__ adj,
+                                                              double* __restrict__ ap, double* __restrict__ prk, int* __restrict__ status,
+                                                              int nwords, Kappas kappas, int nk) {
+#pragma clang fp contract(off)
+    const int u = blockIdx.x, t = threadIdx.x;
+    const unsigned* pm = pmask + (size_t)u * nwords;
+    const unsigned* jm = jmask + (size_t)u * nwords;
+    const int base = ok_off[u], nres = ok_off[u + 1] - base;
+    const int chunk = (nwords + AP_THREADS - 1) / AP_THREADS;
+    const int w0 = t * chunk < nwords ? t * chunk : nwords, w1 = w0 + chunk < nwords ? w0 + chunk : nwords;
+    int cp = 0, cj = 0;
+    for (int w = w0; w < w1; ++w) { cp += __popc(pm[w]); cj += __popc(jm[w]); }
+    // exclusive scan of the per-thread counts: positives and junk before this thread's words
+    __shared__ int sp[AP_THREADS], sj[AP_THREADS];
+    sp[t] = cp; sj[t] = cj;
+    __syncthreads();
+    for (int d = 1; d < AP_THREADS; d <<= 1) {
+        const int a = t >= d ? sp[t - d] : 0, b = t >= d ? sj[t - d] : 0;
+        __syncthreads();
+        sp[t] += a; sj[t] += b;
+        __syncthreads();
+    }
+    const int npos = sp[AP_THREADS - 1];
+    int j = sp[t] - cp, kj = sj[t] - cj;
+    const double rs = 1.0 / (double)nres;                          // recall_step = 1. / nres
+    for (int w = w0; w < w1; ++w) {
+        unsigned pw = pm[w];
+        const unsigned jw = jm[w];
+        while (pw) {
+            const int b = __ffs(pw) - 1;
+            pw &= pw - 1;
+            const int rank = w * 32 + b - (kj + __popc(jw & ((1u << b) - 1u)));
+            const double p0 = rank == 0 ? 1.0 : (double)j / (double)rank;
+            const double p1 = (double)(j + 1) / (double)(rank + 1);
+            terms[base + j] = (p0 + p1) * rs / 2.0;
+            adj[base + j] = rank;
+            ++j;
+        }
+        kj += __popc(jw);
+    }
+    __syncthreads();
+    if (t != 0) return;
+    const double nan = __builtin_nan("");
+    if (nres == 0) {                                               // no positive images: NaN, excluded from the mean
+        ap[u] = nan;
+        for (int i = 0; i < nk; ++i) prk[(size_t)u * nk + i] = nan;
+        return;
+    }
+    double s = 0.0;
+    for (int i = 0; i < npos; ++i) s = s + terms[base + i];       // in rank order, one lane: the reference's sum
+    ap[u] = s;
+    if (npos == 0) {
+        if (nk > 0) atomicOr(status, 2);
+        for (int i = 0; i < nk; ++i) prk[(size_t)u * nk + i] = nan;
+        return;
+    }
+    const int* a = adj + base;
+    const long maxpos = (long)a[npos - 1] + 1;                     // max(pos) after pos += 1
+    for (int i = 0; i < nk; ++i) {
+        const long kq = maxpos < kappas.k[i] ? maxpos : (long)kappas.k[i];
+        int lo = 0, hi = npos;                                     // count of a[] + 1 <= kq: a[] never decreases
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((long)a[mid] + 1 <= kq) lo = mid + 1; else hi = mid;
+        }
+        prk[(size_t)u * nk + i] = (double)lo / (double)kq;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -173,6 +310,67 @@ int gdt_retrieval_select_negatives(const int* ranks_t, const int* pool_cluster, 
     GDT_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int), st));
     hipLaunchKernelGGL(select_negatives_kernel, dim3(nq), dim3(64), 0, st, ranks_t, pool_cluster, query_cluster, vecs, qvecs, neg_pos, neg_dist, status,
                        ndb, nq, d, nnum, index_base);
+    GDT_CHECK_HIP(hipGetLastError());
+    return GDT_OK;
+}
+
+int gdt_retrieval_ap_workspace_bytes(int ndb, int nq, int nsetups, int n_ok, size_t* bytes) {
+    GDT_REQUIRE(bytes != nullptr, "bytes");
+    ApLayout L;
+    int rc = ap_plan(ndb, nq, nsetups, n_ok, L);
+    if (rc != GDT_OK) return rc;
+    *bytes = L.total;
+    return GDT_OK;
+}
+
+int gdt_retrieval_average_precision(const int* ranks_t, int ndb, int nq, int nsetups, const int* ok_offsets, const int* ok_ids,
+                                    const int* junk_offsets, const int* junk_ids, const int* ok_offsets_host, const int* junk_offsets_host,
+                                    const int* kappas, int nk, double* ap, double* prk, int* status, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    GDT_REQUIRE(ok_offsets_host && junk_offsets_host, "null host offsets");
+    GDT_REQUIRE(nk >= 0 && nk <= AP_MAX_KAPPAS, "0 <= nk <= 16 kappas");
+    GDT_REQUIRE(nk == 0 || kappas != nullptr, "null kappas");
+    Kappas K{};
+    for (int i = 0; i < nk; ++i) {
+        GDT_REQUIRE(kappas[i] >= 1, "kappas >= 1");
+        K.k[i] = kappas[i];
+    }
+    ApLayout L;
+    GDT_REQUIRE(ndb >= 1 && nq >= 1 && nsetups >= 1 && (long)nsetups * nq < (1l << 31), "ndb, nq, nsetups >= 1");
+    const long units = (long)nsetups * nq;
+    const int* offs[2] = {ok_offsets_host, junk_offsets_host};
+    for (const int* o : offs) {
+        GDT_REQUIRE(o[0] == 0, "offsets start at 0");
+        for (long u = 0; u < units; ++u) GDT_REQUIRE(o[u + 1] >= o[u], "offsets never decrease");
+    }
+    int rc = ap_plan(ndb, nq, nsetups, ok_offsets_host[units], L);
+    if (rc != GDT_OK) return rc;
+    GDT_REQUIRE(ranks_t && ok_offsets && junk_offsets && ap && status && (nk == 0 || prk) && workspace, "null buffer");
+    GDT_REQUIRE(ok_offsets_host[units] == 0 || ok_ids, "null ok_ids");
+    GDT_REQUIRE(junk_offsets_host[units] == 0 || junk_ids, "null junk_ids");
+    if (L.total > workspace_bytes) {
+        gdt_set_error("workspace too small: need " + std::to_string(L.total) + " bytes, got " + std::to_string(workspace_bytes));
+        return GDT_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)(((uintptr_t)workspace + ALIGN - 1) / ALIGN * ALIGN);
+    int* inv = (int*)(ws + L.inv);
+    unsigned* pmask = (unsigned*)(ws + L.pmask);
+    unsigned* jmask = (unsigned*)(ws + L.jmask);
+    const long total = (long)nq * ndb;
+    GDT_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int), st));
+    GDT_CHECK_HIP(hipMemsetAsync(inv, 0xff, (size_t)total * sizeof(int), st));
+    GDT_CHECK_HIP(hipMemsetAsync(pmask, 0, L.terms - L.pmask, st));          // both bitmasks
+    const int grid = (int)std::min<long>((total + 255) / 256, 8192);
+    hipLaunchKernelGGL(ap_inverse_kernel, dim3(grid), dim3(256), 0, st, ranks_t, inv, status, ndb, total);
+    GDT_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ap_check_kernel, dim3(grid), dim3(256), 0, st, (const int*)inv, status, total);
+    GDT_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ap_mark_kernel, dim3((unsigned)units), dim3(AP_THREADS), 0, st, (const int*)inv, ok_offsets, ok_ids, junk_offsets, junk_ids,
+                       pmask, jmask, ndb, nq, L.nwords);
+    GDT_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ap_terms_kernel, dim3((unsigned)units), dim3(AP_THREADS), 0, st, (const unsigned*)pmask, (const unsigned*)jmask, ok_offsets,
+                       (double*)(ws + L.terms), (int*)(ws + L.adj), ap, prk, status, L.nwords, K, nk);
     GDT_CHECK_HIP(hipGetLastError());
     return GDT_OK;
 }

@@ -7,6 +7,7 @@ per image, views of the library's [N][D] blocks), scores are Ndb x Nq, ranks are
 """
 import ctypes
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -108,3 +109,162 @@ def sharded_topk(vecs_local, qvecs, k, group=None):
     flat_i = all_i.view(world, nq, kk).permute(1, 0, 2).reshape(nq, world * kk)
     order = torch.argsort(flat_s, dim=1, descending=True, stable=True)[:, :k]   # world*k candidates per query: bookkeeping
     return torch.gather(flat_s, 1, order).t(), torch.gather(flat_i, 1, order.long()).t()
+
+
+# ---- mAP evaluation (mdir/external/cirtorch/utils/evaluate.py): average precision and precision@k per query
+
+def _id_list(x):
+    """a ground-truth id list as int64 (ids that no int32 holds cannot match a database index: -1)"""
+    a = np.asarray(x).reshape(-1)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if a.dtype.kind == "f":
+        a = np.where(a == np.floor(a), a, -1)
+    a = a.astype(np.int64)
+    return np.where((a >= 0) & (a < 2 ** 31), a, -1)
+
+
+def _csr(lists):
+    offs = np.zeros(len(lists) + 1, dtype=np.int32)
+    arrs = [_id_list(x) for x in lists]
+    offs[1:] = np.cumsum([len(a) for a in arrs])
+    ids = np.concatenate(arrs).astype(np.int32) if arrs else np.zeros(0, dtype=np.int32)
+    return offs, ids
+
+
+def average_precision(ranks, gnd_setups, kappas=()):
+    """AP and precision@k of every query on the device (gandtr_amd/csrc/retrieval.hip: gdt_retrieval_average_precision).
+
+    ranks: Ndb x Nq database indices best first (cuda; as ``scores_and_ranks`` returns them).  gnd_setups: a list of setups, each a list of
+    Nq dicts ``{"ok": ids, "junk": ids}`` (a missing "junk" is an empty list), matched the way ``compute_map`` matches them (np.in1d).
+    Returns (aps [nsetups][Nq], prs [nsetups][Nq][len(kappas)]) as float64 numpy arrays: ``compute_map``'s ``aps`` / ``prs`` bit for bit,
+    NaN for a query without positives.  Raises ValueError where ranks is not a permutation per query, and where a query with positives
+    finds none of them while kappas are asked for (the reference's ``max()`` of an empty array)."""
+    lib = _hip.load()
+    if not torch.is_tensor(ranks) or not ranks.is_cuda:
+        raise ValueError("average_precision needs the ranks on a HIP device")
+    dev = ranks.device
+    ndb, nq = ranks.shape
+    nsetups = len(gnd_setups)
+    if nsetups < 1 or any(len(g) != nq for g in gnd_setups):
+        raise ValueError("one ground-truth entry per query (%d) in every setup" % nq)
+    kappas = [int(k) for k in kappas]
+    ok_off, ok_ids = _csr([g[i]["ok"] for g in gnd_setups for i in range(nq)])
+    junk_off, junk_ids = _csr([g[i].get("junk", []) for g in gnd_setups for i in range(nq)])
+    kap = (ctypes.c_int * max(len(kappas), 1))(*kappas)
+    need = ctypes.c_size_t()
+    _hip.check(lib.gdt_retrieval_ap_workspace_bytes(ndb, nq, nsetups, int(ok_off[-1]), ctypes.byref(need)))
+    rk = ranks.t().contiguous().to(torch.int32)                                       # [Nq][Ndb]
+    dv = lambda a: torch.from_numpy(a).to(dev)                                          # noqa: E731
+    d_ok_off, d_ok_ids, d_junk_off, d_junk_ids = dv(ok_off), dv(ok_ids), dv(junk_off), dv(junk_ids)
+    ap = torch.empty((nsetups, nq), dtype=torch.float64, device=dev)
+    prk = torch.empty((nsetups, nq, len(kappas)), dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ip = ctypes.POINTER(ctypes.c_int)
+    with torch.cuda.device(dev):
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        _hip.check(lib.gdt_retrieval_average_precision(
+            rk.data_ptr(), ndb, nq, nsetups, d_ok_off.data_ptr(), d_ok_ids.data_ptr() if ok_ids.size else None, d_junk_off.data_ptr(),
+            d_junk_ids.data_ptr() if junk_ids.size else None, ok_off.ctypes.data_as(ip), junk_off.ctypes.data_as(ip), kap, len(kappas),
+            ap.data_ptr(), prk.data_ptr() if len(kappas) else None, status.data_ptr(), ws.data_ptr(), ws.numel(),
+            torch.cuda.current_stream(dev).cuda_stream))
+    st = int(status.item())
+    if st & 1:
+        raise ValueError("ranks is not a permutation of 0..%d in every query column" % (ndb - 1))
+    if st & 2:
+        raise ValueError("max() arg is an empty sequence: a query with positives found none of them, precision@k is undefined")
+    return ap.cpu().numpy(), prk.cpu().numpy()
+
+
+def _mean_over_valid(aps, prs):
+    """compute_map's reduction: in-order sum over the queries with positives, divided by their number (NaN when there are none)"""
+    total, pr, n = 0., np.zeros(prs.shape[1]), 0
+    for i in range(len(aps)):
+        if np.isnan(aps[i]):
+            continue
+        total = total + aps[i]
+        pr = pr + prs[i, :]
+        n += 1
+    if n == 0:
+        return float("nan"), np.full(prs.shape[1], np.nan)
+    return total / n, pr / n
+
+
+def _ap_host(pos, nres):
+    ap = 0
+    step = 1. / nres
+    for j, r in enumerate(pos):
+        p0 = 1. if r == 0 else float(j) / r
+        p1 = float(j + 1) / (r + 1)
+        ap += (p0 + p1) * step / 2.
+    return ap
+
+
+def _map_host(ranks, gnd, kappas):
+    """the numpy restatement of compute_map (evaluate.py:39-118): the CPU branch of ``compute_map``"""
+    nq = len(gnd)
+    aps = np.zeros(nq)
+    prs = np.zeros((nq, len(kappas)))
+    positions = np.arange(ranks.shape[0])
+    for i in range(nq):
+        ok = np.array(gnd[i]["ok"])
+        if ok.shape[0] == 0:
+            aps[i] = np.nan
+            prs[i, :] = np.nan
+            continue
+        junk = np.array(gnd[i]["junk"]) if "junk" in gnd[i] else np.empty(0)
+        pos = positions[np.isin(ranks[:, i], ok)]
+        jpos = positions[np.isin(ranks[:, i], junk)]
+        # a positive moves up by the number of junk images strictly before it
+        pos = pos - np.searchsorted(jpos, pos, side="left")
+        aps[i] = _ap_host(pos, len(ok))
+        pos = pos + 1
+        for j, kappa in enumerate(kappas):
+            kq = min(max(pos), kappa)
+            prs[i, j] = (pos <= kq).sum() / kq
+    return aps, prs
+
+
+def compute_map(ranks, gnd, kappas=[]):
+    """``compute_map`` (evaluate.py:39-118): returns (map, aps, pr, prs).  ranks Ndb x Nq: a cuda tensor runs the device kernel
+    (``average_precision``), a numpy array the host restatement; same doubles either way.  With no query that has positives, map and pr
+    are NaN."""
+    if torch.is_tensor(ranks) and ranks.is_cuda:
+        aps, prs = average_precision(ranks, [gnd], kappas)
+        aps, prs = aps[0], prs[0]
+    else:
+        aps, prs = _map_host(np.asarray(ranks), gnd, list(kappas))
+    m, pr = _mean_over_valid(aps, prs)
+    return m, aps, pr, prs
+
+
+def _revisited_setups(gnd):
+    """easy / medium / hard ground truth of the revisited protocol (evaluate.py:118-140)"""
+    cat = lambda *xs: np.concatenate([np.asarray(x) for x in xs])                     # noqa: E731
+    return [[{"ok": cat(g["easy"]), "junk": cat(g["junk"], g["hard"])} for g in gnd],
+            [{"ok": cat(g["easy"], g["hard"]), "junk": cat(g["junk"])} for g in gnd],
+            [{"ok": cat(g["hard"]), "junk": cat(g["junk"], g["easy"])} for g in gnd]]
+
+
+def compute_map_and_print(dataset, ranks, gnd, kappas=[1, 5, 10]):
+    """``compute_map_and_print`` (evaluate.py:121-155): prints the reference's lines and returns (averages, per-query scores) --
+    ``{"map"}, {"ap"}`` under the old protocol ("ok" in gnd[0]), ``{"map_easy", "map_medium", "map_hard"}, {"ap_easy", ...}`` under the
+    revisited one (roxford5k* / rparis6k*), None for any other dataset as the reference.  On cuda ranks the three setups are one launch."""
+    if "ok" in gnd[0]:
+        m, aps, _, _ = compute_map(ranks, gnd)
+        print('>> {}: mAP {:.2f}'.format(dataset, np.around(m * 100, decimals=2)))
+        return {"map": m}, {"ap": aps}
+    if not (dataset.startswith('roxford5k') or dataset.startswith('rparis6k')):
+        return None
+    setups = _revisited_setups(gnd)
+    if torch.is_tensor(ranks) and ranks.is_cuda:
+        all_aps, all_prs = average_precision(ranks, setups, kappas)
+        per = [(all_aps[s], all_prs[s]) for s in range(3)]
+    else:
+        per = [_map_host(np.asarray(ranks), g, list(kappas)) for g in setups]
+    (mE, mprE), (mM, mprM), (mH, mprH) = [_mean_over_valid(a, p) for a, p in per]
+    print('>> {}: mAP E: {}, M: {}, H: {}'.format(dataset, np.around(mE * 100, decimals=2), np.around(mM * 100, decimals=2),
+                                                  np.around(mH * 100, decimals=2)))
+    print('>> {}: mP@k{} E: {}, M: {}, H: {}'.format(dataset, kappas, np.around(mprE * 100, decimals=2), np.around(mprM * 100, decimals=2),
+                                                     np.around(mprH * 100, decimals=2)))
+    return {"map_easy": mE, "map_medium": mM, "map_hard": mH}, {"ap_easy": per[0][0], "ap_medium": per[1][0], "ap_hard": per[2][0]}

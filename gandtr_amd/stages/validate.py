@@ -6,12 +6,15 @@ The reference wires dataset files, a DataLoader (6 workers, batch size 1) and th
     vecs[:, i] = net(input).cpu().data.squeeze()         for every database / query image (batch 1)
     scores = np.dot(vecs.T, qvecs)
     ranks  = np.argsort(-scores, axis=0)
-Datasets, ground-truth files and ``compute_map`` are out of scope; this mirror takes the images
-in memory -- ``data[0]`` database images, ``data[1]`` query images (omitted: queries = database, the ``self.images == self.qimages``
-branch, cirscore.py:58-59).  ``validate`` keeps the reference's return arity ``(metadata,)`` (ranks / scores inside the metadata) and
-rejects the dataset / criterion parameters it cannot honour; ``rank_images`` returns ``(metadata, ranks, scores)``, ranks Ndb x Nq
-database indices per query column, best first.  On a HIP device the descriptors never leave the GPU between extraction and ranking
-(gandtr_amd/retrieval.py: split-fp16 GEMM + segmented radix sort); on the CPU the reference's two numpy lines run as they are.
+With a ``validation`` section (the reference's schema: SingleValidation / MultiCriterialValidation with ``cirdatasetap`` criteria on named
+cirtorch datasets or TSV datasets) ``validate`` runs the whole evaluation on the device -- JPEG decoding, query crops, descriptors, ranks
+and the mAP (easy / medium / hard under the revisited protocol, gandtr_amd/retrieval.py: compute_map_and_print) -- and returns the
+reference's metadata keys.  Not provided: loader-based (loss) validations, the ``visual`` criterion, R1M distractors.  Without a
+``validation`` section it takes the images in memory -- ``data[0]`` database images, ``data[1]`` query images (omitted: queries =
+database, the ``self.images == self.qimages`` branch, cirscore.py:58-59) -- and returns ranks / scores inside the metadata;
+``rank_images`` returns ``(metadata, ranks, scores)``, ranks Ndb x Nq database indices per query column, best first.  On a HIP device
+the descriptors never leave the GPU between extraction and ranking (gandtr_amd/retrieval.py: split-fp16 GEMM + segmented radix sort); on
+the CPU the reference's two numpy lines run as they are.
 """
 import copy
 import os
@@ -164,23 +167,86 @@ def rank_images(params, data):
     return _rank_images(params, data)
 
 
+class _ValidationMetadata:
+    """The ``{"eval": ...}`` dict the reference's stage returns: ``MetadataKeeper.metadata()`` of the rows the validations log
+    (mdir/tools/eventprocessor.py:75-121, one epoch), restated for the rows a score logs.  Only ``scalar/loss`` / ``scalar/score`` rows count.
+    A row logged once (iteration None) gives ``<label>:<key>`` -> its value; rows logged per iteration give ``<label>:<key>_avg.4`` -> the
+    mean of the non-NaN values.  ``label`` is ``<validation>/validation/<name>``."""
+
+    def __init__(self):
+        self.once, self.per_iteration = {}, {}
+
+    def logger(self, validation):
+        def log(iteration, _size, label, value, dtype):
+            if dtype not in ("scalar/loss", "scalar/score"):
+                return
+            key = "%s/validation/%s" % (validation, label)
+            if iteration is None:
+                self.once[key] = dict(value)
+            else:
+                acc = self.per_iteration.setdefault(key, {})
+                for sub, v in value.items():
+                    acc.setdefault(sub, []).append(v)
+        return log
+
+    def metadata(self):
+        out = {}
+        for key, values in self.once.items():
+            for sub, v in values.items():
+                if isinstance(v, (list, np.ndarray)):
+                    out["%s:%s_avg.4" % (key, sub)] = _nanless_mean(v)
+                else:
+                    out["%s:%s" % (key, sub)] = float(v)
+        for key, values in self.per_iteration.items():
+            for sub, v in values.items():
+                out["%s:%s_avg.4" % (key, sub)] = _nanless_mean(v)
+        return out
+
+
+def _nanless_mean(values):
+    v = np.asarray(values, dtype=np.float64)
+    v = v[~np.isnan(v)]
+    return float(v.mean()) if v.size else float("nan")
+
+
 def validate(params, data):
     """Stage ``mdir.stages.validate.validate`` with the reference's contract (mdir/stages/validate.py:15-39): ``params`` has exactly
     the keys ``network, validation, data`` and the return value is the 1-tuple ``({"eval": {...}},)``.
 
-    The reference builds its validation tasks (datasets from files, mAP / loss criteria) from ``params["validation"]`` and
-    ``params["data"]`` (mdir/learning/validation.py): datasets, ground-truth files and ``compute_map`` are out of scope here
-    (SURVEY.md section 2), so any non-empty content of those two keys raises ``NotImplementedError`` instead of being ignored.
-    With both empty the stage runs the retrieval arithmetic the evaluation is made of on in-memory images (``data[0]`` database,
-    ``data[1]`` queries): descriptor extraction -> scores -> ranks; the arrays are returned inside the metadata under
-    ``"retrieval": {"ranks", "scores"}``.  ``rank_images`` is the same computation with the arrays as output columns."""
+    A non-empty ``params["validation"]`` is the reference's schema (gandtr_amd/learning/validation.py): SingleValidation /
+    MultiCriterialValidation tasks with ``data: null`` and a ``cirdatasetap`` criterion, e.g. mdir/examples/iccv23/parameters/eval.yml.  Every
+    task runs on the device (decoding, descriptors, ranks and mAP; gandtr_amd/components/optim/score/cirscore.py) and ``"eval"`` holds the
+    keys the reference's MetadataKeeper makes of what it logs, ``<task>`` being the MultiCriterialValidation key (``val`` for a
+    SingleValidation):
+        revisited protocol (roxford5k*, rparis6k*): ``<task>/validation/score_avg:map_easy``, ``...:map_medium``, ``...:map_hard`` (the
+            mAPs) and ``<task>/validation/score:ap_easy_avg.4``, ``...:ap_medium_avg.4``, ``...:ap_hard_avg.4`` (mean of the non-NaN APs);
+        old protocol ("ok" lists): ``<task>/validation/score_avg:map`` and ``<task>/validation/score:ap_avg.4``.
+    Validation types other than those two, and loader-based validations (a ``data`` key naming a loader), raise NotImplementedError.
+
+    With an empty ``params["validation"]`` the stage runs the retrieval arithmetic on in-memory images (``data[0]`` database, ``data[1]``
+    queries): descriptor extraction -> scores -> ranks; the arrays are returned inside the metadata under ``"retrieval": {"ranks",
+    "scores"}``.  ``rank_images`` is the same computation with the arrays as output columns.  A non-empty ``params["data"]`` (the
+    reference's loader definitions) raises NotImplementedError."""
     assert params.keys() == {"network", "validation", "data"}, params.keys()
-    for key in ("validation", "data"):
-        if params[key]:
-            raise NotImplementedError("validate: params[%r] = %r asks for the reference's dataset / criterion machinery "
-                                      "(mdir/learning/validation.py), which this build does not provide; pass in-memory images "
-                                      "in `data` and leave it empty, or use gandtr_amd.stages.validate.rank_images"
-                                      % (key, params[key]))
-    metadata, ranks, scores = _rank_images(params, data)
-    metadata["retrieval"] = {"ranks": ranks, "scores": scores}
-    return (metadata,)
+    if params["data"]:
+        raise NotImplementedError("validate: params['data'] = %r asks for the reference's dataset loaders (mdir/learning/validation.py), "
+                                  "which this build does not provide; pass in-memory images in `data` and leave it empty, or use a "
+                                  "validation with data: null" % (params["data"],))
+    if not params["validation"]:
+        metadata, ranks, scores = _rank_images(params, data)
+        metadata["retrieval"] = {"ranks": ranks, "scores": scores}
+        return (metadata,)
+    from ..learning.validation import initialize_validation
+    device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    np.random.seed(0)
+    torch.manual_seed(0)
+    if isinstance(params["validation"], dict) and params["validation"].get("type") not in ("SingleValidation", "MultiCriterialValidation"):
+        initialize_validation(copy.deepcopy(params["validation"]))            # raises NotImplementedError before the network is built
+    network = load_network(copy.deepcopy(params["network"]), device).eval()
+    validation = initialize_validation(copy.deepcopy(params["validation"]), data=data, params_data=params["data"],
+                                       default_criterion=None, network=network)
+    events = _ValidationMetadata()
+    with torch.no_grad():
+        for name, task in validation.validations(epoch=None):
+            task.validate(network, device, events.logger(name))
+    return ({"eval": events.metadata()},)

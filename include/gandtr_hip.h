@@ -214,6 +214,22 @@ int gdt_retrieval_scores_ranks(const float* vecs, const float* qvecs, float* sco
  * vecs [ndb][d], qvecs [nq][d] fp32 rows; every pointer is a device buffer. */
 int gdt_retrieval_select_negatives(const int* ranks_t, const int* pool_cluster, const int* query_cluster, const float* vecs, const float* qvecs,
                                    int* neg_pos, float* neg_dist, int* status, int ndb, int nq, int d, int nnum, int index_base, void* stream);
+/* Average precision and precision@k from ranks -- replaces compute_map / compute_ap
+ *   mdir/external/cirtorch/utils/evaluate.py:3-118 (np.in1d membership, strict junk adjustment, in-order trapezoid sum)
+ * ranks_t [nq][ndb]: database indices (0-based) best first, as gdt_retrieval_scores_ranks writes them with index_base = 0.
+ * Ground truth of unit u = s * nq + q (setup s, query q): positive ids ok_ids[ok_offsets[u] .. ok_offsets[u+1]) and junk ids
+ * junk_ids[junk_offsets[u] .. junk_offsets[u+1]) -- CSR lists, offsets [nsetups * nq + 1] starting at 0.  Ids are matched with set
+ * semantics (duplicates count once, ids outside [0, ndb) match nothing); nres = the raw list length.  ap [nsetups][nq], prk
+ * [nsetups][nq][nk] fp64 (precision at kappas[i], 0 <= nk <= 16, kappas >= 1): the reference's doubles bit for bit; NaN for an empty
+ * positive list.  *status: bit 0 -- ranks_t is not a permutation of 0..ndb-1 per query; bit 1 -- nk > 0 and a non-empty positive list
+ * matched nothing (the reference's max() of an empty array raises).  ok_offsets / junk_offsets / ok_ids / junk_ids / ranks_t / ap / prk /
+ * status are device buffers; ok_offsets_host / junk_offsets_host (the same offsets) and kappas are host arrays, checked before any
+ * HIP call.  n_ok = ok_offsets[nsetups * nq]. */
+int gdt_retrieval_ap_workspace_bytes(int ndb, int nq, int nsetups, int n_ok, size_t* bytes);
+int gdt_retrieval_average_precision(const int* ranks_t, int ndb, int nq, int nsetups, const int* ok_offsets, const int* ok_ids,
+                                    const int* junk_offsets, const int* junk_ids, const int* ok_offsets_host, const int* junk_offsets_host,
+                                    const int* kappas, int nk, double* ap, double* prk, int* status, void* workspace,
+                                    size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * CLAHE post-processing ("next" row of SURVEY.md section 8f, rank 1: the step between generator and embedder)

@@ -5,6 +5,8 @@
     mdir.components.data.wrapper           -> gandtr_amd.components.data.wrapper    (WRAPPERS_LABELS, initialize_wrappers)
     mdir.components.data.transform         -> gandtr_amd.components.data.transform  (initialize_transforms)
     mdir.learning / mdir.learning.network  -> gandtr_amd.learning(.network)         (NETWORKS, initialize_network, load_network)
+    mdir.learning.validation               -> gandtr_amd.learning.validation        (initialize_validation, SingleValidation, ...)
+    mdir.components.optim.score            -> gandtr_amd.components.optim.score     (SCORES, initialize_score: cirdatasetap)
     mdir.stages.infer                      -> gandtr_amd.stages.infer               (infer(params, data))
     mdir.tools.tensors                     -> gandtr_amd.tools.tensors
 
@@ -31,6 +33,10 @@ _ALIASES = {
     "mdir.learning": "gandtr_amd.learning",
     "mdir.learning.network": "gandtr_amd.learning.network",
     "mdir.learning.checkpoints": "gandtr_amd.learning.checkpoints",
+    "mdir.learning.validation": "gandtr_amd.learning.validation",
+    "mdir.components.optim": "gandtr_amd.components.optim",
+    "mdir.components.optim.score": "gandtr_amd.components.optim.score",
+    "mdir.components.optim.score.cirscore": "gandtr_amd.components.optim.score.cirscore",
     "mdir.stages": "gandtr_amd.stages",
     "mdir.stages.infer": "gandtr_amd.stages.infer",
     "mdir.stages.whiten": "gandtr_amd.stages.whiten",
