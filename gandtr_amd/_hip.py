@@ -61,9 +61,12 @@ SIGNATURES = {
                              c_void_p, c_int, _IP]),
     "gdt_net_instance_norm": (c_int, [c_void_p, c_int, c_float, c_int, c_int, _IP]),
     "gdt_net_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _IP]),
+    "gdt_net_maxpool_ceil": (c_int, [c_void_p, c_int, c_int, c_int, _IP]),
+    "gdt_net_conv_dilated": (c_int, [c_void_p, c_int, POINTER(ConvDesc), c_int, c_void_p, c_void_p, _IP]),
     "gdt_net_gem_l2n": (c_int, [c_void_p, c_int, c_float, c_float, c_float, _IP]),
     "gdt_net_output_nchw": (c_int, [c_void_p, c_int, c_void_p, _IP]),
     "gdt_net_hed_head": (c_int, [c_void_p, _IP, POINTER(c_void_p), _FP, _FP, c_float, c_int, _IP]),
+    "gdt_net_rcf_head": (c_int, [c_void_p, _IP, _IP, POINTER(c_void_p), _FP, _FP, c_float, c_int, _IP]),
     "gdt_net_finalize": (c_int, [c_void_p]),
     "gdt_net_output_shape": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _IP, _IP]),
     "gdt_net_num_outputs": (c_int, [c_void_p]),

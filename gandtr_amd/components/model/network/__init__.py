@@ -3,7 +3,7 @@ architectures reachable from the hub entrypoints and BASELINE configs.  Unknown 
 reference (:48)."""
 import torch.nn as nn
 
-from . import cirnet, hed, p2p_networks
+from . import cirnet, hed, p2p_networks, rcf
 
 
 class Identity(nn.Module):
@@ -20,6 +20,7 @@ MODEL_LABELS = {
     "official_resnet_generator": p2p_networks.ResnetGenerator,
     "cirnet": cirnet.init_cirnet,
     "hed_interpolation": hed.HedInterpolation,
+    "rcf": rcf.RCF,
 }
 
 

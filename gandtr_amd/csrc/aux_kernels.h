@@ -28,4 +28,8 @@ int gdt_k_rowsplit_combine(const void* P, int f32, const float* bias, float* out
 int gdt_k_hed_score(const void* x, int f32, const float* w, float bias, float* score, long NP, int C, hipStream_t st);
 int gdt_k_hed_fuse(const float* const* score, const int* h, const int* w, const float* fw, float fb, float* out, int N, int H,
                    int W, int sigmoid, hipStream_t st);
+// RCF head: one stage's score map from its 1-3 tensors (x[j] fp16 / fp32 NHWC with C channels, v[j] fp32 [C]); the fusion of the five maps
+int gdt_k_rcf_stage_score(const void* const* x, const float* const* v, int nx, int f32, float bias, float* score, long NP, int C, hipStream_t st);
+int gdt_k_rcf_fuse(const float* const* score, const int* h, const int* w, const float* const* filt, const int* stride, const int* crop, const float* fw,
+                   float fb, float* out, int N, int H, int W, int sigmoid, hipStream_t st);
 int gdt_conv_bn(int Cout);

@@ -12,6 +12,8 @@
 //   whiten          CirtorchWhiten.postprocess wrapper.py:320-322
 //   unpack_output   fp16 NHWC -> fp32 NCHW (feature taps, p2p_networks.py:316-334)
 //   hed_score / hed_fuse   1x1 score convs, bilinear upsampling to the input size, 1x1 fusion, sigmoid (hed.py:67-83)
+//   rcf_stage_score / rcf_fuse   RCF's side outputs folded to one dot product per conv and stage score maps, then the fixed bilinear
+//                   transposed convs as gathers, the crops, 1x1 fusion, sigmoid (rcf.py:100-155)
 #include "gdt_common.h"
 #include "aux_kernels.h"
 
@@ -461,6 +463,74 @@ __global__ __launch_bounds__(256) void hed_fuse_kernel(const HedFuseArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ RCF head
+// score[n][p] = bias + sum_j sum_c x_j[n][p][c] * v_j[c] over the stage's 1-3 tensors (v_j = W_down_j^T w_dsn, bias = the stage's folded constant,
+// both folded on the host).  8 lanes per pixel as hed_score_kernel; the order of the sum is fixed (tensor by tensor, a lane's channel groups in
+// order, then the butterfly over the 8 lanes): no atomics, bit-reproducible.
+struct RcfStageArgs {
+    const void* x[3]; const float* v[3]; int nx;
+    float bias; float* score; long NP; int C;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void rcf_stage_score_kernel(const RcfStageArgs a) {
+    const long p = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
+    const int sub = threadIdx.x & 7;
+    float s = 0.f;
+    if (p < a.NP) {
+        for (int j = 0; j < a.nx; ++j) {
+            const T* xr = (const T*)a.x[j] + p * a.C;
+            const float* w = a.v[j];
+            for (int c = sub * 8; c < a.C; c += 64) {
+                float v[8];
+                load8(xr + c, v);
+                const float4 w0 = *(const float4*)(w + c), w1 = *(const float4*)(w + c + 4);
+                s += v[0] * w0.x; s += v[1] * w0.y; s += v[2] * w0.z; s += v[3] * w0.w;
+                s += v[4] * w1.x; s += v[5] * w1.y; s += v[6] * w1.z; s += v[7] * w1.w;
+            }
+        }
+    }
+    s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
+    if (p < a.NP && sub == 0) a.score[p] = s + a.bias;
+}
+
+// Per output pixel: stage 1's map as is; stages 2-5 through F.conv_transpose2d(map, filt, stride S) with K = 2 S, read at (y + crop, x + crop).  Output
+// row t sees input rows i with 0 <= t - S i < K: i = t / S (kernel row t mod S) and i - 1 (kernel row t mod S + S), each if inside the map -- at most
+// 2 x 2 taps.  The K x K kernels are the host's _make_bilinear_weights values.  Then the 5 -> 1 fusion and the sigmoid.
+struct RcfFuseArgs {
+    const float* score[5]; int h[5], w[5];
+    const float* filt[4]; int s[4], crop[4];
+    float fw[5], fb;
+    float* out; int N, H, W, sigmoid;
+};
+__global__ __launch_bounds__(256) void rcf_fuse_kernel(const RcfFuseArgs a) {
+    const long total = (long)a.N * a.H * a.W;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int ox = (int)(i % a.W);
+        const long t = i / a.W;
+        const int oy = (int)(t % a.H), n = (int)(t / a.H);
+        float acc = a.fb + a.fw[0] * a.score[0][((long)n * a.h[0] + oy) * a.w[0] + ox];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int S = a.s[k], K = 2 * S, h = a.h[k + 1], w = a.w[k + 1];
+            const int ty = oy + a.crop[k], tx = ox + a.crop[k];
+            const float* p = a.score[k + 1] + (long)n * h * w;
+            const float* f = a.filt[k];
+            float v = 0.f;
+            for (int dy = 0; dy < 2; ++dy) {
+                const int iy = ty / S - dy;
+                if (iy < 0 || iy >= h) continue;
+                for (int dx = 0; dx < 2; ++dx) {
+                    const int ix = tx / S - dx;
+                    if (ix < 0 || ix >= w) continue;
+                    v += p[(long)iy * w + ix] * f[(ty - S * iy) * K + (tx - S * ix)];
+                }
+            }
+            acc += a.fw[k + 1] * v;
+        }
+        a.out[i] = a.sigmoid ? 1.f / (1.f + expf(-acc)) : acc;
+    }
+}
+
 inline int grid_for(long work_items, int cap = 256 * 16) {
     long g = (work_items + 255) / 256;
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -644,6 +714,29 @@ int gdt_k_hed_fuse(const float* const* score, const int* h, const int* w, const 
     for (int k = 0; k < 5; ++k) { a.score[k] = score[k]; a.h[k] = h[k]; a.w[k] = w[k]; a.fw[k] = fw[k]; }
     a.fb = fb; a.out = out; a.N = N; a.H = H; a.W = W; a.sigmoid = sigmoid;
     hipLaunchKernelGGL(hed_fuse_kernel, dim3(grid_for((long)N * H * W)), dim3(256), 0, st, a);
+    GDT_CHECK_HIP(hipGetLastError());
+    return GDT_OK;
+}
+
+int gdt_k_rcf_stage_score(const void* const* x, const float* const* v, int nx, int f32, float bias, float* score, long NP, int C, hipStream_t st) {
+    GDT_REQUIRE(nx >= 1 && nx <= 3 && C % 8 == 0, "rcf_stage_score: 1..3 tensors, C % 8 == 0");
+    RcfStageArgs a;
+    for (int j = 0; j < 3; ++j) { a.x[j] = j < nx ? x[j] : nullptr; a.v[j] = j < nx ? v[j] : nullptr; }
+    a.nx = nx; a.bias = bias; a.score = score; a.NP = NP; a.C = C;
+    const dim3 grid((int)((NP + 31) / 32));
+    if (f32) hipLaunchKernelGGL(rcf_stage_score_kernel<float>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(rcf_stage_score_kernel<f16>, grid, dim3(256), 0, st, a);
+    GDT_CHECK_HIP(hipGetLastError());
+    return GDT_OK;
+}
+
+int gdt_k_rcf_fuse(const float* const* score, const int* h, const int* w, const float* const* filt, const int* stride, const int* crop, const float* fw,
+                   float fb, float* out, int N, int H, int W, int sigmoid, hipStream_t st) {
+    RcfFuseArgs a;
+    for (int k = 0; k < 5; ++k) { a.score[k] = score[k]; a.h[k] = h[k]; a.w[k] = w[k]; a.fw[k] = fw[k]; }
+    for (int k = 0; k < 4; ++k) { a.filt[k] = filt[k]; a.s[k] = stride[k]; a.crop[k] = crop[k]; }
+    a.fb = fb; a.out = out; a.N = N; a.H = H; a.W = W; a.sigmoid = sigmoid;
+    hipLaunchKernelGGL(rcf_fuse_kernel, dim3(grid_for((long)N * H * W)), dim3(256), 0, st, a);
     GDT_CHECK_HIP(hipGetLastError());
     return GDT_OK;
 }

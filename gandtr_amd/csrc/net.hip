@@ -25,7 +25,7 @@ inline size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
 inline int next_pow2(int v) { int p = 8; while (p < v) p <<= 1; return p; }
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED };
+enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF };
 
 struct PackedPhase {
     size_t w_off = 0;                 // byte offset in the device weight blob
@@ -68,15 +68,33 @@ struct Op {
     // fp16 mode: a 1x1 expand conv whose residual is the output of a 1x1 projection conv (ResNet Bottleneck shortcut, stride 1 or 2) carries the two
     // weight matrices K-concatenated (conv1x1_rb.hip, CAT form): kcat_ds = index of the projection op
     int kcat_ds = -1; size_t kcat_frag_off = 0, kcat_bias_off = 0;
+    int dil = 1;          // conv: dilation (gdt_net_conv_dilated); the taps are (dy0 + (t / TW) * dil, ...): only the generic implicit-GEMM kernels take it
     // maxpool
-    int k = 0, s = 0, p = 0;
+    int k = 0, s = 0, p = 0; int ceil = 0;
     // gem
     float gem_p = 3.f, eps_gem = 1e-6f, eps_l2 = 1e-6f;
     // out_nchw
     size_t tap_bias_off = 0; bool tap_has_bias = false;
+    // head ops (OP_HED, OP_RCF): the feature tensors they read -- inputs like `in` / `res` (op_inputs), kept alive until the head runs
+    std::vector<int> feats;
     // hed
-    int feats[5]; size_t score_w_off[5]; float score_b[5], fusion_w[5], fusion_b = 0.f; int sigmoid = 1;
+    size_t score_w_off[5]; float score_b[5], fusion_w[5], fusion_b = 0.f; int sigmoid = 1;
+    // rcf: feats[j] belongs to stage stage_of[j] (stages in order, 1..3 tensors each); side_w_off[j] = the folded C-vector W_down^T w_dsn of feats[j];
+    // score_b[s] = the folded bias of stage s; fusion_w / fusion_b = score_fuse; bilin_off[s - 1] = the fixed bilinear deconv kernel of stage s (fp32 K x K)
+    std::vector<int> stage_of; std::vector<size_t> side_w_off; size_t bilin_off[4];
 };
+
+// every tensor op `o` reads (in, res and a head's feature list; -1 entries skipped)
+template <typename F>
+void op_inputs(const Op& o, F&& f) {
+    if (o.in >= 0) f(o.in);
+    if (o.res >= 0) f(o.res);
+    for (int t : o.feats) f(t);
+}
+
+// RCF's upsampling of stages 2-5 (rcf.py:69-72, :139-148): ConvTranspose2d with the fixed bilinear kernel K = 2 S, stride S, then crop at (c, c)
+constexpr int RCF_K[4] = {4, 8, 16, 16}, RCF_S[4] = {2, 4, 8, 8}, RCF_CROP[4] = {1, 2, 4, 0};
+constexpr int GDT_RCF_FEATURES = 13;          // conv1_1 .. conv5_3
 
 struct Tensor { int C = 0; int Creal = 0; int H = 0, W = 0; int last_use = -1; size_t off = 0, bytes = 0; };   // C: padded, Creal: logical
 
@@ -178,9 +196,19 @@ struct Step {
 };
 struct Plan { std::vector<Step> steps; size_t peak = 0; };
 
-int conv_out_dim(const gdt_conv_desc& c, int in, int k) {
+// MaxPool2d output size, torch's rule (floor, or ceil_mode with the last window starting inside the input or its left padding); <= 0 = empty
+int pool_out_dim(const Op& o, int in) {
+    const int span = in + 2 * o.p - o.k + (o.ceil ? o.s - 1 : 0);
+    if (span < 0) return 0;
+    int out = span / o.s + 1;
+    if (o.ceil && (out - 1) * o.s >= in + o.p) --out;
+    return out;
+}
+
+int conv_out_dim(const Op& o, int in, int k) {
+    const gdt_conv_desc& c = o.cd;
     if (c.transposed) return in * 2;
-    const int span = in + 2 * c.pad - k;
+    const int span = in + 2 * c.pad - (o.dil * (k - 1) + 1);
     return span < 0 ? 0 : span / c.stride + 1;          // floor semantics; 0 = empty (rejected by the planner)
 }
 
@@ -188,7 +216,7 @@ int conv_out_dim(const gdt_conv_desc& c, int in, int k) {
 void conv_geometry(const gdt_net* net, const Op& o, const PackedPhase& ph, int n, const Tensor& ti, ConvLaunch& d) {
     d.N = n; d.H = ti.H; d.W = ti.W; d.Cin = o.cin_pad; d.lc8 = ilog2(o.cin_pad / 8);
     d.Cout = o.cd.cout; d.CoutPad = o.cout_pad;
-    d.OH = conv_out_dim(o.cd, ti.H, o.cd.kh); d.OW = conv_out_dim(o.cd, ti.W, o.cd.kw);
+    d.OH = conv_out_dim(o, ti.H, o.cd.kh); d.OW = conv_out_dim(o, ti.W, o.cd.kw);
     d.pad_reflect = o.cd.pad_reflect; d.relu = o.cd.relu; d.act = o.cd.act;
     d.Kpad = ph.Kpad; d.nk = ph.Kpad / (net->precision ? 32 : 64);
     d.ntaps = ph.ntaps; d.TW = ph.TW; d.invTW = (65536 + ph.TW - 1) / ph.TW;
@@ -203,7 +231,7 @@ void conv_geometry(const gdt_net* net, const Op& o, const PackedPhase& ph, int n
 
 bool conv_fuses_stats(const Op& o, const Tensor& ti) {      // InstanceNorm partial statistics from the conv epilogue
     if (o.stats_for < 0 || o.cd.relu || o.res >= 0) return false;
-    const int hwg = o.cd.transposed ? ti.H * ti.W : conv_out_dim(o.cd, ti.H, o.cd.kh) * conv_out_dim(o.cd, ti.W, o.cd.kw);
+    const int hwg = o.cd.transposed ? ti.H * ti.W : conv_out_dim(o, ti.H, o.cd.kh) * conv_out_dim(o, ti.W, o.cd.kw);
     return hwg % 128 == 0;
 }
 
@@ -246,7 +274,7 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
             case OP_INPUT: h = RH; w = RW; break;
             case OP_CONV: {
                 const Tensor& ti = T[o.in];
-                h = conv_out_dim(o.cd, ti.H, o.cd.kh); w = conv_out_dim(o.cd, ti.W, o.cd.kw);
+                h = conv_out_dim(o, ti.H, o.cd.kh); w = conv_out_dim(o, ti.W, o.cd.kw);
                 if (o.cd.pad_reflect) GDT_REQUIRE(o.cd.pad < ti.H && o.cd.pad < ti.W, "reflection padding needs pad < input size");
                 GDT_REQUIRE(h > 0 && w > 0, "layer output would be empty for this input size");
                 if (o.res >= 0) GDT_REQUIRE(T[o.res].H == h && T[o.res].W == w, "residual shape mismatch");
@@ -254,9 +282,21 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
             }
             case OP_INORM: h = T[o.in].H; w = T[o.in].W; break;
             case OP_MAXPOOL:
-                h = T[o.in].H + 2 * o.p - o.k < 0 ? 0 : (T[o.in].H + 2 * o.p - o.k) / o.s + 1;
-                w = T[o.in].W + 2 * o.p - o.k < 0 ? 0 : (T[o.in].W + 2 * o.p - o.k) / o.s + 1;
+                h = pool_out_dim(o, T[o.in].H); w = pool_out_dim(o, T[o.in].W);
                 break;
+            case OP_RCF: {                              // the reference's crop (rcf.py:95-99) and torch.cat of the five maps at the image size
+                for (int t : o.feats) GDT_REQUIRE(T[t].H > 0 && T[t].W > 0, "layer output would be empty for this input size");
+                for (size_t j = 0; j < o.feats.size(); ++j) {
+                    const Tensor& t = T[o.feats[j]];
+                    const int st = o.stage_of[j];
+                    for (size_t k = 0; k < j; ++k)
+                        if (o.stage_of[k] == st) GDT_REQUIRE(T[o.feats[k]].H == t.H && T[o.feats[k]].W == t.W, "RCF: the tensors of one stage differ in size");
+                    if (st == 0) GDT_REQUIRE(t.H == RH && t.W == RW, "RCF: stage 1 must be at the image size");
+                    else GDT_REQUIRE((t.H - 1) * RCF_S[st - 1] + RCF_K[st - 1] >= RH + RCF_CROP[st - 1] &&
+                                     (t.W - 1) * RCF_S[st - 1] + RCF_K[st - 1] >= RW + RCF_CROP[st - 1], "RCF: an upsampled side output is smaller than the image (crop)");
+                }
+                break;
+            }
             default: break;
         }
         if (o.out >= 0) {
@@ -304,10 +344,7 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
         if (o.kind != OP_CONV || o.cd.transposed || o.rowsplit || o.phases.empty() || !o.phases[0].has_aug) continue;
         if (o.in < 0 || ops[net->input_op].out != o.in) continue;
         int uses = 0;
-        for (int k = 0; k < nops; ++k) {
-            uses += (ops[k].in == o.in) + (ops[k].res == o.in);
-            if (ops[k].kind == OP_HED) for (int f = 0; f < 5; ++f) uses += ops[k].feats[f] == o.in;
-        }
+        for (int k = 0; k < nops; ++k) op_inputs(ops[k], [&](int t) { uses += t == o.in; });
         if (uses != 1) continue;
         ConvLaunch d{};
         conv_geometry(net, o, o.phases[0], N, T[o.in], d);
@@ -344,9 +381,7 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
     std::vector<int> consumers(T.size(), 0), consumer_op(T.size(), -1);
     for (int i = 0; i < nops; ++i) {
         const Op& o = ops[i];
-        auto use = [&](int t) { if (t >= 0) { ++consumers[t]; consumer_op[t] = i; } };
-        use(o.in); use(o.res);
-        if (o.kind == OP_HED) for (int k = 0; k < 5; ++k) use(o.feats[k]);
+        op_inputs(o, [&](int t) { ++consumers[t]; consumer_op[t] = i; });
     }
     for (int j = 0; j < nops && allow_norm_fusion; ++j) {
         const Op& oj = ops[j];
@@ -364,8 +399,8 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
             k = -1;
             for (int i = j + 1; i < nops && k < 0; ++i) {
                 const Op& oi = ops[i];
-                bool uses = oi.in == oj.out || oi.res == oj.out;
-                if (oi.kind == OP_HED) for (int f = 0; f < 5; ++f) uses = uses || oi.feats[f] == oj.out;
+                bool uses = false;
+                op_inputs(oi, [&](int t) { uses = uses || t == oj.out; });
                 if (uses) k = i;
             }
             if (k < 0) continue;
@@ -470,9 +505,10 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
     for (int j = 0; j < nops; ++j) {
         const Op& oj = ops[j];
         if (oj.kind != OP_MAXPOOL || oj.k != 2 || oj.s != 2 || oj.p != 0 || net->precision || consumers[oj.in] != 1) continue;
+        if (oj.ceil && ((T[oj.in].H & 1) || (T[oj.in].W & 1))) continue;        // ceil_mode: the epilogue pools whole 2 x 2 windows only (= floor mode on even sizes)
         int i = -1;
         for (int k = 0; k < j; ++k) if (ops[k].kind == OP_CONV && ops[k].out == oj.in) i = k;
-        if (i < 0 || ops[i].cd.transposed || ops[i].cd.out_f32_nchw || ops[i].res >= 0) continue;
+        if (i < 0 || ops[i].cd.transposed || ops[i].cd.out_f32_nchw || ops[i].res >= 0 || ops[i].dil != 1) continue;
         ConvLaunch d{};
         conv_geometry(net, ops[i], ops[i].phases[0], N, T[ops[i].in], d);
         d.w_frag = ops[i].phases[0].has_frag ? (const f16*)net : nullptr; d.out = (f16*)net;            // non-null markers only
@@ -487,7 +523,7 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
     for (int i = 0; i + 2 < nops && !net->precision; ++i) {
         const Op &a = ops[i], &b = ops[i + 1], &c = ops[i + 2];
         if (a.kind != OP_CONV || b.kind != OP_CONV || c.kind != OP_CONV) continue;
-        auto plain = [&](const Op& o) { return !o.cd.transposed && !o.cd.out_f32_nchw && !o.rowsplit && o.stats_for < 0 && o.cd.stride == 1 && o.phases.size() == 1 && o.phases[0].has_frag && o.has_bias; };
+        auto plain = [&](const Op& o) { return o.dil == 1 && !o.cd.transposed && !o.cd.out_f32_nchw && !o.rowsplit && o.stats_for < 0 && o.cd.stride == 1 && o.phases.size() == 1 && o.phases[0].has_frag && o.has_bias; };
         if (!plain(a) || !plain(b) || !plain(c)) continue;
         if (a.cd.kh != 1 || a.cd.kw != 1 || a.cd.pad != 0 || !a.cd.relu || a.res >= 0) continue;
         if (b.cd.kh != 3 || b.cd.kw != 3 || b.cd.pad != 1 || b.cd.pad_reflect || !b.cd.relu || b.res >= 0 || b.in != a.out) continue;
@@ -508,7 +544,7 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
         const int ia = ds_first ? i + 1 : i, ids = ds_first ? i : i + 1;
         const Op &a = ops[ia], &ds = ops[ids], &b = ops[i + 2], &c = ops[i + 3];
         if (a.kind != OP_CONV || ds.kind != OP_CONV || b.kind != OP_CONV || c.kind != OP_CONV) continue;
-        auto plain = [&](const Op& o) { return !o.cd.transposed && !o.cd.out_f32_nchw && !o.rowsplit && o.stats_for < 0 && o.cd.stride == 1 && o.phases.size() == 1 && o.phases[0].has_frag && o.has_bias; };
+        auto plain = [&](const Op& o) { return o.dil == 1 && !o.cd.transposed && !o.cd.out_f32_nchw && !o.rowsplit && o.stats_for < 0 && o.cd.stride == 1 && o.phases.size() == 1 && o.phases[0].has_frag && o.has_bias; };
         if (!plain(a) || !plain(ds) || !plain(b) || !plain(c)) continue;
         if (a.cd.kh != 1 || a.cd.kw != 1 || a.cd.pad != 0 || !a.cd.relu || a.res >= 0) continue;
         if (ds.cd.kh != 1 || ds.cd.kw != 1 || ds.cd.pad != 0 || ds.cd.relu || ds.res >= 0 || ds.in != a.in) continue;
@@ -532,7 +568,7 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
     for (int i = 0; i + 1 < nops && !net->precision && !(xexp_env && atoi(xexp_env) == 0); ++i) {
         const Op &b = ops[i], &c = ops[i + 1];
         if (b.kind != OP_CONV || c.kind != OP_CONV) continue;
-        auto plain = [&](const Op& o) { return !o.cd.transposed && !o.cd.out_f32_nchw && !o.rowsplit && o.stats_for < 0 && o.cd.stride == 1 && o.phases.size() == 1 && o.phases[0].has_frag && o.has_bias; };
+        auto plain = [&](const Op& o) { return o.dil == 1 && !o.cd.transposed && !o.cd.out_f32_nchw && !o.rowsplit && o.stats_for < 0 && o.cd.stride == 1 && o.phases.size() == 1 && o.phases[0].has_frag && o.has_bias; };
         if (!plain(b) || !plain(c)) continue;
         if (b.cd.kh != 3 || b.cd.kw != 3 || b.cd.pad != 1 || b.cd.pad_reflect || !b.cd.relu || b.res >= 0) continue;
         if (c.cd.kh != 1 || c.cd.kw != 1 || c.cd.pad != 0 || !c.cd.relu || c.in != b.out || c.res < 0 || c.kcat_ds >= 0 || !c.has_bias_frag) continue;
@@ -591,7 +627,7 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
                 // ... and the MaxPool2d(3, 2, 1) behind it, when it is the stem's only consumer: the stem launch writes the pooled tensor
                 static const bool pool_ok = [] { const char* e = getenv("GDT_CONV_STEM_POOL"); return !e || atoi(e) != 0; }();
                 const int jp = consumers[o.out] == 1 ? consumer_op[o.out] : -1;
-                if (pool_ok && jp >= 0 && ops[jp].kind == OP_MAXPOOL && ops[jp].k == 3 && ops[jp].s == 2 && ops[jp].p == 1 && o.cd.relu && o.slot < 0) {
+                if (pool_ok && jp >= 0 && ops[jp].kind == OP_MAXPOOL && ops[jp].k == 3 && ops[jp].s == 2 && ops[jp].p == 1 && !ops[jp].ceil && o.cd.relu && o.slot < 0) {
                     plan.steps[j].pool_into = jp; plan.steps[jp].skip = true;
                 }
             }
@@ -611,7 +647,7 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
             if (nj.res >= 0) T[nj.res].last_use = std::max(T[nj.res].last_use, i);
             if (plan.steps[plan.steps[i].norm_from].wb) T[nj.out].last_use = std::max(T[nj.out].last_use, i);
         }
-        if (o.kind == OP_HED) for (int k = 0; k < 5; ++k) T[o.feats[k]].last_use = i;
+        for (int t : o.feats) T[t].last_use = i;
     }
     Arena arena;
     std::vector<size_t> slab_off(nops, 0), slab_bytes(nops, 0);
@@ -628,7 +664,7 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
             case OP_INPUT: if (!st.direct) alloc_out(); break;      // (direct: the stem conv reads the caller's image, the packed tensor never exists)
             case OP_CONV: {
                 const Tensor& ti = T[o.in];       // same size as the raw tensor when the norm is folded
-                const int oh = conv_out_dim(o.cd, ti.H, o.cd.kh);
+                const int oh = conv_out_dim(o, ti.H, o.cd.kh);
                 if (st.skip) break;                           // (fused Bottleneck: done by the block's first conv)
                 if (st.bneck) {                               // the launch writes the block output; r and t (and the projected shortcut) never exist
                     Tensor& t = T[ops[i + (st.bneck_ds >= 0 ? 3 : 2)].out];
@@ -658,7 +694,7 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
                     arena.release(st.aux_off[1], b);
                 }
                 if (conv_fuses_stats(o, ti)) {
-                    const int hwg = o.cd.transposed ? ti.H * ti.W : oh * conv_out_dim(o.cd, ti.W, o.cd.kw);
+                    const int hwg = o.cd.transposed ? ti.H * ti.W : oh * conv_out_dim(o, ti.W, o.cd.kw);
                     const size_t tiles = (size_t)st.stats_sets * N * (hwg / 128);
                     st.fused_stats = true; st.tiles_per_image = hwg / 128;
                     slab_bytes[i] = tiles * 2 * o.cd.cout * sizeof(float);
@@ -704,6 +740,13 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
                 for (int k = 0; k < 5; ++k) arena.release(st.aux_off[k], sz[k]);
                 break;
             }
+            case OP_RCF: {                              // one fp32 score map per stage, at the stage's size
+                size_t sz[5] = {0, 0, 0, 0, 0};
+                for (size_t j = 0; j < o.feats.size(); ++j) { const Tensor& tf = T[o.feats[j]]; sz[o.stage_of[j]] = (size_t)N * tf.H * tf.W * sizeof(float); }
+                for (int k = 0; k < 5; ++k) st.aux_off[k] = arena.alloc(sz[k]);
+                for (int k = 0; k < 5; ++k) arena.release(st.aux_off[k], sz[k]);
+                break;
+            }
         }
         // free dead inputs
         auto maybe_free = [&](int t) {
@@ -711,7 +754,7 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
         };
         maybe_free(o.kind == OP_CONV ? conv_input(i) : o.in); maybe_free(o.res);
         if (o.kind == OP_CONV && st.kcat) maybe_free(ops[o.kcat_ds].in);
-        if (o.kind == OP_HED) for (int k = 0; k < 5; ++k) maybe_free(o.feats[k]);
+        for (int t : o.feats) maybe_free(t);
         if (o.kind == OP_CONV && st.norm_from >= 0) { maybe_free(ops[st.norm_from].res); maybe_free(ops[st.norm_from].out); }
         if (o.out >= 0 && T[o.out].last_use == -1 && T[o.out].bytes) arena.release(T[o.out].off, T[o.out].bytes);   // never consumed
         for (auto& r : deferred[i]) arena.release(r.first, r.second);
@@ -906,9 +949,10 @@ int gdt_net_input(gdt_net* net, int channels, const int* perm, const float* scal
     return GDT_OK;
 }
 
-int gdt_net_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, const float* weight, const float* bias,
-                 const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
-                 int residual_tensor, int* out_tensor) {
+// gdt_net_conv (dil == 1) and gdt_net_conv_dilated
+static int add_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, int dil, const float* weight, const float* bias,
+                    const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
+                    int residual_tensor, int* out_tensor) {
     GDT_REQUIRE(net && !net->finalized && desc && weight && out_tensor, "net/desc/weight");
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "input tensor id");
     GDT_REQUIRE(residual_tensor < (int)net->tensors.size(), "residual tensor id");
@@ -924,8 +968,8 @@ int gdt_net_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, const f
     if (!cd.out_f32_nchw) GDT_REQUIRE(cd.cout % 8 == 0, "internal conv outputs need cout % 8 == 0");
     if (residual_tensor >= 0) GDT_REQUIRE(net->tensors[residual_tensor].C == cd.cout && !cd.out_f32_nchw, "residual channels");
 
-    Op o; o.kind = OP_CONV; o.in = in_tensor; o.res = residual_tensor; o.cd = cd; o.cin_pad = cin_pad;
-    o.rowsplit = cd.out_f32_nchw && !cd.transposed && cd.stride == 1 && cd.kw >= 3 && cd.cout <= 4 && cd.cout * cd.kw <= 32 &&
+    Op o; o.kind = OP_CONV; o.in = in_tensor; o.res = residual_tensor; o.cd = cd; o.cin_pad = cin_pad; o.dil = dil;
+    o.rowsplit = dil == 1 && cd.out_f32_nchw && !cd.transposed && cd.stride == 1 && cd.kw >= 3 && cd.cout <= 4 && cd.cout * cd.kw <= 32 &&
                  cd.kw == 2 * cd.pad + 1 && !cd.relu && !bn_gamma;
     const int gemm_cout = o.rowsplit ? cd.cout * cd.kw : cd.cout;
     if (o.rowsplit) o.rs_cout8 = (gemm_cout + 7) / 8 * 8;
@@ -1002,7 +1046,7 @@ int gdt_net_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, const f
                     }
             ph.w_frag_off = net->blob_append(pf.data(), pf.size() * sizeof(f16));
             ph.has_frag = true;
-        } else if (net->precision != 0 && cin_pad == 8 && 2 * cd.cin <= 8 && o.cout_pad == 64 && cd.cout == 64 && !cd.transposed) {
+        } else if (net->precision != 0 && dil == 1 && cin_pad == 8 && 2 * cd.cin <= 8 && o.cout_pad == 64 && cd.cout == 64 && !cd.transposed) {
             // conv_stem.hip, f16c form: W1 slots of a tap = [w_hi (cin), w_hi * 2^-8 (cin), 0 ..], W2 = [w - w_hi (cin), 0 ..]; fragments as below
             const int nks = (ph.ntaps + 1) / 2;
             std::vector<f16> p1((size_t)o.cout_pad * ph.Kpad, (f16)0.f), p2(p1.size(), (f16)0.f);
@@ -1029,7 +1073,7 @@ int gdt_net_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, const f
             ph.w_frag_off = net->blob_append(f1.data(), f1.size() * sizeof(f16));
             ph.w_frag2_off = net->blob_append(f2.data(), f2.size() * sizeof(f16));
             ph.has_frag = true; ph.has_aug = true;
-        } else if (!net->precision && cin_pad == 8 && o.cout_pad == 64 && cd.cout == 64 && !cd.transposed) {
+        } else if (!net->precision && dil == 1 && cin_pad == 8 && o.cout_pad == 64 && cd.cout == 64 && !cd.transposed) {
             // conv_stem.hip: one k-step = two taps x 8 channels; fragments [ks][column block j][lane][8], zero past the last tap
             const int nks = (ph.ntaps + 1) / 2;
             std::vector<f16> pf((size_t)nks * 2 * 64 * 8, (f16)0.f);
@@ -1121,11 +1165,11 @@ int gdt_net_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, const f
         o.phases.push_back(ph);
     } else if (!cd.transposed) {
         PackedPhase ph;
-        ph.ntaps = cd.kh * cd.kw; ph.TW = cd.kw; ph.dy0 = -cd.pad; ph.dys = 1; ph.dx0 = -cd.pad; ph.dxs = 1;
+        ph.ntaps = cd.kh * cd.kw; ph.TW = cd.kw; ph.dy0 = -cd.pad; ph.dys = dil; ph.dx0 = -cd.pad; ph.dxs = dil;     // (dil > 1: no patch-kernel form takes these taps)
         const int khw = cd.kh * cd.kw;
         pack(ph, [&](int co, int c, int t) { return weight[((size_t)co * cd.cin + c) * khw + t]; });
         o.phases.push_back(ph);
-        if (net->precision != 0 && cd.stride == 2 && cd.kh == 3 && cd.kw == 3 && cd.pad == 1 && !cd.pad_reflect && !cd.out_f32_nchw &&
+        if (net->precision != 0 && dil == 1 && cd.stride == 2 && cd.kh == 3 && cd.kw == 3 && cd.pad == 1 && !cd.pad_reflect && !cd.out_f32_nchw &&
             residual_tensor < 0 && (cin_pad == 64 || cin_pad == 128) && cd.cin == cin_pad) {
             // shift form: K index = shift * 4cin + parity * cin + c, shift = (dy+1)*2 + (dx+1) with dy, dx in {-1, 0}, parity = py*2 + px of the
             // input pixel (2R + py, 2C + px); kernel row ky = 0 for (dy -1, py 1), 1 for (0, 0), 2 for (0, 1), none for (-1, 0); columns alike
@@ -1273,6 +1317,20 @@ int gdt_net_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, const f
     return GDT_OK;
 }
 
+int gdt_net_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, const float* weight, const float* bias,
+                 const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
+                 int residual_tensor, int* out_tensor) {
+    return add_conv(net, in_tensor, desc, 1, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, residual_tensor, out_tensor);
+}
+
+int gdt_net_conv_dilated(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, int dilation, const float* weight, const float* bias, int* out_tensor) {
+    GDT_REQUIRE(net && !net->finalized && desc && weight && out_tensor, "net/desc/weight");
+    GDT_REQUIRE(dilation >= 1 && dilation <= 16, "dilation must be 1..16");
+    GDT_REQUIRE(dilation == 1 || (!desc->transposed && !desc->pad_reflect && !desc->out_f32_nchw),
+                "a dilated conv is a plain Conv2d with zero padding and an internal output");
+    return add_conv(net, in_tensor, desc, dilation, weight, bias, nullptr, nullptr, nullptr, nullptr, -1, out_tensor);
+}
+
 int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, int residual_tensor, int* out_tensor) {
     GDT_REQUIRE(net && !net->finalized && out_tensor, "net");
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size() && residual_tensor < (int)net->tensors.size(), "tensor id");
@@ -1291,15 +1349,23 @@ int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, int 
     return GDT_OK;
 }
 
-int gdt_net_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int* out_tensor) {
+static int add_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int ceil, int* out_tensor) {
     GDT_REQUIRE(net && !net->finalized && out_tensor, "net");
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "tensor id");
     GDT_REQUIRE(kernel >= 1 && stride >= 1 && pad >= 0 && pad * 2 <= kernel, "maxpool geometry");
-    Op o; o.kind = OP_MAXPOOL; o.in = in_tensor; o.k = kernel; o.s = stride; o.p = pad;
+    Op o; o.kind = OP_MAXPOOL; o.in = in_tensor; o.k = kernel; o.s = stride; o.p = pad; o.ceil = ceil;
     o.out = net->new_tensor(net->tensors[in_tensor].C, net->tensors[in_tensor].Creal);
     net->ops.push_back(o);
     *out_tensor = o.out;
     return GDT_OK;
+}
+
+int gdt_net_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int* out_tensor) {
+    return add_maxpool(net, in_tensor, kernel, stride, pad, 0, out_tensor);
+}
+
+int gdt_net_maxpool_ceil(gdt_net* net, int in_tensor, int kernel, int stride, int* out_tensor) {
+    return add_maxpool(net, in_tensor, kernel, stride, 0, 1, out_tensor);
 }
 
 int gdt_net_gem_l2n(gdt_net* net, int in_tensor, float p, float eps_gem, float eps_l2, int* out_slot) {
@@ -1331,11 +1397,52 @@ int gdt_net_hed_head(gdt_net* net, const int* feature_tensors, const float* cons
                      const float* fusion_w, float fusion_b, int sigmoid, int* out_slot) {
     GDT_REQUIRE(net && !net->finalized && feature_tensors && score_w && score_b && fusion_w && out_slot, "net/args");
     Op o; o.kind = OP_HED; o.sigmoid = sigmoid; o.fusion_b = fusion_b;
+    o.feats.assign(5, -1);
     for (int k = 0; k < 5; ++k) {
         GDT_REQUIRE(feature_tensors[k] >= 0 && feature_tensors[k] < (int)net->tensors.size(), "tensor id");
         o.feats[k] = feature_tensors[k];
         o.score_w_off[k] = net->blob_append(score_w[k], net->tensors[o.feats[k]].C * sizeof(float));
         o.score_b[k] = score_b[k]; o.fusion_w[k] = fusion_w[k];
+    }
+    o.slot = (int)net->out_ops.size();
+    net->out_ops.push_back((int)net->ops.size());
+    net->ops.push_back(o);
+    *out_slot = o.slot;
+    return GDT_OK;
+}
+
+int gdt_net_rcf_head(gdt_net* net, const int* feature_tensors, const int* stage_of, const float* const* side_w, const float* stage_b,
+                     const float* fuse_w, float fuse_b, int sigmoid, int* out_slot) {
+    GDT_REQUIRE(net && !net->finalized && feature_tensors && stage_of && side_w && stage_b && fuse_w && out_slot, "net/args");
+    Op o; o.kind = OP_RCF; o.sigmoid = sigmoid; o.fusion_b = fuse_b;
+    int count[5] = {0, 0, 0, 0, 0};
+    for (int j = 0; j < GDT_RCF_FEATURES; ++j) {
+        GDT_REQUIRE(feature_tensors[j] >= 0 && feature_tensors[j] < (int)net->tensors.size(), "tensor id");
+        GDT_REQUIRE(stage_of[j] >= 0 && stage_of[j] < 5 && (j == 0 || stage_of[j] >= stage_of[j - 1]), "stage_of: stages 0..4 in order");
+        GDT_REQUIRE(side_w[j] != nullptr, "side_w");
+        GDT_REQUIRE(net->tensors[feature_tensors[j]].C % 8 == 0, "feature channels % 8");
+        ++count[stage_of[j]];
+        if (j > 0 && stage_of[j] == stage_of[j - 1])
+            GDT_REQUIRE(net->tensors[feature_tensors[j]].C == net->tensors[feature_tensors[j - 1]].C, "the tensors of one stage need the same channel count");
+    }
+    for (int s = 0; s < 5; ++s) GDT_REQUIRE(count[s] >= 1 && count[s] <= 3, "every stage needs 1..3 feature tensors");
+    for (int j = 0; j < GDT_RCF_FEATURES; ++j) {
+        const Tensor& t = net->tensors[feature_tensors[j]];
+        std::vector<float> v(t.C, 0.f);                            // (padding channels: zero weight)
+        std::copy(side_w[j], side_w[j] + t.Creal, v.begin());
+        o.feats.push_back(feature_tensors[j]); o.stage_of.push_back(stage_of[j]);
+        o.side_w_off.push_back(net->blob_append(v.data(), v.size() * sizeof(float)));
+    }
+    for (int s = 0; s < 5; ++s) { o.score_b[s] = stage_b[s]; o.fusion_w[s] = fuse_w[s]; }
+    // the fixed deconv kernels: RCF._make_bilinear_weights (rcf.py:77-92) -- numpy's float64 arithmetic, stored as float32 like the reference's tensor
+    for (int s = 0; s < 4; ++s) {
+        const int K = RCF_K[s], factor = (K + 1) / 2;
+        const double center = K % 2 == 1 ? factor - 1 : factor - 0.5;
+        std::vector<float> f((size_t)K * K);
+        for (int a = 0; a < K; ++a)
+            for (int b = 0; b < K; ++b)
+                f[(size_t)a * K + b] = (float)((1.0 - std::fabs(a - center) / factor) * (1.0 - std::fabs(b - center) / factor));
+        o.bilin_off[s] = net->blob_append(f.data(), f.size() * sizeof(float));
     }
     o.slot = (int)net->out_ops.size();
     net->out_ops.push_back((int)net->ops.size());
@@ -1352,11 +1459,7 @@ static void build_kcat_weights(gdt_net* net) {
     net->kcat_built = true;
     auto& ops = net->ops;
     std::vector<int> consumers(net->tensors.size(), 0);
-    for (const Op& o : ops) {
-        if (o.in >= 0) ++consumers[o.in];
-        if (o.res >= 0) ++consumers[o.res];
-        if (o.kind == OP_HED) for (int k = 0; k < 5; ++k) ++consumers[o.feats[k]];
-    }
+    for (const Op& o : ops) op_inputs(o, [&](int t) { ++consumers[t]; });
     auto plain1x1 = [](const Op& o) {
         return o.kind == OP_CONV && !o.cd.transposed && !o.cd.out_f32_nchw && !o.rowsplit && o.stats_for < 0 && o.phases.size() == 1 && o.phases[0].has_frag &&
                o.has_bias && o.cd.kh == 1 && o.cd.kw == 1 && o.cd.pad == 0 && o.cin_pad % 64 == 0 && o.phases[0].Kpad == o.cin_pad && o.out >= 0;
@@ -1412,14 +1515,14 @@ int gdt_net_output_shape(gdt_net* net, int slot, int n, int rh, int rw, int* dim
     int rc = make_plan(net, n, rh, rw, plan);
     if (rc != GDT_OK) return rc;
     const Op& o = net->ops[net->out_ops[slot]];
-    const Tensor& ti = net->tensors[o.kind == OP_HED ? 0 : o.in];
+    const Tensor& ti = net->tensors[o.feats.empty() ? o.in : 0];
     switch (o.kind) {
         case OP_CONV:
-            dims[0] = n; dims[1] = o.cd.cout; dims[2] = conv_out_dim(o.cd, ti.H, o.cd.kh); dims[3] = conv_out_dim(o.cd, ti.W, o.cd.kw);
+            dims[0] = n; dims[1] = o.cd.cout; dims[2] = conv_out_dim(o, ti.H, o.cd.kh); dims[3] = conv_out_dim(o, ti.W, o.cd.kw);
             *ndim = 4; break;
         case OP_GEM: dims[0] = n; dims[1] = ti.C; *ndim = 2; break;
         case OP_OUT_NCHW: dims[0] = n; dims[1] = ti.C; dims[2] = ti.H; dims[3] = ti.W; *ndim = 4; break;
-        case OP_HED: dims[0] = n; dims[1] = 1; dims[2] = rh; dims[3] = rw; *ndim = 4; break;
+        case OP_HED: case OP_RCF: dims[0] = n; dims[1] = 1; dims[2] = rh; dims[3] = rw; *ndim = 4; break;     // (edge maps at the network input size)
         default: GDT_REQUIRE(false, "not an output op");
     }
     return GDT_OK;
@@ -1441,12 +1544,17 @@ static double op_flops(const gdt_net* net, const Op& o, int n, int rh, int rw) {
         const Tensor& ti = net->tensors[o.in];
         if (o.cd.transposed)   // every input pixel meets every kernel tap once
             return 2.0 * n * ti.H * ti.W * (double)o.cd.cin * o.cd.cout * o.cd.kh * o.cd.kw;
-        return 2.0 * n * (double)conv_out_dim(o.cd, ti.H, o.cd.kh) * conv_out_dim(o.cd, ti.W, o.cd.kw) * o.cd.cin * o.cd.cout *
+        return 2.0 * n * (double)conv_out_dim(o, ti.H, o.cd.kh) * conv_out_dim(o, ti.W, o.cd.kw) * o.cd.cin * o.cd.cout *
                o.cd.kh * o.cd.kw;
     }
     if (o.kind == OP_HED) {
         double f = 2.0 * n * rh * rw * 5;
         for (int k = 0; k < 5; ++k) { const Tensor& tf = net->tensors[o.feats[k]]; f += 2.0 * n * tf.H * tf.W * tf.C; }
+        return f;
+    }
+    if (o.kind == OP_RCF) {           // the folded side dots + 4 maps x 2 x 2 bilinear taps + the 5 -> 1 fusion per output pixel
+        double f = 2.0 * n * rh * rw * (4 * 4 + 5);
+        for (int t : o.feats) { const Tensor& tf = net->tensors[t]; f += 2.0 * n * tf.H * tf.W * tf.Creal; }
         return f;
     }
     return 0.0;
@@ -1460,7 +1568,7 @@ static double op_bytes(const gdt_net* net, const Op& o, int n) {
     const double es = (double)net->esize();
     const Tensor& ti = net->tensors[o.in];
     // (output geometry from the conv itself: a conv that writes a caller-facing fp32 NCHW slot has no internal output tensor)
-    const double oh = conv_out_dim(o.cd, ti.H, o.cd.kh), ow = conv_out_dim(o.cd, ti.W, o.cd.kw);
+    const double oh = conv_out_dim(o, ti.H, o.cd.kh), ow = conv_out_dim(o, ti.W, o.cd.kw);
     const double out_b = (double)n * oh * ow * o.cd.cout * (o.cd.out_f32_nchw ? 4.0 : es);
     double in_px = (double)n * ti.H * ti.W;
     if (!o.cd.transposed && o.cd.kh == 1 && o.cd.kw == 1 && o.cd.stride > 1) in_px = (double)n * oh * ow;
@@ -1490,6 +1598,16 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
         if (o.kind == OP_INORM) counts[5] += st.norm_into >= 0;
         if (o.kind == OP_MAXPOOL) counts[6] += st.skip;
         if (o.kind == OP_INPUT) counts[7] += st.direct;
+        if (o.kind == OP_CONV && o.dil != 1 && n_counts >= 12) {
+            ++counts[10];
+            ConvLaunch d{};                                   // (what gdt_launch_conv / gdt_launch_conv_x3 would be handed: non-null markers only)
+            conv_geometry(net, o, o.phases[0], n, net->tensors[o.in], d);
+            d.w_frag = o.phases[0].has_frag ? (const f16*)net : nullptr; d.w_lo = net->precision ? (const f16*)net : nullptr; d.out = (f16*)net;
+            if (o.phases[0].has_mx) d.w_cfrag = d.wmx_a = d.wmx_b = d.wmx_s = net;
+            counts[11] += st.skip || st.bneck || st.xexp || st.pool_into >= 0 || st.s2 || st.aug || st.direct || gdt_conv_halo_eligible(d) ||
+                          gdt_conv_halo_rb_eligible(d) || gdt_conv_halo_x3_eligible(d) || gdt_conv_halo_x3_taps_eligible(d) || gdt_conv_halo_c_eligible(d) ||
+                          gdt_conv_stem_eligible(d) || gdt_conv_stem_c_eligible(d) || gdt_conv_1x1_rb_eligible(d);
+        }
     }
     return GDT_OK;
 }
@@ -1845,6 +1963,25 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                     sc[k] = s; hh[k] = tf.H; wwv[k] = tf.W;
                 }
                 if (rc == GDT_OK) rc = gdt_k_hed_fuse(sc, hh, wwv, o.fusion_w, o.fusion_b, (float*)outputs[o.slot], n, rh, rw, o.sigmoid, st);
+                break;
+            }
+            case OP_RCF: {
+                const float* sc[5]; int hh[5], wwv[5];
+                for (int s = 0; s < 5 && rc == GDT_OK; ++s) {
+                    const void* xs[3]; const float* vs[3]; int nx = 0, C = 0;
+                    for (size_t j = 0; j < o.feats.size(); ++j) {
+                        if (o.stage_of[j] != s) continue;
+                        const Tensor& tf = T[o.feats[j]];
+                        xs[nx] = tptr(o.feats[j]); vs[nx] = (const float*)(net->dev_blob + o.side_w_off[j]); ++nx;
+                        hh[s] = tf.H; wwv[s] = tf.W; C = tf.C;
+                    }
+                    float* m = (float*)(ws + stp.aux_off[s]);
+                    rc = gdt_k_rcf_stage_score(xs, vs, nx, f32, o.score_b[s], m, (long)n * hh[s] * wwv[s], C, st);
+                    sc[s] = m;
+                }
+                const float* filt[4];
+                for (int s = 0; s < 4; ++s) filt[s] = (const float*)(net->dev_blob + o.bilin_off[s]);
+                if (rc == GDT_OK) rc = gdt_k_rcf_fuse(sc, hh, wwv, filt, RCF_S, RCF_CROP, o.fusion_w, o.fusion_b, (float*)outputs[o.slot], n, rh, rw, o.sigmoid, st);
                 break;
             }
         }

@@ -6,6 +6,7 @@
   build_generator   ResnetGenerator            mdir/components/model/network/p2p_networks.py:269-313, :454-506
   build_embedder    ImageRetrievalNet (GeM)    mdir/external/cirtorch/networks/imageretrievalnet.py:101-123, :185-190
   build_hed         HedInterpolation           mdir/components/model/network/hed.py:30-83
+  build_rcf         RCF                        mdir/components/model/network/rcf.py:28-155
 
 PyTorch is used for device memory and streams only; no torch op runs on the data path.
 """
@@ -98,12 +99,18 @@ class HipNet:
         return out.value
 
     def conv(self, x, weight, bias=None, bn=None, stride=1, pad=0, reflect=False, transposed=False, relu=False,
-             residual=-1, out_f32=False, act=0):
+             residual=-1, out_f32=False, act=0, dilation=1):
         w = _f32(weight)
         cin, cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
         d = ConvDesc(cin, cout, w.shape[2], w.shape[3], stride, pad, int(reflect), int(transposed), int(relu),
                      int(out_f32), act, 1e-5)
         b = _f32(bias)
+        if dilation != 1:                 # gdt_net_conv_dilated: plain Conv2d + bias, no BN / residual
+            if bn is not None or residual != -1:
+                raise ValueError("a dilated conv takes no BatchNorm and no residual")
+            out = ctypes.c_int()
+            _hip.check(self.lib.gdt_net_conv_dilated(self.handle, x, ctypes.byref(d), int(dilation), _ptr(w), _ptr(b), ctypes.byref(out)))
+            return out.value
         g = be = m = v = None
         if bn is not None:
             g, be, m, v = (_f32(t) for t in bn)
@@ -117,9 +124,14 @@ class HipNet:
         _hip.check(self.lib.gdt_net_instance_norm(self.handle, x, eps, int(relu), residual, ctypes.byref(out)))
         return out.value
 
-    def maxpool(self, x, kernel, stride, pad=0):
+    def maxpool(self, x, kernel, stride, pad=0, ceil=False):
         out = ctypes.c_int()
-        _hip.check(self.lib.gdt_net_maxpool(self.handle, x, kernel, stride, pad, ctypes.byref(out)))
+        if ceil:
+            if pad:
+                raise ValueError("ceil-mode max-pooling takes no padding here")
+            _hip.check(self.lib.gdt_net_maxpool_ceil(self.handle, x, kernel, stride, ctypes.byref(out)))
+        else:
+            _hip.check(self.lib.gdt_net_maxpool(self.handle, x, kernel, stride, pad, ctypes.byref(out)))
         return out.value
 
     def gem_l2n(self, x, p, eps_gem=1e-6, eps_l2=1e-6):
@@ -141,6 +153,18 @@ class HipNet:
                                              (ctypes.c_float * 5)(*[float(b) for b in score_b]),
                                              (ctypes.c_float * 5)(*[float(w) for w in fusion_w]), float(fusion_b),
                                              int(sigmoid), ctypes.byref(out)))
+        return out.value
+
+    def rcf_head(self, feats, stage_of, side_w, stage_b, fuse_w, fuse_b, sigmoid=True):
+        """gdt_net_rcf_head: 13 feature tensors, their stages, the folded side vectors (one per feature) and stage biases"""
+        if len(feats) != 13 or len(stage_of) != 13 or len(side_w) != 13 or len(stage_b) != 5 or len(fuse_w) != 5:
+            raise ValueError("the RCF head takes 13 features (and stages / side vectors) and 5 stage biases / fusion weights")
+        ws = [_f32(w).reshape(-1) for w in side_w]
+        wp = (ctypes.c_void_p * 13)(*[w.ctypes.data for w in ws])
+        out = ctypes.c_int()
+        _hip.check(self.lib.gdt_net_rcf_head(self.handle, (ctypes.c_int * 13)(*feats), (ctypes.c_int * 13)(*stage_of), wp,
+                                             (ctypes.c_float * 5)(*[float(b) for b in stage_b]),
+                                             (ctypes.c_float * 5)(*[float(w) for w in fuse_w]), float(fuse_b), int(sigmoid), ctypes.byref(out)))
         return out.value
 
     def finalize(self):
@@ -185,12 +209,12 @@ class HipNet:
         return list(self._geometry(n, rh, rw)[1])
 
     PLAN_KEYS = ("conv_launches", "bottlenecks_fused", "conv3x3_expand", "chained_reduce", "shortcuts_folded", "norms_folded", "pools_fused", "direct_stem",
-                 "transposed_fused", "stride2_shift")
+                 "transposed_fused", "stride2_shift", "dilated_convs", "dilated_special_forms")
 
     def plan_summary(self, n, rh, rw, resize=False):
         """the planner's fusion decisions for a geometry as a dict of counts (gdt_net_plan_summary: host logic, no device call)"""
-        c = (ctypes.c_int * 10)()
-        _hip.check(self.lib.gdt_net_plan_summary(self.handle, n, rh, rw, int(bool(resize)), c, 10))
+        c = (ctypes.c_int * 12)()
+        _hip.check(self.lib.gdt_net_plan_summary(self.handle, n, rh, rw, int(bool(resize)), c, 12))
         return dict(zip(self.PLAN_KEYS, list(c)))
 
     def flops(self, n, rh, rw):
@@ -598,6 +622,52 @@ def build_hed(sd, device, perm=None, in_affine=None, sigmoid=True, precision="f1
     net.out_slot = net.hed_head(
         feats, [sd["score%d.weight" % (k + 1)] for k in range(5)], [float(sd["score%d.bias" % (k + 1)]) for k in range(5)],
         [float(v) for v in sd["fusion.0.weight"].reshape(-1)], float(sd["fusion.0.bias"]), sigmoid)
+    if finalize:
+        net.finalize()
+    return net
+
+
+RCF_BLOCKS = ((64, 64), (128, 128), (256, 256, 256), (512, 512, 512), (512, 512, 512))
+
+
+def rcf_fold_side(sd):
+    """The linear part of RCF's side outputs folded per conv (rcf.py:115-133): conv*_down (21 x C, bias) then score_dsn (1 x 21, bias) of its stage is
+    ONE C-vector W_down^T w_dsn per conv plus one constant per stage (w_dsn . sum of the stage's down biases + b_dsn), in float64.  Returns
+    (stage_of [13], side vectors [13] (float64 numpy), stage biases [5])."""
+    stage_of, side_w, stage_b = [], [], []
+    for bi, chans in enumerate(RCF_BLOCKS):
+        wd = sd["score_dsn%d.weight" % (bi + 1)].double().reshape(-1)
+        bsum = sd["score_dsn%d.bias" % (bi + 1)].double().reshape(-1)[0]
+        for ci in range(len(chans)):
+            k = "conv%d_%d_down" % (bi + 1, ci + 1)
+            w = sd[k + ".weight"].double().reshape(21, -1)
+            side_w.append((w.t() @ wd).numpy())
+            bsum = bsum + (wd * sd[k + ".bias"].double()).sum()
+            stage_of.append(bi)
+        stage_b.append(float(bsum))
+    return stage_of, side_w, stage_b
+
+
+def build_rcf(sd, device, perm=None, in_affine=None, sigmoid=True, precision="f16", finalize=True):
+    """RCF.forward (rcf.py:100-155): the VGG trunk with ceil-mode pools (pool4 at stride 1) and dilated conv5_x, then the RCF head.  ``perm`` /
+    ``in_affine`` fold the rcfngan wrapper chain (MeanStdPre, RgbToBgrPre, MeanStdPre; wrapper.py:182-194, :351-364) into the input pack; with no
+    resize, in the fp16 mode, the first conv reads the caller's fp32 image itself (conv_stem.hip pair form)."""
+    net = HipNet(device, precision)
+    x = net.input(3, perm=perm, scale=None if in_affine is None else in_affine[0],
+                  shift=None if in_affine is None else in_affine[1])
+    feats = []
+    pools = ((2, 2), (2, 2), (2, 2), (2, 1))          # pool1-3: MaxPool2d(2, 2, ceil_mode=True); pool4: stride 1 (rcf.py:43-46)
+    for bi, chans in enumerate(RCF_BLOCKS):
+        if bi > 0:
+            x = net.maxpool(x, pools[bi - 1][0], pools[bi - 1][1], ceil=True)
+        dil = 2 if bi == 4 else 1                      # conv5_x: padding 2, dilation 2
+        for ci in range(len(chans)):
+            k = "conv%d_%d" % (bi + 1, ci + 1)
+            x = net.conv(x, sd[k + ".weight"], sd[k + ".bias"], pad=dil, relu=True, dilation=dil)
+            feats.append(x)
+    stage_of, side_w, stage_b = rcf_fold_side(sd)
+    net.out_slot = net.rcf_head(feats, stage_of, side_w, stage_b, [float(v) for v in sd["score_fuse.weight"].reshape(-1)],
+                                float(sd["score_fuse.bias"].reshape(-1)[0]), sigmoid)
     if finalize:
         net.finalize()
     return net

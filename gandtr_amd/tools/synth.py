@@ -10,6 +10,7 @@ State-dict key names follow the reference modules:
   embedders  -- torchvision vgg16/resnet101 as sliced by external/cirtorch/networks/imageretrievalnet.py:185-190
                 (``features.<i>...``) plus ``pool.p`` (layers/pooling.py:40)
   HED        -- mdir/components/model/network/hed.py:30-45
+  RCF        -- mdir/components/model/network/rcf.py:28-66
 """
 import math
 import zlib
@@ -144,6 +145,26 @@ def hed_state(seed=0, width_div=1):
             cin = c // width_div
         _conv(sd, seed, "score%d" % (bi + 1), 1, cin, 1, True, gain=1.0 / math.sqrt(cin))
     _conv(sd, seed, "fusion.0", 1, 5, 1, True, gain=0.5)
+    return sd
+
+
+RCF_BLOCKS = ((64, 64), (128, 128), (256, 256, 256), (512, 512, 512), (512, 512, 512))
+
+
+def rcf_state(seed=0, width_div=1):
+    """RCF state dict (rcf.py:28-66): kaiming trunk, and side / score / fuse weights scaled so that on Caffe-range inputs (|x| ~ 100, what the
+    rcfngan wrapper chain produces) the pre-sigmoid edge map is O(1-10): the sigmoid is not saturated and still tells results apart."""
+    sd, cin = {}, 3
+    for bi, chans in enumerate(RCF_BLOCKS):
+        for ci, c in enumerate(chans):
+            _conv(sd, seed, "conv%d_%d" % (bi + 1, ci + 1), c // width_div, cin, 3, True)
+            cin = c // width_div
+    for bi, chans in enumerate(RCF_BLOCKS):
+        for ci, c in enumerate(chans):
+            _conv(sd, seed, "conv%d_%d_down" % (bi + 1, ci + 1), 21, c // width_div, 1, True, gain=0.02 / math.sqrt(c // width_div))
+    for bi in range(5):
+        _conv(sd, seed, "score_dsn%d" % (bi + 1), 1, 21, 1, True, gain=1.0 / math.sqrt(21))
+    _conv(sd, seed, "score_fuse", 1, 5, 1, True, gain=0.5)
     return sd
 
 

@@ -40,6 +40,7 @@ const char* gdt_version(void);
  *   ResnetGenerator.forward          mdir/components/model/network/p2p_networks.py:315-337 (layers :269-313, :454-506)
  *   ImageRetrievalNet.forward        mdir/external/cirtorch/networks/imageretrievalnet.py:101-123
  *   HedInterpolation.forward         mdir/components/model/network/hed.py:60-83
+ *   RCF.forward                      mdir/components/model/network/rcf.py:100-155
  * Tensors are referred to by the integer ids the builder returns.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct gdt_net gdt_net;
@@ -86,12 +87,22 @@ typedef struct gdt_conv_desc {
 int gdt_net_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, const float* weight, const float* bias,
                  const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
                  int residual_tensor, int* out_tensor);
+/* Conv2d(cin, cout, k, stride, padding = desc->pad, dilation) + bias (may be NULL) (+ ReLU: desc->relu), internal output: RCF conv5_1-5_3
+ * (nn.Conv2d(512, 512, 3, padding=2, dilation=2), rcf.py:40-42).  desc->transposed, pad_reflect and out_f32_nchw must be 0 when dilation > 1;
+ * dilation 1 is gdt_net_conv.  Tap t reads input offset (t / kw * dilation - pad, t % kw * dilation - pad): the generic implicit-GEMM kernels run
+ * it (conv_igemm / conv_igemm_rb, conv_igemm_x3 in the split modes); the 3x3 patch kernels, which stage a one-pixel halo, and every fused form
+ * of the planner are not taken (gdt_net_plan_summary counts [10], [11]). */
+int gdt_net_conv_dilated(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, int dilation, const float* weight, const float* bias, int* out_tensor);
 
 /* nn.InstanceNorm2d(affine=False, eps) (+ fused ReLU) (+ fused residual add AFTER the norm): p2p_networks.py:29,:272,:505 */
 int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, int residual_tensor, int* out_tensor);
 
 /* nn.MaxPool2d(kernel, stride, padding), floor mode */
 int gdt_net_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int* out_tensor);
+/* nn.MaxPool2d(kernel, stride, ceil_mode=True), no padding (RCF pool1-3: (2, 2), pool4: (2, 1); rcf.py:43-46): torch's output size -- ceil, then one
+ * less when the last window would start outside the input; a window that hangs over the edge takes the maximum of its pixels inside.  Fused into
+ * its producer's epilogue only where the result equals floor mode (2 x 2, stride 2, even sizes). */
+int gdt_net_maxpool_ceil(gdt_net* net, int in_tensor, int kernel, int stride, int* out_tensor);
 
 /* l2n(gem(x, p, eps_gem), eps_l2): cirtorch layers/functional.py:21-22,:130-131.  External output: fp32 [N][D]
  * row-major, i.e. the memory the reference's `o.permute(1,0)` view aliases (imageretrievalnet.py:123). */
@@ -105,6 +116,21 @@ int gdt_net_output_nchw(gdt_net* net, int in_tensor, const float* bias, int* out
  * External output fp32 [N][1][H][W]. */
 int gdt_net_hed_head(gdt_net* net, const int* feature_tensors, const float* const* score_w, const float* score_b,
                      const float* fusion_w, float fusion_b, int sigmoid, int* out_slot);
+
+/* RCF head (rcf.py:115-155).  feature_tensors[13]: conv1_1 .. conv5_3, stage_of[13] their stage 0..4 (in order; 1..3 tensors of one size and
+ * channel count per stage).  The reference's side convs conv*_down (21 x C) and score_dsn* (1 x 21) are linear, so the caller folds them (in
+ * fp64): side_w[j] = W_down_j^T w_dsn (C floats), stage_b[s] = w_dsn . sum_j b_down_j + b_dsn; a stage's score map is then
+ * stage_b[s] + sum_j side_w[j] . x_j, one dot product per pixel and conv.  Stages 2-5 are upsampled by F.conv_transpose2d with the fixed
+ * bilinear kernels of RCF._make_bilinear_weights (kernel 4 / 8 / 16 / 16, stride 2 / 4 / 8 / 8: computed here on the host, fp64 -> fp32 as
+ * numpy + torch do) and cropped at (1, 1), (2, 2), (4, 4), (0, 0); the upsampled stage sizes must cover the image plus the crop (the
+ * reference's assertion, rcf.py:95-99: GDT_ERR_INVALID at plan time).  score_fuse (fuse_w[5], fuse_b), then the sigmoid unless sigmoid = 0.
+ * External output fp32 [N][1][H][W] at the network input size.
+ * Workspace: the head is ONE op at the end of the graph, so all thirteen conv outputs stay alive until it runs -- the plan keeps them, as HED's
+ * head keeps its five (gdt_net_workspace_bytes, fp16: 2.44 GB for 64 x 3 x 256^2, against 1.41 GB for HED).  Scoring each stage right after its
+ * last conv would free them earlier, but it splits the head into six ops with a hand-off of the score maps between them; a few GB of the
+ * MI355X's 288 GB do not pay for that. */
+int gdt_net_rcf_head(gdt_net* net, const int* feature_tensors, const int* stage_of, const float* const* side_w, const float* stage_b,
+                     const float* fuse_w, float fuse_b, int sigmoid, int* out_slot);
 
 /* Upload packed weights to the current device.  No more ops can be added afterwards. */
 int gdt_net_finalize(gdt_net* net);
@@ -152,12 +178,14 @@ int gdt_net_flops(gdt_net* net, int n, int rh, int rw, double* flops);
 /* The planner's decisions for a geometry as counts (host logic only, no device call): counts[0] conv launches (a fused launch counts once), [1] whole Bottlenecks in one
  * launch, [2] 3x3 + expand launches, [3] of those with the next block's reduce conv chained in, [4] projection shortcuts folded into their expand conv, [5] InstanceNorms
  * applied by their consumer's staging, [6] max-pools written by their producer, [7] 1 if the stem reads the caller's image itself (resize = 0 only), [8] transposed convs as
- * one fused-phase launch, [9] stride-2 convs as the shift form.  n_counts >= 10.  (Diagnostics / tests; no reference counterpart.) */
+ * one fused-phase launch, [9] stride-2 convs as the shift form.  n_counts >= 10; with n_counts >= 12 also [10] dilated convs (gdt_net_conv_dilated) and
+ * [11] of those on any special form (a patch kernel, a fused launch): 0 -- dilation runs on the generic implicit-GEMM kernels only.  (Diagnostics / tests;
+ * no reference counterpart.) */
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts);
 
 /* Per-op timing for bench.py's roofline line: when enabled, gdt_net_forward records HIP events on the caller's stream
  * around every op.  gdt_net_profile_read (after the forward) returns per op: kind (0 input, 1 conv, 2 instance-norm,
- * 3 maxpool, 4 gem, 5 tap, 6 hed), the conv kernel variant (BM*1000+BN: conv_igemm_kernel<BM,BN>; 900000+BN:
+ * 3 maxpool, 4 gem, 5 tap, 6 hed, 7 rcf head), the conv kernel variant (BM*1000+BN: conv_igemm_kernel<BM,BN>; 900000+BN:
  * conv3x3_halo_kernel<BN>), elapsed ms and the algorithmic FLOPs.  No reference counterpart (the reference has wall-clock StopWatch only, mdir/tools/stats.py:48-68). */
 int gdt_net_set_profiling(gdt_net* net, int enable);
 int gdt_net_profile_read(gdt_net* net, int max_ops, int* n_ops, int* kinds, int* tile_n, double* ms, double* flops);

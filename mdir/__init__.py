@@ -26,6 +26,7 @@ _ALIASES = {
     "mdir.components.model.network.p2p_networks": "gandtr_amd.components.model.network.p2p_networks",
     "mdir.components.model.network.cirnet": "gandtr_amd.components.model.network.cirnet",
     "mdir.components.model.network.hed": "gandtr_amd.components.model.network.hed",
+    "mdir.components.model.network.rcf": "gandtr_amd.components.model.network.rcf",
     "mdir.components.model.weight_initialization": "gandtr_amd.components.model.weight_initialization",
     "mdir.components.data": "gandtr_amd.components.data",
     "mdir.components.data.wrapper": "gandtr_amd.components.data.wrapper",
