@@ -8,6 +8,7 @@ Drop-in surface (mirrors the reference's own modules):
   gandtr_amd.stages                      infer, whiten, learn_lw_whitening (stage ABI)
 "Next" rows of SURVEY.md section 8f (device paths beside the hot path):
   gandtr_amd.clahe / ingest / retrieval / whiten_learn
+  gandtr_amd.mining                      an epoch's training tuples: diverse anchors + hard negatives (create_epoch_tuples)
 Compute: gandtr_amd/csrc (HIP kernels for gfx950) behind the C ABI in include/gandtr_hip.h.
 """
 __version__ = "0.1.0"

@@ -93,6 +93,8 @@ SIGNATURES = {
     "gdt_retrieval_ap_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "gdt_retrieval_average_precision": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _IP, _IP, _IP, c_int,
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gdt_retrieval_diverse_anchors_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "gdt_retrieval_diverse_anchors": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gdt_l2n_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "gdt_gem_l2n": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "gdt_mfma_only_tflops": (c_int, [c_int, POINTER(c_double), c_void_p]),

@@ -244,6 +244,181 @@ __global__ __launch_bounds__(AP_THREADS) void ap_terms_kernel(const unsigned* __
     }
 }
 
+// Diverse-anchor selection (mdir/components/data/dataset/cirtorch_datasets.py:77-100): a greedy chain of nsel - 1 dependent steps.  The reference
+// grows a [nq][t] matrix of similarities, takes its row maximum and argsorts it every step; the chain only needs the running maximum.  Per step two
+// launches in stream order (no host round trip, no wait between workgroups):
+//   1. da_update_kernel: ms[i] = max(ms[i], <vecs[i], vecs[out_idx[t]]>) for every row, fp32 FMA, DA_ROWS rows per wave in flight, the pivot row
+//      staged in LDS in chunks of DA_CHUNK floats (any d), float4 loads where d and the base address allow them;
+//   2. da_select_kernel: one workgroup finds the entry at ascending position target_rank[t] of ms -- a radix select over order-preserving uint32
+//      keys (4 passes of 8 bits, LDS histogram), then the index among the entries that share the selected key (lower index first).
+// The summation order of a dot product is fixed by (d, lane), so two runs give the same bits.
+constexpr int DA_THREADS = 256, DA_ROWS = 4, DA_CHUNK = 4096, DA_ROWS_PER_BLOCK = DA_THREADS / 64 * DA_ROWS;
+constexpr int DS_THREADS = 1024, DS_WAVES = DS_THREADS / 64;
+
+template <bool VEC4>
+__global__ __launch_bounds__(DA_THREADS) void da_update_kernel(const float* __restrict__ vecs, float* __restrict__ ms, int* out_idx, int nq, int d,
+                                                               int t, int first_idx) {
+    __shared__ __attribute__((aligned(16))) float piv[DA_CHUNK];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int p = t == 0 ? first_idx : out_idx[t];
+    p = p < 0 ? 0 : (p >= nq ? nq - 1 : p);                        // written by da_select_kernel, always in range: the clamp only guards the loads
+    if (t == 0 && blockIdx.x == 0 && threadIdx.x == 0) out_idx[0] = p;
+    const int row0 = blockIdx.x * DA_ROWS_PER_BLOCK + wave * DA_ROWS;
+    const float* rows[DA_ROWS];
+    float acc[DA_ROWS];
+#pragma unroll
+    for (int r = 0; r < DA_ROWS; ++r) {
+        const int row = row0 + r < nq ? row0 + r : nq - 1;         // a row past the end re-reads the last one and is not written
+        rows[r] = vecs + (size_t)row * d;
+        acc[r] = 0.f;
+    }
+    const float* prow = vecs + (size_t)p * d;
+    for (int c0 = 0; c0 < d; c0 += DA_CHUNK) {
+        const int n = d - c0 < DA_CHUNK ? d - c0 : DA_CHUNK;
+        if (c0) __syncthreads();
+        if (VEC4) {
+            for (int i = threadIdx.x * 4; i < n; i += DA_THREADS * 4) *(float4*)(piv + i) = *(const float4*)(prow + c0 + i);
+        } else {
+            for (int i = threadIdx.x; i < n; i += DA_THREADS) piv[i] = prow[c0 + i];
+        }
+        __syncthreads();
+        if (VEC4) {
+            for (int i = lane * 4; i < n; i += 256) {
+                const float4 b = *(const float4*)(piv + i);
+                float4 a[DA_ROWS];
+#pragma unroll
+                for (int r = 0; r < DA_ROWS; ++r) a[r] = *(const float4*)(rows[r] + c0 + i);
+#pragma unroll
+                for (int r = 0; r < DA_ROWS; ++r) {
+                    acc[r] = fmaf(a[r].x, b.x, acc[r]);
+                    acc[r] = fmaf(a[r].y, b.y, acc[r]);
+                    acc[r] = fmaf(a[r].z, b.z, acc[r]);
+                    acc[r] = fmaf(a[r].w, b.w, acc[r]);
+                }
+            }
+        } else {
+            for (int i = lane; i < n; i += 64) {
+                const float b = piv[i];
+#pragma unroll
+                for (int r = 0; r < DA_ROWS; ++r) acc[r] = fmaf(rows[r][c0 + i], b, acc[r]);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < DA_ROWS; ++r) {
+        float v = acc[r];
+        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+        const int row = row0 + r;
+        if (lane == 0 && row < nq) ms[row] = t == 0 ? v : fmaxf(ms[row], v);
+    }
+}
+
+// ascending float order == ascending unsigned order of the key (-0.f below +0.f; NaNs at the two ends by their sign)
+__device__ inline unsigned da_key(float x) {
+    const unsigned u = __float_as_uint(x);
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+__global__ __launch_bounds__(DS_THREADS) void da_select_kernel(const float* ms, const int* __restrict__ target_rank, int* out_idx, float* out_score,
+                                                               int nq, int t) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned s_prefix, s_k;
+    __shared__ int wave_count[DS_WAVES];
+    __shared__ int s_found;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) {
+        const int k = target_rank[t];
+        s_k = (unsigned)(k < 0 ? 0 : (k >= nq ? nq - 1 : k));      // checked on the host before the upload; clamped so that the search below always ends inside ms
+        s_prefix = 0;
+        s_found = 0;
+    }
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        const unsigned prefix = s_prefix, k = s_k;
+        const unsigned himask = shift == 24 ? 0u : 0xffffffffu << (shift + 8);
+        for (int base = 0; base < nq; base += DS_THREADS) {
+            const int i = base + tid;
+            bool live = false;
+            unsigned bin = 0;
+            if (i < nq) {
+                const unsigned key = da_key(ms[i]);
+                live = (key & himask) == prefix;
+                bin = (key >> shift) & 255u;
+            }
+            if (shift == 24) {
+                // similarities crowd into a few sign/exponent bins: one LDS add per distinct bin of the wave instead of one per lane
+                unsigned long long todo = __ballot(live);
+                while (todo) {
+                    const int leader = __ffsll((long long)todo) - 1;
+                    const unsigned b = (unsigned)__shfl((int)bin, leader);
+                    const unsigned long long same = __ballot(live && bin == b);
+                    if (lane == leader) atomicAdd(&hist[b], (unsigned)__popcll(same));
+                    todo &= ~same;
+                }
+            } else if (live) {
+                atomicAdd(&hist[bin], 1u);
+            }
+        }
+        __syncthreads();
+        if (wave == 0) {                                           // the bin in which the running count passes k: lane l owns bins 4l .. 4l+3
+            const unsigned c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
+            const unsigned own = c0 + c1 + c2 + c3;
+            unsigned incl = own;
+            for (int m = 1; m < 64; m <<= 1) {
+                const unsigned up = (unsigned)__shfl_up((int)incl, m);
+                if (lane >= m) incl += up;
+            }
+            const unsigned long long hit = __ballot(k < incl);     // never empty: k is below the number of live entries
+            const int owner = hit ? __ffsll((long long)hit) - 1 : 63;
+            if (lane == owner) {
+                unsigned below = incl - own, b = 4 * lane;
+                if (k >= below + c0) { below += c0; ++b;
+                    if (k >= below + c1) { below += c1; ++b;
+                        if (k >= below + c2) { below += c2; ++b; } } }
+                s_prefix = prefix | (b << shift);
+                s_k = k - below;
+            }
+        }
+        __syncthreads();
+    }
+    // s_prefix is the key at the target position, s_k the position among the entries that carry it, in index order
+    const unsigned key = s_prefix;
+    const int want = (int)s_k;
+    int seen = 0;
+    for (int base = 0; base < nq; base += DS_THREADS) {
+        const int i = base + tid;
+        const bool m = i < nq && da_key(ms[i]) == key;
+        const unsigned long long b = __ballot(m);
+        if (lane == 0) wave_count[wave] = __popcll(b);
+        __syncthreads();
+        int before = seen, total = seen;
+        for (int w = 0; w < DS_WAVES; ++w) {
+            const int c = wave_count[w];
+            if (w < wave) before += c;
+            total += c;
+        }
+        if (m && before + __popcll(b & ((1ull << lane) - 1ull)) == want) {
+            out_idx[t + 1] = i;
+            out_score[t] = ms[i];
+            s_found = 1;
+        }
+        seen = total;
+        __syncthreads();
+        if (s_found) break;
+    }
+}
+
+struct DaLayout { size_t ms, total; };
+
+int da_plan(int nq, int d, int nsel, DaLayout& L) {
+    GDT_REQUIRE(nq >= 2 && d >= 1, "diverse anchors need nq >= 2 descriptors of size d >= 1");
+    GDT_REQUIRE(nsel >= 2 && nsel <= nq, "2 <= nsel <= nq");
+    L.ms = 0;
+    L.total = align_up((size_t)nq * sizeof(float)) + ALIGN;
+    return GDT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -371,6 +546,37 @@ int gdt_retrieval_average_precision(const int* ranks_t, int ndb, int nq, int nse
     GDT_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(ap_terms_kernel, dim3((unsigned)units), dim3(AP_THREADS), 0, st, (const unsigned*)pmask, (const unsigned*)jmask, ok_offsets,
                        (double*)(ws + L.terms), (int*)(ws + L.adj), ap, prk, status, L.nwords, K, nk);
+    GDT_CHECK_HIP(hipGetLastError());
+    return GDT_OK;
+}
+
+int gdt_retrieval_diverse_anchors_workspace_bytes(int nq, int d, int nsel, size_t* bytes) {
+    GDT_REQUIRE(bytes != nullptr, "bytes");
+    DaLayout L;
+    int rc = da_plan(nq, d, nsel, L);
+    if (rc != GDT_OK) return rc;
+    *bytes = L.total;
+    return GDT_OK;
+}
+
+int gdt_retrieval_diverse_anchors(const float* vecs, int nq, int d, const int* target_rank, int nsel, int first_idx, int* out_idx,
+                                  float* out_score, void* workspace, size_t workspace_bytes, void* stream) {
+    GDT_REQUIRE(vecs && target_rank && out_idx && out_score && workspace, "null buffer");
+    DaLayout L;
+    int rc = da_plan(nq, d, nsel, L);
+    if (rc != GDT_OK) return rc;
+    GDT_REQUIRE(first_idx >= 0 && first_idx < nq, "0 <= first_idx < nq");
+    GDT_REQUIRE(workspace_bytes >= L.total, "workspace too small (gdt_retrieval_diverse_anchors_workspace_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)(((uintptr_t)workspace + ALIGN - 1) / ALIGN * ALIGN);
+    float* ms = (float*)(ws + L.ms);
+    const bool vec4 = d % 4 == 0 && (uintptr_t)vecs % 16 == 0;
+    const dim3 grid((unsigned)((nq + DA_ROWS_PER_BLOCK - 1) / DA_ROWS_PER_BLOCK));
+    for (int t = 0; t < nsel - 1; ++t) {
+        if (vec4) hipLaunchKernelGGL(da_update_kernel<true>, grid, dim3(DA_THREADS), 0, st, vecs, ms, out_idx, nq, d, t, first_idx);
+        else hipLaunchKernelGGL(da_update_kernel<false>, grid, dim3(DA_THREADS), 0, st, vecs, ms, out_idx, nq, d, t, first_idx);
+        hipLaunchKernelGGL(da_select_kernel, dim3(1), dim3(DS_THREADS), 0, st, (const float*)ms, target_rank, out_idx, out_score, nq, t);
+    }
     GDT_CHECK_HIP(hipGetLastError());
     return GDT_OK;
 }

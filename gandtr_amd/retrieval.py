@@ -81,6 +81,86 @@ def search_hard_negatives(qidxs, qvecs, idxs2images, poolvecs, clusters, nnum):
     return nidxs, {"average_negative_distance": dist_.cpu().reshape(-1).tolist()}
 
 
+# ---- diverse-anchor selection (mdir/components/data/dataset/cirtorch_datasets.py:77-100)
+
+def diverse_anchor_targets(qpool_size, qsize, similar_exclude, similar_include, shuffle):
+    """The position in the ascending order of ``most_similar`` that every step of the reference's loop picks (cirtorch_datasets.py:88-95),
+    evaluated up front: int64 [qsize-1].  The slice ``argsort()[dissimilar_split:similar_split]`` depends on the step number alone, so with
+    ``shuffle`` the ``torch.randint(slice size, (1,))`` draws happen here, one per step in step order -- the global generator is consumed
+    exactly as by the reference's loop, which draws nothing else."""
+    targets = torch.empty(max(qsize - 1, 0), dtype=torch.int64)
+    for t in range(qsize - 1):
+        valid_size = qpool_size - (t + 1)
+        similar_split = max(int(valid_size * (1 - similar_exclude)), 1)
+        dissimilar_split = min(int(valid_size * (1 - similar_include)), similar_split - 1)
+        size = similar_split - dissimilar_split
+        choice = torch.randint(size, (1,)).item() if shuffle else size - 1
+        targets[t] = dissimilar_split + choice
+    return targets
+
+
+def diverse_anchors(qvecs, target_rank, first_idx=0):
+    """The chain of ``gdt_retrieval_diverse_anchors`` on explicit targets.  qvecs: D x Q fp32 on a HIP device (any strides); target_rank:
+    host integers, one per step, each in [0, Q) -- checked here, before anything is launched.  Returns (idxs int32 [len + 1], scores fp32
+    [len]) on the device, enqueued on the current stream without a synchronisation.  Equal similarities rank by lower index first."""
+    lib = _hip.load()
+    if not torch.is_tensor(qvecs) or not qvecs.is_cuda:
+        raise ValueError("diverse_anchors needs the descriptors on a HIP device")
+    v = _rows(qvecs)
+    nq, d = v.shape
+    tr = torch.as_tensor(target_rank, dtype=torch.int64).reshape(-1).cpu()
+    nsel = tr.numel() + 1
+    if nsel < 2 or nsel > nq:
+        raise ValueError("between 1 and %d steps for %d descriptors, got %d" % (nq - 1, nq, nsel - 1))
+    if int(tr.min()) < 0 or int(tr.max()) >= nq:
+        raise ValueError("target_rank outside [0, %d)" % nq)
+    dev = v.device
+    need = ctypes.c_size_t()
+    with torch.cuda.device(dev):
+        _hip.check(lib.gdt_retrieval_diverse_anchors_workspace_bytes(nq, d, nsel, ctypes.byref(need)))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        d_tr = tr.to(torch.int32).to(dev)
+        idxs = torch.empty(nsel, dtype=torch.int32, device=dev)
+        scores = torch.empty(nsel - 1, dtype=torch.float32, device=dev)
+        _hip.check(lib.gdt_retrieval_diverse_anchors(v.data_ptr(), nq, d, d_tr.data_ptr(), nsel, int(first_idx), idxs.data_ptr(), scores.data_ptr(),
+                                                     ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    return idxs, scores
+
+
+def _diverse_anchors_host(qvecs, targets):
+    """the reference's loop on a running maximum instead of the growing ``cat`` (the same values); ties by lower index"""
+    idx, idxs, qscore_acc = 0, [0], []
+    most_similar = torch.full((qvecs.shape[1],), -float("inf"), dtype=qvecs.dtype)
+    for target in targets.tolist():
+        most_similar = torch.maximum(most_similar, torch.mm(qvecs.t(), qvecs[:, idx:idx + 1])[:, 0])
+        idx = most_similar.argsort(stable=True)[target].item()
+        qscore_acc.append(most_similar[idx].item())
+        idxs.append(idx)
+    return idxs, qscore_acc
+
+
+def select_diverse_anchors(qvecs, qsize, similar_exclude, similar_include, shuffle=True):
+    """The diverse-anchor selection of ``DiverseAnchorsDataset._select_positive_pairs_db`` (cirtorch_datasets.py:77-100).  qvecs: D x Q
+    descriptors of the query pool.  Starting from column 0, every step keeps the largest similarity of each column to the anchors picked
+    so far and takes the column at a position of that ascending order inside [dissimilar_split, similar_split) -- the last one, or with
+    ``shuffle`` a random one (``diverse_anchor_targets``).  A HIP tensor runs the device chain (``diverse_anchors``), a CPU tensor the
+    torch restatement.  Returns (idxs: qsize columns, qscore_acc: the qsize-1 similarities at which they were picked).  Columns already
+    picked are not excluded, as in the reference; where two similarities are equal the lower column comes first (the reference's
+    ``argsort`` leaves that order open)."""
+    assert similar_exclude <= similar_include
+    nq = qvecs.shape[1]
+    if qsize < 2 or qsize > nq:
+        raise ValueError("2 <= qsize <= %d descriptors, got %d" % (nq, qsize))
+    targets = diverse_anchor_targets(nq, qsize, similar_exclude, similar_include, shuffle)
+    if int(targets.min()) < 0 or int(targets.max()) >= nq:
+        raise ValueError("similar_exclude / similar_include put a target outside [0, %d)" % nq)
+    with torch.no_grad():
+        if qvecs.is_cuda:
+            idxs, scores = diverse_anchors(qvecs, targets)
+            return idxs.cpu().tolist(), scores.cpu().tolist()
+        return _diverse_anchors_host(qvecs, targets)
+
+
 def sharded_topk(vecs_local, qvecs, k, group=None):
     """Database sharded over the ranks of one node (contiguous chunks, as gandtr_amd.sharding), queries replicated.
     Every rank scores its shard, keeps its local top-k per query and all-gathers the candidates (k scores + k global ids per

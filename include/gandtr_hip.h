@@ -258,6 +258,19 @@ int gdt_retrieval_average_precision(const int* ranks_t, int ndb, int nq, int nse
                                     const int* junk_offsets, const int* junk_ids, const int* ok_offsets_host, const int* junk_offsets_host,
                                     const int* kappas, int nk, double* ap, double* prk, int* status, void* workspace,
                                     size_t workspace_bytes, void* stream);
+/* Diverse-anchor selection -- replaces the greedy loop of
+ *   DiverseAnchorsDataset._select_positive_pairs_db   mdir/components/data/dataset/cirtorch_datasets.py:77-100
+ * vecs [nq][d] fp32 rows (any d >= 1, nq >= 2), 2 <= nsel <= nq.  out_idx[0] = first_idx (the reference starts at 0), most_similar[i] = -inf;
+ * for t = 0 .. nsel-2:  most_similar[i] = max(most_similar[i], <vecs[i], vecs[out_idx[t]]>) for every i;  out_idx[t+1] = the index at position
+ * target_rank[t] of the ascending order of most_similar;  out_score[t] = that value.  Indices already picked are not excluded (their similarity
+ * is maximal: the reference relies on the same).  Equal values are ordered by lower index first -- the reference's argsort leaves the order of
+ * exact ties unspecified.  Dot products are fp32 FMAs in a fixed order (two runs give the same bits); the descriptors are never down-converted.
+ * target_rank int32 [nsel-1], out_idx int32 [nsel], out_score fp32 [nsel-1] and the workspace are device buffers; a target outside [0, nq) is
+ * clamped on the device (the caller checks its host copy).  The whole chain, 2 * (nsel - 1) launches, is enqueued on `stream` without a host
+ * synchronisation.  Bad arguments (null buffer, nsel or first_idx out of range, workspace too small) return GDT_ERR_INVALID. */
+int gdt_retrieval_diverse_anchors_workspace_bytes(int nq, int d, int nsel, size_t* bytes);
+int gdt_retrieval_diverse_anchors(const float* vecs, int nq, int d, const int* target_rank, int nsel, int first_idx, int* out_idx,
+                                  float* out_score, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * CLAHE post-processing ("next" row of SURVEY.md section 8f, rank 1: the step between generator and embedder)
