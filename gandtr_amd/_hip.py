@@ -64,6 +64,7 @@ SIGNATURES = {
     "gdt_net_maxpool_ceil": (c_int, [c_void_p, c_int, c_int, c_int, _IP]),
     "gdt_net_conv_dilated": (c_int, [c_void_p, c_int, POINTER(ConvDesc), c_int, c_void_p, c_void_p, _IP]),
     "gdt_net_gem_l2n": (c_int, [c_void_p, c_int, c_float, c_float, c_float, _IP]),
+    "gdt_net_pool_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, _IP]),
     "gdt_net_output_nchw": (c_int, [c_void_p, c_int, c_void_p, _IP]),
     "gdt_net_hed_head": (c_int, [c_void_p, _IP, POINTER(c_void_p), _FP, _FP, c_float, c_int, _IP]),
     "gdt_net_rcf_head": (c_int, [c_void_p, _IP, _IP, POINTER(c_void_p), _FP, _FP, c_float, c_int, _IP]),
@@ -97,6 +98,8 @@ SIGNATURES = {
     "gdt_retrieval_diverse_anchors": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gdt_l2n_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "gdt_gem_l2n": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "gdt_rpool_regions": (c_int, [c_int, c_int, c_int, _IP, c_int, _IP]),
+    "gdt_pool_regions": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_float, c_int, c_void_p, c_void_p]),
     "gdt_mfma_only_tflops": (c_int, [c_int, POINTER(c_double), c_void_p]),
     "gdt_ingest_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "gdt_ingest_resize_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int, c_void_p, c_void_p,

@@ -1,11 +1,14 @@
-"""GeM retrieval embedder -- host mirror of
-  mdir/external/cirtorch/layers/functional.py:21-22 (gem), :130-131 (l2n)
-  mdir/external/cirtorch/layers/pooling.py:36-47 (GeM), layers/normalization.py:10-20 (L2N)
+"""Retrieval embedder -- host mirror of
+  mdir/external/cirtorch/layers/functional.py:11-123 (mac, spoc, gem, rmac, roipool), :130-131 (l2n)
+  mdir/external/cirtorch/layers/pooling.py:12-113 (MAC, SPoC, GeM, GeMmp, RMAC, Rpool), layers/normalization.py:10-20 (L2N)
   mdir/external/cirtorch/networks/imageretrievalnet.py:86-123 (ImageRetrievalNet), :146-309 (init_network)
   mdir/components/model/network/cirnet.py:8-65 (CirRetrievalNet, init_cirnet)
-Only the hub configuration is on the HIP hot path: GeM pooling, no local / regional / final whitening layers
-(mdir/hub/embedding.yml:6-10).
+The whole descriptor head runs on the HIP path: any of the five poolings, made regional or not, with the local, the regional
+and the final whitening layers (engine.build_embedder, csrc/pool_head.hip); the hub configuration (mdir/hub/embedding.yml:6-10:
+plain GeM, no whitening layers) keeps its own two-launch op.
 """
+import math
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -23,6 +26,72 @@ def l2n(x, eps=1e-6):
     return x / (torch.norm(x, p=2, dim=1, keepdim=True) + eps).expand_as(x)
 
 
+def mac(x):
+    return F.max_pool2d(x, (x.size(-2), x.size(-1)))
+
+
+def spoc(x):
+    return F.avg_pool2d(x, (x.size(-2), x.size(-1)))
+
+
+def region_grid(H, W, L=3):
+    """The square regions R-MAC lays over an H x W map, as (y0, x0, side) in the order the reference visits them (levels 1..L, rows, columns;
+    the whole map is not in the list).  The reference places them with float32 TENSOR arithmetic (functional.py:79-115) and so does this: the
+    same expressions in double or integer arithmetic put some regions one pixel off for some map sizes.  csrc/pool_head.hip (gdt_rpool_regions)
+    restates it in C for the planner; tests/test_descriptor_heads_host.py holds both to the reference's own grid for every size up to 72 x 72."""
+    ovr = 0.4                                           # desired overlap of neighbouring regions
+    steps = torch.tensor([2., 3., 4., 5., 6., 7.])      # candidate region counts along the long side
+    w = min(W, H)
+    b = (max(H, W) - w) / (steps - 1)
+    idx = int(torch.min(torch.abs(((w ** 2 - w * b) / w ** 2) - ovr), 0)[1])
+    Wd = idx + 1 if H < W else 0                        # extra regions along the longer side
+    Hd = idx + 1 if H > W else 0
+    out = []
+    for l in range(1, L + 1):
+        wl = math.floor(2 * w / (l + 1))
+        if wl == 0:
+            continue
+        wl2 = math.floor(wl / 2 - 1)
+        bw = 0 if l + Wd == 1 else (W - wl) / (l + Wd - 1)
+        bh = 0 if l + Hd == 1 else (H - wl) / (l + Hd - 1)
+        xs = (torch.floor(wl2 + torch.arange(l + Wd, dtype=torch.float32) * bw).int() - wl2).tolist()
+        ys = (torch.floor(wl2 + torch.arange(l + Hd, dtype=torch.float32) * bh).int() - wl2).tolist()
+        out.extend((y, x, wl) for y in ys for x in xs)
+    return out
+
+
+def rmac(x, L=3, eps=1e-6):
+    """R-MAC: the l2-normalised maxima of the whole map and of every region, summed (not normalised again)"""
+    v = l2n(mac(x), eps)
+    for y0, x0, wl in region_grid(x.size(2), x.size(3), L):
+        v = v + l2n(mac(x[:, :, y0:y0 + wl, x0:x0 + wl]), eps)
+    return v
+
+
+def roipool(x, rpool, L=3, eps=1e-6):
+    """``rpool`` of the whole map and of every region: N x R x D x 1 x 1"""
+    vecs = [rpool(x).unsqueeze(1)]
+    for y0, x0, wl in region_grid(x.size(2), x.size(3), L):
+        vecs.append(rpool(x.narrow(2, y0, wl).narrow(3, x0, wl)).unsqueeze(1))
+    return torch.cat(vecs, dim=1)
+
+
+class MAC(nn.Module):
+    def forward(self, x):
+        return mac(x)
+
+    def __repr__(self):
+        return type(self).__name__ + "()"
+
+
+class SPoC(nn.Module):
+    def forward(self, x):
+        return spoc(x)
+
+    def __repr__(self):
+        return type(self).__name__ + "()"
+
+
 class GeM(nn.Module):
     def __init__(self, p=3, eps=1e-6):
         super().__init__()
@@ -34,6 +103,35 @@ class GeM(nn.Module):
 
     def __repr__(self):
         return "%s(p=%.4f, eps=%s)" % (type(self).__name__, self.p.data.tolist()[0], self.eps)
+
+
+class GeMmp(nn.Module):
+    """GeM with one exponent per channel"""
+
+    def __init__(self, p=3, mp=1, eps=1e-6):
+        super().__init__()
+        self.p = Parameter(torch.ones(mp) * p)
+        self.mp = mp
+        self.eps = eps
+
+    def forward(self, x):
+        return gem(x, p=self.p.unsqueeze(-1).unsqueeze(-1), eps=self.eps)
+
+    def __repr__(self):
+        return "%s(p=[%s], eps=%s)" % (type(self).__name__, self.mp, self.eps)
+
+
+class RMAC(nn.Module):
+    def __init__(self, L=3, eps=1e-6):
+        super().__init__()
+        self.L = L
+        self.eps = eps
+
+    def forward(self, x):
+        return rmac(x, L=self.L, eps=self.eps)
+
+    def __repr__(self):
+        return "%s(L=%s)" % (type(self).__name__, self.L)
 
 
 class L2N(nn.Module):
@@ -48,11 +146,40 @@ class L2N(nn.Module):
         return "%s(eps=%s)" % (type(self).__name__, self.eps)
 
 
+class Rpool(nn.Module):
+    """A pooling made regional: ``rpool`` per region, l2n, optional whitening + l2n per region, then sum + l2n over an image's regions"""
+
+    def __init__(self, rpool, whiten=None, L=3, eps=1e-6):
+        super().__init__()
+        self.rpool = rpool
+        self.L = L
+        self.whiten = whiten
+        self.norm = L2N()
+        self.eps = eps
+
+    def forward(self, x, aggregate=True):
+        o = roipool(x, self.rpool, self.L, self.eps)             # N x R x D x 1 x 1
+        s = o.size()
+        o = self.norm(o.view(s[0] * s[1], s[2], s[3], s[4]))
+        if self.whiten is not None:
+            o = self.norm(self.whiten(o.squeeze(-1).squeeze(-1)))
+        o = o.view(s[0], s[1], s[2], s[3], s[4])
+        if aggregate:
+            o = self.norm(o.sum(1, keepdim=False))              # N x D x 1 x 1
+        return o
+
+    def __repr__(self):
+        return super().__repr__() + "(L=%s)" % self.L
+
+
+POOLING = {"mac": MAC, "spoc": SPoC, "gem": GeM, "gemmp": GeMmp, "rmac": RMAC}
+
+
 OUTPUT_DIM = {"vgg16": 512, "resnet50": 2048, "resnet101": 2048, "resnet152": 2048}
 
 
 class ImageRetrievalNet(HipBacked, nn.Module):
-    """features -> GeM -> L2N; returns D x N (one column per image)."""
+    """features -> (local whitening) -> pool -> L2N -> (whitening -> L2N); returns D x N (one column per image)."""
 
     def __init__(self, features, lwhiten, pool, whiten, meta):
         super().__init__()
@@ -81,29 +208,44 @@ class ImageRetrievalNet(HipBacked, nn.Module):
             o = self.norm(self.whiten(o))
         return o.permute(1, 0)
 
-    def _forward_hip(self, x, scale):
+    HIP_TRUNKS = ("vgg16", "resnet50", "resnet101", "resnet152")
+
+    def _hip_head(self):
+        """What engine.build_embedder needs to know about the head beyond the state dict, as a hashable tuple (it is part of the cache key of
+        the HIP net, so swapping ``pool`` or a whitening layer rebuilds): (pooling kind, regional, L, eps of the pooling, local whitening, final
+        whitening).  None for the hub configuration (plain GeM, no whitening layers), which keeps its own op."""
+        pool = self.pool
+        regional = isinstance(pool, Rpool)
+        inner = pool.rpool if regional else pool
+        kinds = {MAC: "mac", SPoC: "spoc", GeM: "gem", GeMmp: "gemmp", RMAC: "rmac"}
+        kind = kinds.get(type(inner))
+        if kind is None or (regional and kind == "rmac"):
+            raise NotImplementedError("HIP embedder: pooling %r is not one of mac / spoc / gem / gemmp / rmac (regional or not; no regions of "
+                                      "R-MAC regions)" % (pool,))
+        if kind == "gem" and not regional and self.lwhiten is None and self.whiten is None:
+            return None
+        L = pool.L if regional else (inner.L if kind == "rmac" else 0)
+        return (kind, regional, int(L), float(getattr(inner, "eps", 1e-6)), self.lwhiten is not None, self.whiten is not None)
+
+    def _hip_embedder(self):
         from .... import engine
-        if self.lwhiten is not None or self.whiten is not None or not isinstance(self.pool, GeM):
-            raise NotImplementedError("HIP embedder supports GeM pooling without local/final whitening layers (hub configuration)")
-        if self.meta.get("architecture") not in ("vgg16", "resnet50", "resnet101", "resnet152"):
+        if self.meta.get("architecture") not in self.HIP_TRUNKS:
             raise NotImplementedError("HIP embedder supports vgg16 / resnet50 / resnet101 / resnet152 trunks")
+        head = self._hip_head()
         self._hip_check_inference()
         prec = self._hip_precision()
-        net = self._hip_net(("embed", prec), lambda sd, dev: engine.build_embedder(sd, dev, precision=prec))
+        return self._hip_net(("embed", prec, head), lambda sd, dev: engine.build_embedder(sd, dev, precision=prec, head=head))
+
+    def _forward_hip(self, x, scale):
+        net = self._hip_embedder()
         return net.forward(x, scale=scale)[net.out_slot].t()      # N x D storage, D x N view (imageretrievalnet.py:123)
 
     def forward_many(self, xs):
         """``[self(x) for x in xs]`` with the HIP forwards of the list issued concurrently (engine.HipNet.forward_many): the levels of a
         multi-scale pyramid are independent and each is too small to fill the chip."""
-        from .... import engine
         if self._hip_device().type != "cuda" or len(xs) < 2:
             return [self(x) for x in xs]
-        if self.lwhiten is not None or self.whiten is not None or not isinstance(self.pool, GeM) or \
-                self.meta.get("architecture") not in ("vgg16", "resnet50", "resnet101", "resnet152"):
-            return [self(x) for x in xs]                          # (raises the same NotImplementedError as the single call)
-        self._hip_check_inference()
-        prec = self._hip_precision()
-        net = self._hip_net(("embed", prec), lambda sd, dev: engine.build_embedder(sd, dev, precision=prec))
+        net = self._hip_embedder()
         pairs = [(x.tensor, x.scale) if isinstance(x, ScaledInput) else (x, None) for x in xs]
         return [outs[net.out_slot].t() for outs in net.forward_many(pairs)]
 
@@ -118,9 +260,9 @@ class ImageRetrievalNet(HipBacked, nn.Module):
 
 
 def init_network(params):
-    """cirtorch init_network reduced to the configurations reachable from the hub / cirnet registry entry:
-    random-initialised trunk (weights arrive through load_state_dict), GeM pooling, optional plain-Linear whitening
-    layers are rejected on the hot path."""
+    """cirtorch init_network for the configurations that need no download: a randomly initialised trunk (weights arrive through
+    load_state_dict) and the head layers created in the reference's order -- local whitening, pooling, regional whitening, final whitening --
+    so that a seeded construction draws the same numbers as the reference's."""
     architecture = params.get("architecture", "resnet101")
     local_whitening = params.get("local_whitening", False)
     pooling = params.get("pooling", "gem")
@@ -134,6 +276,13 @@ def init_network(params):
         raise ValueError("Unsupported or unknown architecture: {}!".format(architecture))
     if pretrained:
         raise ValueError("pretrained ImageNet trunks need a download; use pretrained=False and load a checkpoint")
+    if isinstance(pooling, dict):
+        raise NotImplementedError("dict-valued pooling (the POOLINGS kinds of mdir/components/model/layers/pooling.py) is not mirrored; "
+                                  "use one of %s" % sorted(POOLING))
+    if pooling not in POOLING:
+        raise KeyError(pooling)
+    if regional and pooling == "rmac":
+        raise NotImplementedError("regional=True with pooling='rmac' (R-MAC regions of R-MAC regions) is not mirrored; no published network uses it")
     net_in = backbones.ARCHITECTURES[architecture](pretrained=False)
     if architecture.startswith("vgg"):
         features = list(net_in.features.children())[:-1]      # drop the last MaxPool
@@ -141,23 +290,41 @@ def init_network(params):
         features = list(net_in.children())[:-2]               # drop avgpool, fc
     last_convs = [m for f in features[-2:] for m in f.modules() if isinstance(m, nn.Conv2d)]
     dim = last_convs[-1].out_channels
-    if local_whitening or regional or whitening:
-        raise NotImplementedError("local / regional / final whitening layers are outside the gandtr hot path "
-                                  "(mdir/hub/embedding.yml uses none)")
-    if pooling != "gem":
-        raise NotImplementedError("only GeM pooling is on the gandtr hot path")
+
+    lwhiten = nn.Linear(dim, dim, bias=True) if local_whitening else None
+    pool = POOLING[pooling](mp=dim) if pooling == "gemmp" else POOLING[pooling]()
+    if regional:
+        pool = Rpool(pool, nn.Linear(dim, dim, bias=True))
+    whiten = None
+    if whitening:
+        whiten = nn.Linear(dim, dim, bias=True)
+        if isinstance(whitening, str):          # a learned {P, m} file: W v + b = P (v - m)
+            from ....tools.utils import fs_load_pickle
+            lw = fs_load_pickle(whitening)
+            P, m = torch.tensor(lw["P"]), torch.tensor(lw["m"])
+            whiten.load_state_dict({"weight": P, "bias": -torch.mm(P, m).squeeze()})
     meta = {"architecture": architecture, "local_whitening": local_whitening, "pooling": pooling, "regional": regional,
             "whitening": whitening, "mean": mean, "std": std, "outputdim": dim, "out_channels": dim}
-    return ImageRetrievalNet(features, None, GeM(), None, meta)
+    return ImageRetrievalNet(features, lwhiten, pool, whiten, meta)
 
 
 class CirRetrievalNet(ImageRetrievalNet):
     """cirtorch retrieval net with the optimiser parameter groups of the reference (pool exponent: 10x lr, no weight
-    decay) and BatchNorm layers frozen in eval mode while training."""
+    decay; whitening layers at the base rate) and BatchNorm layers frozen in eval mode while training."""
 
     def parameter_groups(self, optimizer_opts):
-        return [{"params": self.features.parameters()},
-                {"params": self.pool.parameters(), "lr": optimizer_opts["lr"] * 10, "weight_decay": 0}]
+        groups = [{"params": self.features.parameters()}]
+        if self.meta["local_whitening"]:
+            groups.append({"params": self.lwhiten.parameters()})
+        if not self.meta["regional"]:
+            groups.append({"params": self.pool.parameters(), "lr": optimizer_opts["lr"] * 10, "weight_decay": 0})
+        else:                                   # the exponent of the regions' pooling, then the regional whitening at the base rate
+            groups.append({"params": self.pool.rpool.parameters(), "lr": optimizer_opts["lr"] * 10, "weight_decay": 0})
+            if self.pool.whiten is not None:
+                groups.append({"params": self.pool.whiten.parameters()})
+        if self.whiten is not None:
+            groups.append({"params": self.whiten.parameters()})
+        return groups
 
     def train(self, mode=True):
         res = super().train(mode)

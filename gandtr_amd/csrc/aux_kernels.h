@@ -2,6 +2,8 @@
 // `f32` selects the activation element type: 0 = fp16 NHWC (default), 1 = fp32 NHWC ("f16x3" / "f16c" precision modes);
 // gdt_k_pack_input also takes 2 = fp16 NHWC8 pixel words augmented with their own rounding residuals (conv_stem.hip, f16c form).
 #pragma once
+#include <vector>
+
 #include "gdt_common.h"
 
 int gdt_k_pack_input(const float* x, void* y, int f32, int N, int C, int H, int W, int OH, int OW, float rscale, int resize,
@@ -33,3 +35,29 @@ int gdt_k_rcf_stage_score(const void* const* x, const float* const* v, int nx, i
 int gdt_k_rcf_fuse(const float* const* score, const int* h, const int* w, const float* const* filt, const int* stride, const int* crop, const float* fw,
                    float fb, float* out, int N, int H, int W, int sigmoid, hipStream_t st);
 int gdt_conv_bn(int Cout);
+
+// ---- descriptor head (pool_head.hip) ----
+enum { GDT_POOL_MAX = 0, GDT_POOL_MEAN = 1, GDT_POOL_GEM = 2, GDT_POOL_GEMMP = 3 };      // the `kind` of include/gandtr_hip.h
+constexpr int GDT_POOL_MAX_REGIONS = 64;
+struct GdtPoolBox { int y0, x0, h, w; };
+// the regions of one map size as the pooling kernel takes them (by value): region r = rows [ry0, ry0 + rh) x column band rband[r]; band b = columns
+// [bx0, bx0 + bw).  Regions that share their columns share a band.
+struct GdtPoolRegions {
+    int R, B;
+    short ry0[GDT_POOL_MAX_REGIONS], rh[GDT_POOL_MAX_REGIONS], rband[GDT_POOL_MAX_REGIONS];
+    short bx0[GDT_POOL_MAX_REGIONS], bw[GDT_POOL_MAX_REGIONS];
+};
+struct GdtPoolHead {
+    int kind = GDT_POOL_GEM; float p = 3.f; const float* p_channels = nullptr; float eps = 1e-6f, eps_l2 = 1e-6f;
+    int aggregate = 0;                                      // 0: one vector per image, 1: R-MAC, 2: Rpool (gdt_k_pool_head)
+    const float *rw = nullptr, *rb = nullptr, *fw = nullptr, *fb = nullptr;     // regional / final whitening (device, fp32 [D][D] and [D])
+};
+int gdt_pool_grid(int H, int W, int L, std::vector<GdtPoolBox>& boxes);          // the whole map, then the L levels of LF.roipool (host)
+int gdt_pool_regions_of(const std::vector<GdtPoolBox>& boxes, GdtPoolRegions& g);
+int gdt_k_pool_regions(const void* x, int f32, float* out, int N, int H, int W, int D, int kind, float p, const float* p_channels, float eps,
+                       const GdtPoolRegions& g, hipStream_t st);
+int gdt_k_linear_rows(const float* a, const float* w, const float* bias, float* out, int rows, int K, int Dout, hipStream_t st);
+int gdt_k_region_sum(const float* v, float* y, int N, int R, int D, float eps, int l2n, hipStream_t st);
+size_t gdt_pool_head_scratch_floats(int N, int R, int D);
+int gdt_k_pool_head(const void* x, int f32, int N, int H, int W, int D, const GdtPoolHead& hd, const GdtPoolRegions& g, float* scratch, float* out,
+                    hipStream_t st);

@@ -25,7 +25,7 @@ inline size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
 inline int next_pow2(int v) { int p = 8; while (p < v) p <<= 1; return p; }
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF };
+enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF, OP_POOL_HEAD };
 
 struct PackedPhase {
     size_t w_off = 0;                 // byte offset in the device weight blob
@@ -73,6 +73,10 @@ struct Op {
     int k = 0, s = 0, p = 0; int ceil = 0;
     // gem
     float gem_p = 3.f, eps_gem = 1e-6f, eps_l2 = 1e-6f;
+    // pool head (pool_head.hip): pooling kind (GDT_POOL_*), exponent(s) and eps in gem_p / eps_gem / eps_l2 above; aggregate 0 = one vector per image,
+    // 1 = R-MAC, 2 = Rpool over `levels` levels of regions; the per-channel exponents and the two whitening layers in the blob (fp32)
+    int pool_kind = 0, pool_aggregate = 0, pool_levels = 0;
+    size_t pch_off = 0, rw_off = 0, rb_off = 0, fw_off = 0, fb_off = 0; bool has_rw = false, has_fw = false;
     // out_nchw
     size_t tap_bias_off = 0; bool tap_has_bias = false;
     // head ops (OP_HED, OP_RCF): the feature tensors they read -- inputs like `in` / `res` (op_inputs), kept alive until the head runs
@@ -729,6 +733,17 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok = 
                 arena.release(st.aux_off[0], (size_t)N * ti.C * sizeof(float));
                 break;
             }
+            case OP_POOL_HEAD: {                        // the [N][R][D] pooled vectors and their normalised copy, two [N][D] rows (gdt_k_pool_head)
+                const Tensor& ti = T[o.in];
+                std::vector<GdtPoolBox> boxes;
+                const int rc = gdt_pool_grid(ti.H, ti.W, o.pool_aggregate ? o.pool_levels : 0, boxes);
+                if (rc != GDT_OK) return rc;
+                GDT_REQUIRE((int)boxes.size() <= GDT_POOL_MAX_REGIONS, "pool head: more than 64 regions per image for this map size");
+                const size_t b = gdt_pool_head_scratch_floats(N, (int)boxes.size(), ti.C) * sizeof(float);
+                st.aux_off[0] = arena.alloc(b);
+                arena.release(st.aux_off[0], b);
+                break;
+            }
             case OP_OUT_NCHW: break;
             case OP_HED: {
                 size_t sz[5];
@@ -1381,6 +1396,35 @@ int gdt_net_gem_l2n(gdt_net* net, int in_tensor, float p, float eps_gem, float e
     return GDT_OK;
 }
 
+int gdt_net_pool_head(gdt_net* net, int in_tensor, int kind, const float* p, int n_p, float eps, int aggregate, int levels, const float* rw,
+                      const float* rb, const float* fw, const float* fb, float eps_l2, int* out_slot) {
+    GDT_REQUIRE(net && !net->finalized && out_slot, "net");
+    GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "tensor id");
+    const int D = net->tensors[in_tensor].C;
+    GDT_REQUIRE(D % 64 == 0 && D == net->tensors[in_tensor].Creal, "pool head needs channels % 64 == 0");
+    GDT_REQUIRE(kind >= GDT_POOL_MAX && kind <= GDT_POOL_GEMMP, "pool head: kind 0 max, 1 mean, 2 GeM, 3 per-channel GeM");
+    GDT_REQUIRE(aggregate >= 0 && aggregate <= 2, "pool head: aggregate 0 none, 1 R-MAC, 2 regional pooling");
+    GDT_REQUIRE(aggregate != 1 || kind == GDT_POOL_MAX, "pool head: R-MAC aggregates maxima");
+    GDT_REQUIRE(!aggregate || (levels >= 1 && levels <= 3), "pool head: 1..3 levels of regions (at most 51 regions per image)");
+    GDT_REQUIRE((rw == nullptr) == (rb == nullptr) && (fw == nullptr) == (fb == nullptr), "pool head: a whitening layer is a weight and a bias");
+    GDT_REQUIRE(!rw || aggregate == 2, "pool head: the regional whitening belongs to a regional pooling");
+    if (kind == GDT_POOL_GEM) GDT_REQUIRE(p && n_p == 1 && p[0] > 0.f, "pool head: GeM takes one positive exponent");
+    if (kind == GDT_POOL_GEMMP) {
+        GDT_REQUIRE(p && n_p == D, "pool head: per-channel GeM takes one exponent per channel");
+        for (int i = 0; i < D; ++i) GDT_REQUIRE(p[i] > 0.f, "pool head: GeM exponents must be positive");
+    }
+    Op o; o.kind = OP_POOL_HEAD; o.in = in_tensor; o.pool_kind = kind; o.pool_aggregate = aggregate; o.pool_levels = aggregate ? levels : 0;
+    o.gem_p = kind == GDT_POOL_GEM ? p[0] : 1.f; o.eps_gem = eps; o.eps_l2 = eps_l2;
+    if (kind == GDT_POOL_GEMMP) o.pch_off = net->blob_append(p, (size_t)D * sizeof(float));
+    if (rw) { o.rw_off = net->blob_append(rw, (size_t)D * D * sizeof(float)); o.rb_off = net->blob_append(rb, (size_t)D * sizeof(float)); o.has_rw = true; }
+    if (fw) { o.fw_off = net->blob_append(fw, (size_t)D * D * sizeof(float)); o.fb_off = net->blob_append(fb, (size_t)D * sizeof(float)); o.has_fw = true; }
+    o.slot = (int)net->out_ops.size();
+    net->out_ops.push_back((int)net->ops.size());
+    net->ops.push_back(o);
+    *out_slot = o.slot;
+    return GDT_OK;
+}
+
 int gdt_net_output_nchw(gdt_net* net, int in_tensor, const float* bias, int* out_slot) {
     GDT_REQUIRE(net && !net->finalized && out_slot, "net");
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "tensor id");
@@ -1520,7 +1564,7 @@ int gdt_net_output_shape(gdt_net* net, int slot, int n, int rh, int rw, int* dim
         case OP_CONV:
             dims[0] = n; dims[1] = o.cd.cout; dims[2] = conv_out_dim(o, ti.H, o.cd.kh); dims[3] = conv_out_dim(o, ti.W, o.cd.kw);
             *ndim = 4; break;
-        case OP_GEM: dims[0] = n; dims[1] = ti.C; *ndim = 2; break;
+        case OP_GEM: case OP_POOL_HEAD: dims[0] = n; dims[1] = ti.C; *ndim = 2; break;
         case OP_OUT_NCHW: dims[0] = n; dims[1] = ti.C; dims[2] = ti.H; dims[3] = ti.W; *ndim = 4; break;
         case OP_HED: case OP_RCF: dims[0] = n; dims[1] = 1; dims[2] = rh; dims[3] = rw; *ndim = 4; break;     // (edge maps at the network input size)
         default: GDT_REQUIRE(false, "not an output op");
@@ -1582,7 +1626,8 @@ static double op_bytes(const gdt_net* net, const Op& o, int n) {
 // counts[0] launches of conv ops (a fused launch counts once), [1] whole Bottlenecks in one launch (conv_bneck.hip), [2] 3x3 + expand launches (conv3x3_expand_rb.hip),
 // [3] of those with the next block's reduce conv chained in, [4] projection shortcuts folded into their expand conv (K-concatenated 1x1), [5] InstanceNorms applied by
 // their consumer's staging, [6] max-pools written by their producer, [7] 1 if the stem reads the caller's image itself (calls that do not resize),
-// [8] transposed convs as one fused-phase launch, [9] stride-2 convs as the shift form
+// [8] transposed convs as one fused-phase launch, [9] stride-2 convs as the shift form, [10] dilated convs, [11] of those on a special form; with n_counts >= 14:
+// [12] launches of the pool-head ops (gdt_net_pool_head), [13] of those the ones that read the feature map
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts) {
     GDT_REQUIRE(net && counts && n_counts >= 10 && n >= 1 && rh >= 1 && rw >= 1, "plan summary arguments");
     if (!net->finalized && !net->precision) build_kcat_weights(net);       // (what finalize would add: the K-concatenated shortcut weights the planner may choose)
@@ -1597,6 +1642,10 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
         if (o.kind == OP_CONV) { counts[1] += st.bneck; counts[2] += st.xexp; counts[3] += st.xchain >= 0; counts[4] += st.kcat; counts[8] += st.ctf; counts[9] += st.s2; }
         if (o.kind == OP_INORM) counts[5] += st.norm_into >= 0;
         if (o.kind == OP_MAXPOOL) counts[6] += st.skip;
+        if (o.kind == OP_POOL_HEAD && n_counts >= 14) {   // the launches of gdt_k_pool_head: fixed by the layers present, whatever the batch and the number of regions
+            counts[12] += 1 + (o.pool_aggregate ? 2 + (o.has_rw ? 2 : 0) + (o.pool_aggregate == 2 ? 1 : 0) : 1) + (o.has_fw ? 2 : 0);
+            counts[13] += 1;                              // ... of which read the feature map: the pooling pass
+        }
         if (o.kind == OP_INPUT) counts[7] += st.direct;
         if (o.kind == OP_CONV && o.dil != 1 && n_counts >= 12) {
             ++counts[10];
@@ -1945,6 +1994,21 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                 const Tensor& ti = T[o.in];
                 rc = gdt_k_gem_l2n(tptr(o.in), f32, (float*)(ws + stp.aux_off[0]), (float*)outputs[o.slot], n, ti.H * ti.W, ti.C, o.gem_p,
                                    o.eps_gem, o.eps_l2, st);
+                break;
+            }
+            case OP_POOL_HEAD: {
+                const Tensor& ti = T[o.in];
+                std::vector<GdtPoolBox> boxes;
+                GdtPoolRegions g{};
+                rc = gdt_pool_grid(ti.H, ti.W, o.pool_aggregate ? o.pool_levels : 0, boxes);
+                if (rc == GDT_OK) rc = gdt_pool_regions_of(boxes, g);
+                if (rc != GDT_OK) break;
+                GdtPoolHead hd;
+                hd.kind = o.pool_kind; hd.p = o.gem_p; hd.eps = o.eps_gem; hd.eps_l2 = o.eps_l2; hd.aggregate = o.pool_aggregate;
+                if (o.pool_kind == GDT_POOL_GEMMP) hd.p_channels = (const float*)(net->dev_blob + o.pch_off);
+                if (o.has_rw) { hd.rw = (const float*)(net->dev_blob + o.rw_off); hd.rb = (const float*)(net->dev_blob + o.rb_off); }
+                if (o.has_fw) { hd.fw = (const float*)(net->dev_blob + o.fw_off); hd.fb = (const float*)(net->dev_blob + o.fb_off); }
+                rc = gdt_k_pool_head(tptr(o.in), f32, n, ti.H, ti.W, ti.C, hd, g, (float*)(ws + stp.aux_off[0]), (float*)outputs[o.slot], st);
                 break;
             }
             case OP_OUT_NCHW: {

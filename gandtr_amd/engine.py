@@ -4,7 +4,7 @@
 (names as produced by the reference modules, see gandtr_amd/tools/synth.py) into layer graphs:
 
   build_generator   ResnetGenerator            mdir/components/model/network/p2p_networks.py:269-313, :454-506
-  build_embedder    ImageRetrievalNet (GeM)    mdir/external/cirtorch/networks/imageretrievalnet.py:101-123, :185-190
+  build_embedder    ImageRetrievalNet          mdir/external/cirtorch/networks/imageretrievalnet.py:101-123, :185-190
   build_hed         HedInterpolation           mdir/components/model/network/hed.py:30-83
   build_rcf         RCF                        mdir/components/model/network/rcf.py:28-155
 
@@ -139,6 +139,19 @@ class HipNet:
         _hip.check(self.lib.gdt_net_gem_l2n(self.handle, x, float(p), eps_gem, eps_l2, ctypes.byref(out)))
         return out.value
 
+    POOL_KINDS = {"mac": 0, "spoc": 1, "gem": 2, "gemmp": 3}         # include/gandtr_hip.h, gdt_net_pool_head
+
+    def pool_head(self, x, kind, p=None, eps=1e-6, aggregate=0, levels=3, rwhiten=None, whiten=None, eps_l2=1e-6):
+        """gdt_net_pool_head: pooling ``kind`` (global, ``aggregate`` 1 = R-MAC, 2 = regional over ``levels`` levels) -> l2n -> optional final
+        whitening + l2n; ``rwhiten`` / ``whiten`` = (weight [D][D], bias [D]) of the nn.Linear layers or None"""
+        pa = _f32(p).reshape(-1) if p is not None else None
+        rw, rb = (_f32(rwhiten[0]), _f32(rwhiten[1])) if rwhiten is not None else (None, None)
+        fw, fb = (_f32(whiten[0]), _f32(whiten[1])) if whiten is not None else (None, None)
+        out = ctypes.c_int()
+        _hip.check(self.lib.gdt_net_pool_head(self.handle, x, self.POOL_KINDS[kind], _ptr(pa), 0 if pa is None else pa.size, float(eps), int(aggregate),
+                                              int(levels), _ptr(rw), _ptr(rb), _ptr(fw), _ptr(fb), float(eps_l2), ctypes.byref(out)))
+        return out.value
+
     def output_nchw(self, x, bias=None):
         out = ctypes.c_int()
         b = _f32(bias)
@@ -216,6 +229,12 @@ class HipNet:
         c = (ctypes.c_int * 12)()
         _hip.check(self.lib.gdt_net_plan_summary(self.handle, n, rh, rw, int(bool(resize)), c, 12))
         return dict(zip(self.PLAN_KEYS, list(c)))
+
+    def head_launches(self, n, rh, rw):
+        """(launches of the net's pool-head ops, launches among them that read the feature map) for a geometry -- the planner's count, no device call"""
+        c = (ctypes.c_int * 14)()
+        _hip.check(self.lib.gdt_net_plan_summary(self.handle, n, rh, rw, 0, c, 14))
+        return c[12], c[13]
 
     def flops(self, n, rh, rw):
         f = ctypes.c_double()
@@ -585,13 +604,31 @@ def embedder_arch(sd):
     return "resnet" if "features.4.0.conv1.weight" in sd else "vgg16"
 
 
-def build_embedder(sd, device, in_affine=None, feature_tap=False, precision="f16", finalize=True):
-    """GeM embedder (ImageRetrievalNet.forward with lwhiten=None, whiten=None).  External output 0: descriptors as a
-    row-major [N][D] fp32 matrix (the reference returns its transpose view, D x N)."""
+def build_embedder(sd, device, in_affine=None, feature_tap=False, precision="f16", finalize=True, head=None):
+    """ImageRetrievalNet.forward as a HIP graph.  External output 0: descriptors as a row-major [N][D] fp32 matrix (the reference returns its
+    transpose view, D x N).
+
+    ``head`` None: the hub configuration -- GeM, no whitening layers (lwhiten=None, whiten=None) -- on its own op (gem_l2n).  Otherwise the tuple
+    ``ImageRetrievalNet._hip_head`` gives: (pooling "mac" | "spoc" | "gem" | "gemmp" | "rmac", regional, L, eps of the pooling, local whitening, final
+    whitening); the layers' weights are the reference's state-dict entries (``lwhiten.*``, ``pool.p`` / ``pool.rpool.p``, ``pool.whiten.*``,
+    ``whiten.*``).  The local whitening is a 1x1 conv with bias and no ReLU in front of the pool; everything behind the map is one pool_head op."""
     net = HipNet(device, precision)
     x = net.input(3, scale=in_affine[0], shift=in_affine[1]) if in_affine is not None else net.input(3)
     f = _resnet_trunk(net, x, sd) if embedder_arch(sd) == "resnet" else _vgg16_trunk(net, x, sd)
-    net.out_slot = net.gem_l2n(f, float(sd["pool.p"].reshape(-1)[0]))
+    if head is None:
+        net.out_slot = net.gem_l2n(f, float(sd["pool.p"].reshape(-1)[0]))
+    else:
+        kind, regional, levels, eps, local_whitening, whitening = head
+        if regional and kind == "rmac":
+            raise NotImplementedError("regions of R-MAC regions are not on the HIP path")
+        if local_whitening:
+            w = sd["lwhiten.weight"]
+            f = net.conv(f, w.reshape(w.shape[0], w.shape[1], 1, 1), sd["lwhiten.bias"], relu=False)
+        p = sd.get("pool.rpool.p" if regional else "pool.p") if kind in ("gem", "gemmp") else None
+        rwhiten = (sd["pool.whiten.weight"], sd["pool.whiten.bias"]) if regional and "pool.whiten.weight" in sd else None
+        whiten = (sd["whiten.weight"], sd["whiten.bias"]) if whitening else None
+        net.out_slot = net.pool_head(f, "mac" if kind == "rmac" else kind, p=p, eps=eps, aggregate=2 if regional else (1 if kind == "rmac" else 0),
+                                     levels=levels or 3, rwhiten=rwhiten, whiten=whiten)
     net.feature_slot = net.output_nchw(f) if feature_tap else None
     if finalize:
         net.finalize()

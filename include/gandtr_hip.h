@@ -108,6 +108,20 @@ int gdt_net_maxpool_ceil(gdt_net* net, int in_tensor, int kernel, int stride, in
  * row-major, i.e. the memory the reference's `o.permute(1,0)` view aliases (imageretrievalnet.py:123). */
 int gdt_net_gem_l2n(gdt_net* net, int in_tensor, float p, float eps_gem, float eps_l2, int* out_slot);
 
+/* The complete descriptor head of ImageRetrievalNet.forward (imageretrievalnet.py:115-123) behind `in_tensor`: pool -> l2n -> (whiten -> l2n).
+ *   kind       0 max (MAC), 1 mean (SPoC), 2 GeM (p[0], n_p = 1), 3 GeM with one exponent per channel (GeMmp, n_p = channels); eps: GeM's clamp
+ *   aggregate  0: the pooling of the whole map.
+ *              1: R-MAC (LF.rmac, kind 0): the maxima of the whole map and of every region of `levels` levels, each l2-normalised, summed.
+ *              2: regional pooling (Rpool.forward, layers/pooling.py:87-110): the pooling of the whole map and of every region, each
+ *                 l2-normalised, through the regional whitening rw / rb (nn.Linear, [D][D] row-major and [D]; NULL: none) and l2-normalised
+ *                 again, summed, l2-normalised.
+ *   fw / fb    the final whitening (nn.Linear) with its l2n, NULL: none.  eps_l2: the eps of every l2n (x / (||x|| + eps)).
+ * levels: 1..3 (cirtorch's L = 3).  The regions of a map size are those of gdt_rpool_regions.  All regions are pooled in ONE pass over the map; the
+ * number of launches depends on the layers present, never on the batch or the number of regions; the whitening layers run in fp32 in every
+ * precision mode.  External output: fp32 [N][D] row-major, as gdt_net_gem_l2n. */
+int gdt_net_pool_head(gdt_net* net, int in_tensor, int kind, const float* p, int n_p, float eps, int aggregate, int levels, const float* rw,
+                      const float* rb, const float* fw, const float* fb, float eps_l2, int* out_slot);
+
 /* Feature tap: internal fp16 NHWC tensor -> external fp32 NCHW (+ optional per-channel bias), p2p_networks.py:316-334 */
 int gdt_net_output_nchw(gdt_net* net, int in_tensor, const float* bias, int* out_slot);
 
@@ -179,8 +193,9 @@ int gdt_net_flops(gdt_net* net, int n, int rh, int rw, double* flops);
  * launch, [2] 3x3 + expand launches, [3] of those with the next block's reduce conv chained in, [4] projection shortcuts folded into their expand conv, [5] InstanceNorms
  * applied by their consumer's staging, [6] max-pools written by their producer, [7] 1 if the stem reads the caller's image itself (resize = 0 only), [8] transposed convs as
  * one fused-phase launch, [9] stride-2 convs as the shift form.  n_counts >= 10; with n_counts >= 12 also [10] dilated convs (gdt_net_conv_dilated) and
- * [11] of those on any special form (a patch kernel, a fused launch): 0 -- dilation runs on the generic implicit-GEMM kernels only.  (Diagnostics / tests;
- * no reference counterpart.) */
+ * [11] of those on any special form (a patch kernel, a fused launch): 0 -- dilation runs on the generic implicit-GEMM kernels only; with n_counts >= 14 also
+ * [12] the launches of the pool-head ops (gdt_net_pool_head: fixed by the layers present, whatever the batch and the number of regions) and [13] those
+ * among them that read the feature map (one per op).  (Diagnostics / tests; no reference counterpart.) */
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts);
 
 /* Per-op timing for bench.py's roofline line: when enabled, gdt_net_forward records HIP events on the caller's stream
@@ -221,6 +236,18 @@ int gdt_gem_l2n(const float* fmap, int n, int d, int h, int w, float p, float ep
 
 /* x / (||x||_2 + eps) over rows of a [N][D] matrix (cirtorch layers/functional.py:130-131) */
 int gdt_l2n_rows(const float* x, float* y, int n, int d, float eps, void* stream);
+
+/* The boxes LF.roipool / LF.rmac pool an h x w map over (cirtorch layers/functional.py:26-123): the whole map first, then the regions of levels
+ * 1..levels in the reference's loop order (level, row, column), four ints each: y0, x0, height, width.  Host arithmetic only (float32, as the
+ * reference's tensors: a double or integer restatement puts some regions one pixel off), no device call.  count: the number of boxes (2 to 51 for
+ * levels = 3); capacity: boxes the buffer holds, 0 to ask for the count alone. */
+int gdt_rpool_regions(int h, int w, int levels, int* boxes, int capacity, int* count);
+
+/* The pooling kernel of gdt_net_pool_head on its own: fmap is an NHWC map [n][h][w][d] on the device (f32 = 0: fp16, 1: fp32; d % 64 == 0), out fp32
+ * [n][R][d] with R = the boxes of gdt_rpool_regions(h, w, levels) (levels = 0: the whole map alone, R = 1; at most 64).  kind / p / eps as in
+ * gdt_net_pool_head; p_channels: d exponents on the device (kind 3).  One pass over the map; max is exact, the sums have a fixed order. */
+int gdt_pool_regions(const void* fmap, int f32, int n, int h, int w, int d, int kind, float p, const float* p_channels, float eps, int levels,
+                     float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Retrieval scoring ("next" row of SURVEY.md section 8f: the consumer of the gathered descriptors)
