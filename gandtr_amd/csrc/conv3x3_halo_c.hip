@@ -306,7 +306,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
         smem[E_OFF + (stage_off ? HALO_ROWS_PAD : 0) + row] = (char)(127 + ex - 13);      // (the row's 8 lanes store the same byte)
     };
 
-    // ---- weights, streamed L2 -> registers in MFMA fragment order.  Grouped layouts (net.hip pack_mx): the four 32-channel
+    // ---- weights, streamed L2 -> registers in MFMA fragment order.  Grouped layouts (net_build.hip pack_mx): the four 32-channel
     // fragments a wave needs for one k-substep are contiguous, so one scalar base + 32-bit lane offset + an immediate (j * 1 KB)
     // addresses each of them (the scalar-base form of global_load: no 64-bit vector address arithmetic):
     //   w_cfrag [cout/128][K/16][4][64 lanes][16 B]    wmx_a [cout/128][K/32][4][64][16 B]    wmx_b [..][64][8 B]    wmx_s [..][64][4 B]

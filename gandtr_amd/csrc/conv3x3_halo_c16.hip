@@ -307,7 +307,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
 #undef GDT_PIN8
     };
 
-    // ---- weights, streamed L2 -> registers in fragment order (net.hip pack_mx16): per 64 output channels (a wave's slice)
+    // ---- weights, streamed L2 -> registers in fragment order (net_build.hip pack_mx16): per 64 output channels (a wave's slice)
     //   w_c16 [cout/64][K/32][4 blocks][64 lanes][16 B]: lane (n, g) = W[cout block * 16 + n][k = 32 step + 8 g ..+7]
     //   wmx16_a [cout/64][K/64][4][64][16 B] + wmx16_b [..][8 B] + wmx16_s [..][4 B]: lane (n, blk): 32 e2m3 values + E8M0 scale of
     //   blk 0: fp16(w) of k 0-31, 1: w - fp16(w) of k 0-31, 2 / 3: the same of k 32-63 (of the 64 k-values of a (tap, chunk))

@@ -7,7 +7,7 @@
 // take at 128 B/clk -- and it pays a workgroup barrier per step because the weight tile is shared through LDS.
 //
 // Here only the activations go through LDS (they are reused by the 9 taps).  The weights are pre-packed on the host in MFMA
-// B-fragment order ([cout/32][K/16][lane][8], see net.hip) so that one wave-wide 16-byte load is a contiguous 1 KB line
+// B-fragment order ([cout/32][K/16][lane][8], see net_build.hip) so that one wave-wide 16-byte load is a contiguous 1 KB line
 // fetch that lands directly in the B operand registers of v_mfma_f32_32x32x16_f16; each register is re-loaded for the next
 // step right after its last MFMA of the current step has issued, a full step (~2000 cycles) ahead of its use.
 //   * LDS traffic per step: 128 KB of A fragments (was 224 KB), no weight stages in LDS;
@@ -84,7 +84,7 @@ struct TileAt { int n, y0, x0, tile_m, tile_n; bool valid; };
 // the ResnetBlock output folded into the next block's first conv).
 // CT = true: ConvTranspose2d(k3, s2, p1, op1) (p2p_networks.py:289-300) on the same machinery.  The 16x16 patch is a patch of
 // INPUT pixels with a 17x17 halo (one extra row / column, zero past the image); the "taps" are the four input shifts (dy, dx);
-// the GEMM columns are the four sub-pixel phases x cout in the paired order of gdt_ctf_column() (weights: Op::ctf in net.hip),
+// the GEMM columns are the four sub-pixel phases x cout in the paired order of gdt_ctf_column() (weights: Op::ctf in net_internal.h),
 // and a wave skips the (shift, phase) blocks that are all zero; the epilogue scatters column blocks to output pixels
 // (2y + py, 2x + px).  MODE 3 (norm + residual, no write-back) exists for this form: y9 = y8 + IN(.) feeds only the first
 // transposed conv.

@@ -338,7 +338,7 @@ bool gdt_conv_halo_x3_eligible(const ConvLaunch& d) {
 }
 
 // FORM 1 (a tap table inside the 3 x 3 window, strided output: the phase launches of a transposed conv) and FORM 2 (d.x3_form == 2: stride-2 3x3 conv over the
-// virtual space-to-depth view, net.hip s2_geometry); plain InstanceNorm (+ReLU) folding only
+// virtual space-to-depth view, net_plan.hip s2_geometry); plain InstanceNorm (+ReLU) folding only
 bool gdt_conv_halo_x3_taps_eligible(const ConvLaunch& d) {
     const char* e = getenv("GDT_CONV_HALO_X3_FORMS");           // 0 off (A/B: the generic GEMM), 1 auto, 2 force (read per call)
     const int mode = e ? atoi(e) : 1;

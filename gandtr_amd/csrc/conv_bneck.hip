@@ -545,7 +545,7 @@ int launch(const BneckLaunch& d, hipStream_t stream) {
 
 }  // namespace
 
-// Eligible: the three convs of an identity Bottleneck (checked by the planner in net.hip) with (C, MID) = (256, 64) or (512, 128), maps that
+// Eligible: the three convs of an identity Bottleneck (checked by the planner in net_plan.hip) with (C, MID) = (256, 64) or (512, 128), maps that
 // the patches tile exactly, enough patches to fill the chip, offsets within 32 bits.
 bool gdt_bneck_eligible(int cin, int C, int mid, int N, int H, int W) {
     const char* e = getenv("GDT_CONV_BNECK");          // 0: off (read at plan time, once per net and geometry: A/B inside one process)

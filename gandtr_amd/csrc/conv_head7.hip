@@ -53,7 +53,7 @@ __device__ __forceinline__ void lds_barrier() {
 
 // F32IN ("f16c" precision mode): the input is the fp32 NHWC tensor of that mode; the halo goes through registers (load, folded
 // InstanceNorm + ReLU in fp32, split into fp16(a) and the residual) instead of LDS-DMA + in-place normalisation.  With the
-// block-scaled correction operands present (d.wmx_a: packed by net.hip for the f16c head) the product is compensated like the other
+// block-scaled correction operands present (d.wmx_a: packed by net_build.hip for the f16c head) the product is compensated like the other
 // layers of the mode (conv3x3_halo_c.hip):  a w ~= a_hi w_hi (fp16 MFMA) + [a_lo | a_hi]_fp4 . [w_hi | w_lo]_fp6 (one MX MFMA per 32
 // k-values).  LDS holds one plane at a time -- two workgroups per CU must keep fitting -- so the fp4 words (two dwords per piece, 34
 // registers per thread) wait in registers while the fp16 plane is consumed, are then written over it, and a second, shorter MFMA
