@@ -77,6 +77,7 @@ SIGNATURES = {
     "gdt_net_forward_levels": (c_int, [c_void_p, POINTER(Level), c_int, c_void_p]),
     "gdt_net_levels_joined": (c_int, [c_void_p, _IP]),
     "gdt_net_set_group_factor": (c_int, [c_void_p, c_float]),
+    "gdt_plan_knob_name": (c_char_p, [c_int]),
     "gdt_net_flops": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_double)]),
     "gdt_net_set_profiling": (c_int, [c_void_p, c_int]),
     "gdt_net_profile_read": (c_int, [c_void_p, c_int, _IP, _IP, _IP, POINTER(c_double), POINTER(c_double)]),
@@ -153,6 +154,16 @@ def load():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def plan_knobs():
+    """Names of the environment knobs the library reads every time it plans a geometry (gdt_plan_knob_name), in its order."""
+    lib, names = load(), []
+    while True:
+        name = lib.gdt_plan_knob_name(len(names))
+        if name is None:
+            return tuple(names)
+        names.append(name.decode())
 
 
 def check(rc):

@@ -269,39 +269,39 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_rb_multi_kernel(const MultiConv
     conv1x1_rb_body<RES, DEPTH, TM, CAT>(m.lev[l], m.vblocks[l], blockIdx.x - m.prefix[l], m.prefix[l + 1] - m.prefix[l]);
 }
 
+GDT_KNOB_LATCHED(knob_mode, "GDT_CONV_1X1", 1)               // 0 off, 2 force
+GDT_KNOB_LATCHED(knob_min_tiles, "GDT_CONV_1X1_MIN_TILES", 64)   // (batch 2-4 @1024^2: +7 % over 512; multi-scale config +3 %)
+GDT_KNOB_LATCHED(knob_cat_mode, "GDT_CONV_1X1_CAT", 1)       // 0 off
+GDT_KNOB_LATCHED(knob_wpc, "GDT_CONV_1X1_WPC", 3)            // cap on the workgroups per CU
+GDT_KNOB_LATCHED(knob_rev, "GDT_CONV_1X1_REV", 1)            // rows walked from the end: 1 reduce convs, 2 expand convs, 3 both, 0 none
+GDT_KNOB_LATCHED(knob_max_depth, "GDT_CONV_1X1_DEPTH", 4)
+GDT_KNOB_LATCHED(knob_wide, "GDT_CONV_1X1_WIDE", 1)          // 0: no 128 x 256 tiles
+GDT_KNOB_LATCHED(knob_wide_min, "GDT_CONV_1X1_WIDE_MIN", 256)
+
 template <bool RES, int DEPTH, int TM, bool CAT = false>
 int launch_1x1(const ConvLaunch* dl, int L, hipStream_t stream) {
     const ConvLaunch& d = dl[0];
-    static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
-    int slots = 0;
-    {
-        const int rc = gdt_per_device(per_dev, slots, [](int, int cus, int& v) {
-            int per_cu = 0;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv1x1_rb_kernel<RES, DEPTH, TM, CAT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv1x1_rb_multi_kernel<RES, DEPTH, TM, CAT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-            GDT_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv1x1_rb_kernel<RES, DEPTH, TM, CAT>, NT, LDS_BYTES));
-            static const int cap = [] { const char* e = getenv("GDT_CONV_1X1_WPC"); return e ? atoi(e) : 3; }();
-            if (per_cu < 1) per_cu = 1;
-            if (per_cu > cap) per_cu = cap;
-            v = cus / 8 * 8 * per_cu;                 // a multiple of 8: a workgroup's tiles stay on its XCD
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
+    using K = GdtKernel<conv1x1_rb_kernel<RES, DEPTH, TM, CAT>, (int)LDS_BYTES>;
+    using KM = GdtKernel<conv1x1_rb_multi_kernel<RES, DEPTH, TM, CAT>, (int)LDS_BYTES>;
+    int slots = 0;           // the figure cached with the single-geometry kernel: workgroup slots of the chip
+    GDT_CHECK(K::figure(slots, [](int cus, int& v) {
+        int per_cu = 0;
+        GDT_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv1x1_rb_kernel<RES, DEPTH, TM, CAT>, NT, LDS_BYTES));
+        if (per_cu < 1) per_cu = 1;
+        if (per_cu > knob_wpc()) per_cu = knob_wpc();
+        v = cus / 8 * 8 * per_cu;                 // a multiple of 8: a workgroup's tiles stay on its XCD
+        return GDT_OK;
+    }));
     if (L > 1) {
+        int unused = 0;
+        GDT_CHECK(KM::figure(unused));
         MultiConv m;
         m.nlev = L;
         for (int l = 0; l < L; ++l) { m.lev[l] = dl[l]; m.vblocks[l] = gdt_grid_for_tiles((dl[l].M + BM - 1) / BM, dl[l].CoutPad / (TM == 4 ? 256 : 128)); }
-        const int grid = gdt_multi_partition(m.prefix, m.vblocks, L, slots);
-        hipLaunchKernelGGL((conv1x1_rb_multi_kernel<RES, DEPTH, TM, CAT>), dim3(grid), dim3(NT), LDS_BYTES, stream, m);
-        GDT_CHECK_HIP(hipGetLastError());
-        return GDT_OK;
+        return KM::launch(gdt_multi_partition(m.prefix, m.vblocks, L, slots), NT, stream, m);
     }
     const int vblocks = gdt_grid_for_tiles((d.M + BM - 1) / BM, d.CoutPad / (TM == 4 ? 256 : 128));
-    const int grid = vblocks < slots ? vblocks : slots;
-    hipLaunchKernelGGL((conv1x1_rb_kernel<RES, DEPTH, TM, CAT>), dim3(grid), dim3(NT), LDS_BYTES, stream, d, vblocks);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    return K::launch(vblocks < slots ? vblocks : slots, NT, stream, d, vblocks);
 }
 
 }  // namespace
@@ -309,7 +309,7 @@ int launch_1x1(const ConvLaunch* dl, int L, hipStream_t stream) {
 // Eligible: a dense 1x1 stride-1 conv in fp16 NHWC with fragment-ordered weights, Cin % 64 == 0, Cout in whole 128-column tiles,
 // an even number of K-steps (or a single one), no fused statistics / input transform, 32-bit element offsets, enough tiles.
 bool gdt_conv_1x1_rb_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_1X1"); return e ? atoi(e) : 1; }();   // 0 off, 2 force
+    const int mode = knob_mode();
     if (mode == 0 || !d.w_frag || d.out_f32 || !d.out) return false;
     if (d.ntaps != 1 || d.sy != 1 || d.sx != 1 || d.dy0 != 0 || d.dx0 != 0 || d.osy != 1 || d.osx != 1 || d.ooy != 0 || d.oox != 0) return false;
     if (d.OHg != d.OH || d.OWg != d.OW || d.OH != d.H || d.OW != d.W) return false;
@@ -317,24 +317,22 @@ bool gdt_conv_1x1_rb_eligible(const ConvLaunch& d) {
     const int nk = d.Kpad / 64;
     if (nk != 1 && nk % 2 != 0) return false;
     if (d.stats || d.in_norm || d.in_res || d.in_out || d.phase_cout || d.pool2) return false;
-    if ((long)d.M * d.Cin >= (1L << 32) || (long)d.M * d.Cout >= (1L << 32)) return false;
+    if (!gdt_offsets_fit(1, 1, d.M, d.Cin) || !gdt_offsets_fit(1, 1, d.M, d.Cout)) return false;
     if (mode == 2) return true;
-    static const int min_tiles = [] { const char* e = getenv("GDT_CONV_1X1_MIN_TILES"); return e ? atoi(e) : 64; }();     // (batch 2-4 @1024^2: +7 % over 512; multi-scale config +3 %)
-    return (long)((d.M + BM - 1) / BM) * (d.CoutPad / 128) >= min_tiles;
+    return gdt_enough_tiles((d.M + BM - 1) / BM, d.CoutPad / 128, knob_min_tiles());
 }
 
 // K-concatenated form: both operands in whole 64-channel K-steps, an even number of them in total, 256-wide tiles, no residual read (the shortcut
 // IS the second operand), 32-bit element offsets into both inputs
 bool gdt_conv_1x1_cat_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_1X1_CAT"); return e ? atoi(e) : 1; }();   // 0 off
-    if (mode == 0 || !d.in2 || !d.w_frag || d.out_f32 || !d.out || d.res) return false;
+    if (knob_cat_mode() == 0 || !d.in2 || !d.w_frag || d.out_f32 || !d.out || d.res) return false;
     if (d.ntaps != 1 || d.sy != 1 || d.sx != 1 || d.dy0 != 0 || d.dx0 != 0 || d.osy != 1 || d.osx != 1 || d.ooy != 0 || d.oox != 0) return false;
     if (d.OHg != d.OH || d.OWg != d.OW || d.OH != d.H || d.OW != d.W) return false;
     if (d.Cin % 64 != 0 || d.in2_cin % 64 != 0 || d.Kpad != d.Cin + d.in2_cin || (d.Kpad / 64) % 2 != 0 || d.CoutPad % 256 != 0 || d.CoutPad > MAX_COUT || d.Cout % 8 != 0) return false;
     if (d.in2_stride < 1 || d.in2_stride > 2 || (d.OH - 1) * d.in2_stride >= d.in2_h || (d.OW - 1) * d.in2_stride >= d.in2_w) return false;
     if (d.stats || d.in_norm || d.in_res || d.in_out || d.phase_cout || d.pool2) return false;
-    if ((long)d.M * d.Cin >= (1L << 32) || (long)d.M * d.Cout >= (1L << 32) || (long)d.N * d.in2_h * d.in2_w * d.in2_cin >= (1L << 32)) return false;
-    return (long)((d.M + BM - 1) / BM) * (d.CoutPad / 128) >= 64;
+    if (!gdt_offsets_fit(1, 1, d.M, d.Cin) || !gdt_offsets_fit(1, 1, d.M, d.Cout) || !gdt_offsets_fit(d.N, d.in2_h, d.in2_w, d.in2_cin)) return false;
+    return gdt_enough_tiles((d.M + BM - 1) / BM, d.CoutPad / 128, 64);
 }
 
 // `dl[0 .. L)`: the same conv on L independent geometries (the levels of a pyramid) as ONE launch; the instantiation is chosen for the levels together
@@ -343,7 +341,7 @@ int gdt_launch_conv_1x1_rb_levels(const ConvLaunch* dl_in, int L, hipStream_t st
     // written front to back, so the rows written last -- the ones still in the 256 MB Infinity Cache -- are read first (and the 3x3
     // conv that follows, front to back, starts on the rows THIS launch wrote last).  ResNet-101 batch 32: 1860 -> 1882 descriptors/s;
     // reversing the expand convs instead gives the same, reversing both nothing (GDT_CONV_1X1_REV: 1 reduce, 2 expand, 3 both, 0 none).
-    static const int rev = [] { const char* e = getenv("GDT_CONV_1X1_REV"); return e ? atoi(e) : 1; }();
+    const int rev = knob_rev();
     GDT_REQUIRE(L >= 1 && L <= GDT_MAX_LEVELS, "1..4 geometries per launch");
     ConvLaunch dl[GDT_MAX_LEVELS];
     long wide_tiles = 0;
@@ -357,13 +355,10 @@ int gdt_launch_conv_1x1_rb_levels(const ConvLaunch* dl_in, int L, hipStream_t st
     const ConvLaunch& d = dl[0];
     if (d.in2) return launch_1x1<false, 2, 4, true>(dl, L, stream);
     const int nk = d.Kpad / 64;
-    static const int max_depth = [] { const char* e = getenv("GDT_CONV_1X1_DEPTH"); return e ? atoi(e) : 4; }();
-    static const int wide = [] { const char* e = getenv("GDT_CONV_1X1_WIDE"); return e ? atoi(e) : 1; }();
     if (d.res) return nk > 1 ? launch_1x1<true, 2, 2>(dl, L, stream) : launch_1x1<true, 1, 2>(dl, L, stream);
     // (the 128 x 256 tile halves the weight stream per MFMA but also the number of workgroups: below ~one per CU the 128 x 128 tile fills the chip better)
-    static const int wide_min = [] { const char* e = getenv("GDT_CONV_1X1_WIDE_MIN"); return e ? atoi(e) : 256; }();
-    if (wide && nk > 1 && d.CoutPad % 256 == 0 && wide_tiles >= wide_min) return launch_1x1<false, 2, 4>(dl, L, stream);
-    if (nk % 4 == 0 && max_depth >= 4) return launch_1x1<false, 4, 2>(dl, L, stream);
+    if (knob_wide() && nk > 1 && d.CoutPad % 256 == 0 && wide_tiles >= knob_wide_min()) return launch_1x1<false, 2, 4>(dl, L, stream);
+    if (nk % 4 == 0 && knob_max_depth() >= 4) return launch_1x1<false, 4, 2>(dl, L, stream);
     return nk > 1 ? launch_1x1<false, 2, 2>(dl, L, stream) : launch_1x1<false, 1, 2>(dl, L, stream);
 }
 

@@ -542,60 +542,51 @@ __global__ __launch_bounds__(Geo<PH>::NT, PH == 16 ? 1 : 2) void conv3x3_expand_
 
 // Eligible: 3x3 / stride 1 / zero pad 1, 256 -> 256 channels with fragment-ordered weights and a bias (BatchNorm folded), ReLU; expand 1x1 to a multiple of 256
 // channels with bias, residual and ReLU; enough patches for one per CU; at most 15 % of the patch area hanging over the image.
-static int xexp_patch_height() {
-    static const int ph = [] { const char* e = getenv("GDT_XEXP_PH"); return e ? atoi(e) : 8; }();       // 16: one 512-thread workgroup per CU on 16 x 16 patches
-    return ph == 16 ? 16 : 8;
-}
+GDT_KNOB_LATCHED(knob_ph, "GDT_XEXP_PH", 8)                  // 16: one 512-thread workgroup per CU on 16 x 16 patches
+GDT_KNOB_LATCHED(knob_min_tiles, "GDT_XEXP_MIN_TILES", 256)  // in 16 x 16 patches' worth of work
+GDT_KNOB_LATCHED(knob_group_min_tiles, "GDT_XEXP_GROUP_MIN_TILES", 192)
+GDT_KNOB_LIVE(knob_chain, XEXP_CHAIN, 1)                     // 0: the reduce conv stays its own launch (live: a net reads it when it plans a geometry)
+GDT_KNOB_LATCHED(knob_cu_limit, "GDT_CU_LIMIT", 0)           // dev: persistent grid on part of the chip (concurrent-stream experiments)
+GDT_KNOB_LATCHED(knob_stagger_us, "GDT_XEXP_STAGGER_US", 30)
+static int xexp_patch_height() { return knob_ph() == 16 ? 16 : 8; }
 
 bool gdt_conv3x3_expand_eligible(const ConvLaunch& d) {
     if (!d.w_frag || !d.x_w_frag || !d.bias || !d.x_bias || !d.res || !d.out || d.out_f32) return false;
     if (d.Cin != 256 || d.Cout != 256 || d.CoutPad != 256 || d.x_cout < 256 || d.x_cout % 256 != 0) return false;
     if (d.ntaps != 9 || d.sy != 1 || d.sx != 1 || d.pad_reflect || d.in_norm || d.in_res || d.in_out || d.stats || d.pool2 || d.phase_cout || !d.relu) return false;
-    if ((long)d.N * d.H * d.W * d.x_cout >= (1L << 32)) return false;                                  // 32-bit element offsets
+    if (!gdt_offsets_fit(d.N, d.H, d.W, d.x_cout)) return false;
     // (both figures for the patch height that WILL be launched: PH x 16 patches, 16 / PH workgroups per CU -- GDT_XEXP_MIN_TILES counts 16 x 16 patches' worth of work)
     const int ph = xexp_patch_height();
-    const long tiles = (long)d.N * ((d.W + 15) / 16) * ((d.H + ph - 1) / ph);
-    const double useful = (double)d.H * d.W / ((double)((d.H + ph - 1) / ph * ph) * ((d.W + 15) / 16 * 16));
-    static const int min_tiles = [] { const char* e = getenv("GDT_XEXP_MIN_TILES"); return e ? atoi(e) : 256; }();
+    const long tiles = gdt_patches(d.N, d.H, d.W, ph);
+    const bool useful = gdt_useful_area(d.H, d.W, ph) >= GDT_MIN_USEFUL_AREA;
     if (d.group_factor > 1.f) {
         // one of several geometries in flight together (pyramid levels on side streams): what has to fill the chip is the group.  Measured, GeM-ResNet-101 hub
         // scales, levels concurrent: 8 x 1024^2 (128 + 72 + 32 patches of 16 x 16) 7.40 -> 6.72 ms with the fused launches, 4 x 1024^2 (116 patches) 3.88 -> 4.40,
         // 2 x 3.16 -> 3.72, 1 x 2.85 -> 3.15: fused from ~200 patches in the group, and never below 16 of its own
-        static const int group_min = [] { const char* e = getenv("GDT_XEXP_GROUP_MIN_TILES"); return e ? atoi(e) : 192; }();
-        return (double)tiles * ph * d.group_factor >= (double)group_min * 16 && tiles * ph >= 16 * 16 && useful >= 0.85;
+        return (double)tiles * ph * d.group_factor >= (double)knob_group_min_tiles() * 16 && tiles * ph >= 16 * 16 && useful;
     }
-    return tiles * ph >= (long)min_tiles * 16 && useful >= 0.85;
+    return gdt_enough_tiles(tiles, ph, knob_min_tiles() * 16) && useful;
 }
 
 // CHAIN form (phase C): the next block's reduce conv -- a 1x1 conv x_cout = 1024 -> 256 with bias and ReLU on the tensor this launch writes
 bool gdt_conv3x3_expand_chain_eligible(const ConvLaunch& d) {
-    const char* e = getenv("GDT_XEXP_CHAIN");                  // 0: the reduce conv stays its own launch (read when a net plans a geometry: A/B inside one process)
-    return !(e && atoi(e) == 0) && xexp_patch_height() == 8 && d.x_cout == 1024 && gdt_conv3x3_expand_eligible(d);
+    return knob_chain() != 0 && xexp_patch_height() == 8 && d.x_cout == 1024 && gdt_conv3x3_expand_eligible(d);
 }
 
 template <int PH, bool CHAIN = false>
 static int launch_xexp(const ConvLaunch& d_in, hipStream_t stream) {
     using G = Geo<PH>;
     ConvLaunch d = d_in;
-    const int tiles = d.N * ((d.W + 15) / 16) * ((d.H + PH - 1) / PH);
-    static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
+    const int tiles = (int)gdt_patches(d.N, d.H, d.W, PH);
+    using K = GdtKernel<conv3x3_expand_rb_kernel<PH, CHAIN>, G::LDS_BYTES>;
     int cus = 0;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_expand_rb_kernel<PH, CHAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
+    GDT_CHECK(K::figure(cus));
     const int vblocks = gdt_grid_for_tiles(tiles, 1), slots = cus * (PH == 16 ? 1 : 2);
     int grid = vblocks < slots ? vblocks : slots;
-    static const int cu_limit = [] { const char* e = getenv("GDT_CU_LIMIT"); return e ? atoi(e) : 0; }();      // dev: persistent grid on part of the chip (concurrent-stream experiments)
-    if (cu_limit > 0 && grid > cu_limit) grid = cu_limit;
-    static const int stagger = [] { const char* e = getenv("GDT_XEXP_STAGGER_US"); return e ? atoi(e) : 30; }();
+    if (knob_cu_limit() > 0 && grid > knob_cu_limit()) grid = knob_cu_limit();
     // a workgroup with a single patch has no steady state to de-phase, the delay is then a plain loss: GeM-ResNet-101 hub pyramid, 8 x 1024^2 per call (256 + 144 + 64
     // patches) 6.72 -> 6.36 ms without it, 16 x 12.87 -> 12.69
-    d.stagger_us = tiles > slots ? stagger : 0;
+    d.stagger_us = tiles > slots ? knob_stagger_us() : 0;
 #ifdef GDT_XEXP_STAMP
     constexpr int W = G::WAVES;
     static unsigned long long* stamp_buf = nullptr;
@@ -603,7 +594,7 @@ static int launch_xexp(const ConvLaunch& d_in, hipStream_t stream) {
     if (!stamp_buf) GDT_CHECK_HIP(hipMalloc((void**)&stamp_buf, (size_t)cus * 2 * W * 8 * sizeof(unsigned long long)));
     GDT_CHECK_HIP(hipMemsetAsync(stamp_buf, 0, (size_t)cus * 2 * W * 8 * sizeof(unsigned long long), stream));
     d.stamp_out = stamp_buf;
-    hipLaunchKernelGGL((conv3x3_expand_rb_kernel<PH, CHAIN>), dim3(grid), dim3(G::NT), G::LDS_BYTES, stream, d, tiles);
+    GDT_CHECK(K::launch(grid, G::NT, stream, d, tiles));
     if (++stamp_calls % 100 < 4) {
         GDT_CHECK_HIP(hipStreamSynchronize(stream));
         std::vector<unsigned long long> h((size_t)grid * W * 8);
@@ -616,11 +607,10 @@ static int launch_xexp(const ConvLaunch& d_in, hipStream_t stream) {
         fprintf(stderr, "[xexp stamp] PH %d chain %d tiles/wave %.1f; per tile: phase A %.0f, hand-over %.0f, phase B k-loops %.0f, phase B epilogues %.0f, phase C %.0f, next-tile staging %.0f (per wave) cycles; total per wave %.0f\n",
                 PH, (int)CHAIN, nt, s[0] / nw / nt, s[1] / nw / nt, s[2] / nw / nt, s[3] / nw / nt, sc / nw / nt, s[4] / nw, s[6] / nw);
     }
-#else
-    hipLaunchKernelGGL((conv3x3_expand_rb_kernel<PH, CHAIN>), dim3(grid), dim3(G::NT), G::LDS_BYTES, stream, d, tiles);
-#endif
-    GDT_CHECK_HIP(hipGetLastError());
     return GDT_OK;
+#else
+    return K::launch(grid, G::NT, stream, d, tiles);
+#endif
 }
 
 int gdt_launch_conv3x3_expand(const ConvLaunch& d, hipStream_t stream) {

@@ -281,31 +281,24 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_kernel(const Conv
 
 template <int PH, int BN, int WGM, int WGN>
 int launch_halo(const ConvLaunch& d, hipStream_t stream) {
-    const int tiles = d.N * ((d.W + 15) / 16) * ((d.H + PH - 1) / PH), ntn = d.CoutPad / BN;
-    constexpr size_t lds = halo_lds_bytes<PH, BN, WGM, WGN>();
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    static GdtPerDevice per_dev;          // one attribute call per template instantiation AND device (gdt_common.h)
-    int attr_set = 0;
-    {
-        const int rc = gdt_per_device(per_dev, attr_set, [](int, int, int& v) {
-            v = 1;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_halo_kernel<PH, BN, WGM, WGN>,
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
-    hipLaunchKernelGGL((conv3x3_halo_kernel<PH, BN, WGM, WGN>), dim3(gdt_grid_for_tiles(tiles, ntn)), dim3(WGM * WGN * 64), lds, stream, d);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    using K = GdtKernel<conv3x3_halo_kernel<PH, BN, WGM, WGN>, (int)halo_lds_bytes<PH, BN, WGM, WGN>()>;
+    int unused = 0;
+    GDT_CHECK(K::figure(unused));
+    return K::launch(gdt_grid_for_tiles((int)gdt_patches(d.N, d.H, d.W, PH), d.CoutPad / BN), WGM * WGN * 64, stream, d);
 }
+
+GDT_KNOB_LATCHED(knob_mode, "GDT_CONV_HALO", 1)              // 0 off, 1 auto, 2 force
+GDT_KNOB_LATCHED(knob_min_tiles, "GDT_CONV_MIN_TILES", 0)    // 0: the rule in gdt_conv_halo_eligible
+GDT_KNOB_LATCHED(knob_dbg, "GDT_CONV_DBG", 0)
+GDT_KNOB_LATCHED(knob_stamp, "GDT_CONV_STAMP", 0)
+GDT_KNOB_LATCHED(knob_small, "GDT_HALO_SMALL", 0)            // experiment knob
 
 }  // namespace
 
 // Eligibility: 3x3, stride 1, pad 1, Cin a multiple of 64, fp16 NHWC output, enough tiles to fill the chip, and -- when the
 // InstanceNorm statistics are fused -- whole 16x16 patches (H, W multiples of 16) so that the 128-row records line up.
 bool gdt_conv_halo_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_HALO"); return e ? atoi(e) : 1; }();   // 0 off, 1 auto, 2 force
+    const int mode = knob_mode();
     if (mode == 0) return false;
     const bool shape = d.ntaps == 9 && d.TW == 3 && d.sy == 1 && d.sx == 1 && d.dy0 == -1 && d.dx0 == -1 && d.dys == 1 && d.dxs == 1 &&
                        d.osy == 1 && d.osx == 1 && d.ooy == 0 && d.oox == 0 && d.Cin % 64 == 0 && !d.out_f32 && d.Cout % 8 == 0 &&
@@ -313,25 +306,21 @@ bool gdt_conv_halo_eligible(const ConvLaunch& d) {
     if (!shape) return false;
     if (d.stats && ((d.H & 15) || (d.W & 15))) return false;     // whole patches: the 128-row statistics records line up
     if (mode == 2) return true;
-    const long tiles = (long)d.N * ((d.W + 15) / 16) * ((d.H + 15) / 16);
     const int bn = d.CoutPad % 256 == 0 ? 256 : (d.CoutPad % 128 == 0 ? 128 : 64);
-    // padded patches waste work on ragged sizes: require >= 85 % useful pixels
-    const double useful = (double)d.H * d.W / ((double)((d.H + 15) / 16 * 16) * ((d.W + 15) / 16 * 16));
-    static const int min_env = [] { const char* e = getenv("GDT_CONV_MIN_TILES"); return e ? atoi(e) : 0; }();
+    const int min_env = knob_min_tiles();
     // (batch-1 sweeps of the first-generation kernel: 64-128 best, 512 loses 25 % on a 1024^2 image.  With fragment-ordered weights the layer runs on
     // conv3x3_halo_rb.hip, whose 128-column four-wave tiles keep winning down to 16 patches: GeM-ResNet-101 8 x 512^2 2.38 -> 2.15 ms, 1 x 1024^2 2.17 -> 2.03)
     const int min_tiles = min_env ? min_env : ((d.w_frag && !d.in_norm && !d.stats) ? 16 : 128);       // (the folded-norm modes only exist in the eight-wave form)
-    return tiles * (d.CoutPad / bn) >= min_tiles && useful >= 0.85;
+    // padded patches waste work on ragged sizes: require >= 85 % useful pixels
+    return gdt_enough_tiles(gdt_patches(d.N, d.H, d.W), d.CoutPad / bn, min_tiles) && gdt_useful_area(d.H, d.W) >= GDT_MIN_USEFUL_AREA;
 }
 
 int gdt_launch_conv_halo(const ConvLaunch& d_in, hipStream_t stream) {
-    static const int dbg = [] { const char* e = getenv("GDT_CONV_DBG"); return e ? atoi(e) : 0; }();
     ConvLaunch d = d_in;
-    d.dbg = dbg;
-    static const int want_stamp = [] { const char* e = getenv("GDT_CONV_STAMP"); return e ? atoi(e) : 0; }();
+    d.dbg = knob_dbg();
     static unsigned long long* stamp_buf = nullptr;
-    const int stamp_blocks = (d.N * ((d.W + 15) / 16) * ((d.H + 15) / 16) + 7) / 8 * 8 * (d.CoutPad / 256 ? d.CoutPad / 256 : 1);
-    if (want_stamp && d.CoutPad % 256 == 0) {            // diagnostic: per-wave cycle totals printed after a blocking sync
+    const int stamp_blocks = ((int)gdt_patches(d.N, d.H, d.W) + 7) / 8 * 8 * (d.CoutPad / 256 ? d.CoutPad / 256 : 1);
+    if (knob_stamp() && d.CoutPad % 256 == 0) {            // diagnostic: per-wave cycle totals printed after a blocking sync
         if (!stamp_buf) GDT_CHECK_HIP(hipMalloc((void**)&stamp_buf, (size_t)65536 * 8 * 4 * sizeof(unsigned long long)));
         GDT_CHECK_HIP(hipMemsetAsync(stamp_buf, 0, (size_t)stamp_blocks * 8 * 4 * sizeof(unsigned long long), stream));
         d.dbg |= 16; d.stamp_out = stamp_buf;
@@ -345,7 +334,7 @@ int gdt_launch_conv_halo(const ConvLaunch& d_in, hipStream_t stream) {
                 bar / steps, body / steps, epi / nw, steps / nw);
         return rc;
     }
-    static const int small = [] { const char* e = getenv("GDT_HALO_SMALL"); return e ? atoi(e) : 0; }();   // experiment knob
+    const int small = knob_small();
     if (small == 1 && d.CoutPad % 128 == 0) return launch_halo<8, 128, 2, 2>(d, stream);  // two workgroups per CU
     // 16 wavefronts (64x64 per wave, 4 per SIMD): equal to the 8-wave form on plain layers (0.281 vs 0.283 ms).  With the
     // producer's InstanceNorm applied while staging it is the slower one (0.51 vs 0.32 ms) since the staging moved into the

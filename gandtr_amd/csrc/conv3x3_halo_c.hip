@@ -847,8 +847,16 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
 #endif
 }
 
-// timing-only ablation knob: GDT_C_DBG=4 skips the epilogue
-static int c_dbg() { static const int v = [] { const char* e = getenv("GDT_C_DBG"); return e ? atoi(e) : 0; }(); return v; }
+GDT_KNOB_LATCHED(knob_mode, "GDT_CONV_HALO_C", 1)            // 0 off, 1 auto, 2 force (the 3x3 form; the transposed and stride-2 forms: 0 off)
+GDT_KNOB_LATCHED(knob_min_tiles, "GDT_CONV_MIN_TILES", 16)   // (below: the generic f16x3 kernels; batch 1-4 at 256^2 measured 2.09 vs 2.38 ms with the patch kernels on 16 tiles)
+GDT_KNOB_LATCHED(knob_narrow_below, "GDT_C_NARROW_BELOW", 192)
+GDT_KNOB_LATCHED(knob_rb_dbg, "GDT_RB_DBG", 0)               // timing-only ablation, the 3x3 form
+GDT_KNOB_LATCHED(knob_c_dbg, "GDT_C_DBG", 0)                 // ... the transposed and stride-2 forms: 4 skips the epilogue
+GDT_KNOB_LATCHED(knob_stagger_us, "GDT_C_STAGGER_US", 0)
+GDT_KNOB_LATCHED(knob_tall, "GDT_C_TALL", 1)                 // 0: the 2 x 2 wave layout
+GDT_KNOB_LATCHED(knob_waves, "GDT_C_WAVES", 0)               // 8: the 1 x 8 layout, two waves per SIMD
+GDT_KNOB_LATCHED(knob_s2_waves, "GDT_C_S2_WAVES", 8)         // two waves per SIMD (2 x 4): 0.55 -> 0.51 ms; 4: back to four
+GDT_KNOB_LATCHED(knob_tall_s2, "GDT_C_TALL_S2", 1)           // 0: the 2 x 2 wave layout
 
 // Four waves, one per SIMD (512 registers each: 256 accumulator AGPRs + 256 VGPRs).  TALL = false: 2 x 2 waves of 128 pixels x 128
 // channels; TALL = true: 1 x 4 waves of 256 pixels x 64 channels -- every wave reads all 256 pixels' fragments from LDS (twice the
@@ -872,19 +880,10 @@ int launch_c(const ConvLaunch& d, hipStream_t stream) {
     //  with 2 x 4 waves the phases of a wave depend on its column -- not instantiated; the 256-column stride-2 form spills at 256 registers: 0.35 -> 0.61 ms)
     static_assert(!W8 || (TALL && FORM == 0) || (!TALL && MODE == 1 && FORM == 2 && BN == 128), "the eight-wave layouts: 1 x 8 for the 3x3 form; 2 x 4 for the 128-column stride-2 form");
     const int gh = FORM == 2 ? d.OH : d.H, gw = FORM == 2 ? d.OW : d.W;
-    const int tiles = d.N * ((gw + 15) / 16) * ((gh + PH - 1) / PH), ntn = d.CoutPad / BN;
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-    static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
+    using K = GdtKernel<conv3x3_halo_c_kernel<BN, WGM, WGN, MODE, FORM>, (int)LDS_BYTES>;
     int cus = 0;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_halo_c_kernel<BN, WGM, WGN, MODE, FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
-    const int vblocks = gdt_grid_for_tiles(tiles, ntn);
+    GDT_CHECK(K::figure(cus));
+    const int vblocks = gdt_grid_for_tiles((int)gdt_patches(d.N, gh, gw, PH), d.CoutPad / BN);
     const int grid = vblocks < cus ? vblocks : cus;
 #ifdef GDT_C_STAMP
     static unsigned long long* stamp_buf = nullptr;
@@ -894,7 +893,7 @@ int launch_c(const ConvLaunch& d, hipStream_t stream) {
     if (!stamp_buf) GDT_CHECK_HIP(hipMalloc((void**)&stamp_buf, (size_t)cus * NWV * 8 * sizeof(unsigned long long)));
     GDT_CHECK_HIP(hipMemsetAsync(stamp_buf, 0, (size_t)cus * NWV * 8 * sizeof(unsigned long long), stream));
     ds.stamp_out = stamp_buf;
-    hipLaunchKernelGGL((conv3x3_halo_c_kernel<BN, WGM, WGN, MODE, FORM>), dim3(grid), dim3(WGM * WGN * 64), LDS_BYTES, stream, ds, vblocks);
+    GDT_CHECK(K::launch(grid, WGM * WGN * 64, stream, ds, vblocks));
     if (++stamp_calls % 200 < 20) {          // a few launches per variant of a sustained run
         GDT_CHECK_HIP(hipStreamSynchronize(stream));
         std::vector<unsigned long long> h((size_t)grid * NWV * 8);
@@ -905,11 +904,33 @@ int launch_c(const ConvLaunch& d, hipStream_t stream) {
         fprintf(stderr, "[c stamp] MODE %d FORM %d BN %d waves %d: tiles/wave %.1f; per tile: chunk bodies %.0f, chunk barriers %.0f, tile barrier %.0f, epilogue %.0f cycles; total per wave %.0f\n",
                 MODE, FORM, BN, NWV, nt, s[0] / nw / nt, s[1] / nw / nt, s[2] / nw / nt, s[3] / nw / nt, s[4] / nw);
     }
-#else
-    hipLaunchKernelGGL((conv3x3_halo_c_kernel<BN, WGM, WGN, MODE, FORM>), dim3(grid), dim3(WGM * WGN * 64), LDS_BYTES, stream, d, vblocks);
-#endif
-    GDT_CHECK_HIP(hipGetLastError());
     return GDT_OK;
+#else
+    return K::launch(grid, WGM * WGN * 64, stream, d, vblocks);
+#endif
+}
+
+// the fold modes this file instantiates -- 3x3 form (FORM 0): all five; transposed (1): no write-back; stride-2 (2): no residual
+template <int FORM, bool TALL = false, int BN = 256, bool W8 = false>
+int launch_c_fold(const ConvLaunch& d, hipStream_t stream) {
+    const int mode = gdt_fold_mode(d);
+    if (mode == 0) return launch_c<0, FORM, TALL, BN, W8>(d, stream);
+    if (mode == 1) return launch_c<1, FORM, TALL, BN, W8>(d, stream);
+    if constexpr (FORM != 2) {
+        if (mode == 3) return launch_c<3, FORM, TALL, BN, W8>(d, stream);
+    }
+    if constexpr (FORM != 1) {
+        if (mode == 5) return launch_c<5, FORM, TALL, BN, W8>(d, stream);
+    }
+    if constexpr (FORM == 0) {
+        if (mode == 7) return launch_c<7, FORM, TALL, BN, W8>(d, stream);
+    }
+    return gdt_fold_refused(mode);
+}
+
+// the eligibility tail of the three forms: enough 16 x 16 patches of the H x W grid the tiles cover to fill the chip, at most 15 % of their area padding
+bool c_fills_chip(const ConvLaunch& d, int H, int W, int column_tiles) {
+    return gdt_enough_tiles(gdt_patches(d.N, H, W), column_tiles, knob_min_tiles()) && gdt_useful_area(H, W) >= GDT_MIN_USEFUL_AREA;
 }
 
 }  // namespace
@@ -917,7 +938,7 @@ int launch_c(const ConvLaunch& d, hipStream_t stream) {
 // Eligible: 3x3 / stride 1 / pad 1 (zero or reflect), Cin % 64 == 0, 256-wide output tiles, the fp16 + MX fragment-ordered weights
 // present, whole patches when statistics are taken, enough patches to fill the chip; with a folded InstanceNorm 128 <= Cin <= 256.
 bool gdt_conv_halo_c_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_HALO_C"); return e ? atoi(e) : 1; }();   // 0 off, 1 auto, 2 force
+    const int mode = knob_mode();
     if (mode == 0 || !d.w_cfrag || !d.wmx_a || !d.wmx_b || !d.wmx_s) return false;
     const bool shape = d.ntaps == 9 && d.TW == 3 && d.sy == 1 && d.sx == 1 && d.dy0 == -1 && d.dx0 == -1 && d.dys == 1 && d.dxs == 1 &&
                        d.osy == 1 && d.osx == 1 && d.ooy == 0 && d.oox == 0 && d.Cin % 64 == 0 && !d.out_f32 && d.Cout % 8 == 0 &&
@@ -926,66 +947,26 @@ bool gdt_conv_halo_c_eligible(const ConvLaunch& d) {
     if (d.in_norm && (d.Cin > 256 || d.Cin < 128)) return false;
     if ((d.in_res || d.in_out) && !d.in_norm) return false;
     if (d.stats && ((d.H & 15) || (d.W & 15))) return false;
-    if ((long)d.N * d.H * d.W * d.Cin >= (1L << 30) || (long)d.N * d.H * d.W * d.Cout >= (1L << 32)) return false;
+    if (!gdt_offsets_fit(d.N, d.H, d.W, d.Cin, 30) || !gdt_offsets_fit(d.N, d.H, d.W, d.Cout)) return false;
     if (mode == 2) return true;
-    const long tiles = (long)d.N * ((d.W + 15) / 16) * ((d.H + 15) / 16);
-    const double useful = (double)d.H * d.W / ((double)((d.H + 15) / 16 * 16) * ((d.W + 15) / 16 * 16));
-    static const int min_tiles = [] { const char* e = getenv("GDT_CONV_MIN_TILES"); return e ? atoi(e) : 16; }();      // (below: the generic f16x3 kernels; batch 1-4 at 256^2 measured 2.09 vs 2.38 ms with the patch kernels on 16 tiles)
-    return tiles * (d.CoutPad / 256) >= min_tiles && useful >= 0.85;
+    return c_fills_chip(d, d.H, d.W, d.CoutPad / 256);
 }
 
 // few patches (batch 1-4 at 256^2: 16-64 tiles for 256 CUs): 128-column tiles double the number of workgroups
 int gdt_conv_halo_c_columns(const ConvLaunch& d) {
-    static const int narrow_below = [] { const char* e = getenv("GDT_C_NARROW_BELOW"); return e ? atoi(e) : 192; }();
-    const long tiles256 = (long)d.N * ((d.W + 15) / 16) * ((d.H + PH - 1) / PH) * (d.CoutPad / 256);
-    return tiles256 < narrow_below ? 128 : 256;
+    return gdt_patches(d.N, d.H, d.W, PH) * (d.CoutPad / 256) < knob_narrow_below() ? 128 : 256;
 }
 
 int gdt_launch_conv_halo_c(const ConvLaunch& d_in, hipStream_t stream) {
-    static const int dbg = [] { const char* e = getenv("GDT_RB_DBG"); return e ? atoi(e) : 0; }();
     ConvLaunch d = d_in;
-    d.dbg = dbg;
-    static const int stagger = [] { const char* e = getenv("GDT_C_STAGGER_US"); return e ? atoi(e) : 0; }();
-    d.stagger_us = stagger;
+    d.dbg = knob_rb_dbg();
+    d.stagger_us = knob_stagger_us();
 #ifdef GDT_C_DEV_W8_ONLY      // dev builds (resource reports, asm): only the eight-wave instantiations are compiled
-    {
-        if (!d.in_norm) return launch_c<0, 0, true, 256, true>(d, stream);
-        if (d.in_res) return d.in_out ? launch_c<7, 0, true, 256, true>(d, stream) : launch_c<3, 0, true, 256, true>(d, stream);
-        return d.in_out ? launch_c<5, 0, true, 256, true>(d, stream) : launch_c<1, 0, true, 256, true>(d, stream);
-    }
+    return launch_c_fold<0, true, 256, true>(d, stream);
 #else
-    if (gdt_conv_halo_c_columns(d) == 128) {
-        if (!d.in_norm) return launch_c<0, 0, false, 128>(d, stream);
-        if (d.in_res) {
-            if (d.in_out) return launch_c<7, 0, false, 128>(d, stream);
-            return launch_c<3, 0, false, 128>(d, stream);
-        }
-        return d.in_out ? launch_c<5, 0, false, 128>(d, stream) : launch_c<1, 0, false, 128>(d, stream);
-    }
-    static const int tall = [] { const char* e = getenv("GDT_C_TALL"); return e ? atoi(e) : 1; }();      // 0: the 2 x 2 wave layout
-    static const int waves8 = [] { const char* e = getenv("GDT_C_WAVES"); return e ? atoi(e) == 8 : false; }();      // 8: the 1 x 8 layout, two waves per SIMD
-    if (tall && waves8) {
-        if (!d.in_norm) return launch_c<0, 0, true, 256, true>(d, stream);
-        if (d.in_res) {
-            if (d.in_out) return launch_c<7, 0, true, 256, true>(d, stream);
-            return launch_c<3, 0, true, 256, true>(d, stream);
-        }
-        return d.in_out ? launch_c<5, 0, true, 256, true>(d, stream) : launch_c<1, 0, true, 256, true>(d, stream);
-    }
-    if (tall) {
-        if (!d.in_norm) return launch_c<0, 0, true>(d, stream);
-        if (d.in_res) {
-            if (d.in_out) return launch_c<7, 0, true>(d, stream);
-            return launch_c<3, 0, true>(d, stream);
-        }
-        return d.in_out ? launch_c<5, 0, true>(d, stream) : launch_c<1, 0, true>(d, stream);
-    }
-    if (!d.in_norm) return launch_c<0>(d, stream);
-    if (d.in_res) {
-        if (d.in_out) return launch_c<7>(d, stream);
-        return launch_c<3>(d, stream);
-    }
-    return d.in_out ? launch_c<5>(d, stream) : launch_c<1>(d, stream);
+    if (gdt_conv_halo_c_columns(d) == 128) return launch_c_fold<0, false, 128>(d, stream);
+    if (knob_tall() && knob_waves() == 8) return launch_c_fold<0, true, 256, true>(d, stream);
+    return knob_tall() ? launch_c_fold<0, true>(d, stream) : launch_c_fold<0>(d, stream);
 #endif
 }
 
@@ -993,18 +974,14 @@ int gdt_launch_conv_halo_c(const ConvLaunch& d_in, hipStream_t stream) {
 // channels per phase, enough patches to fill the chip, at most 15 % padding waste; with statistics whole 16x16 patches; a folded
 // InstanceNorm needs 128 <= Cin <= 256 (table slots, staged one chunk ahead).
 bool gdt_conv_halo_c_ct_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_HALO_C"); return e ? atoi(e) : 1; }();   // 0 off
-    if (mode == 0 || !d.phase_cout || !d.w_cfrag || !d.wmx_a || !d.wmx_b || !d.out || d.out_f32 || d.res || d.in_out) return false;
+    if (knob_mode() == 0 || !d.phase_cout || !d.w_cfrag || !d.wmx_a || !d.wmx_b || !d.out || d.out_f32 || d.res || d.in_out) return false;
     if ((d.phase_cout != 64 && d.phase_cout != 128) || d.Cout != 4 * d.phase_cout || d.CoutPad != d.Cout || d.Cin % 64 != 0) return false;
     if (d.ntaps != 4 || d.TW != 2 || d.Kpad != 4 * d.Cin || d.pad_reflect) return false;
     if (d.in_norm && (d.Cin > 256 || d.Cin < 128)) return false;
     if (d.in_res && !d.in_norm) return false;
     if (d.stats && ((d.H & 15) || (d.W & 15))) return false;
-    if ((long)d.N * d.H * d.W * d.Cin >= (1L << 30) || (long)d.N * d.OH * d.OW * d.phase_cout >= (1L << 32)) return false;
-    const long tiles = (long)d.N * ((d.W + 15) / 16) * ((d.H + 15) / 16);
-    const double useful = (double)d.H * d.W / ((double)((d.H + 15) / 16 * 16) * ((d.W + 15) / 16 * 16));
-    static const int min_tiles = [] { const char* e = getenv("GDT_CONV_MIN_TILES"); return e ? atoi(e) : 16; }();      // (below: the generic f16x3 kernels; batch 1-4 at 256^2 measured 2.09 vs 2.38 ms with the patch kernels on 16 tiles)
-    return tiles * (d.CoutPad / 256) >= min_tiles && useful >= 0.85;
+    if (!gdt_offsets_fit(d.N, d.H, d.W, d.Cin, 30) || !gdt_offsets_fit(d.N, d.OH, d.OW, d.phase_cout)) return false;
+    return c_fills_chip(d, d.H, d.W, d.CoutPad / 256);
 }
 
 int gdt_launch_conv_halo_c_ct(const ConvLaunch& d_in, hipStream_t stream) {
@@ -1012,9 +989,8 @@ int gdt_launch_conv_halo_c_ct(const ConvLaunch& d_in, hipStream_t stream) {
     return GDT_ERR_INVALID;
 #else
     ConvLaunch d = d_in;
-    d.dbg = c_dbg();
-    if (!d.in_norm) return launch_c<0, 1>(d, stream);
-    return d.in_res ? launch_c<3, 1>(d, stream) : launch_c<1, 1>(d, stream);
+    d.dbg = knob_c_dbg();
+    return launch_c_fold<1>(d, stream);
 #endif
 }
 
@@ -1023,18 +999,14 @@ int gdt_launch_conv_halo_c_ct(const ConvLaunch& d_in, hipStream_t stream) {
 // input size, OH / OW the output the patches tile.  Real Cin 64 or 128 (a 64-channel chunk must not straddle two sub-pixel parities; a folded
 // InstanceNorm keeps its table of the REAL channels in the 256-entry slots), 256-wide output tiles (Cout 128 is padded with zero columns).
 bool gdt_conv_halo_c_s2_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_HALO_C"); return e ? atoi(e) : 1; }();   // 0 off
-    if (mode == 0 || !d.w_cfrag || !d.wmx_a || !d.wmx_b || !d.out || d.out_f32 || d.res || d.phase_cout || d.pool2 || d.pad_reflect) return false;
+    if (knob_mode() == 0 || !d.w_cfrag || !d.wmx_a || !d.wmx_b || !d.out || d.out_f32 || d.res || d.phase_cout || d.pool2 || d.pad_reflect) return false;
     const int cr = d.Cin >> 2;
     if ((cr != 64 && cr != 128) || d.ntaps != 4 || d.TW != 2 || d.Kpad != 4 * d.Cin || d.CoutPad % 128 != 0 || d.Cout % 8 != 0) return false;
     if (d.OH != (d.H - 1) / 2 + 1 || d.OW != (d.W - 1) / 2 + 1) return false;
     if (d.in_res || (d.in_out && !d.in_norm)) return false;      // no residual mode in the stride-2 launch: a residual would be dropped silently
     if (d.stats && ((d.OH & 15) || (d.OW & 15))) return false;
-    if ((long)d.N * d.H * d.W * cr >= (1L << 30) || (long)d.N * d.OH * d.OW * d.Cout >= (1L << 32)) return false;
-    const long tiles = (long)d.N * ((d.OW + 15) / 16) * ((d.OH + 15) / 16);
-    const double useful = (double)d.OH * d.OW / ((double)((d.OH + 15) / 16 * 16) * ((d.OW + 15) / 16 * 16));
-    static const int min_tiles = [] { const char* e = getenv("GDT_CONV_MIN_TILES"); return e ? atoi(e) : 16; }();      // (below: the generic f16x3 kernels; batch 1-4 at 256^2 measured 2.09 vs 2.38 ms with the patch kernels on 16 tiles)
-    return tiles * (d.CoutPad % 256 == 0 ? d.CoutPad / 256 : d.CoutPad / 128) >= min_tiles && useful >= 0.85;
+    if (!gdt_offsets_fit(d.N, d.H, d.W, cr, 30) || !gdt_offsets_fit(d.N, d.OH, d.OW, d.Cout)) return false;
+    return c_fills_chip(d, d.OH, d.OW, d.CoutPad % 256 == 0 ? d.CoutPad / 256 : d.CoutPad / 128);
 }
 
 int gdt_launch_conv_halo_c_s2(const ConvLaunch& d_in, hipStream_t stream) {
@@ -1042,19 +1014,11 @@ int gdt_launch_conv_halo_c_s2(const ConvLaunch& d_in, hipStream_t stream) {
     return GDT_ERR_INVALID;
 #else
     ConvLaunch d = d_in;
-    d.dbg = c_dbg();
+    d.dbg = knob_c_dbg();
     if (d.CoutPad % 256 != 0) {
-        static const int w8s2 = [] { const char* e = getenv("GDT_C_S2_WAVES"); return e ? atoi(e) == 8 : true; }();      // two waves per SIMD (2 x 4): 0.55 -> 0.51 ms; GDT_C_S2_WAVES=4: back to four
-        if (w8s2 && d.in_norm && !d.in_out) return launch_c<1, 2, false, 128, true>(d, stream);
-        if (!d.in_norm) return launch_c<0, 2, false, 128>(d, stream);
-        return d.in_out ? launch_c<5, 2, false, 128>(d, stream) : launch_c<1, 2, false, 128>(d, stream);
+        if (knob_s2_waves() == 8 && gdt_fold_mode(d) == GDT_FOLD_NORM) return launch_c<1, 2, false, 128, true>(d, stream);      // (the only eight-wave instantiation of this form)
+        return launch_c_fold<2, false, 128>(d, stream);
     }
-    static const int tall = [] { const char* e = getenv("GDT_C_TALL_S2"); return e ? atoi(e) : 1; }();      // 0: the 2 x 2 wave layout
-    if (tall) {
-        if (!d.in_norm) return launch_c<0, 2, true>(d, stream);
-        return d.in_out ? launch_c<5, 2, true>(d, stream) : launch_c<1, 2, true>(d, stream);
-    }
-    if (!d.in_norm) return launch_c<0, 2>(d, stream);
-    return d.in_out ? launch_c<5, 2>(d, stream) : launch_c<1, 2>(d, stream);
+    return knob_tall_s2() ? launch_c_fold<2, true>(d, stream) : launch_c_fold<2>(d, stream);
 #endif
 }

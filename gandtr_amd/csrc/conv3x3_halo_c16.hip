@@ -634,19 +634,10 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
 
 template <int MODE>
 int launch_c16(const ConvLaunch& d, hipStream_t stream) {
-    const int tiles = d.N * (d.W >> 4) * (d.H >> 4), ntn = d.CoutPad >> 8;
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-    static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
+    using K = GdtKernel<conv3x3_halo_c16_kernel<MODE>, (int)LDS_BYTES>;
     int cus = 0;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_halo_c16_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
-    const int vblocks = gdt_grid_for_tiles(tiles, ntn);
+    GDT_CHECK(K::figure(cus));
+    const int vblocks = gdt_grid_for_tiles(d.N * (d.W >> 4) * (d.H >> 4), d.CoutPad >> 8);
     const int grid = vblocks < cus ? vblocks : cus;
 #ifdef GDT_C_STAMP
     static unsigned long long* stamp_buf = nullptr;
@@ -655,7 +646,7 @@ int launch_c16(const ConvLaunch& d, hipStream_t stream) {
     if (!stamp_buf) GDT_CHECK_HIP(hipMalloc((void**)&stamp_buf, (size_t)cus * 4 * 8 * sizeof(unsigned long long)));
     GDT_CHECK_HIP(hipMemsetAsync(stamp_buf, 0, (size_t)cus * 4 * 8 * sizeof(unsigned long long), stream));
     ds.stamp_out = stamp_buf;
-    hipLaunchKernelGGL((conv3x3_halo_c16_kernel<MODE>), dim3(grid), dim3(NT), LDS_BYTES, stream, ds, vblocks);
+    GDT_CHECK(K::launch(grid, NT, stream, ds, vblocks));
     if (++stamp_calls % 200 < 20) {
         GDT_CHECK_HIP(hipStreamSynchronize(stream));
         std::vector<unsigned long long> h((size_t)grid * 4 * 8);
@@ -666,28 +657,33 @@ int launch_c16(const ConvLaunch& d, hipStream_t stream) {
         fprintf(stderr, "[c stamp] MODE %d FORM 16 BN 256 waves 4: tiles/wave %.1f; per tile: chunk bodies %.0f, chunk barriers %.0f, tile barrier %.0f, epilogue %.0f cycles; total per wave %.0f\n",
                 MODE, nt, s[0] / nw / nt, s[1] / nw / nt, s[2] / nw / nt, s[3] / nw / nt, s[4] / nw);
     }
-#else
-    hipLaunchKernelGGL((conv3x3_halo_c16_kernel<MODE>), dim3(grid), dim3(NT), LDS_BYTES, stream, d, vblocks);
-#endif
-    GDT_CHECK_HIP(hipGetLastError());
     return GDT_OK;
+#else
+    return K::launch(grid, NT, stream, d, vblocks);
+#endif
 }
+
+GDT_KNOB_LATCHED(knob_mode, "GDT_CONV_HALO_C16", 1)          // 0 off
 
 }  // namespace
 
 // Eligible: what conv3x3_halo_c.hip's 256-column form takes (gdt_conv_halo_c_eligible is checked by the caller), restricted to whole 16 x 16
 // patches and whole 256-column tiles, with the 16 x 16 fragment-ordered weights present.
 bool gdt_conv_halo_c16_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_HALO_C16"); return e ? atoi(e) : 1; }();   // 0 off
-    if (mode == 0 || !d.w_c16) return false;
+    if (knob_mode() == 0 || !d.w_c16) return false;
     if (!gdt_conv_halo_c_eligible(d) || gdt_conv_halo_c_columns(d) != 256) return false;
     if ((d.H & 15) || (d.W & 15) || d.Cout != d.CoutPad || (d.Cout & 255)) return false;
     if (d.res && d.in_norm) return false;
     return true;
 }
 
+// every fold mode is instantiated here
 int gdt_launch_conv_halo_c16(const ConvLaunch& d, hipStream_t stream) {
-    if (!d.in_norm) return launch_c16<0>(d, stream);
-    if (d.in_res) return d.in_out ? launch_c16<7>(d, stream) : launch_c16<3>(d, stream);
-    return d.in_out ? launch_c16<5>(d, stream) : launch_c16<1>(d, stream);
+    switch (gdt_fold_mode(d)) {
+        case 0: return launch_c16<0>(d, stream);
+        case 1: return launch_c16<1>(d, stream);
+        case 3: return launch_c16<3>(d, stream);
+        case 5: return launch_c16<5>(d, stream);
+        default: return launch_c16<7>(d, stream);
+    }
 }

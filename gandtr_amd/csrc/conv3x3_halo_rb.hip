@@ -476,57 +476,60 @@ __global__ __launch_bounds__(WGM * WGN * 64, 1) void conv3x3_halo_rb_multi_kerne
     conv3x3_halo_rb_body<BN, WGM, WGN, 0, false, 16, false>(m.lev[l], m.vblocks[l], blockIdx.x - m.prefix[l], m.prefix[l + 1] - m.prefix[l]);
 }
 
+GDT_KNOB_LATCHED(knob_mode, "GDT_CONV_RB", 1)                // 0 off
+GDT_KNOB_LATCHED(knob_narrow, "GDT_CONV_RB128", 1)           // 0: no 128- / 64-column four-wave forms
+GDT_KNOB_LATCHED(knob_single, "GDT_CONV_RB_SINGLE", 1)       // 0: no single-stage form (two workgroups per CU) for Cin == 64
+GDT_KNOB_LATCHED(knob_split_below, "GDT_RB_SPLIT_BELOW", 192)
+GDT_KNOB_LATCHED(knob_persist, "GDT_RB_PERSIST", 1)          // 0: one workgroup per tile; n > 1: n / 2 workgroups per CU
+GDT_KNOB_LATCHED(knob_cu_limit, "GDT_CU_LIMIT", 0)           // dev: persistent grid on part of the chip (concurrent-stream experiments)
+GDT_KNOB_LATCHED(knob_dbg, "GDT_RB_DBG", 0)                  // timing-only ablation
+GDT_KNOB_LATCHED(knob_ct_mode, "GDT_CONV_HALO_CT", 1)        // 0 off
+GDT_KNOB_LATCHED(knob_ct_min_tiles, "GDT_CONV_MIN_TILES", 128)   // (batch-1 sweeps: 64-128 best; 512 loses 25 % on a 1024^2 image)
+
 template <int BN, int WGM, int WGN>
 int launch_rb_multi(const ConvLaunch* dl, int L, hipStream_t stream) {
-    constexpr size_t lds = rb_lds_bytes<BN, 16, false>();
-    static GdtPerDevice per_dev;
+    using K = GdtKernel<conv3x3_halo_rb_multi_kernel<BN, WGM, WGN>, (int)rb_lds_bytes<BN, 16, false>()>;
     int cus = 0;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_halo_rb_multi_kernel<BN, WGM, WGN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
-    static const int dbg = [] { const char* e = getenv("GDT_RB_DBG"); return e ? atoi(e) : 0; }();
+    GDT_CHECK(K::figure(cus));
     MultiConv m;
     m.nlev = L;
     for (int l = 0; l < L; ++l) {
-        m.lev[l] = dl[l]; m.lev[l].dbg = dbg;
-        m.vblocks[l] = gdt_grid_for_tiles(dl[l].N * ((dl[l].W + 15) / 16) * ((dl[l].H + 15) / 16), dl[l].CoutPad / BN);
+        m.lev[l] = dl[l]; m.lev[l].dbg = knob_dbg();
+        m.vblocks[l] = gdt_grid_for_tiles((int)gdt_patches(dl[l].N, dl[l].H, dl[l].W), dl[l].CoutPad / BN);
     }
     const int grid = gdt_multi_partition(m.prefix, m.vblocks, L, cus);
-    hipLaunchKernelGGL((conv3x3_halo_rb_multi_kernel<BN, WGM, WGN>), dim3(grid), dim3(WGM * WGN * 64), lds, stream, m);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    return K::launch(grid, WGM * WGN * 64, stream, m);
 }
 
 template <int BN, int WGM, int WGN, int MODE, bool CT = false, int PHT = 16, bool SINGLE = false>
 int launch_rb(const ConvLaunch& d, hipStream_t stream) {
-    const int tiles = d.N * ((d.W + 15) / 16) * ((d.H + PHT - 1) / PHT), ntn = d.CoutPad / BN;
     constexpr size_t lds = rb_lds_bytes<BN, PHT, SINGLE>();
     static_assert(!SINGLE || 2 * lds <= 160 * 1024, "two workgroups per CU");
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
+    using K = GdtKernel<conv3x3_halo_rb_kernel<BN, WGM, WGN, MODE, CT, PHT, SINGLE>, (int)lds>;
     int cus = 0;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_halo_rb_kernel<BN, WGM, WGN, MODE, CT, PHT, SINGLE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
-    const int vblocks = gdt_grid_for_tiles(tiles, ntn);
-    static const int persist = [] { const char* e = getenv("GDT_RB_PERSIST"); return e ? atoi(e) : 1; }();
+    GDT_CHECK(K::figure(cus));
+    const int vblocks = gdt_grid_for_tiles((int)gdt_patches(d.N, d.H, d.W, PHT), d.CoutPad / BN);
+    const int persist = knob_persist(), cu_limit = knob_cu_limit();
     int grid = (vblocks < cus || !persist) ? vblocks : cus * (persist > 1 ? persist : 1) / (persist > 1 ? 2 : 1);
-    static const int cu_limit = [] { const char* e = getenv("GDT_CU_LIMIT"); return e ? atoi(e) : 0; }();      // dev: persistent grid on part of the chip (concurrent-stream experiments)
     if (cu_limit > 0 && grid > cu_limit) grid = cu_limit;
     if (SINGLE) grid = vblocks < 2 * cus ? vblocks : 2 * cus;
-    hipLaunchKernelGGL((conv3x3_halo_rb_kernel<BN, WGM, WGN, MODE, CT, PHT, SINGLE>), dim3(grid), dim3(WGM * WGN * 64), lds, stream, d, vblocks);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    return K::launch(grid, WGM * WGN * 64, stream, d, vblocks);
+}
+
+// the fold modes this file instantiates: the 256-column eight-wave form, plain / norm / norm + write-back / norm + residual + write-back; transposed
+// (CT): plain / norm / norm + residual
+template <bool CT>
+int launch_rb_fold(const ConvLaunch& d, hipStream_t stream) {
+    const int mode = gdt_fold_mode(d);
+    if (mode == 0) return launch_rb<256, 2, 4, 0, CT>(d, stream);
+    if (mode == 1) return launch_rb<256, 2, 4, 1, CT>(d, stream);
+    if constexpr (CT) {
+        if (mode == 3) return launch_rb<256, 2, 4, 3, true>(d, stream);
+    } else {
+        if (mode == 5) return launch_rb<256, 2, 4, 5>(d, stream);
+        if (mode == 7) return launch_rb<256, 2, 4, 7>(d, stream);
+    }
+    return gdt_fold_refused(mode);
 }
 
 }  // namespace
@@ -535,43 +538,36 @@ int launch_rb(const ConvLaunch& d, hipStream_t stream) {
 // 256 channels wide and -- with a folded InstanceNorm -- the (scale, shift) tables of two images fit their 4 KB and there
 // are at least two channel chunks (the next tile's table is staged one chunk ahead).
 bool gdt_conv_halo_rb_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_RB"); return e ? atoi(e) : 1; }();   // 0 off
     // 128 output channels (VGG16 conv2_x, HED): the four-wave form, 2 x 2 waves of the same 128 x 64 wave tile (plain input only)
-    static const int narrow = [] { const char* e = getenv("GDT_CONV_RB128"); return e ? atoi(e) : 1; }();
+    const int narrow = knob_narrow();
     const bool plain = !d.in_norm && !d.in_res && !d.in_out && !d.stats;
     bool n128 = narrow && d.CoutPad == 128 && plain;
     // 64 output channels (VGG16 conv1_2, HED): 4 x 1 waves on a tall 16 x 32 patch; at most 15 % of the patch rows may hang over the image
     if (narrow && d.CoutPad == 64 && plain && (double)d.H / ((d.H + 31) / 32 * 32) >= 0.85) n128 = true;
-    if (mode == 0 || !d.w_frag || (d.CoutPad % 256 != 0 && !n128)) return false;
+    if (knob_mode() == 0 || !d.w_frag || (d.CoutPad % 256 != 0 && !n128)) return false;
     if (d.in_norm && (d.Cin > 256 || d.Cin < 128)) return false;
-    if ((long)d.N * d.H * d.W * d.Cin >= (1L << 32) || (long)d.N * d.H * d.W * d.Cout >= (1L << 32)) return false;    // 32-bit element offsets
+    if (!gdt_offsets_fit(d.N, d.H, d.W, d.Cin) || !gdt_offsets_fit(d.N, d.H, d.W, d.Cout)) return false;
     return gdt_conv_halo_eligible(d);
 }
 
-static bool narrow_ok() { static const int v = [] { const char* e = getenv("GDT_CONV_RB128"); return e ? atoi(e) : 1; }(); return v != 0; }
-
 int gdt_launch_conv_halo_rb(const ConvLaunch& d_in, hipStream_t stream) {
-    static const int dbg = [] { const char* e = getenv("GDT_RB_DBG"); return e ? atoi(e) : 0; }();
     ConvLaunch d = d_in;
-    d.dbg = dbg;
-    static const int single = [] { const char* e = getenv("GDT_CONV_RB_SINGLE"); return e ? atoi(e) : 1; }();
+    d.dbg = knob_dbg();
+    const int single = knob_single();
     if (d.CoutPad == 128) return (single && d.Cin == 64) ? launch_rb<128, 2, 2, 0, false, 16, true>(d, stream) : launch_rb<128, 2, 2, 0>(d, stream);
     if (d.CoutPad == 64) return (single && d.Cin == 64) ? launch_rb<64, 4, 1, 0, false, 32, true>(d, stream) : launch_rb<64, 4, 1, 0, false, 32>(d, stream);
     if (!d.in_norm) {
         // few patches (small images / small batches: ResNet layer3 / 4 on 256^2 inputs, the small levels of a pyramid): 128-column tiles of the four-wave form
         // double the number of workgroups -- every CU gets one wave per SIMD instead of half the CUs getting two
-        static const int split_below = [] { const char* e = getenv("GDT_RB_SPLIT_BELOW"); return e ? atoi(e) : 192; }();
-        const long tiles256 = (long)d.N * ((d.W + 15) / 16) * ((d.H + 15) / 16) * (d.CoutPad / 256);
+        const long tiles256 = gdt_patches(d.N, d.H, d.W) * (d.CoutPad / 256);
         // ... and so do tile counts that leave the last round of the persistent walk half empty (384 patches on 256 CUs: two rounds for 1.5 rounds of work):
         // the narrow form is ~0.85x as efficient per tile but its 2x finer grain can more than make up for that
         static const int cus = [] { int dev = 0, n = 256; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256; return n / 8 * 8; }();
         auto fill = [&](long t) { return (double)t / (double)((t + cus - 1) / cus * cus); };
         const bool tail = fill(tiles256) < 0.85 * fill(2 * tiles256) - 0.02;
-        if (narrow_ok() && (tiles256 < split_below || tail) && !d.in_res && !d.in_out && !d.stats) return launch_rb<128, 2, 2, 0>(d, stream);
-        return launch_rb<256, 2, 4, 0>(d, stream);
+        if (knob_narrow() && (tiles256 < knob_split_below() || tail) && !d.in_res && !d.in_out && !d.stats) return launch_rb<128, 2, 2, 0>(d, stream);
     }
-    if (d.in_res) { GDT_REQUIRE(d.in_out != nullptr, "residual fold without write-back target"); return launch_rb<256, 2, 4, 7>(d, stream); }
-    return d.in_out ? launch_rb<256, 2, 4, 5>(d, stream) : launch_rb<256, 2, 4, 1>(d, stream);
+    return launch_rb_fold<false>(d, stream);
 }
 
 // The same plain 3x3 conv (no folded norm, no fused pool, no statistics, 256 output channels per tile) on L independent geometries as ONE launch; false when the
@@ -589,10 +585,9 @@ bool gdt_conv_halo_rb_levels_ok(const ConvLaunch* dl, int L) {
 int gdt_launch_conv_halo_rb_levels(const ConvLaunch* dl, int L, hipStream_t stream) {
     GDT_REQUIRE(gdt_conv_halo_rb_levels_ok(dl, L), "geometries that cannot share a launch");
     // the tile shape for the levels together (gdt_launch_conv_halo_rb's rule on the summed patch count)
-    static const int split_below = [] { const char* e = getenv("GDT_RB_SPLIT_BELOW"); return e ? atoi(e) : 192; }();
     long tiles256 = 0;
-    for (int l = 0; l < L; ++l) tiles256 += (long)dl[l].N * ((dl[l].W + 15) / 16) * ((dl[l].H + 15) / 16) * (dl[l].CoutPad / 256);
-    if (narrow_ok() && tiles256 < split_below) return launch_rb_multi<128, 2, 2>(dl, L, stream);
+    for (int l = 0; l < L; ++l) tiles256 += gdt_patches(dl[l].N, dl[l].H, dl[l].W) * (dl[l].CoutPad / 256);
+    if (knob_narrow() && tiles256 < knob_split_below()) return launch_rb_multi<128, 2, 2>(dl, L, stream);
     return launch_rb_multi<256, 2, 4>(dl, L, stream);
 }
 
@@ -600,23 +595,18 @@ int gdt_launch_conv_halo_rb_levels(const ConvLaunch* dl, int L, hipStream_t stre
 // phase, enough patches to fill the chip, at most 15 % padding waste; with statistics whole 16x16 patches; a folded InstanceNorm
 // needs 128 <= Cin <= 256 (table slots, staged one chunk ahead).
 bool gdt_conv_halo_ct_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_HALO_CT"); return e ? atoi(e) : 1; }();   // 0 off
-    if (mode == 0 || !d.phase_cout || !d.w_frag || !d.out || d.out_f32 || d.res || d.in_out) return false;
+    if (knob_ct_mode() == 0 || !d.phase_cout || !d.w_frag || !d.out || d.out_f32 || d.res || d.in_out) return false;
     if ((d.phase_cout != 64 && d.phase_cout != 128) || d.Cout != 4 * d.phase_cout || d.CoutPad != d.Cout || d.Cin % 64 != 0) return false;
     if (d.ntaps != 4 || d.TW != 2 || d.Kpad != 4 * d.Cin || d.pad_reflect) return false;
     if (d.in_norm && (d.Cin > 256 || d.Cin < 128)) return false;
     if (d.in_res && !d.in_norm) return false;
     if (d.stats && ((d.H & 15) || (d.W & 15))) return false;
-    if ((long)d.N * d.H * d.W * d.Cin >= (1L << 32) || (long)d.N * d.OH * d.OW * d.phase_cout >= (1L << 32)) return false;
-    const long tiles = (long)d.N * ((d.W + 15) / 16) * ((d.H + 15) / 16);
-    const double useful = (double)d.H * d.W / ((double)((d.H + 15) / 16 * 16) * ((d.W + 15) / 16 * 16));
-    static const int min_tiles = [] { const char* e = getenv("GDT_CONV_MIN_TILES"); return e ? atoi(e) : 128; }();   // (batch-1 sweeps: 64-128 best; 512 loses 25 % on a 1024^2 image)
-    return tiles * (d.CoutPad / 256) >= min_tiles && useful >= 0.85;
+    if (!gdt_offsets_fit(d.N, d.H, d.W, d.Cin) || !gdt_offsets_fit(d.N, d.OH, d.OW, d.phase_cout)) return false;
+    return gdt_enough_tiles(gdt_patches(d.N, d.H, d.W), d.CoutPad / 256, knob_ct_min_tiles()) && gdt_useful_area(d.H, d.W) >= GDT_MIN_USEFUL_AREA;
 }
 
 int gdt_launch_conv_halo_ct(const ConvLaunch& d_in, hipStream_t stream) {
     ConvLaunch d = d_in;
     d.dbg = 0;
-    if (!d.in_norm) return launch_rb<256, 2, 4, 0, true>(d, stream);
-    return d.in_res ? launch_rb<256, 2, 4, 3, true>(d, stream) : launch_rb<256, 2, 4, 1, true>(d, stream);
+    return launch_rb_fold<true>(d, stream);
 }

@@ -322,26 +322,29 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_x3_kernel(const ConvLaunch d)
 
 }  // namespace
 
+GDT_KNOB_LIVE(knob_mode, CONV_HALO_X3, 1)                    // 0 off, 1 auto, 2 force (live: tests force the patch kernels at small batches)
+GDT_KNOB_LIVE(knob_forms_mode, CONV_HALO_X3_FORMS, 1)        // 0 off (A/B: the generic GEMM), 1 auto, 2 force
+
+// enough patches of the H x W grid the tiles cover to fill the chip with 128-column tiles, at most 15 % of their area padding
+static bool x3_fills_chip(const ConvLaunch& d, int H, int W) {
+    return gdt_enough_tiles(gdt_patches(d.N, H, W), d.CoutPad / 128, 512) && gdt_useful_area(H, W) >= GDT_MIN_USEFUL_AREA;
+}
+
 bool gdt_conv_halo_x3_eligible(const ConvLaunch& d) {
-    const char* e = getenv("GDT_CONV_HALO_X3");                 // 0 off, 1 auto, 2 force (read per call: tests force the patch kernels at small batches)
-    const int mode = e ? atoi(e) : 1;
+    const int mode = knob_mode();
     if (mode == 0) return false;
     const bool shape = d.ntaps == 9 && d.TW == 3 && d.sy == 1 && d.sx == 1 && d.dy0 == -1 && d.dx0 == -1 && d.dys == 1 && d.dxs == 1 &&
                        d.osy == 1 && d.osx == 1 && d.ooy == 0 && d.oox == 0 && d.Cin % 32 == 0 && !d.out_f32 && d.OH == d.H &&
                        d.OW == d.W && d.Kpad == 9 * d.Cin && d.CoutPad % 128 == 0 && d.w_lo != nullptr;
     if (!shape) return false;
     if (d.stats && ((d.H & 15) || (d.W & 15))) return false;
-    if (mode == 2) return true;
-    const long tiles = (long)d.N * ((d.W + 15) / 16) * ((d.H + 15) / 16);
-    const double useful = (double)d.H * d.W / ((double)((d.H + 15) / 16 * 16) * ((d.W + 15) / 16 * 16));
-    return tiles * (d.CoutPad / 128) >= 512 && useful >= 0.85;
+    return mode == 2 || x3_fills_chip(d, d.H, d.W);
 }
 
 // FORM 1 (a tap table inside the 3 x 3 window, strided output: the phase launches of a transposed conv) and FORM 2 (d.x3_form == 2: stride-2 3x3 conv over the
 // virtual space-to-depth view, net_plan.hip s2_geometry); plain InstanceNorm (+ReLU) folding only
 bool gdt_conv_halo_x3_taps_eligible(const ConvLaunch& d) {
-    const char* e = getenv("GDT_CONV_HALO_X3_FORMS");           // 0 off (A/B: the generic GEMM), 1 auto, 2 force (read per call)
-    const int mode = e ? atoi(e) : 1;
+    const int mode = knob_forms_mode();
     if (mode == 0 || !d.w_lo || d.out_f32 || d.in_res || d.in_out || d.pool2 || d.CoutPad % 128 != 0 || d.osy < 1 || d.osx < 1) return false;
     if (d.pair_cout && (d.pair_cout != 64 || d.CoutPad != 128 || d.Cout != 64 || d.x3_form != 0)) return false;      // paired phases: one 128-column tile = 2 x 64 channels
     if (d.x3_form == 2) {
@@ -356,32 +359,19 @@ bool gdt_conv_halo_x3_taps_eligible(const ConvLaunch& d) {
             if (dy < -1 || dy > 1 || dx < -1 || dx > 1) return false;
         }
     }
-    if ((long)d.N * d.H * d.W * (d.x3_form == 2 ? d.Cin / 4 : d.Cin) >= (1L << 31)) return false;
+    if (!gdt_offsets_fit(d.N, d.H, d.W, d.x3_form == 2 ? d.Cin / 4 : d.Cin, 31)) return false;
     if (d.stats && ((d.OHg & 15) || (d.OWg & 15))) return false;
-    if (mode == 2) return true;
-    const long tiles = (long)d.N * ((d.OWg + 15) / 16) * ((d.OHg + 15) / 16);
-    const double useful = (double)d.OHg * d.OWg / ((double)((d.OHg + 15) / 16 * 16) * ((d.OWg + 15) / 16 * 16));
-    return tiles * (d.CoutPad / 128) >= 512 && useful >= 0.85;
+    return mode == 2 || x3_fills_chip(d, d.OHg, d.OWg);
 }
 
 template <int FORM>
 static int launch_halo_x3(const ConvLaunch& d, hipStream_t stream) {
-    const int tiles = d.N * ((d.OWg + 15) / 16) * ((d.OHg + 15) / 16), ntn = d.CoutPad / BN;
     constexpr size_t lds = 2 * (size_t)STAGE_A + 2 * (size_t)STAGE_B;
-    static_assert(lds <= 160 * 1024 && (size_t)4 * BN * 8 <= lds, "LDS budget");
-    static GdtPerDevice per_dev;          // one attribute call per template instantiation AND device (gdt_common.h)
-    int attr_set = 0;
-    {
-        const int rc = gdt_per_device(per_dev, attr_set, [](int, int, int& v) {
-            v = 1;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_halo_x3_kernel<FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
-    hipLaunchKernelGGL(conv3x3_halo_x3_kernel<FORM>, dim3(gdt_grid_for_tiles(tiles, ntn)), dim3(NT), lds, stream, d);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    static_assert((size_t)4 * BN * 8 <= lds, "LDS budget");
+    using K = GdtKernel<conv3x3_halo_x3_kernel<FORM>, (int)lds>;
+    int unused = 0;
+    GDT_CHECK(K::figure(unused));
+    return K::launch(gdt_grid_for_tiles((int)gdt_patches(d.N, d.OHg, d.OWg), d.CoutPad / BN), NT, stream, d);
 }
 
 int gdt_launch_conv_halo_x3(const ConvLaunch& d, hipStream_t stream) { return launch_halo_x3<0>(d, stream); }

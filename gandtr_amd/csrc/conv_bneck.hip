@@ -479,45 +479,26 @@ __global__ __launch_bounds__(NT) void conv_bneck_multi_kernel(const MultiBneck m
 
 template <int C, int MID, int PH, int CIN = C, bool DS = false, bool RAGGED = false>
 int launch_multi(const BneckLaunch* dl, int L, hipStream_t stream) {
-    using G = Geo<C, MID, PH, CIN, DS>;
-    static GdtPerDevice per_dev;
+    using K = GdtKernel<conv_bneck_multi_kernel<C, MID, PH, CIN, DS, RAGGED>, Geo<C, MID, PH, CIN, DS>::LDS>;
     int cus = 0;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_bneck_multi_kernel<C, MID, PH, CIN, DS, RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
+    GDT_CHECK(K::figure(cus));
     MultiBneck m;
     m.nlev = L;
     int want[GDT_MAX_LEVELS];
     for (int l = 0; l < L; ++l) {
         m.lev[l] = dl[l];
-        m.ntiles[l] = dl[l].N * ((dl[l].W + PW - 1) / PW) * ((dl[l].H + PH - 1) / PH);
+        m.ntiles[l] = (int)gdt_patches(dl[l].N, dl[l].H, dl[l].W, PH, PW);
         want[l] = (m.ntiles[l] + 7) / 8 * 8;
     }
-    const int grid = gdt_multi_partition(m.prefix, want, L, cus);
-    hipLaunchKernelGGL((conv_bneck_multi_kernel<C, MID, PH, CIN, DS, RAGGED>), dim3(grid), dim3(NT), G::LDS, stream, m);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    return K::launch(gdt_multi_partition(m.prefix, want, L, cus), NT, stream, m);
 }
 
 template <int C, int MID, int PH, int CIN = C, bool DS = false, bool RAGGED = false>
 int launch(const BneckLaunch& d, hipStream_t stream) {
-    using G = Geo<C, MID, PH, CIN, DS>;
-    static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
+    using K = GdtKernel<conv_bneck_kernel<C, MID, PH, CIN, DS, RAGGED>, Geo<C, MID, PH, CIN, DS>::LDS>;
     int cus = 0;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_bneck_kernel<C, MID, PH, CIN, DS, RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
-    const int ntiles = d.N * ((d.W + PW - 1) / PW) * ((d.H + PH - 1) / PH);
+    GDT_CHECK(K::figure(cus));
+    const int ntiles = (int)gdt_patches(d.N, d.H, d.W, PH, PW);
     const int grid = min(cus, (ntiles + 7) / 8 * 8);
 #ifdef GDT_BNECK_STAMP
     static unsigned long long* sb = nullptr;
@@ -525,7 +506,7 @@ int launch(const BneckLaunch& d, hipStream_t stream) {
     if (!sb) GDT_CHECK_HIP(hipMalloc((void**)&sb, (size_t)cus * NWAVE * 4 * 8));
     BneckLaunch ds = d; ds.stamps = sb;
     GDT_CHECK_HIP(hipMemsetAsync(sb, 0, (size_t)cus * NWAVE * 4 * 8, stream));
-    hipLaunchKernelGGL((conv_bneck_kernel<C, MID, PH, CIN, DS, RAGGED>), dim3(grid), dim3(NT), G::LDS, stream, ds, ntiles);
+    GDT_CHECK(K::launch(grid, NT, stream, ds, ntiles));
     if (++calls % 50 < 3) {
         GDT_CHECK_HIP(hipStreamSynchronize(stream));
         std::vector<unsigned long long> h((size_t)grid * NWAVE * 4);
@@ -538,27 +519,26 @@ int launch(const BneckLaunch& d, hipStream_t stream) {
     }
     return GDT_OK;
 #endif
-    hipLaunchKernelGGL((conv_bneck_kernel<C, MID, PH, CIN, DS, RAGGED>), dim3(grid), dim3(NT), G::LDS, stream, d, ntiles);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    return K::launch(grid, NT, stream, d, ntiles);
 }
+
+GDT_KNOB_LIVE(knob_mode, CONV_BNECK, 1)                      // 0 off (live: a net reads it once per geometry it plans)
+GDT_KNOB_LATCHED(knob_min_tiles, "GDT_BNECK_MIN_TILES", 256)
 
 }  // namespace
 
 // Eligible: the three convs of an identity Bottleneck (checked by the planner in net_plan.hip) with (C, MID) = (256, 64) or (512, 128), maps that
 // the patches tile exactly, enough patches to fill the chip, offsets within 32 bits.
 bool gdt_bneck_eligible(int cin, int C, int mid, int N, int H, int W) {
-    const char* e = getenv("GDT_CONV_BNECK");          // 0: off (read at plan time, once per net and geometry: A/B inside one process)
-    if (e && atoi(e) == 0) return false;
+    if (knob_mode() == 0) return false;
     int ph = 0;
     if (C == 256 && mid == 64 && (cin == 256 || cin == 64)) ph = 16;        // cin 64: the projection-shortcut form (layer1's first block)
     else if (C == 512 && mid == 128 && cin == 512) ph = 8;
     else return false;
     // patches that hang over the image (ragged form) may waste at most 15 % of the patch area
-    if ((double)H * W / ((double)((H + ph - 1) / ph * ph) * ((W + PW - 1) / PW * PW)) < 0.85) return false;
-    if ((long)N * H * W * C >= (1L << 31)) return false;
-    static const int min_tiles = [] { const char* m = getenv("GDT_BNECK_MIN_TILES"); return m ? atoi(m) : 256; }();
-    return (long)N * ((H + ph - 1) / ph) * ((W + PW - 1) / PW) >= min_tiles;
+    if (gdt_useful_area(H, W, ph, PW) < GDT_MIN_USEFUL_AREA) return false;
+    if (!gdt_offsets_fit(N, H, W, C, 31)) return false;
+    return gdt_enough_tiles(gdt_patches(N, H, W, ph, PW), 1, knob_min_tiles());
 }
 
 int gdt_launch_bneck(const f16* x, f16* y, const f16* wr, const f16* w3, const f16* we, const float* br, const float* b3, const float* be,

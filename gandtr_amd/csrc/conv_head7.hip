@@ -418,40 +418,31 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
     }
 }
 
+GDT_KNOB_LATCHED(knob_mode, "GDT_CONV_HEAD7", 1)             // 0 off
+GDT_KNOB_LATCHED(knob_wgs, "GDT_HEAD7_WGS", 2)               // workgroups per CU
+GDT_KNOB_LATCHED(knob_dbg, "GDT_HEAD7_DBG", 0)
+
+template <bool F32, bool MX = false, bool X3 = false>
+int launch_head7(const ConvLaunch& d_in, hipStream_t stream) {
+    using K = GdtKernel<conv_head7_kernel<F32, MX, X3>, MX ? HBYTES + E_BYTES : HBYTES>;
+    int cus = 0;
+    GDT_CHECK(K::figure(cus));
+    const int ntiles = d_in.N * ((d_in.W + PW - 1) / PW) * ((d_in.H + PH - 1) / PH);
+    const int grid = min(knob_wgs() * cus, (ntiles + 7) / 8 * 8);     // two workgroups per CU: one loads while the other computes
+    ConvLaunch d = d_in;
+    d.dbg = knob_dbg();
+    return K::launch(grid, NT, stream, d, ntiles);
+}
+
 }  // namespace
 
 // 7x7 stride-1 pad-3 conv, 64 input channels, <= 4 output channels, fp32 NCHW output, fragment-ordered row-split weights
 bool gdt_conv_head7_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_HEAD7"); return e ? atoi(e) : 1; }();
-    return mode != 0 && d.w_frag && d.out_f32 && d.Cin == 64 && d.Cout >= 1 && d.Cout <= 4 && d.ntaps == KT &&
-           (long)d.N * d.H * d.W * 64 < (1L << 31);
+    return knob_mode() != 0 && d.w_frag && d.out_f32 && d.Cin == 64 && d.Cout >= 1 && d.Cout <= 4 && d.ntaps == KT && gdt_offsets_fit(d.N, d.H, d.W, 64, 31);
 }
 
 int gdt_launch_conv_head7(const ConvLaunch& d, hipStream_t stream) {
-    static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
-    int cus = 0;
-    constexpr int lds = HBYTES, lds_mx = HBYTES + E_BYTES;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_head7_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_head7_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_head7_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_mx));
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_head7_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
-    const int ntiles = d.N * ((d.W + PW - 1) / PW) * ((d.H + PH - 1) / PH);
-    static const int wgs = [] { const char* e = getenv("GDT_HEAD7_WGS"); return e ? atoi(e) : 2; }();
-    const int grid = min(wgs * cus, (ntiles + 7) / 8 * 8);     // two workgroups per CU: one loads while the other computes
-    static const int dbg = [] { const char* e = getenv("GDT_HEAD7_DBG"); return e ? atoi(e) : 0; }();
-    ConvLaunch dd = d;
-    dd.dbg = dbg;
-    if (d.in_f32 && d.w_frag2) hipLaunchKernelGGL((conv_head7_kernel<true, false, true>), dim3(grid), dim3(NT), lds, stream, dd, ntiles);       // f16x3: w_frag2 = the lo parts
-    else if (d.in_f32 && d.wmx_a && d.wmx_b && d.wmx_s) hipLaunchKernelGGL((conv_head7_kernel<true, true>), dim3(grid), dim3(NT), lds_mx, stream, dd, ntiles);
-    else if (d.in_f32) hipLaunchKernelGGL(conv_head7_kernel<true>, dim3(grid), dim3(NT), lds, stream, dd, ntiles);
-    else hipLaunchKernelGGL(conv_head7_kernel<false>, dim3(grid), dim3(NT), lds, stream, dd, ntiles);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    if (d.in_f32 && d.w_frag2) return launch_head7<true, false, true>(d, stream);       // f16x3: w_frag2 = the lo parts
+    if (d.in_f32 && d.wmx_a && d.wmx_b && d.wmx_s) return launch_head7<true, true>(d, stream);
+    return d.in_f32 ? launch_head7<true>(d, stream) : launch_head7<false>(d, stream);
 }

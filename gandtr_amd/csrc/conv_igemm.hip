@@ -274,26 +274,16 @@ constexpr size_t lds_bytes() {
 
 template <int BM, int BN, int WGM, int WGN, bool NORM = false>
 int launch_cfg(const ConvLaunch& d, hipStream_t stream) {
-    const int ntm = (d.M + BM - 1) / BM, ntn = d.CoutPad / BN;
-    constexpr size_t lds = lds_bytes<BM, BN, WGM, WGN>();
-    static_assert(lds <= 160 * 1024, "LDS budget (160 KiB per CU on gfx950)");
-    if (lds > 64 * 1024) {
-        static GdtPerDevice per_dev;          // one attribute call per template instantiation AND device (gdt_common.h)
-        int attr_set = 0;
-        {
-            const int rc = gdt_per_device(per_dev, attr_set, [](int, int, int& v) {
-                v = 1;
-                GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_igemm_kernel<BM, BN, WGM, WGN, NORM>,
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                return GDT_OK;
-            });
-            if (rc != GDT_OK) return rc;
-        }
-    }
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, NORM>), dim3(gdt_grid_for_tiles(ntm, ntn)), dim3(WGM * WGN * 64), lds, stream, d);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    using K = GdtKernel<conv_igemm_kernel<BM, BN, WGM, WGN, NORM>, (int)lds_bytes<BM, BN, WGM, WGN>()>;
+    int unused = 0;
+    if (lds_bytes<BM, BN, WGM, WGN>() > 64 * 1024) GDT_CHECK(K::figure(unused));      // (up to 64 KB need no set-up)
+    return K::launch(gdt_grid_for_tiles((d.M + BM - 1) / BM, d.CoutPad / BN), WGM * WGN * 64, stream, d);
 }
+
+GDT_KNOB_LATCHED(knob_pool, "GDT_CONV_POOL", 1)              // 0: no 2x2 max pool fused into the patch kernels' epilogue
+GDT_KNOB_LATCHED(knob_dbg, "GDT_CONV_DBG", 0)                // timing-only ablation: 1 skip staging loads, 2 skip MFMAs
+GDT_KNOB_LATCHED(knob_force_tile, "GDT_CONV_TILE", 0)        // test knob: 128 / 256 forces the M tile
+GDT_KNOB_LATCHED(knob_min_nk, "GDT_CONV_MINK", 0)            // fewest K-steps for the 256-row tiles
 
 }  // namespace
 
@@ -306,8 +296,7 @@ bool gdt_conv_igemm_norm_eligible(const ConvLaunch& d) {
 // A fused 2x2 max pool needs a patch kernel (16x16 patches: conv3x3_halo_rb.hip / conv3x3_halo.hip) and a plain
 // epilogue (no statistics, residual or write-back).
 bool gdt_conv_pool2_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_POOL"); return e ? atoi(e) : 1; }();
-    if (mode == 0 || d.H < 2 || d.W < 2 || d.stats || d.res || d.in_out || d.out_f32 || d.phase_cout) return false;
+    if (knob_pool() == 0 || d.H < 2 || d.W < 2 || d.stats || d.res || d.in_out || d.out_f32 || d.phase_cout) return false;
     return gdt_conv_halo_rb_eligible(d) || gdt_conv_halo_eligible(d);
 }
 
@@ -326,9 +315,8 @@ int gdt_conv_family(const ConvLaunch& d) {
 
 int gdt_launch_conv(const ConvLaunch& d_in, hipStream_t stream, int* variant) {
     int vdummy; if (!variant) variant = &vdummy;
-    static const int dbg = [] { const char* e = getenv("GDT_CONV_DBG"); return e ? atoi(e) : 0; }();
     ConvLaunch d = d_in;
-    d.dbg = dbg;
+    d.dbg = knob_dbg();
     GDT_REQUIRE(d.Cin >= 8 && (d.Cin & (d.Cin - 1)) == 0, "Cin must be a power of two >= 8");
     GDT_REQUIRE((1 << d.lc8) * 8 == d.Cin, "lc8 mismatch");
     GDT_REQUIRE(d.Kpad % BK == 0 && d.nk == d.Kpad / BK && d.nk >= 1, "Kpad must be a multiple of 64");
@@ -359,9 +347,8 @@ int gdt_launch_conv(const ConvLaunch& d_in, hipStream_t stream, int* variant) {
     // large problems: 256-row tiles with 8 wavefronts (half the L2->LDS bytes per FLOP of the 128x128 tile); the grid must
     // still cover the 256 CUs a few times over
     const long tiles256 = ((long)d.M + 255) / 256;
-    static const int force_tile = [] { const char* e = getenv("GDT_CONV_TILE"); return e ? atoi(e) : 0; }();   // test knob
+    const int force_tile = knob_force_tile(), min_nk = knob_min_nk();
     const long min_blocks = force_tile == 256 ? 1 : 512;
-    static const int min_nk = [] { const char* e = getenv("GDT_CONV_MINK"); return e ? atoi(e) : 0; }();
     if (force_tile != 128 && (d.nk >= min_nk || force_tile == 256)) {
         if (!d.in_norm && d.CoutPad % 256 == 0 && tiles256 * (d.CoutPad / 256) >= min_blocks) { *variant = 256256; return launch_cfg<256, 256, 2, 4>(d, stream); }
         if (bn == 128 && tiles256 * (d.CoutPad / 128) >= min_blocks) { *variant = 256128; return launch_cfg<256, 128, 4, 2>(d, stream); }

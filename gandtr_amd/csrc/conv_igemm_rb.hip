@@ -376,24 +376,16 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_rb_kernel(const Con
 
 template <int BN, int WGM, int WGN, bool NORM, bool CTF = false>
 int launch_irb(const ConvLaunch& d, hipStream_t stream) {
-    constexpr size_t lds = irb_lds_bytes<BN, WGM>();
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
+    using K = GdtKernel<conv_igemm_rb_kernel<BN, WGM, WGN, NORM, CTF>, (int)irb_lds_bytes<BN, WGM>()>;
     int cus = 0;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_igemm_rb_kernel<BN, WGM, WGN, NORM, CTF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
+    GDT_CHECK(K::figure(cus));
     const int vblocks = gdt_grid_for_tiles((d.M + BM - 1) / BM, d.CoutPad / BN);
-    const int grid = vblocks < cus ? vblocks : cus;
-    hipLaunchKernelGGL((conv_igemm_rb_kernel<BN, WGM, WGN, NORM, CTF>), dim3(grid), dim3(WGM * WGN * 64), lds, stream, d, vblocks);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    return K::launch(vblocks < cus ? vblocks : cus, WGM * WGN * 64, stream, d, vblocks);
 }
+
+GDT_KNOB_LATCHED(knob_mode, "GDT_CONV_IRB", 1)               // 0 off, 2 force
+GDT_KNOB_LATCHED(knob_min_tiles, "GDT_IRB_MIN_TILES", 256)
+GDT_KNOB_LATCHED(knob_dbg, "GDT_IRB_DBG", 0)
 
 }  // namespace
 
@@ -408,11 +400,11 @@ int gdt_conv_igemm_rb_stats_sets(const ConvLaunch& d) {
 }
 
 bool gdt_conv_igemm_rb_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_IRB"); return e ? atoi(e) : 1; }();   // 0 off, 2 force
+    const int mode = knob_mode();
     if (mode == 0 || !d.w_frag || d.out_f32 || !d.out || d.Cin % 64 != 0 || d.Kpad != d.ntaps * d.Cin || d.Kpad < 128) return false;
     if (d.CoutPad % 64 != 0 || d.Cout % 8 != 0 || d.in_res || d.in_out) return false;
     if (d.phase_cout && (d.CoutPad % 256 != 0 || 256 % d.phase_cout != 0 || d.phase_cout < 64 || d.Cout != 4 * d.phase_cout || d.res || d.M % 128 != 0)) return false;
-    if ((long)d.N * d.H * d.W * d.Cin >= (1L << 32) || (long)d.N * d.OH * d.OW * (d.phase_cout ? d.phase_cout : d.Cout) >= (1L << 32)) return false;
+    if (!gdt_offsets_fit(d.N, d.H, d.W, d.Cin) || !gdt_offsets_fit(d.N, d.OH, d.OW, d.phase_cout ? d.phase_cout : d.Cout)) return false;
     if (d.stats && ((d.OHg * d.OWg) % 128 != 0 || d.CoutPad % 128 != 0 || d.M % 128 != 0)) return false;    // (64-wide tiles with statistics: conv_igemm.hip measured faster)
     if (d.in_norm && (d.Cin > 256 || (d.OHg * d.OWg) % BM != 0)) return false;
     if (mode == 2) return true;
@@ -420,14 +412,12 @@ bool gdt_conv_igemm_rb_eligible(const ConvLaunch& d) {
     // with conv_igemm.hip on the plain 1x1 convs of ResNet-101 (1526 vs 1545 descriptors/s) and was used only where it also
     // folds an InstanceNorm; with the wave-private epilogue it is ahead there too (1777 vs 1671).
     const int bn = d.CoutPad % 256 == 0 ? 256 : (d.CoutPad % 128 == 0 ? 128 : 64);
-    static const int min_tiles = [] { const char* e = getenv("GDT_IRB_MIN_TILES"); return e ? atoi(e) : 256; }();
-    return (long)((d.M + BM - 1) / BM) * (d.CoutPad / bn) >= min_tiles;
+    return gdt_enough_tiles((d.M + BM - 1) / BM, d.CoutPad / bn, knob_min_tiles());
 }
 
 int gdt_launch_conv_igemm_rb(const ConvLaunch& d_in, hipStream_t stream, int* variant) {
-    static const int dbg = [] { const char* e = getenv("GDT_IRB_DBG"); return e ? atoi(e) : 0; }();
     ConvLaunch d = d_in;
-    d.dbg = dbg;
+    d.dbg = knob_dbg();
     const int bn = d.CoutPad % 256 == 0 ? 256 : (d.CoutPad % 128 == 0 ? 128 : 64);
     *variant = 940000 + bn;
     if (d.phase_cout) return d.in_norm ? launch_irb<256, 2, 4, true, true>(d, stream) : launch_irb<256, 2, 4, false, true>(d, stream);

@@ -268,21 +268,12 @@ template <int KS, int S, bool AUG = false>
 int launch_stem(const ConvLaunch& d, hipStream_t stream) {
     using C = StemCfg<KS, S>;
     static_assert(2 * C::LDS <= 160 * 1024, "two workgroups per CU");
-    static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
+    using K = GdtKernel<conv_stem_kernel<KS, S, AUG>, C::LDS>;
     int cus = 0;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_stem_kernel<KS, S, AUG>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
+    GDT_CHECK(K::figure(cus));
     const int ntiles = d.N * ((d.OW + TW - 1) / TW) * ((d.OH + C::TH - 1) / C::TH);
     const int grid = min(2 * cus, (ntiles + 7) / 8 * 8);
-    hipLaunchKernelGGL((conv_stem_kernel<KS, S, AUG>), dim3(grid), dim3(NT), C::LDS, stream, d, ntiles);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    return K::launch(grid, NT, stream, d, ntiles);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -642,13 +633,15 @@ __global__ __launch_bounds__(NT, 2) void conv_stem_pair_pool_kernel(const ConvLa
     }
 }
 
+GDT_KNOB_LATCHED(knob_mode, "GDT_CONV_STEM", 1)              // 0 off (the fp16 and the f16c form)
+GDT_KNOB_LATCHED(knob_pair_mode, "GDT_CONV_STEM_PAIR", 1)    // 0 off
+
 }  // namespace
 
 // 8-channel (image) input, exactly 64 output channels, fp16 NHWC output, 7x7 (stride 1 or 2, pad 3) or 3x3 (stride 1, pad 1);
 // fused statistics need whole 128-pixel records per wave: stride 1 and OW % 32 == 0, OH % 16 == 0.
 bool gdt_conv_stem_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_STEM"); return e ? atoi(e) : 1; }();
-    if (mode == 0 || !d.w_frag || d.Cin != 8 || d.Cout != 64 || d.CoutPad != 64 || d.out_f32 || !d.out || d.res || d.in_norm || d.pool2) return false;
+    if (knob_mode() == 0 || !d.w_frag || d.Cin != 8 || d.Cout != 64 || d.CoutPad != 64 || d.out_f32 || !d.out || d.res || d.in_norm || d.pool2) return false;
     if (d.sy != d.sx || d.dys != 1 || d.dxs != 1 || d.osy != 1 || d.osx != 1 || d.ooy != 0 || d.oox != 0) return false;
     const bool k7 = d.ntaps == 49 && d.TW == 7 && d.dy0 == -3 && d.dx0 == -3 && (d.sy == 1 || d.sy == 2);
     const bool k3 = d.ntaps == 9 && d.TW == 3 && d.dy0 == -1 && d.dx0 == -1 && d.sy == 1;
@@ -656,7 +649,7 @@ bool gdt_conv_stem_eligible(const ConvLaunch& d) {
     if (d.pad_reflect && (d.H <= 3 || d.W <= 3)) return false;
     if (d.stats && (d.sy != 1 || d.OW % 32 != 0 || d.OH % 16 != 0)) return false;
     // (pixel indices are ints, element offsets longs: 32 x 3 x 1024 x 1024 -> 2^31 output elements is fine)
-    return (long)d.N * d.OH * d.OW < (1L << 31) && (long)d.N * d.H * d.W < (1L << 31) && (long)d.N * d.OH * d.OW >= 65536;
+    return gdt_offsets_fit(d.N, d.OH, d.OW, 1, 31) && gdt_offsets_fit(d.N, d.H, d.W, 1, 31) && (long)d.N * d.OH * d.OW >= 65536;
 }
 
 int gdt_launch_conv_stem(const ConvLaunch& d, hipStream_t stream) {
@@ -667,15 +660,14 @@ int gdt_launch_conv_stem(const ConvLaunch& d, hipStream_t stream) {
 // "f16c" form (AUG): the input tensor holds augmented fp16 pixel words (gdt_k_pack_input, aug = 1), weights W1 (augmented, w_frag) and W2
 // (residuals, w_frag2) in the stem fragment order; fp32 NHWC output.  Same shapes as the fp16 form.
 bool gdt_conv_stem_c_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_STEM"); return e ? atoi(e) : 1; }();
-    if (mode == 0 || !d.w_frag || !d.w_frag2 || d.Cin != 8 || d.Cout != 64 || d.CoutPad != 64 || d.out_f32 || !d.out || d.res || d.in_norm || d.pool2) return false;
+    if (knob_mode() == 0 || !d.w_frag || !d.w_frag2 || d.Cin != 8 || d.Cout != 64 || d.CoutPad != 64 || d.out_f32 || !d.out || d.res || d.in_norm || d.pool2) return false;
     if (d.sy != d.sx || d.dys != 1 || d.dxs != 1 || d.osy != 1 || d.osx != 1 || d.ooy != 0 || d.oox != 0) return false;
     const bool k7 = d.ntaps == 49 && d.TW == 7 && d.dy0 == -3 && d.dx0 == -3 && (d.sy == 1 || d.sy == 2);
     const bool k3 = d.ntaps == 9 && d.TW == 3 && d.dy0 == -1 && d.dx0 == -1 && d.sy == 1;
     if (!k7 && !k3) return false;
     if (d.pad_reflect && (d.H <= 3 || d.W <= 3)) return false;
     if (d.stats && (d.sy != 1 || d.OW % 32 != 0 || d.OH % 16 != 0)) return false;
-    return (long)d.N * d.OH * d.OW * 64 < (1L << 32) && (long)d.N * d.H * d.W < (1L << 31) && (long)d.N * d.OH * d.OW >= 65536;      // (unsigned 32-bit element offsets in the fp32 epilogue)
+    return gdt_offsets_fit(d.N, d.OH, d.OW, 64) && gdt_offsets_fit(d.N, d.H, d.W, 1, 31) && (long)d.N * d.OH * d.OW >= 65536;      // (unsigned 32-bit element offsets in the fp32 epilogue)
 }
 
 int gdt_launch_conv_stem_c(const ConvLaunch& d, hipStream_t stream) {
@@ -687,34 +679,24 @@ int gdt_launch_conv_stem_c(const ConvLaunch& d, hipStream_t stream) {
 // Direct form of the ResNet stem (see conv_stem_pair_kernel): the descriptor is the stem conv's (H, W = the image, w_frag = the pair-packed weights of
 // net_build.hip, fp16 NHWC output), x the caller's fp32 NCHW image with at most 3 channels, perm / scale / shift the input op's per-channel transform.
 bool gdt_conv_stem_pair_eligible(const ConvLaunch& d) {
-    static const int mode = [] { const char* e = getenv("GDT_CONV_STEM_PAIR"); return e ? atoi(e) : 1; }();
-    if (mode == 0 || !d.w_frag || d.Cout != 64 || d.CoutPad != 64 || d.out_f32 || !d.out || d.res || d.in_norm || d.pool2 || d.stats || d.pad_reflect) return false;
+    if (knob_pair_mode() == 0 || !d.w_frag || d.Cout != 64 || d.CoutPad != 64 || d.out_f32 || !d.out || d.res || d.in_norm || d.pool2 || d.stats || d.pad_reflect) return false;
     const bool k7s2 = d.ntaps == 49 && d.TW == 7 && d.dy0 == -3 && d.dx0 == -3 && d.sy == 2 && d.sx == 2;
     const bool k3s1 = d.ntaps == 9 && d.TW == 3 && d.dy0 == -1 && d.dx0 == -1 && d.sy == 1 && d.sx == 1;
     if ((!k7s2 && !k3s1) || d.dys != 1 || d.dxs != 1) return false;
     if (d.osy != 1 || d.osx != 1 || d.ooy != 0 || d.oox != 0 || d.H < 8 || d.W < 8) return false;
-    return (long)d.N * d.OH * d.OW < (1L << 31) && (long)d.H * d.W < (1L << 31) && (long)d.N * d.OH * d.OW >= 65536;
+    return gdt_offsets_fit(d.N, d.OH, d.OW, 1, 31) && gdt_offsets_fit(1, d.H, d.W, 1, 31) && (long)d.N * d.OH * d.OW >= 65536;
 }
 
 template <int KS, int S>
 static int launch_stem_pair(const ConvLaunch& d, const StemPairArgs& a, hipStream_t stream) {
     using C = PairCfg<KS, S>;
     static_assert(2 * C::LDS <= 160 * 1024, "two workgroups per CU");
-    static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
+    using K = GdtKernel<conv_stem_pair_kernel<KS, S>, C::LDS>;
     int cus = 0;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_stem_pair_kernel<KS, S>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
+    GDT_CHECK(K::figure(cus));
     const int ntiles = d.N * ((d.OW + TW - 1) / TW) * ((d.OH + C::TH - 1) / C::TH);
     const int grid = min(2 * cus, (ntiles + 7) / 8 * 8);
-    hipLaunchKernelGGL((conv_stem_pair_kernel<KS, S>), dim3(grid), dim3(NT), C::LDS, stream, d, a, ntiles);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    return K::launch(grid, NT, stream, d, a, ntiles);
 }
 
 int gdt_launch_conv_stem_pair(const ConvLaunch& d, const float* x, int C, const int* perm, const float* scale, const float* shift, hipStream_t stream) {
@@ -731,23 +713,14 @@ int gdt_launch_conv_stem_pair_pool(const ConvLaunch& d, const float* x, int C, c
     GDT_REQUIRE(x != nullptr && C >= 1 && C <= 3, "stem: 1..3 image channels");
     GDT_REQUIRE(PH == (d.OH - 1) / 2 + 1 && PW == (d.OW - 1) / 2 + 1, "stem: pooled size");
     static_assert(2 * SQ_LDS <= 160 * 1024, "two workgroups per CU");
-    static GdtPerDevice per_dev;          // (hipFuncSetAttribute is per device: gdt_common.h)
+    using K = GdtKernel<conv_stem_pair_pool_kernel, SQ_LDS>;
     int cus = 0;
-    {
-        const int rc = gdt_per_device(per_dev, cus, [](int, int ncu, int& v) {
-            v = ncu / 8 * 8;
-            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)conv_stem_pair_pool_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SQ_LDS));
-            return GDT_OK;
-        });
-        if (rc != GDT_OK) return rc;
-    }
+    GDT_CHECK(K::figure(cus));
     StemPairArgs a;
     a.x = x; a.C = C;
     for (int c = 0; c < 4; ++c) { a.perm[c] = c < C ? perm[c] : 0; a.scale[c] = c < C ? scale[c] : 0.f; a.shift[c] = c < C ? shift[c] : 0.f; }
     const int ntiles = d.N * ((PW + 14) / 15) * ((PH + 6) / 7);
     const int grid = min(2 * cus, (ntiles + 7) / 8 * 8);
-    hipLaunchKernelGGL(conv_stem_pair_pool_kernel, dim3(grid), dim3(NT), SQ_LDS, stream, d, a, ntiles, PH, PW);
-    GDT_CHECK_HIP(hipGetLastError());
-    return GDT_OK;
+    return K::launch(grid, NT, stream, d, a, ntiles, PH, PW);
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <mutex>
 #include <string>
 
@@ -40,33 +41,67 @@ void gdt_set_error(const std::string& msg);
         }                                                                                       \
     } while (0)
 
-// ---- one-time set-up of a kernel PER DEVICE ----
+#define GDT_CHECK(expr)                                                                         \
+    do {                                                                                        \
+        const int _rc = (expr);                                                                 \
+        if (_rc != GDT_OK) return _rc;                                                          \
+    } while (0)
+
+// ---- environment knobs (the table of all of them: DESIGN.md, "Knobs") ----
+// The only getenv of the library.  Every knob is ONE named accessor in the file that uses it, declared with one of the macros below: its name, default
+// and latch class are written there once.  LATCHED knobs are read at the accessor's first call and hold for the process; LIVE knobs are read at every
+// call -- a net reads them whenever it plans a geometry, so one process can A/B them -- and must be part of anything that caches a plan: they exist
+// only as entries of GDT_LIVE_KNOBS, which is also what gdt_plan_knob_name() (include/gandtr_hip.h) hands to such a cache.
+inline int gdt_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline bool gdt_env_set(const char* name) { return getenv(name) != nullptr; }
+#define GDT_LIVE_KNOBS(X) X(CONV_XEXP) X(XEXP_CHAIN) X(CONV_BNECK) X(CONV_HALO_X3) X(CONV_HALO_X3_FORMS) X(X3_NORM_FOLD)
+#define GDT_LIVE_KNOB_NAME(id) "GDT_" #id,
+constexpr const char* GDT_LIVE_KNOB_NAMES[] = { GDT_LIVE_KNOBS(GDT_LIVE_KNOB_NAME) };
+#define GDT_LIVE_KNOB_ID(id) GDT_LIVE_##id,
+enum GdtLiveKnob { GDT_LIVE_KNOBS(GDT_LIVE_KNOB_ID) GDT_LIVE_KNOB_COUNT };
+#define GDT_KNOB_LATCHED(fn, name, dflt) [[maybe_unused]] static int fn() { static const int v = gdt_env_int(name, dflt); return v; }
+#define GDT_KNOB_LATCHED_SET(fn, name) [[maybe_unused]] static bool fn() { static const bool v = gdt_env_set(name); return v; }      // presence, whatever the value
+#define GDT_KNOB_LIVE(fn, id, dflt) [[maybe_unused]] static int fn() { return gdt_env_int(GDT_LIVE_KNOB_NAMES[GDT_LIVE_##id], dflt); }
+
+// ---- a kernel's launcher: its dynamic-LDS set-up PER DEVICE, its cached CU figure, its launch ----
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the current device only, and a process may build nets on several GPUs and launch from
-// several threads (the JPEG staging explicitly supports that): the launchers keep their "done" state per device id behind a mutex.  `setup(dev, cus,
-// value)` runs once per device with the device's CU count and leaves the launcher's cached figure in `value` (non-zero).
-struct GdtPerDevice {
-    std::mutex mu;
-    int value[64] = {};
+// several threads (the JPEG staging explicitly supports that): the "done" state is kept per device id behind a mutex, one per kernel instantiation
+// (the kernel is the template argument: it is named once).  figure() does the set-up on the device's first use and hands back the figure cached with
+// it: the CU count rounded down to whole XCD rounds, or what `fig(ncu, value)` makes of the CU count (non-zero).  launch() = launch + hipGetLastError.
+inline int gdt_whole_xcd_rounds(int ncu, int& v) { v = ncu / 8 * 8; return GDT_OK; }
+template <auto Kernel, int LDS>
+struct GdtKernel {
+    static_assert(LDS <= 160 * 1024, "LDS budget");
+    template <typename Fig>
+    static int figure(int& out, Fig&& fig) {
+        static std::mutex mu;
+        static int value[64] = {};
+        int dev = 0;
+        GDT_CHECK_HIP(hipGetDevice(&dev));
+        if (dev < 0 || dev >= 64) {
+            gdt_set_error("device id out of range");
+            return GDT_ERR_INVALID;
+        }
+        std::lock_guard<std::mutex> lock(mu);
+        if (!value[dev]) {
+            int cus = 0;
+            GDT_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+            GDT_CHECK_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+            int v = 0;
+            GDT_CHECK(fig(cus, v));
+            value[dev] = v ? v : 1;
+        }
+        out = value[dev];
+        return GDT_OK;
+    }
+    static int figure(int& out) { return figure(out, gdt_whole_xcd_rounds); }
+    template <typename... Args>
+    static int launch(int grid, int block, hipStream_t stream, const Args&... args) {
+        hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), LDS, stream, args...);
+        GDT_CHECK_HIP(hipGetLastError());
+        return GDT_OK;
+    }
 };
-template <typename Setup>
-inline int gdt_per_device(GdtPerDevice& st, int& out, Setup&& setup) {
-    int dev = 0;
-    GDT_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) {
-        gdt_set_error("device id out of range");
-        return GDT_ERR_INVALID;
-    }
-    std::lock_guard<std::mutex> lock(st.mu);
-    if (!st.value[dev]) {
-        int cus = 0, v = 0;
-        GDT_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        const int rc = setup(dev, cus, v);
-        if (rc != GDT_OK) return rc;
-        st.value[dev] = v ? v : 1;
-    }
-    out = st.value[dev];
-    return GDT_OK;
-}
 
 // ---- implicit-GEMM convolution launch descriptor ----
 // Activations are NHWC fp16; weights are packed [CoutPad][Kpad] fp16 with k = tap * Cin + c.
@@ -212,6 +247,28 @@ __device__ __forceinline__ bool gdt_tile_of_block(int b, int ntm, int ntn, int& 
     return lm < mchunk && tile_m < ntm;
 }
 inline int gdt_grid_for_tiles(int ntm, int ntn) { return 8 * ((ntm + 7) / 8) * ntn; }
+
+// ---- tile arithmetic of the patch kernels (host: what the eligibility predicates and the launchers count) ----
+// patches of `ph` rows x `pw` columns that tile N images of H x W (ragged edges count as whole patches)
+inline long gdt_patches(int N, int H, int W, int ph = 16, int pw = 16) { return (long)N * ((W + pw - 1) / pw) * ((H + ph - 1) / ph); }
+// share of those patches' pixels that lies inside an H x W image; the patch kernels want GDT_MIN_USEFUL_AREA of it (padded patches are wasted work)
+inline double gdt_useful_area(int H, int W, int ph = 16, int pw = 16) { return (double)H * W / ((double)((H + ph - 1) / ph * ph) * ((W + pw - 1) / pw * pw)); }
+constexpr double GDT_MIN_USEFUL_AREA = 0.85;
+// "enough tiles to fill the chip": patches x column tiles against a form's threshold
+inline bool gdt_enough_tiles(long patches, int column_tiles, int min_tiles) { return patches * column_tiles >= min_tiles; }
+// element offsets of an [N][H][W][C] tensor fit `bits` bits (the kernels index with 32-bit offsets; the f16c halo staging with 30)
+inline bool gdt_offsets_fit(int N, int H, int W, int C, int bits = 32) { return (long)N * H * W * C < (1L << bits); }
+
+// ---- fold modes of the patch kernels: the MODE template bits ----
+// 1: the producer's InstanceNorm (+ReLU) applied while staging (in_norm); 2: ... then + residual (in_res); 4: ... and the transformed input written back
+// (in_out).  The residual and the write-back ride on the norm's staging pass: without a folded norm the mode is 0.  Every kernel file maps the mode onto the
+// set it instantiates with a small dispatcher; a mode outside that set is refused with gdt_fold_refused, never instantiated on the side.
+enum { GDT_FOLD_NORM = 1, GDT_FOLD_RES = 2, GDT_FOLD_OUT = 4 };
+inline int gdt_fold_mode(const ConvLaunch& d) { return d.in_norm ? GDT_FOLD_NORM | (d.in_res ? GDT_FOLD_RES : 0) | (d.in_out ? GDT_FOLD_OUT : 0) : 0; }
+inline int gdt_fold_refused(int mode) {
+    GDT_REQUIRE(mode != (GDT_FOLD_NORM | GDT_FOLD_RES), "residual fold without write-back target");
+    GDT_REQUIRE(false, "fold mode " + std::to_string(mode) + " does not exist in this form of the kernel");
+}
 
 int gdt_launch_conv(const ConvLaunch& d, hipStream_t stream, int* variant = nullptr);
 int gdt_conv_family(const ConvLaunch& d);                  // conv_igemm.hip: 1 conv1x1_rb, 2 conv3x3_halo_rb, 0 other (the families with a multi-geometry entry)

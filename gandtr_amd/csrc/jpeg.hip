@@ -42,6 +42,8 @@
 
 namespace {
 
+GDT_KNOB_LATCHED_SET(knob_trace, "GDT_JPEG_TRACE")           // set: the repair rounds of the parallel entropy decoder are printed
+
 constexpr unsigned SUB_BITS = 1024;          // bits per piece of the parallel entropy decoder
 constexpr size_t ALIGN = 256;
 
@@ -737,8 +739,7 @@ int run_decode(const gdt_jpeg_item* items, int n, int mode, const Plan& p, char*
             converged = flags[group - 1] == 0;
         }
         if (!converged) { gdt_set_error("jpeg: the parallel entropy decoder did not reach a fixed point"); return GDT_ERR_NOT_CONVERGED; }
-        static const bool trace = getenv("GDT_JPEG_TRACE") != nullptr;
-        if (trace) fprintf(stderr, "[jpeg] %d files, %u intervals, %u pieces (longest interval %u): fixed point after %u repair rounds\n", n, nseg, p.nsub, longest, round);
+        if (knob_trace()) fprintf(stderr, "[jpeg] %d files, %u intervals, %u pieces (longest interval %u): fixed point after %u repair rounds\n", n, nseg, p.nsub, longest, round);
         hipLaunchKernelGGL(jpeg_scan_kernel, dim3(nseg), dim3(256), 0, stream, d_segs, d_nblk, d_blk0);
     } else {
         GDT_CHECK_HIP(hipMemsetAsync(d_blk0, 0, (size_t)p.nsub * 4, stream));

@@ -8,6 +8,8 @@
 
 using namespace gdtn;
 
+GDT_KNOB_LATCHED(knob_head7_x3, "GDT_HEAD7_X3", 1)           // 0: the f16x3 head stays on the generic GEMM + combine launch (A/B)
+
 static thread_local std::string g_last_error;
 void gdt_set_error(const std::string& msg) { g_last_error = msg; }
 
@@ -305,7 +307,7 @@ static void pack_rowsplit(ConvPack& cp) {
                 }
     ph.w_off = net->blob_append(pk.data(), pk.size() * sizeof(f16));
     if (net->precision) ph.w_lo_off = net->blob_append(pl.data(), pl.size() * sizeof(f16));
-    static const bool head7_x3 = env_int("GDT_HEAD7_X3", 1) != 0;      // 0: the f16x3 head stays on the generic GEMM + combine launch (A/B)
+    const bool head7_x3 = knob_head7_x3() != 0;
     if ((net->precision != 1 || head7_x3) && cin_pad == 64 && cd.kh == 7 && cd.kw == 7 && o.cout_pad == 32) {
         // conv_head7.hip keeps the whole matrix in registers: B fragment ks of lane (fh, fr) = column fr, k = ks*16 + fh*8 ..
         std::vector<f16> pf = frag_order(pk, o.cout_pad, ph.Kpad);

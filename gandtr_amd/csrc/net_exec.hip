@@ -4,6 +4,8 @@
 
 using namespace gdtn;
 
+GDT_KNOB_LATCHED_SET(knob_levels_debug, "GDT_LEVELS_DEBUG")  // set: what every op of gdt_net_forward_levels handed to the lock-step driver is printed
+
 namespace {
 
 // one geometry of a forward: its input, outputs, workspace and the plan made for it (a snapshot of the planned tensor table: make_plan works on net->tensors)
@@ -362,8 +364,7 @@ int forward_levels(gdt_net* net, LevelCtx* cx, int L, hipStream_t st) {
                 else if (fam == 2 && gdt_conv_halo_rb_levels_ok(dl, L)) { rc = gdt_launch_conv_halo_rb_levels(dl, L, st); joined = true; if (net->profiling) net->last_variant[i] = 910256; }
             }
             if (joined) ++net->last_joined;
-            static const bool lv_dbg = getenv("GDT_LEVELS_DEBUG") != nullptr;
-            if (lv_dbg && (nconv || nbneck)) {
+            if (knob_levels_debug() && (nconv || nbneck)) {
                 fprintf(stderr, "[levels] op %d joined %d:", i, (int)joined);
                 for (int l = 0; l < L; ++l) {
                     if (df[l].kind == DEFER_CONV) fprintf(stderr, " [conv%s fam %d M %d Cin %d Cout %d taps %d s%d]", df[l].kcat ? " kcat" : "", gdt_conv_family(df[l].d), df[l].d.M, df[l].d.Cin, df[l].d.Cout, df[l].d.ntaps, df[l].d.sy);

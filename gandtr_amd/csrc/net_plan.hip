@@ -4,6 +4,13 @@
 
 using namespace gdtn;
 
+GDT_KNOB_LATCHED(knob_ctf, "GDT_CONV_CTF", 1)                // transposed convs as one fused launch: 0 never, 1 where it pays (Planner::conv_forms), 2 whenever eligible
+GDT_KNOB_LATCHED(knob_norm_fusion, "GDT_NORM_FUSION", 1)     // 0: no InstanceNorm is folded into its consumer
+GDT_KNOB_LIVE(knob_x3_norm_fold, X3_NORM_FOLD, 2)            // f16x3: 0 no folded norms, 1 the plain norm (+ReLU) only, 2 also residual / write-back and the generic GEMM
+GDT_KNOB_LIVE(knob_xexp, CONV_XEXP, 1)                       // 0: no 3x3 + expand fusion (conv3x3_expand_rb.hip)
+GDT_KNOB_LATCHED(knob_stem_pool, "GDT_CONV_STEM_POOL", 1)    // 0: the max pool behind the direct stem stays its own launch
+GDT_KNOB_LATCHED_SET(knob_plan_debug, "GDT_PLAN_DEBUG")      // set: the norm-fold decisions are printed
+
 namespace gdtn {
 
 // geometry part of a conv launch (everything but the pointers) for one phase of op `o` reading a tensor of size ti
@@ -289,7 +296,7 @@ void Planner::transposed_forms() {
         }
         // GDT_CONV_CTF: 0 never, 1 (default) the LDS-resident kernel whenever eligible and the generic persistent GEMM only where
         // it lets the producer's InstanceNorm be folded in, 2 whenever eligible
-        static const int ctf_mode = env_int("GDT_CONV_CTF", 1);
+        const int ctf_mode = knob_ctf();
         bool want = ctf_mode == 2 || (ctf_mode == 1 && gdt_conv_halo_ct_eligible(d));       // the LDS-resident form always pays
         if (ctf_mode == 1 && !want) {                      // is the input an InstanceNorm (without residual) consumed only here?
             for (int j = 0; j < i; ++j)
@@ -334,12 +341,12 @@ void Planner::split_mode_forms() {
 
 // ---- pass 2: fold InstanceNorm(+ReLU) into the input staging of its only consumer when that is a halo-kernel conv
 void Planner::norm_folds() {
-    static const bool allow_norm_fusion = env_int("GDT_NORM_FUSION", 1) != 0;
+    const bool allow_norm_fusion = knob_norm_fusion() != 0;
     for (int j = 0; j < nops && allow_norm_fusion; ++j) {
         const Op& oj = ops[j];
         // f16x3: the patch kernel folds InstanceNorm (+ReLU, + residual, + write-back) while it stages; GDT_X3_NORM_FOLD=0 switches that off, 1 keeps it to the plain
         // norm (+ReLU) without residual / write-back (the round-5 first form)
-        const int x3_fold = env_int("GDT_X3_NORM_FOLD", 2);      // (read per plan)
+        const int x3_fold = knob_x3_norm_fold();
         if (oj.kind != OP_INORM || (net->precision == 1 && !x3_fold)) continue;
         // plain norm(+ReLU): exactly one consumer.  norm + residual (ResnetBlock output): the tensor itself is still needed
         // later (as the next block's residual), so the consuming conv also writes it out -- every other consumer must come
@@ -401,8 +408,7 @@ void Planner::norm_folds() {
                                             (x3_fold >= 2 && !wb && !res && !ok.rowsplit && !ok.cd.out_f32_nchw && gdt_conv_x3_norm_eligible(d)))
                                          : (gdt_conv_halo_eligible(d) || (!wb && (gdt_conv_igemm_norm_eligible(d) || gdt_conv_igemm_rb_eligible(dn))));
         if (take) fold_norm(j, k, wb);
-        static const bool plan_dbg = getenv("GDT_PLAN_DEBUG") != nullptr;
-        if (plan_dbg) fprintf(stderr, "[plan] inorm %d -> conv %d: Cin %d s%d k%d rowsplit %d fold %d\n", j, k, d.Cin, ok.cd.stride, ok.cd.kh, (int)ok.rowsplit, (int)take);
+        if (knob_plan_debug()) fprintf(stderr, "[plan] inorm %d -> conv %d: Cin %d s%d k%d rowsplit %d fold %d\n", j, k, d.Cin, ok.cd.stride, ok.cd.kh, (int)ok.rowsplit, (int)take);
     }
 }
 
@@ -481,7 +487,7 @@ void Planner::bottlenecks() {
 // ---- pass 2c'' (fp16 mode): Bottlenecks that did not fuse as a whole (MID = 256: ResNet-101 layer3): 3x3 conv + expand conv + residual as one launch; the
 // 3x3's output tensor has no other consumer and is never allocated
 void Planner::expand_folds() {
-    if (env_int("GDT_CONV_XEXP", 1) == 0) return;                   // 0: off (read when a net plans a geometry: A/B inside one process)
+    if (knob_xexp() == 0) return;
     for (int i = 0; i + 1 < nops && !net->precision; ++i) {
         const Op &b = ops[i], &c = ops[i + 1];
         if (!plain_s1(b) || !plain_s1(c)) continue;
@@ -529,7 +535,7 @@ void Planner::direct_stem() {
     if (!gdt_conv_stem_pair_eligible(conv_desc_stem_direct(probe, j, -1))) return;
     plan.steps[0].direct = true; plan.steps[j].direct = true;
     // ... and the MaxPool2d(3, 2, 1) behind it, when it is the stem's only consumer: the stem launch writes the pooled tensor
-    static const bool pool_ok = env_int("GDT_CONV_STEM_POOL", 1) != 0;
+    const bool pool_ok = knob_stem_pool() != 0;
     const int jp = consumers[o.out] == 1 ? consumer_op[o.out] : -1;
     if (pool_ok && jp >= 0 && ops[jp].kind == OP_MAXPOOL && ops[jp].k == 3 && ops[jp].s == 2 && ops[jp].p == 1 && !ops[jp].ceil && o.cd.relu && o.slot < 0) {
         plan.steps[j].pool_into = jp; plan.steps[jp].skip = true;
@@ -708,6 +714,8 @@ double op_bytes(const gdt_net* net, const Op& o, int n) {
 
 // ================================================================================================ C ABI: the queries that only plan
 extern "C" {
+
+const char* gdt_plan_knob_name(int index) { return index >= 0 && index < GDT_LIVE_KNOB_COUNT ? GDT_LIVE_KNOB_NAMES[index] : nullptr; }
 
 int gdt_net_output_shape(gdt_net* net, int slot, int n, int rh, int rw, int* dims, int* ndim) {
     GDT_REQUIRE(net && dims && ndim && slot >= 0 && slot < (int)net->out_ops.size(), "slot");

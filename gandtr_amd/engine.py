@@ -194,13 +194,11 @@ class HipNet:
             return h, w
         return int(math.floor(float(h * scale))), int(math.floor(float(w * scale)))
 
-    #: knobs the planner reads when it plans a geometry (A/B inside one process): part of the key of the per-geometry cache below
-    _PLAN_KNOBS = ("GDT_CONV_XEXP", "GDT_XEXP_CHAIN", "GDT_CONV_BNECK", "GDT_CONV_HALO_X3", "GDT_CONV_HALO_X3_FORMS", "GDT_X3_NORM_FOLD")
-
     def _geometry(self, n, rh, rw):
         """(workspace bytes, output shapes) of a geometry, planned once: every query plans the whole graph (make_plan, csrc/net.hip: ~0.1 ms for ResNet-101), and a
         forward asks three times per pyramid level -- 1.2 ms of the 8.6 ms a synchronised multi-scale call took (round 5)."""
-        key = (n, rh, rw, getattr(self, "_group_factor", 1.0)) + tuple(os.environ.get(k) for k in self._PLAN_KNOBS)
+        # (the knobs the library reads every time it plans, A/B inside one process, are part of the key: the library names them itself)
+        key = (n, rh, rw, getattr(self, "_group_factor", 1.0)) + tuple(os.environ.get(k) for k in _hip.plan_knobs())
         cache = self.__dict__.setdefault("_geo_cache", {})
         hit = cache.get(key)
         if hit is None:
@@ -418,7 +416,8 @@ class HipNet:
             pools["streams"].append(side_stream(dev, len(pools["streams"])))
             pools["ws"].append(None)
         results = []
-        with torch.cuda.device(dev):
+        try:
+          with torch.cuda.device(dev):
             for lo in range(0, len(inputs), self.MAX_LEVELS):
                 group = inputs[lo:lo + self.MAX_LEVELS]
                 levels = (_hip.Level * len(group))()
@@ -453,6 +452,8 @@ class HipNet:
                     if w is not None:
                         w.record_stream(cur)
                         pools["ws"][k] = None
+        finally:
+            self.set_group_factor(1.0)       # (also when a level of a group is refused half-way: the next plan is a single geometry's)
         return results
 
     def _capture(self, x, key, need, shapes):

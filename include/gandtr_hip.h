@@ -181,6 +181,9 @@ int gdt_net_forward_levels(gdt_net* net, const gdt_level* levels, int n_levels, 
  * group's patches.  It applies to every later plan (gdt_net_workspace_bytes, gdt_net_output_shape, gdt_net_plan_summary, gdt_net_forward) until set again;
  * gdt_net_forward_levels sets it per level itself.  Host calls on one handle are serialised (see the threading note above). */
 int gdt_net_set_group_factor(gdt_net* net, float factor);
+/* The environment knobs that a net reads EVERY time it plans a geometry (all others are read once per process): name of knob `index` (0, 1, ..), NULL past the
+ * last.  Whoever caches something derived from a plan (workspace sizes, output shapes) keys the cache on the values of these. */
+const char* gdt_plan_knob_name(int index);
 /* diagnostics of the last gdt_net_forward_levels call: returns the number of ops whose levels ran as ONE launch; *level_launches = launches the levels handed
  * to the lock-step driver in total (joined or not) */
 int gdt_net_levels_joined(gdt_net* net, int* level_launches);

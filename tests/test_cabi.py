@@ -57,3 +57,11 @@ def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_hip, "_LIB_PATH", "/nonexistent/libgandtr_hip.so")
     with pytest.raises(_hip.HipLibraryMissing):
         _hip.load()
+
+
+def test_plan_knob_names_end_with_null():
+    from gandtr_amd import _hip
+    lib = _hip.load()
+    names = _hip.plan_knobs()
+    assert len(names) >= 1 and all(n.startswith("GDT_") for n in names) and len(set(names)) == len(names)
+    assert lib.gdt_plan_knob_name(len(names)) is None and lib.gdt_plan_knob_name(-1) is None

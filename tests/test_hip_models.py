@@ -414,6 +414,30 @@ def test_pyramid_levels_share_launches_bitwise(cuda_device):
         del net
 
 
+def test_refused_level_group_leaves_the_handle_planning_alone(cuda_device):
+    """A group of levels that is refused half-way (gdt_net_forward_levels path: the planner's group factor is set per level) must leave the handle at factor 1: the
+    next single forward plans -- and computes -- what a fresh handle does."""
+    import os
+    from gandtr_amd import engine
+    sd = synth.resnet101_state(0)
+    net, fresh = engine.build_embedder(sd, cuda_device), engine.build_embedder(sd, cuda_device)
+    x = synth.synth_input(92, (2, 3, 128, 128)).to(cuda_device)
+    bad = torch.zeros(2, 1, 128, 128, device=cuda_device)                      # wrong channel count: refused after the first level set its factor (2.0)
+    os.environ["GANDTR_HIP_JOINT_LEVELS"] = "1"
+    try:
+        with pytest.raises(ValueError):
+            net.forward_many([(x, 1.0), (bad, 1.0)])
+    finally:
+        del os.environ["GANDTR_HIP_JOINT_LEVELS"]
+    # 8 x 1024^2 has 128 layer3 patches: fused 3x3 + expand launches only with a group factor >= 1.5 (tests/test_planner_cpu.py)
+    assert fresh.plan_summary(8, 1024, 1024)["conv3x3_expand"] == 0
+    assert net.plan_summary(8, 1024, 1024) == fresh.plan_summary(8, 1024, 1024)
+    assert net.workspace_bytes(8, 1024, 1024) == fresh.workspace_bytes(8, 1024, 1024)
+    got, want = net.forward(x), fresh.forward(x)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(got, want))
+
+
 def test_hipgraph_replay_equals_eager_launches(cuda_device):
     """opt-in hipGraph replay of whole forwards (GANDTR_HIP_GRAPHS=1 / HipNet.use_graphs): from the second call of a geometry on the forward is captured once and
     replayed -- same kernels, same results bit for bit, for the generator (f16c) and the embedder; another geometry falls back to eager launches"""

@@ -152,3 +152,36 @@ def test_planner_fusion_decisions_at_the_benchmarked_geometries(monkeypatch):
     monkeypatch.setenv("GDT_X3_NORM_FOLD", "1")                                # the first form: plain norm + ReLU into the stride-1 patch kernel only
     assert exact.plan_summary(64, 256, 256)["norms_folded"] == 10                # (9 inside the resblocks + the head's)
     monkeypatch.delenv("GDT_X3_NORM_FOLD")
+
+
+LIVE_KNOBS = ("GDT_CONV_XEXP", "GDT_XEXP_CHAIN", "GDT_CONV_BNECK", "GDT_CONV_HALO_X3", "GDT_CONV_HALO_X3_FORMS", "GDT_X3_NORM_FOLD")
+
+
+def test_library_names_its_live_knobs():
+    """the knobs read at every plan are exactly these six, and the geometry cache of HipNet is keyed on the library's own list"""
+    from gandtr_amd import _hip
+    assert _hip.plan_knobs() == LIVE_KNOBS
+    lib = _hip.load()
+    assert lib.gdt_plan_knob_name(-1) is None and lib.gdt_plan_knob_name(len(LIVE_KNOBS)) is None
+
+
+def test_live_knob_changes_the_next_plan_and_a_latched_one_does_not(monkeypatch):
+    for k in LIVE_KNOBS + ("GDT_NORM_FUSION", "GDT_XEXP_PH", "GDT_XEXP_MIN_TILES"):
+        monkeypatch.delenv(k, raising=False)
+    r101 = engine.build_embedder(synth.resnet101_state(0), DEV, finalize=False)
+    base = r101.plan_summary(32, 1024, 1024)
+    assert base["conv3x3_expand"] == 22 and base["bottlenecks_fused"] == 6, base
+    monkeypatch.setenv("GDT_CONV_XEXP", "0")                                   # live: the next plan of the same handle follows it
+    assert r101.plan_summary(32, 1024, 1024)["conv3x3_expand"] == 0
+    monkeypatch.delenv("GDT_CONV_XEXP")
+    monkeypatch.setenv("GDT_CONV_BNECK", "0")
+    assert r101.plan_summary(32, 1024, 1024)["bottlenecks_fused"] == 0
+    monkeypatch.delenv("GDT_CONV_BNECK")
+    assert r101.plan_summary(32, 1024, 1024) == base
+    gen = engine.build_generator(synth.generator_state(0, "instance"), DEV, finalize=False)
+    g = gen.plan_summary(64, 256, 256)
+    assert g["norms_folded"] == 23, g                                          # (GDT_NORM_FUSION was read here, unset)
+    for k, v in (("GDT_NORM_FUSION", "0"), ("GDT_XEXP_PH", "16"), ("GDT_XEXP_MIN_TILES", "1000000")):
+        monkeypatch.setenv(k, v)                                               # latched at their first read above: nothing changes
+    assert gen.plan_summary(64, 256, 256) == g
+    assert r101.plan_summary(32, 1024, 1024) == base
