@@ -19,7 +19,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "gdt_common.h"
+#include "conv_device.h"
 
 #ifndef GDT_1X1_NT_RES
 #define GDT_1X1_NT_RES 0       // 1: the residual (its last use in a ResNet block) is fetched non-temporal
@@ -36,7 +36,6 @@ constexpr int BIAS_OFF = C_OFF + 4 * 32 * PCP * 2;
 constexpr int MAX_COUT = 2048;                  // bias vector kept in LDS
 constexpr size_t LDS_BYTES = (size_t)BIAS_OFF + MAX_COUT * 4;       // 59392: two workgroups per CU
 
-struct TileAt { int tile_m, tile_n; bool valid; };
 struct Pend { f16x8 v[4]; };
 
 // TM = 2: waves 2 x 2, 64 x 64 each (tile 128 x 128); TM = 4: waves 1 x 4, 128 x 64 each (tile 128 x 256) -- a weight fragment
@@ -55,15 +54,15 @@ __device__ __forceinline__ void conv1x1_rb_body(const ConvLaunch& d, const int v
     const int fr = lane & 31, fh = lane >> 5;
 
     const int ntm = (d.M + BM - 1) / BM, ntn = d.CoutPad / BN;
-    auto tile_at = [&](int vb) -> TileAt {
-        TileAt t;
+    auto tile_at = [&](int vb) -> GdtTile {
+        GdtTile t;                                  // (local: gdt_tile_at followed by the dbg flip changes this file's code generation)
         t.valid = vb < vblocks && gdt_tile_of_block(vb, ntm, ntn, t.tile_m, t.tile_n);
         if (!t.valid) { t.tile_m = 0; t.tile_n = 0; }
         else if (d.dbg & 2) t.tile_m = ntm - 1 - t.tile_m;        // rows from the end (see gdt_launch_conv_1x1_rb)
         return t;
     };
     int vb = bid;
-    TileAt cur = tile_at(vb);
+    GdtTile cur = tile_at(vb);
     if (!cur.valid) return;                   // (validity is monotone in vb)
     const int nk = d.Kpad >> 6, nks = d.Kpad >> 4;
 
@@ -105,7 +104,7 @@ __device__ __forceinline__ void conv1x1_rb_body(const ConvLaunch& d, const int v
     auto advance = [&]() {
         if (++s_step == nk) {
             s_step = 0;
-            const TileAt nx = tile_at(s_vb + gdim);
+            const GdtTile nx = tile_at(s_vb + gdim);
             if (nx.valid) { s_tile_m = nx.tile_m; s_vb += gdim; set_rows2(); }
         }
     };
@@ -140,7 +139,7 @@ __device__ __forceinline__ void conv1x1_rb_body(const ConvLaunch& d, const int v
     f16* patch = (f16*)(smem + C_OFF) + wave * (32 * PCP);
     int so = 0;
     for (;;) {
-        const TileAt nxt = tile_at(vb + gdim);
+        const GdtTile nxt = tile_at(vb + gdim);
         f32x16 acc[TM][2];
 #pragma unroll
         for (int i = 0; i < TM; ++i)

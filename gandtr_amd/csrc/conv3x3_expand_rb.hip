@@ -47,7 +47,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "gdt_common.h"
+#ifdef GDT_XEXP_STAMP              // diagnostic build: GDT_STAMP is live
+#define GDT_STAMP_ON
+#endif
+#include "conv_device.h"
 
 #ifndef GDT_XEXP_CABL
 #define GDT_XEXP_CABL 0        // timing-only ablations of phase C (results are wrong by design): 1 no y loads / LDS writes, 2 no per-chunk barrier, 4 no weight re-loads
@@ -190,9 +193,6 @@ __global__ __launch_bounds__(Geo<PH>::NT, PH == 16 ? 1 : 2) void conv3x3_expand_
 #ifdef GDT_XEXP_STAMP
     unsigned long long st_a = 0, st_ho = 0, st_bk = 0, st_be = 0, st_nx = 0, st_c = 0, st_t = __builtin_amdgcn_s_memtime(), st_n = 0;
     const unsigned long long st_begin = st_t;
-#define GDT_STAMP(acc_) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc_ += now_ - st_t; st_t = now_; }
-#else
-#define GDT_STAMP(acc_)
 #endif
     for (;;) {
         TileAt nxt = tile_at(vb + gridDim.x);

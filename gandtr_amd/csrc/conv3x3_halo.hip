@@ -16,10 +16,7 @@
 #include <vector>
 
 #include "conv_epilogue.h"
-#include "gdt_common.h"
-
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
+#include "conv_device.h"
 
 namespace {
 
@@ -29,10 +26,6 @@ constexpr int HALO_W = 18;
 constexpr int halo_rows(int PH) { return (PH + 2) * HALO_W; }
 constexpr int halo_rows_pad(int PH) { return (halo_rows(PH) + 7) / 8 * 8; }
 constexpr int a_bytes(int PH) { return halo_rows_pad(PH) * ROWB; }
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gsrc, (LDS_AS void*)lds_dst, 16, 0, 0);
-}
 
 template <int PH, int BN, int WGM, int WGN>
 constexpr size_t halo_lds_bytes() {
@@ -82,9 +75,8 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_kernel(const Conv
         a_q[r] = (lane & 7) ^ ((hx >> 1) & 7);
         a_int |= (((hy >= 1) & (hy <= PH) & (hx >= 1) & (hx <= 16) & (y0 - 1 + hy < d.H) & (x0 - 1 + hx < d.W)) ? 1u : 0u) << r;
         const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
-        int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-        int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
-        ry = min(max(ry, 0), d.H - 1); rx = min(max(rx, 0), d.W - 1);
+        int ry, rx;
+        GDT_REFLECT_CLAMP(iy, ix, d.H, d.W, ry, rx)
         const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
         a_pix[r] = (n * d.H + ry) * d.W + rx;
         a_ok |= ((h < HALO_ROWS) & (inb | refl) ? 1u : 0u) << r;
@@ -94,7 +86,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_kernel(const Conv
     auto issue_a = [&](int chunk, int stage, int r) {
         if (r >= NR || r * RPR + wave * 8 >= HALO_ROWS_PAD) return;  // wave-uniform: rows beyond the padded halo
         const f16* src = d.in + (((long)a_pix[r] << (d.lc8 + 3)) + (chunk * 8 + a_q[r]) * 8);
-        glds16(((a_ok >> r) & 1u) ? src : d.zeros, smem + stage * A_BYTES + (r * RPR + wave * 8) * ROWB);
+        gdt_glds16(((a_ok >> r) & 1u) ? src : d.zeros, smem + stage * A_BYTES + (r * RPR + wave * 8) * ROWB);
     };
     // Fused InstanceNorm (+ReLU) of the producer (p2p_networks.py:29,:272): when d.in_norm is set the halo goes through
     // registers instead -- load 8 raw fp16 channels, x -> max((x - mean) * rstd, 0) in fp32, store to the same swizzled LDS
@@ -148,7 +140,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_kernel(const Conv
             *(f16x8*)(d.in_out + (((long)a_pix[r] << (d.lc8 + 3)) + (chunk * 8 + a_q[r]) * 8)) = o;
     };
     auto issue_b = [&](int koff, int stage, int r) {
-        glds16(b_src + ((long)r * RPR * d.Kpad + koff), smem + 2 * A_BYTES + stage * B_BYTES + (r * RPR + wave * 8) * ROWB);
+        gdt_glds16(b_src + ((long)r * RPR * d.Kpad + koff), smem + 2 * A_BYTES + stage * B_BYTES + (r * RPR + wave * 8) * ROWB);
     };
 
     f32x16 acc[TM][TN];

@@ -41,7 +41,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "gdt_common.h"
+#ifdef GDT_C_STAMP                 // diagnostic build (tools/build_variant.sh stamp): GDT_STAMP is live
+#define GDT_STAMP_ON
+#endif
+#include "conv_device.h"
 
 // timing-only ablations (profiles/experiments): compile with -DGDT_C_ABL=<bits>; results are wrong by design
 //   1 no halo staging after the prologue   2 no MX MFMAs / MX weight loads   4 no fp16 weight re-loads   8 no fp16 MFMAs   256 no fp16 fragment re-loads
@@ -100,12 +103,6 @@ constexpr int BM = PH * 16;
 // + epilogue patches: two 4 KB patches per wave with four waves (pipelined body), one with eight (all 160 KB are taken then)
 constexpr size_t lds_bytes(int waves) { return 2 * (size_t)STAGE_BYTES + NORM_BYTES + E_BYTES + (waves > 4 ? waves * 4096 : 4 * 8192); }
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v2i __attribute__((ext_vector_type(2)));
-
-struct TileAt { int n, y0, x0, tile_m, tile_n; bool valid; };
-
 // MODE bits: 1 = the producer's InstanceNorm (+ReLU) is applied while staging; 2 = ... plus a residual; 4 = the transformed
 // tensor is written back.  CT: transposed form (see conv3x3_halo_rb.hip).
 // FORM 0: 3x3 / stride 1.  FORM 1 (CT): ConvTranspose2d(k3,s2,p1,op1), see conv3x3_halo_rb.hip.  FORM 2 (S2): Conv2d(k3, s2, p1, zero
@@ -158,17 +155,9 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
     const int GH = S2 ? d.OH : d.H, GW = S2 ? d.OW : d.W;              // the grid the 16x16 patches tile (S2: the output)
     const int tiles_x = (GW + 15) >> 4, tiles_y = (GH + PH - 1) / PH;
     const int tpi = tiles_x * tiles_y, ntm = d.N * tpi, ntn = d.CoutPad / BN;
-    auto tile_at = [&](int vb) -> TileAt {
-        TileAt t;
-        t.valid = vb < vblocks && gdt_tile_of_block(vb, ntm, ntn, t.tile_m, t.tile_n);
-        if (!t.valid) { t.tile_m = 0; t.tile_n = 0; }
-        t.n = t.tile_m / tpi;
-        const int tr = t.tile_m - t.n * tpi;
-        t.y0 = (tr / tiles_x) * PH; t.x0 = (tr % tiles_x) << 4;
-        return t;
-    };
+    auto tile_at = [&](int vb) -> GdtPatch { return gdt_patch_at(vb, vblocks, ntm, ntn, tpi, tiles_x, PH); };
     int vb = blockIdx.x;
-    TileAt cur = tile_at(vb);
+    GdtPatch cur = tile_at(vb);
     if (!cur.valid) return;
     // Stagger: every workgroup runs the same number of equally long tiles, so without it all 256 CUs reach their epilogue in the
     // same microsecond, the chip's whole output (64 MB per round at batch 64) leaves in one burst and every wave then sits behind its
@@ -184,11 +173,12 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
     const int lrow = tid >> 3;
     const bool refl = d.pad_reflect != 0;
     struct Pend { float4 r0, r1, s0, s1; unsigned goff; bool ok; };
-    auto load_piece = [&](const TileAt& ta, int chunk, int r) -> Pend {
+    auto load_piece = [&](const GdtPatch& ta, int chunk, int r) -> Pend {
         const int tl = tid_now();
         int lr = REMAT ? tl >> 3 : lrow;
         asm volatile("" : "+v"(lr));
         const int h = min(r * RPR + lr, HROWS_PAD - 1);
+        // (local, here and below: the shared gdt_halo_yx changes this file's code generation -- a shift of the fp16 plane's swizzle key)
         const int hy = (h * (SHIFT ? 3856 : 3641)) >> 16, hx = h - hy * HW_;
         const int q = tl & 7;          // a lane always fetches the same 8-channel group of its pixel; the swizzle is applied at the LDS write
         int iy = ta.y0 - (CT ? 0 : 1) + hy, ix = ta.x0 - (CT ? 0 : 1) + hx;
@@ -199,14 +189,12 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
             iy = 2 * iy + (par >> 1); ix = 2 * ix + (par & 1);
             cbyte = (vch & ((1 << lcr) - 1)) * 4;
         }
-        int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-        int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
-        ry = min(max(ry, 0), d.H - 1); rx = min(max(rx, 0), d.W - 1);
+        int ry, rx;
+        GDT_REFLECT_CLAMP(iy, ix, d.H, d.W, ry, rx)
         const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
         Pend p;
         p.goff = (((unsigned)((ta.n * d.H + ry) * d.W + rx) << (d.lc8 + (S2 ? 3 : 5))) + cbyte);      // byte offset (< 2^32, checked on the host)
         p.ok = (h < HROWS) & (inb | refl);
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
         auto ldh = [](const float4* q) -> float4 {
             if constexpr ((GDT_C_NT & 2) != 0) { const f32x4 v = __builtin_nontemporal_load((const f32x4*)q); return make_float4(v[0], v[1], v[2], v[3]); }
             else return *q;
@@ -216,12 +204,9 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
         return p;
     };
     float* nlds = (float*)(smem + 2 * STAGE_BYTES);
-    auto stage_norm = [&](const TileAt& ta, int slot) {
+    auto stage_norm = [&](const GdtPatch& ta, int slot) {
         const int creal = S2 ? d.Cin >> 2 : d.Cin;
-        for (int i = tid_now(); i < creal / 2; i += NT) {              // float4 = 2 channels x (mean, rstd) -> (scale, shift)
-            const float4 v = *(const float4*)(d.in_norm + (long)ta.n * creal * 2 + i * 4);
-            *(float4*)(nlds + slot * 512 + i * 4) = make_float4(v.y, -v.x * v.y, v.w, -v.z * v.w);
-        }
+        gdt_stage_norm(nlds, slot, d.in_norm, creal, ta.n, tid_now(), NT);
     };
     // (scale, shift) of the lane's 8 channels in the chunk being staged: a lane's channel group is the same for every piece of a chunk,
     // so the factors are fetched from the LDS table once per chunk, not per piece (per piece: four dependent LDS reads, each behind an
@@ -275,24 +260,14 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] = p.ok ? a[e] : 0.f;
-        // split: o = fp16(a) (round to nearest even, two per instruction), a_lo = a - o in ONE v_fma_mix_f32 each (fp16 source read
-        // in place), both planes quantised to fp4 by the scaled converts (the convert divides by its scale operand) at the pixel's own
-        // scale (gdt_c_pixel_exp)
+        // the split (gdt_c_split) at the pixel's own scale (gdt_c_pixel_exp)
         const int ex = gdt_c_pixel_exp(a);
         const float lo_scale = gdt_exp2i(ex - 13), hi_scale = gdt_exp2i(ex - 2);
         unsigned ou[4], qlo = 0, qhi = 0;
-#define GDT_Q4(k)                                                                                                                    \
-        {                                                                                                                            \
-            asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(ou[k]) : "v"(a[2 * k]), "v"(a[2 * k + 1]));                                     \
-            float l0, l1;                                                                                                            \
-            asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(ou[k]), "v"(a[2 * k]));            \
-            asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(ou[k]), "v"(a[2 * k + 1]));        \
-            qlo = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(qlo, l0, l1, lo_scale, k);                                                \
-            qhi = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(qhi, __builtin_bit_cast(f16x2, ou[k]), hi_scale, k);                       \
-        }
-        GDT_Q4(0) GDT_Q4(1) GDT_Q4(2) GDT_Q4(3)
-#undef GDT_Q4
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        gdt_c_split<0>(a[0], a[1], lo_scale, hi_scale, ou[0], qlo, qhi);
+        gdt_c_split<1>(a[2], a[3], lo_scale, hi_scale, ou[1], qlo, qhi);
+        gdt_c_split<2>(a[4], a[5], lo_scale, hi_scale, ou[2], qlo, qhi);
+        gdt_c_split<3>(a[6], a[7], lo_scale, hi_scale, ou[3], qlo, qhi);
         const u32x4 ov = {ou[0], ou[1], ou[2], ou[3]};
         const f16x8 o = __builtin_bit_cast(f16x8, ov);
         *(f16x8*)(smem + stage_off + row * ROWB + (((tl & 7) ^ ((phx >> 1) & 7)) << 4)) = o;      // source chunk q at position q ^ key (a_frag)
@@ -330,7 +305,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
     const int wgrp_of_wave = (wn * WTN) >> 7, wblk = ((wn * WTN) >> 5) & 3;      // the wave's 128-column weight group within the tile, its first 32-column block in it
     const int nks = d.Kpad >> 4, nms = d.Kpad >> 5, cin16 = d.Cin >> 4;
     f16x8 b[RING][TN];
-    typedef int v6i __attribute__((ext_vector_type(6)));
     v6i bq[TN];             // the lane's 32 e2m3 values: the MFMA's 6-register operand tuple, loaded in place (dwordx4 + dwordx2)
     int bqs[TN];            // its E8M0 block scale
     auto lane_bytes = [&](int per_lane) -> unsigned {     // (opaque: keeps the zero-extension next to its load, which is what lets the
@@ -432,12 +406,9 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
 #ifdef GDT_C_STAMP                 // diagnostic build (tools/build_variant.sh stamp): per-wave s_memtime totals, written to d.stamp_out only
     unsigned long long st_body = 0, st_cbar = 0, st_tbar = 0, st_epi = 0, st_t = __builtin_amdgcn_s_memtime(), st_n = 0;
     const unsigned long long st_begin = st_t;
-#define GDT_STAMP(acc) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc += now_ - st_t; st_t = now_; }
-#else
-#define GDT_STAMP(acc)
 #endif
     for (;;) {
-        const TileAt nxt = tile_at(vb + gridDim.x);
+        const GdtPatch nxt = tile_at(vb + gridDim.x);
         f32x16 acc[TM][TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -459,7 +430,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
             auto s2_ld = [](int t) -> bool { return !S2 || S2M == 0 || ((S2M >> t) & 1u) != 0; };              // its loads (static masks only)
             const bool last = c + 1 == nchunks;
             const bool to_next = last && nxt.valid;
-            const TileAt sta = to_next ? nxt : cur;
+            const GdtPatch sta = to_next ? nxt : cur;
             const int sc = last ? 0 : c + 1, sslot = to_next ? slot ^ 1 : slot;
             if (NORM && nxt.valid && c == nchunks - 2) stage_norm(nxt, slot ^ 1);
             load_nf(sslot, sc);                 // (the table of the next tile was written during the previous chunk, a barrier ago)

@@ -33,7 +33,10 @@
 
 #include <vector>
 
-#include "gdt_common.h"
+#ifdef GDT_C_STAMP                 // diagnostic build: GDT_STAMP is live
+#define GDT_STAMP_ON
+#endif
+#include "conv_device.h"
 
 #ifndef GDT_C16_SCHED
 #define GDT_C16_SCHED 1         // 1: sched_group_barrier interleave (per MFMA: at most one LDS read, two VALU; a memory operation every fourth)
@@ -72,14 +75,6 @@ constexpr int SDIST = GDT_C16_SDIST;           // rounds in flight per thread: a
                                                // with one, ~1300 cycles, every round began with a wait for HBM (13-25 k cycles per tile, stamped)
 static_assert((NR + SDIST) * SPR <= SLOTS, "halo rounds are spread over the slots of the previous chunk");
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v6i __attribute__((ext_vector_type(6)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v2i __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct TileAt { int n, y0, x0, tile_m, tile_n; bool valid; };
-
 // The MFMAs as inline asm with the accumulator tied to an AGPR tuple ("+a"): for the four-pass 16 x 16 shapes the compiler does not tie vdst
 // to src2, lets the 64 accumulator tuples wander through the 256 AGPRs -- all of which they occupy -- and moves them through VGPRs and scratch
 // around every MFMA (first build: 1580 v_accvgpr_read + 1520 v_accvgpr_write + 250 scratch operations per chunk).  Operands arrive from LDS /
@@ -109,34 +104,26 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
 
     const int tiles_x = d.W >> 4, tiles_y = d.H >> 4;
     const int tpi = tiles_x * tiles_y, ntm = d.N * tpi, ntn = d.CoutPad >> 8;
-    auto tile_at = [&](int vb) -> TileAt {
-        TileAt t;
-        t.valid = vb < vblocks && gdt_tile_of_block(vb, ntm, ntn, t.tile_m, t.tile_n);
-        if (!t.valid) { t.tile_m = 0; t.tile_n = 0; }
-        t.n = t.tile_m / tpi;
-        const int tr = t.tile_m - t.n * tpi;
-        t.y0 = (tr / tiles_x) << 4; t.x0 = (tr % tiles_x) << 4;
-        return t;
-    };
+    auto tile_at = [&](int vb) -> GdtPatch { return gdt_patch_at(vb, vblocks, ntm, ntn, tpi, tiles_x, 16); };
     int vb = blockIdx.x;
-    TileAt cur = tile_at(vb);
+    GdtPatch cur = tile_at(vb);
     if (!cur.valid) return;
 
     // ---- halo loader: through registers, branch-free (conv3x3_halo_c.hip)
     const int lrow = tid >> 3;
     const bool refl = d.pad_reflect != 0;
     struct Pend { float4 r0, r1, s0, s1; unsigned goff; bool ok; };
-    auto load_piece = [&](const TileAt& ta, int chunk, int r) -> Pend {
+    auto load_piece = [&](const GdtPatch& ta, int chunk, int r) -> Pend {
         int lr = lrow;
         asm volatile("" : "+v"(lr));
         const int h = min(r * RPR + lr, HROWS_PAD - 1);
-        const int hy = (h * 3641) >> 16, hx = h - hy * HW_;
+        int hy, hx;
+        gdt_halo_yx<HW_>(h, hy, hx);
         const int q = lane & 7;
         const int iy = ta.y0 - 1 + hy, ix = ta.x0 - 1 + hx;
         const int cbyte = (chunk * 8 + q) * 32;
-        int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-        int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
-        ry = min(max(ry, 0), d.H - 1); rx = min(max(rx, 0), d.W - 1);
+        int ry, rx;
+        GDT_REFLECT_CLAMP(iy, ix, d.H, d.W, ry, rx)
         const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
         Pend p;
         p.goff = (((unsigned)((ta.n * d.H + ry) * d.W + rx) << (d.lc8 + 5)) + cbyte);      // byte offset (< 2^32, checked on the host)
@@ -147,17 +134,17 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     };
     // ... one load instruction per call (main loop): part 0 computes the address and fetches the first 16 bytes
     Pend pendv[SDIST];
-    auto load_piece_part = [&](const TileAt& ta, int chunk, int r, int part) {
+    auto load_piece_part = [&](const GdtPatch& ta, int chunk, int r, int part) {
         Pend& pend = pendv[r % SDIST];
         if (part == 0) {
             int lr = lrow;
             asm volatile("" : "+v"(lr));
             const int h = min(r * RPR + lr, HROWS_PAD - 1);
-            const int hy = (h * 3641) >> 16, hx = h - hy * HW_;
+            int hy, hx;
+            gdt_halo_yx<HW_>(h, hy, hx);
             const int iy = ta.y0 - 1 + hy, ix = ta.x0 - 1 + hx;
-            int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-            int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
-            ry = min(max(ry, 0), d.H - 1); rx = min(max(rx, 0), d.W - 1);
+            int ry, rx;
+            GDT_REFLECT_CLAMP(iy, ix, d.H, d.W, ry, rx)
             const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
             pend.goff = (((unsigned)((ta.n * d.H + ry) * d.W + rx) << (d.lc8 + 5)) + (chunk * 8 + (lane & 7)) * 32);
             pend.ok = (h < HROWS) & (inb | refl);
@@ -168,11 +155,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
         if (RES && part == 3) pend.s1 = *(const float4*)((const char*)resf + pend.goff + 16);
     };
     float* nlds = (float*)(smem + 2 * STAGE_BYTES);
-    auto stage_norm = [&](const TileAt& ta, int slot) {
-        for (int i = tid; i < d.Cin / 2; i += NT) {              // float4 = 2 channels x (mean, rstd) -> (scale, shift)
-            const float4 v = *(const float4*)(d.in_norm + (long)ta.n * d.Cin * 2 + i * 4);
-            *(float4*)(nlds + slot * 512 + i * 4) = make_float4(v.y, -v.x * v.y, v.w, -v.z * v.w);
-        }
+    auto stage_norm = [&](const GdtPatch& ta, int slot) {
+        gdt_stage_norm(nlds, slot, d.in_norm, d.Cin, ta.n, tid, NT);
     };
     float4 nf[4];
     auto load_nf = [&](int slot, int chunk) {
@@ -183,7 +167,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     };
     auto store_piece = [&](int stage_off, int r, const Pend& p) {
         const int row = min(r * RPR + lrow, HROWS_PAD - 1);
-        const int phy = (row * 3641) >> 16, phx = row - phy * HW_;
+        int phy, phx;
+        gdt_halo_yx<HW_>(row, phy, phx);
         float a[8] = {p.r0.x, p.r0.y, p.r0.z, p.r0.w, p.r1.x, p.r1.y, p.r1.z, p.r1.w};
         if (NORM) {
             const float lo = d.in_relu ? 0.f : -3.0e38f;
@@ -207,18 +192,10 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
         const int ex = gdt_c_pixel_exp(a);                       // the pixel's scale: the converts divide by it
         const float lo_scale = gdt_exp2i(ex - 13), hi_scale = gdt_exp2i(ex - 2);
         unsigned ou[4], qlo = 0, qhi = 0;
-#define GDT_Q4(k)                                                                                                                    \
-        {                                                                                                                            \
-            asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(ou[k]) : "v"(a[2 * k]), "v"(a[2 * k + 1]));                                     \
-            float l0, l1;                                                                                                            \
-            asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(ou[k]), "v"(a[2 * k]));            \
-            asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(ou[k]), "v"(a[2 * k + 1]));        \
-            qlo = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(qlo, l0, l1, lo_scale, k);                                                \
-            qhi = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(qhi, __builtin_bit_cast(f16x2, ou[k]), hi_scale, k);                       \
-        }
-        GDT_Q4(0) GDT_Q4(1) GDT_Q4(2) GDT_Q4(3)
-#undef GDT_Q4
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        gdt_c_split<0>(a[0], a[1], lo_scale, hi_scale, ou[0], qlo, qhi);
+        gdt_c_split<1>(a[2], a[3], lo_scale, hi_scale, ou[1], qlo, qhi);
+        gdt_c_split<2>(a[4], a[5], lo_scale, hi_scale, ou[2], qlo, qhi);
+        gdt_c_split<3>(a[6], a[7], lo_scale, hi_scale, ou[3], qlo, qhi);
         const u32x4 ov = {ou[0], ou[1], ou[2], ou[3]};
         const int q = lane & 7;
         // fp16 plane: source chunk q (8 channels) at 16-byte position q ^ key, key = (x >> 1) & 7
@@ -240,7 +217,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     unsigned sou[4], sqlo = 0, sqhi = 0;
     int sex = 0;                      // the pixel's scale exponent (gdt_c_pixel_exp) and the converts' scales
     float slo_scale = 1.f, shi_scale = 1.f;
-    auto stage_phase = [&](const TileAt& ta, int chunk, int stage_off, int sl, int ph) {
+    auto stage_phase = [&](const GdtPatch& ta, int chunk, int stage_off, int sl, int ph) {
         if ((GDT_C16_ABL & 1) || sl % SPR != 0) return;
         const int r = sl / SPR;
         const bool st = r >= SDIST && r - SDIST < NR, ld = r < NR;
@@ -278,21 +255,14 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
             sex = gdt_c_pixel_exp(sa);
             slo_scale = gdt_exp2i(sex - 13); shi_scale = gdt_exp2i(sex - 2);
         }
-#define GDT_Q4P(k)                                                                                                                   \
-        if (st && ph == 5 + k) {                                                                                                     \
-            asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(sou[k]) : "v"(sa[2 * k]), "v"(sa[2 * k + 1]));                                  \
-            float l0, l1;                                                                                                            \
-            asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(sou[k]), "v"(sa[2 * k]));         \
-            asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(sou[k]), "v"(sa[2 * k + 1]));     \
-            sqlo = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(sqlo, l0, l1, slo_scale, k);                                             \
-            sqhi = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(sqhi, __builtin_bit_cast(f16x2, sou[k]), shi_scale, k);                  \
-        }
-        GDT_Q4P(0) GDT_Q4P(1) GDT_Q4P(2) GDT_Q4P(3)
-#undef GDT_Q4P
+        if (st && ph == 5) gdt_c_split<0>(sa[0], sa[1], slo_scale, shi_scale, sou[0], sqlo, sqhi);
+        if (st && ph == 6) gdt_c_split<1>(sa[2], sa[3], slo_scale, shi_scale, sou[1], sqlo, sqhi);
+        if (st && ph == 7) gdt_c_split<2>(sa[4], sa[5], slo_scale, shi_scale, sou[2], sqlo, sqhi);
+        if (st && ph == 8) gdt_c_split<3>(sa[6], sa[7], slo_scale, shi_scale, sou[3], sqlo, sqhi);
         if (st && ph == 9) {
             const int row = min((r - SDIST) * RPR + lrow, HROWS_PAD - 1);
-            const int phy = (row * 3641) >> 16, phx = row - phy * HW_;
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+            int phy, phx;
+            gdt_halo_yx<HW_>(row, phy, phx);
             const u32x4 ov = {sou[0], sou[1], sou[2], sou[3]};
             const int q = lane & 7;
             *(f16x8*)(smem + stage_off + row * ROWB + ((q ^ ((phx >> 1) & 7)) << 4)) = __builtin_bit_cast(f16x8, ov);
@@ -409,12 +379,9 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
 #ifdef GDT_C_STAMP
     unsigned long long st_body = 0, st_cbar = 0, st_tbar = 0, st_epi = 0, st_t = __builtin_amdgcn_s_memtime(), st_n = 0;
     const unsigned long long st_begin = st_t;
-#define GDT_STAMP(acc_) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc_ += now_ - st_t; st_t = now_; }
-#else
-#define GDT_STAMP(acc_)
 #endif
     for (;;) {
-        const TileAt nxt = tile_at(vb + gridDim.x);
+        const GdtPatch nxt = tile_at(vb + gridDim.x);
         f32x4 acc[16][4];
 #pragma unroll
         for (int i = 0; i < 16; ++i)
@@ -426,7 +393,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
         for (int c = 0; c < nchunks; ++c) {
             const bool last = c + 1 == nchunks;
             const bool to_next = last && nxt.valid;
-            const TileAt sta = to_next ? nxt : cur;
+            const GdtPatch sta = to_next ? nxt : cur;
             const int sc = last ? 0 : c + 1, sslot = to_next ? slot ^ 1 : slot;
             if (NORM && nxt.valid && c == nchunks - 2) stage_norm(nxt, slot ^ 1);
             load_nf(sslot, sc);                 // (the table of the next tile was written during the previous chunk, a barrier ago)

@@ -20,10 +20,7 @@
 #include <cstdlib>
 
 #include "conv_epilogue.h"
-#include "gdt_common.h"
-
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
+#include "conv_device.h"
 
 namespace {
 
@@ -38,29 +35,6 @@ constexpr int BM = PH * 16; static_assert(BM == 256, "16 x 16 patches at file sc
 
 constexpr int C_OFF = 2 * A_BYTES + NORM_BYTES;            // epilogue transpose patches (one per wave), disjoint from the halo stages
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// two fp16 lanes of `raw` -> fp16 pair { raw.lo * s0 + h0, raw.hi * s1 + h1 }, each an fp32 fma rounded once to fp16:
-// v_fma_mix{lo,hi}_f16 convert the fp16 source, do the fp32 fma and write the fp16 half in ONE instruction (the compiler's own
-// choice for the C expression is 2 cvt + packed fma + cvt_pk + register moves: 3x the VALU work in the staging path)
-__device__ __forceinline__ unsigned norm_pair(unsigned raw, float s0, float h0, float s1, float h1) {
-    unsigned o;
-    asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(o) : "v"(raw), "v"(s0), "v"(h0));
-    asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(o) : "v"(raw), "v"(s1), "v"(h1));
-    return o;
-}
-// ... the same with a ReLU floor and a residual: { max(raw.lo * s0 + h0, lo) + res.lo, ... } in fp32, rounded once
-__device__ __forceinline__ unsigned norm_res_pair(unsigned raw, unsigned res, float s0, float h0, float s1, float h1, float lo) {
-    float t0, t1;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(t0) : "v"(raw), "v"(s0), "v"(h0));
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(t1) : "v"(raw), "v"(s1), "v"(h1));
-    t0 = fmaxf(t0, lo); t1 = fmaxf(t1, lo);
-    unsigned o;
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(o) : "v"(res), "v"(t0));
-    asm("v_fma_mixhi_f16 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(o) : "v"(res), "v"(t1));
-    return o;
-}
-
 // PHT = 16: two halo stages, the (scale, shift) tables, eight wave-private transpose patches.  PHT = 32 (tall 16 x 32 patches, 64-channel layers): the two
 // 77 KB stages fill the LDS; the patches alias the stage the tile has just finished with (one more workgroup barrier per tile)
 // SINGLE (one 64-channel chunk per tile, i.e. Cin = 64): ONE halo stage per workgroup and two workgroups per CU instead of a double-buffered one -- a tile is only
@@ -71,8 +45,6 @@ constexpr size_t rb_lds_bytes() {
     if (SINGLE) return PHT == 16 ? (size_t)HALO_ROWS_PAD * ROWB + (size_t)4 * 32 * (64 + 8) * 2 : (size_t)(((PHT + 2) * HALO_W + 7) / 8 * 8) * ROWB;
     return PHT == 16 ? (size_t)C_OFF + (size_t)8 * 32 * (BN / 4 + 8) * 2 : (size_t)2 * (((PHT + 2) * HALO_W + 7) / 8 * 8) * ROWB;
 }
-
-struct TileAt { int n, y0, x0, tile_m, tile_n; bool valid; };
 
 // PERSISTENT: the grid is one workgroup per CU; workgroup b walks the virtual block ids b, b + G, b + 2G, ... of the XCD-chunked
 // tile mapping (gdt_tile_of_block; G is a multiple of 8, so a workgroup's tiles stay on its XCD).  The chunk pipeline runs
@@ -114,17 +86,9 @@ __device__ __forceinline__ void conv3x3_halo_rb_body(const ConvLaunch& d, const 
 
     const int tiles_x = (d.W + 15) >> 4, tiles_y = (d.H + PH - 1) / PH;
     const int tpi = tiles_x * tiles_y, ntm = d.N * tpi, ntn = d.CoutPad / BN;
-    auto tile_at = [&](int vb) -> TileAt {
-        TileAt t;
-        t.valid = vb < vblocks && gdt_tile_of_block(vb, ntm, ntn, t.tile_m, t.tile_n);
-        if (!t.valid) { t.tile_m = 0; t.tile_n = 0; }
-        t.n = t.tile_m / tpi;
-        const int tr = t.tile_m - t.n * tpi;
-        t.y0 = (tr / tiles_x) * PH; t.x0 = (tr % tiles_x) << 4;
-        return t;
-    };
+    auto tile_at = [&](int vb) -> GdtPatch { return gdt_patch_at(vb, vblocks, ntm, ntn, tpi, tiles_x, PH); };
     int vb = bid;
-    TileAt cur = tile_at(vb);
+    GdtPatch cur = tile_at(vb);
     if (!cur.valid) return;                   // (validity is monotone in vb: nothing later either)
 
     // ---- halo loader (column swizzle as conv3x3_halo.hip: chunk' = chunk ^ ((halo column >> 1) & 7)).
@@ -136,17 +100,17 @@ __device__ __forceinline__ void conv3x3_halo_rb_body(const ConvLaunch& d, const 
     const int lrow = tid >> 3;
     const bool refl = d.pad_reflect != 0;
     struct Pend { f16x8 raw, res; unsigned goff; bool ok; };
-    auto load_piece = [&](const TileAt& ta, int chunk, int r) -> Pend {
+    auto load_piece = [&](const GdtPatch& ta, int chunk, int r) -> Pend {
         // (the empty asm keeps this address arithmetic from being hoisted out of the chunk loop: hoisted, its dozen values per
         // round get spilled, and every scratch reload is a vmcnt(0) of its own)
         int lr = lrow;
         asm volatile("" : "+v"(lr));
         const int h = min(r * RPR + lr, HROWS_PAD - 1);            // rows past the padded halo repeat its last (all-zero) row
-        const int hy = (h * (CT ? 3856 : 3641)) >> 16, hx = h - hy * HW_;       // h / 17 or h / 18 for h < 2^9
+        int hy, hx;
+        gdt_halo_yx<HW_>(h, hy, hx);
         const int iy = ta.y0 - (CT ? 0 : 1) + hy, ix = ta.x0 - (CT ? 0 : 1) + hx;
-        int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-        int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
-        ry = min(max(ry, 0), d.H - 1); rx = min(max(rx, 0), d.W - 1);          // always a valid pixel
+        int ry, rx;
+        GDT_REFLECT_CLAMP(iy, ix, d.H, d.W, ry, rx)          // always a valid pixel
         const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
         const int q = (lane & 7) ^ ((hx >> 1) & 7);
         Pend p;
@@ -161,11 +125,8 @@ __device__ __forceinline__ void conv3x3_halo_rb_body(const ConvLaunch& d, const 
     // all-zero entry that padded positions are pointed at (so that they come out as exactly zero without a select).
     float* nlds = (float*)(smem + 2 * A_BYTES);
     constexpr int ZERO_ENTRY = 2 * 512;                            // floats
-    auto stage_norm = [&](const TileAt& ta, int slot) {
-        for (int i = tid; i < d.Cin / 2; i += NT) {              // float4 = 2 channels x (mean, rstd)
-            const float4 v = *(const float4*)(d.in_norm + (long)ta.n * d.Cin * 2 + i * 4);
-            *(float4*)(nlds + slot * 512 + i * 4) = make_float4(v.y, -v.x * v.y, v.w, -v.z * v.w);
-        }
+    auto stage_norm = [&](const GdtPatch& ta, int slot) {
+        gdt_stage_norm(nlds, slot, d.in_norm, d.Cin, ta.n, tid, NT);
         if (tid < 4) *(float4*)(nlds + ZERO_ENTRY + tid * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
     };
     auto store_piece = [&](int slot, int stage_off, int r, const Pend& p) {
@@ -185,7 +146,7 @@ __device__ __forceinline__ void conv3x3_halo_rb_body(const ConvLaunch& d, const 
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float4 v = np4[k];
-                ou[k] = RES ? norm_res_pair(rawu[k], resu[k], v.x, v.y, v.z, v.w, lo) : norm_pair(rawu[k], v.x, v.y, v.z, v.w);
+                ou[k] = RES ? gdt_norm_res_pair(rawu[k], resu[k], v.x, v.y, v.z, v.w, lo) : gdt_norm_pair(rawu[k], v.x, v.y, v.z, v.w);
             }
             o = __builtin_bit_cast(f16x8, ou);
             if (!RES) {                              // ReLU on the packed halves (rounding is monotone and 0 is exact)
@@ -247,7 +208,7 @@ __device__ __forceinline__ void conv3x3_halo_rb_body(const ConvLaunch& d, const 
     int so = 0;                   // LDS offset of the halo stage of the current chunk (0 or A_BYTES)
     int slot = 0;                 // (scale, shift) slot of the current tile
     for (;;) {
-        const TileAt nxt = tile_at(vb + gdim);
+        const GdtPatch nxt = tile_at(vb + gdim);
         if (SINGLE) {                    // the tile's whole halo: every load issued before the first is consumed, then the LDS writes, then the barrier
             Pend pp[NR];
 #pragma unroll
@@ -273,7 +234,7 @@ __device__ __forceinline__ void conv3x3_halo_rb_body(const ConvLaunch& d, const 
             // the chunk staged during this one: the next chunk of this tile, chunk 0 of the next tile, or -- when nothing
             // follows -- chunk 0 of this tile once more (idempotent, never read)
             const bool to_next = last && nxt.valid;
-            const TileAt sta = to_next ? nxt : cur;
+            const GdtPatch sta = to_next ? nxt : cur;
             const int sc = last ? 0 : c + 1, sslot = to_next ? slot ^ 1 : slot;
             // the next tile's (scale, shift) table goes in one chunk ahead of its first use (published by this chunk's barrier)
             if (NORM && nxt.valid && c == nchunks - 2) stage_norm(nxt, slot ^ 1);

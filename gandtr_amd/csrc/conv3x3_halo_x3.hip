@@ -20,7 +20,7 @@
 //   MFMAs of its last one.
 #include <cstdlib>
 
-#include "gdt_common.h"
+#include "conv_device.h"
 
 // Where a step's time goes (round 5, FORM 0 at 64 x 256^2: 0.93 ms per launch, 18 launches = 70 % of the exact mode's forward; 2 waves per SIMD, one step = one tap
 // of one 32-channel chunk = 24 MFMAs per wave behind one workgroup barrier):
@@ -44,9 +44,6 @@
 #define GDT_X3_ABL 0
 #endif
 
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
-
 namespace {
 
 constexpr int ROWB = 64;                   // bytes per LDS row: 32 halves of K
@@ -56,10 +53,6 @@ constexpr int BN = 128, B_BYTES = BN * ROWB;
 constexpr int NT = 512;
 constexpr int STAGE_A = 2 * A_BYTES, STAGE_B = 2 * B_BYTES;
 constexpr float LO_SCALE = 2048.f, LO_INV = 1.f / 2048.f;
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gsrc, (LDS_AS void*)lds_dst, 16, 0, 0);
-}
 
 template <int FORM>
 __global__ __launch_bounds__(NT) void conv3x3_halo_x3_kernel(const ConvLaunch d) {
@@ -92,9 +85,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_x3_kernel(const ConvLaunch d)
         const int hy = h / HALO_W, hx = h - hy * HALO_W;
         const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
         const int IH = S2D ? GH : d.H, IW = S2D ? GW : d.W;        // (FORM 2: halo coordinates are space-to-depth pixels (R, C) = input pixels (2R + py, 2C + px))
-        int ry = iy < 0 ? -iy : (iy >= IH ? 2 * IH - 2 - iy : iy);
-        int rx = ix < 0 ? -ix : (ix >= IW ? 2 * IW - 2 - ix : ix);
-        ry = min(max(ry, 0), IH - 1); rx = min(max(rx, 0), IW - 1);
+        int ry, rx;
+        GDT_REFLECT_CLAMP(iy, ix, IH, IW, ry, rx)
         const bool inb = ((unsigned)iy < (unsigned)IH) & ((unsigned)ix < (unsigned)IW);
         a_pix[r] = S2D ? (n * d.H + 2 * ry) * d.W + 2 * rx : (n * d.H + ry) * d.W + rx;
         a_ok |= ((h < HALO_ROWS) & (inb | refl) ? 1u : 0u) << r;
@@ -160,8 +152,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_x3_kernel(const ConvLaunch d)
     const f16* bl_src = d.w_lo + ((long)(tile_n * BN + brow) * d.Kpad + bq * 8);
     auto issue_b = [&](int koff, int stage) {
         char* Bh = smem + 2 * STAGE_A + stage * STAGE_B;
-        glds16(bh_src + koff, Bh + (wave * 16) * ROWB);
-        glds16(bl_src + koff, Bh + B_BYTES + (wave * 16) * ROWB);
+        gdt_glds16(bh_src + koff, Bh + (wave * 16) * ROWB);
+        gdt_glds16(bl_src + koff, Bh + B_BYTES + (wave * 16) * ROWB);
     };
 
     f32x16 acc[TM][TN], accl[TM][TN];

@@ -30,7 +30,10 @@
 #include <cstdlib>
 #include <vector>
 
-#include "gdt_common.h"
+#ifdef GDT_BNECK_STAMP             // diagnostic build: GDT_STAMP is live
+#define GDT_STAMP_ON
+#endif
+#include "conv_device.h"
 
 namespace {
 
@@ -41,12 +44,6 @@ constexpr int NT = 512, NWAVE = 8, PW = 16, HW_ = PW + 2;
 __device__ __forceinline__ float4 bias4(const float* __restrict__ b, int base_uniform, int g, int fh) {
     const float4 lo = *(const float4*)(b + base_uniform + 8 * g), hi = *(const float4*)(b + base_uniform + 8 * g + 4);
     return fh ? hi : lo;
-}
-
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
 }
 
 // DS: the block's shortcut is a 1x1 projection W_d (CIN -> C, BatchNorm folded) of x instead of x itself -- layer1's first block (CIN 64): the x halo
@@ -182,13 +179,10 @@ __device__ __forceinline__ void conv_bneck_body(const BneckLaunch& d, const int 
     load_x(tile, 0, xa);
     if (G::NC > 1) load_x(tile, 1, xb);
     store_x(xa, xbuf0);
-    lds_barrier();
+    gdt_lds_barrier();
 
 #ifdef GDT_BNECK_STAMP
     unsigned long long st_t = __builtin_amdgcn_s_memtime(), st_acc[4] = {0, 0, 0, 0};
-#define BN_STAMP(k) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st_acc[k] += now_ - st_t; st_t = now_; }
-#else
-#define BN_STAMP(k)
 #endif
     for (;;) {
         // (uniform base + 32-bit lane offset, refreshed per patch behind an opaque copy: as 64-bit per-lane addresses the fragment
@@ -239,7 +233,7 @@ __device__ __forceinline__ void conv_bneck_body(const BneckLaunch& d, const int 
                 }
             }
             if (c + 1 < G::NC) store_x(xin, (c & 1) ? xbuf0 : xbuf1);   // chunk c + 1 -> the buffer chunk c - 1 has left (barrier of iteration c - 1)
-            lds_barrier();
+            gdt_lds_barrier();
         }
         // r -> LDS (fp16) over the x buffers (all consumed: the loop ends with a barrier): lane holds pixel `row`, channels
         // rmb * 32 + 8 g + 4 fh + {0..3}; zero outside the image
@@ -270,8 +264,8 @@ __device__ __forceinline__ void conv_bneck_body(const BneckLaunch& d, const int 
             }
         }
         if (!G::W3_RES) store_w3(wq0, w3s);
-        lds_barrier();                     // r (and tap 0 of W_3) complete
-        BN_STAMP(0)
+        gdt_lds_barrier();                 // r (and tap 0 of W_3) complete
+        GDT_STAMP(st_acc[0])
         // the first two x chunks of the NEXT patch and the residual rows of this one are requested now: the memory system works through
         // the 3x3 phase, which itself touches LDS only (layer1) / L2 only (layer2's W_3 taps, which queue behind these loads once)
         if (has_next) { load_x(next, 0, xa); if (G::NC > 1) load_x(next, 1, xb); }
@@ -342,7 +336,7 @@ __device__ __forceinline__ void conv_bneck_body(const BneckLaunch& d, const int 
                             tacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, af, tacc[j], 0, 0, 0);
                         }
                     }
-                    if (q + 1 < G::NW3) { store_w3(win, w3s + ((q + 1) & 1) * G::W3P); lds_barrier(); }
+                    if (q + 1 < G::NW3) { store_w3(win, w3s + ((q + 1) & 1) * G::W3P); gdt_lds_barrier(); }
                 }
             }
             // (t has a region of its own -- behind r in the x buffers, or separate: no barrier before it is written)
@@ -370,8 +364,8 @@ __device__ __forceinline__ void conv_bneck_body(const BneckLaunch& d, const int 
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int kg = 0; kg < MID / 16; ++kg) wef[j][kg] = *(const f16x8*)((const char*)d.we + (((ecp * 2 + j) * (MID / 16) + kg) << 10) + lo16);
-        lds_barrier();                     // t complete; r consumed (its buffer becomes the waves' store patches)
-        BN_STAMP(1)
+        gdt_lds_barrier();                 // t complete; r consumed (its buffer becomes the waves' store patches)
+        GDT_STAMP(st_acc[1])
 
         // ================================================================ expand: y = ReLU(W_e t + b_e + x)
         {
@@ -455,12 +449,12 @@ __device__ __forceinline__ void conv_bneck_body(const BneckLaunch& d, const int 
                 }
             }
         }
-        BN_STAMP(2)
+        GDT_STAMP(st_acc[2])
         if (!has_next) break;
         tile = next;
-        lds_barrier();                     // every wave has left the expand phase: the x buffers (r, patches) may be rewritten
+        gdt_lds_barrier();                 // every wave has left the expand phase: the x buffers (r, patches) may be rewritten
         store_x(xa, xbuf0);
-        lds_barrier();
+        gdt_lds_barrier();
     }
 #ifdef GDT_BNECK_STAMP
     if (lane == 0 && d.stamps) { unsigned long long* o = d.stamps + ((size_t)bid * NWAVE + wave) * 4; o[0] = st_acc[0]; o[1] = st_acc[1]; o[2] = st_acc[2]; }

@@ -19,10 +19,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "gdt_common.h"
-
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
+#include "conv_device.h"
 
 namespace {
 
@@ -36,20 +33,9 @@ constexpr int LOAD_ROWS8 = (HPIX + 7) / 8;       // 67 wave-wide 1 KB loads per 
 constexpr int LROWS = 552;                       // LDS rows of the halo buffer: >= NBLK * 32 - 1 + 6 * HWD + 1 = 548
 constexpr int HBYTES = LROWS * 128;              // 70,656 B: two workgroups per CU
 constexpr int E_BYTES = (LROWS + 15) / 16 * 16;  // MX form: the activation scale byte of each halo pixel behind the halo (gdt_c_pixel_exp)
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int ROUNDS = (HPIX + NT / 8 - 1) / (NT / 8);      // 17 staging rounds of 32 halo pixels (F32IN form)
 constexpr int PSTRIDE = 33;                      // floats per partial-sum pixel (odd: the 7-tap combine is conflict free)
 static_assert(NBLK * 32 >= MROWS && NBLK * 32 * PSTRIDE * 4 <= HBYTES && LROWS >= LOAD_ROWS8 * 8 && NBLK <= 3 * NWAVE && ROUNDS * (NT / 8) <= LROWS, "layout");
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gsrc, (LDS_AS void*)lds_dst, 16, 0, 0);
-}
-// LDS-only workgroup barrier (no global-memory fence: global stores / loads stay in flight across it)
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // F32IN ("f16c" precision mode): the input is the fp32 NHWC tensor of that mode; the halo goes through registers (load, folded
 // InstanceNorm + ReLU in fp32, split into fp16(a) and the residual) instead of LDS-DMA + in-place normalisation.  With the
@@ -155,11 +141,11 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
             unsigned okmask = 0;
             auto issue = [&](int j, float4 (&rg)[2]) {
                 const int hp = t8 + j * (NT / 8);
-                const int hy = (hp * 1725) >> 16, hx = hp - hy * HWD;
+                int hy, hx;
+                gdt_halo_yx<HWD>(hp, hy, hx);
                 const int iy = y0 - 3 + hy, ix = x0 - 3 + hx;
-                int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-                int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
-                ry = min(max(ry, 0), d.H - 1); rx = min(max(rx, 0), d.W - 1);
+                int ry, rx;
+                GDT_REFLECT_CLAMP(iy, ix, d.H, d.W, ry, rx)
                 const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
                 if ((hp < HPIX) & (inb | refl)) okmask |= 1u << j;
                 const float* src = inf + ((size_t)((n * d.H + ry) * d.W + rx) * 64 + c8 * 8);
@@ -181,30 +167,21 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
                     smem[HBYTES + t8 + j * (NT / 8)] = (char)(127 + ex - 13);
                 }
                 // per channel pair k: normalise, round to fp16 (two per instruction); (MX) residuals p - fp16(p) in one v_fma_mix each, both
-                // planes to fp4 by the scaled converts (the byte select must be a literal: hence the macro; see conv3x3_halo_c.hip)
-#define GDT_H7_PAIR(k)                                                                                                                     \
-                {                                                                                                                          \
-                    const float p0 = pv[2 * k], p1 = pv[2 * k + 1];                                                                        \
-                    unsigned w;                                                                                                            \
-                    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(w) : "v"(p0), "v"(p1));                                                       \
-                    if (MX) {                                                                                                              \
-                        float l0, l1;                                                                                                      \
-                        asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(w), "v"(p0));                \
-                        asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(w), "v"(p1));                \
-                        qlo = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(qlo, l0, l1, lo_scale, k);                                          \
-                        qhi = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(qhi, __builtin_bit_cast(f16x2, w), hi_scale, k);                     \
-                    }                                                                                                                      \
-                    if (X3 && LO) {                                                                                                        \
-                        float l0, l1;                                                                                                      \
-                        asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(w), "v"(p0));                \
-                        asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(w), "v"(p1));                \
-                        l0 *= 2048.f; l1 *= 2048.f;                                                                                         \
-                        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(w) : "v"(l0), "v"(l1));                                                   \
-                    }                                                                                                                      \
-                    o[k] = ok ? w : 0u;                                                                                                    \
-                }
-                GDT_H7_PAIR(0) GDT_H7_PAIR(1) GDT_H7_PAIR(2) GDT_H7_PAIR(3)
-#undef GDT_H7_PAIR
+                // planes to fp4 by the scaled converts (gdt_c_quant)
+                auto pair = [&](auto kc) {
+                    constexpr int k = decltype(kc)::value;
+                    const float p0 = pv[2 * k], p1 = pv[2 * k + 1];
+                    unsigned w = gdt_pk_f16(p0, p1);
+                    if (MX) gdt_c_quant<k>(w, p0, p1, lo_scale, hi_scale, qlo, qhi);
+                    if (X3 && LO) {
+                        float l0, l1;
+                        gdt_pk_f16_rest(w, p0, p1, l0, l1);
+                        l0 *= 2048.f; l1 *= 2048.f;
+                        w = gdt_pk_f16(l0, l1);
+                    }
+                    o[k] = ok ? w : 0u;
+                };
+                pair(std::integral_constant<int, 0>{}); pair(std::integral_constant<int, 1>{}); pair(std::integral_constant<int, 2>{}); pair(std::integral_constant<int, 3>{});
                 if (MX) { qq[MX ? j : 0][0] = ok ? qlo : 0u; qq[MX ? j : 0][1] = ok ? qhi : 0u; }
                 // row hp = t8 + 32 j: the swizzle term (hp >> 1) & 7 does not depend on j, so the 17 addresses are one base + j * 4 KB
                 // (ROUNDS * 32 <= LROWS: every row exists)
@@ -218,7 +195,7 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
                 if (j + RING < ROUNDS) issue(j + RING, ring[j % RING]);
                 if (MX) __builtin_amdgcn_sched_barrier(0);        // (round by round: interleaved across rounds the 17 unrolled rounds spill)
             }
-            lds_barrier();
+            gdt_lds_barrier();
         };
         if (F32IN) {
             stage_f32(std::false_type{});
@@ -229,16 +206,16 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
             for (int j = 0; j < (LOAD_ROWS8 + NWAVE - 1) / NWAVE; ++j) {
                 const int row8 = min(wave + j * NWAVE, LOAD_ROWS8 - 1);     // (the surplus round repeats the last one)
                 const int hp = row8 * 8 + (lane >> 3);
-                const int hy = (hp * 1725) >> 16, hx = hp - hy * HWD;       // hp / 38 for hp < 2^11
+                int hy, hx;
+                gdt_halo_yx<HWD>(hp, hy, hx);
                 const int iy = y0 - 3 + hy, ix = x0 - 3 + hx;
-                int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-                int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
-                ry = min(max(ry, 0), d.H - 1); rx = min(max(rx, 0), d.W - 1);
+                int ry, rx;
+                GDT_REFLECT_CLAMP(iy, ix, d.H, d.W, ry, rx)
                 const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
                 const bool ok = (hp < HPIX) & (inb | refl);
                 const int q = (lane & 7) ^ ((hp >> 1) & 7);                   // XOR swizzle on the 16-byte chunk (as conv_igemm.hip)
                 const f16* src = d.in + ((long)((n * d.H + ry) * d.W + rx) * 64 + q * 8);
-                glds16(ok ? src : d.zeros, smem + row8 * 1024);
+                gdt_glds16(ok ? src : d.zeros, smem + row8 * 1024);
             }
         }
         __syncthreads();                               // DMA landed (the barrier drains vmcnt) and visible
@@ -256,7 +233,8 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
 #pragma unroll 2
             for (int j = 0; j < (HPIX + NT / 8 - 1) / (NT / 8); ++j) {
                 const int hp = t8 + j * (NT / 8);
-                const int hy = (hp * 1725) >> 16, hx = hp - hy * HWD;
+                int hy, hx;
+                gdt_halo_yx<HWD>(hp, hy, hx);
                 const int iy = y0 - 3 + hy, ix = x0 - 3 + hx;
                 const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
                 const bool ok = (hp < HPIX) & (inb | refl);
@@ -273,7 +251,7 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
                 }
                 if (hp < LROWS) *(u32x4*)pp = o;
             }
-            lds_barrier();
+            gdt_lds_barrier();
         }
 
         }
@@ -323,7 +301,7 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
                 }
             }
         }
-        lds_barrier();                                 // the halo has been consumed by every wave
+        gdt_lds_barrier();                             // the halo has been consumed by every wave
         if constexpr (MX) {
             // ---- correction pass: the fp4 plane over the consumed halo -- 64-byte rows [lo 0-31 | hi 0-31 | lo 32-63 | hi 32-63], 16-byte
             // pieces XOR-swizzled by (row >> 2) & 3 (conflict-free 16-lane fragment reads) -- then 14 MX MFMAs per block, weight fragments
@@ -337,10 +315,6 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
                 *(unsigned*)(smem + qbase + j * (NT / 8) * 64) = qq[j][0];
                 *(unsigned*)(smem + (qbase ^ 16) + j * (NT / 8) * 64) = qq[j][1];
             }
-            typedef int v4i __attribute__((ext_vector_type(4)));
-            typedef int v2i __attribute__((ext_vector_type(2)));
-            typedef int v6i __attribute__((ext_vector_type(6)));
-            typedef int v8i __attribute__((ext_vector_type(8)));
             v6i wq[2]; int wqs[2];
             auto load_wq = [&](int slot, int ms) {
                 const v4i qa = *(const v4i*)((const char*)d.wmx_a + ms * 4096 + lo16);
@@ -349,7 +323,7 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
                 wqs[slot] = *(const int*)((const char*)d.wmx_s + ms * 1024 + lo4);
             };
             load_wq(0, 0);
-            lds_barrier();
+            gdt_lds_barrier();
             const int a_scale_off = fh_t ? GDT_C_HI_SCALE_OFF : 0;       // lanes 0-31 carry a_lo, lanes 32-63 a_hi, at their pixel's scale
             const int qrow0 = wrot * 32 + fr_t;
 #pragma unroll
@@ -366,7 +340,7 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
                         acc[b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, wv, acc[b], 4, 2, 0, a_scale, 0, wqs[ms & 1]);
                     }
             }
-            lds_barrier();                             // the fp4 plane has been consumed
+            gdt_lds_barrier();                         // the fp4 plane has been consumed
         }
         if constexpr (X3) {
             // ---- second plane: a_lo over the consumed halo (read again, split again), then a_lo w_hi into the correction accumulators
@@ -389,7 +363,7 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
                 for (int b = 0; b < 2; ++b) accl[X3 ? b : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(afr[ks % PF][b], wk, accl[X3 ? b : 0], 0, 0, 0);
                 if (nb == 3) accl[X3 ? 2 : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(afr[ks % PF][2], wk, accl[X3 ? 2 : 0], 0, 0, 0);
             }
-            lds_barrier();                             // the lo plane has been consumed
+            gdt_lds_barrier();                         // the lo plane has been consumed
 #pragma unroll
             for (int b = 0; b < 3; ++b)
 #pragma unroll
@@ -402,7 +376,7 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
 #pragma unroll
                 for (int e = 0; e < 16; ++e) P[((wrot + b * NWAVE) * 32 + (e & 3) + 8 * (e >> 2) + 4 * fh_t) * PSTRIDE + fr_t] = acc[b][e];
             }
-        lds_barrier();
+        gdt_lds_barrier();
         for (int idx = tid; idx < cout * PH * PW && !(d.dbg & 4); idx += NT) {
             const int co = idx >> 8, y = (idx >> 5) & 7, x = idx & 31;
             float v = d.bias ? d.bias[co] : 0.f;
@@ -414,7 +388,7 @@ __global__ __launch_bounds__(NT, 2) void conv_head7_kernel(const ConvLaunch d, c
         }
         tile += S;
         if (tile >= span_hi) break;
-        lds_barrier();                                 // the partial sums have been read: the buffer may be refilled
+        gdt_lds_barrier();                             // the partial sums have been read: the buffer may be refilled
     }
 }
 

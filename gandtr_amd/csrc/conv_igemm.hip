@@ -16,19 +16,12 @@
 #include <cstdlib>
 
 #include "conv_epilogue.h"
-#include "gdt_common.h"
-
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
+#include "conv_device.h"
 
 namespace {
 
 constexpr int BK = 64;           // K-step (halves) = 128 B per tile row
 constexpr int ROWB = BK * 2;     // bytes per LDS tile row
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gsrc, (LDS_AS void*)lds_dst, 16, 0, 0);
-}
 
 template <int BM, int BN, int WGM, int WGN, bool NORM = false>
 __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_kernel(const ConvLaunch d) {
@@ -86,13 +79,13 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_kernel(const ConvLa
         char* As = smem + stage * A_BYTES;
         // branch-free padding: compute the reflected index and the in-bounds predicate, select afterwards
         const int iy = a_iy0[r] + n_dy, ix = a_ix0[r] + n_dx;
-        const int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-        const int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
+        int ry, rx;
+        GDT_REFLECT(iy, ix, d.H, d.W, ry, rx)
         const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
         const bool ok = n_tap_ok & (((a_valid >> r) & 1u) != 0) & (inb | refl);
         const int pix = a_base[r] + ry * d.W + rx;           // reflected == identity when in bounds
         const f16* src = d.in + (((long)pix << (d.lc8 + 3)) + n_c8 * 8);
-        glds16(ok ? src : d.zeros, As + (r * RPR + wave * 8) * ROWB);
+        gdt_glds16(ok ? src : d.zeros, As + (r * RPR + wave * 8) * ROWB);
     };
     // Fused InstanceNorm(+ReLU) of the producer for 64-channel inputs (generator: stem -> first down conv, last up conv -> head;
     // p2p_networks.py:271-272, :299-300): the A operand goes through registers -- raw fp16 chunk, x -> max((x-mean)*rstd, 0)
@@ -112,8 +105,8 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_kernel(const ConvLa
 #pragma unroll
         for (int r = 0; r < AR; ++r) {
             const int iy = a_iy0[r] + n_dy, ix = a_ix0[r] + n_dx;
-            const int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-            const int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
+            int ry, rx;
+            GDT_REFLECT(iy, ix, d.H, d.W, ry, rx)
             const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
             const bool ok = n_tap_ok & (((a_valid >> r) & 1u) != 0) & (inb | refl);
             const int pix = a_base[r] + ry * d.W + rx;
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_kernel(const ConvLa
     };
     auto issue_b = [&](int ks, int stage, int r) {
         char* Bs = smem + 2 * A_BYTES + stage * B_BYTES;
-        glds16(b_src + ((long)r * RPR * d.Kpad + ks * BK), Bs + (r * RPR + wave * 8) * ROWB);
+        gdt_glds16(b_src + ((long)r * RPR * d.Kpad + ks * BK), Bs + (r * RPR + wave * 8) * ROWB);
     };
 
     f32x16 acc[TM][TN];

@@ -21,7 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "gdt_common.h"
+#include "conv_device.h"
 
 namespace {
 
@@ -30,22 +30,12 @@ constexpr int BM = 256;
 constexpr int A_BYTES = BM * ROWB;                         // 32 KB per stage
 constexpr int NORM_BYTES = 4096 + 64;                      // (scale, shift): two slots of up to 256 input channels + a zero entry
 constexpr int C_OFF = 2 * A_BYTES + NORM_BYTES;            // epilogue transpose region (half a C tile)
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned norm_pair(unsigned raw, float s0, float h0, float s1, float h1) {
-    unsigned o;
-    asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(o) : "v"(raw), "v"(s0), "v"(h0));
-    asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(o) : "v"(raw), "v"(s1), "v"(h1));
-    return o;
-}
 
 // epilogue region: half a C tile (each wave's row blocks in two halves), or the whole tile when a wave owns a single row block
 template <int BN, int WGM>
 constexpr int irb_region_rows() { return (BM / WGM) / 32 >= 2 ? BM / 2 : BM; }
 template <int BN, int WGM>
 constexpr size_t irb_lds_bytes() { return (size_t)C_OFF + (size_t)8 * 32 * (64 + 8) * 2; }        // + eight wave-private transpose patches
-
-struct TileAt { int tile_m, tile_n; bool valid; };
 
 template <int BN, int WGM, int WGN, bool NORM, bool CTF = false>
 __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_rb_kernel(const ConvLaunch d, const int vblocks) {
@@ -61,14 +51,9 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_rb_kernel(const Con
     const int fr = lane & 31, fh = lane >> 5;
 
     const int ntm = (d.M + BM - 1) / BM, ntn = d.CoutPad / BN;
-    auto tile_at = [&](int vb) -> TileAt {
-        TileAt t;
-        t.valid = vb < vblocks && gdt_tile_of_block(vb, ntm, ntn, t.tile_m, t.tile_n);
-        if (!t.valid) { t.tile_m = 0; t.tile_n = 0; }
-        return t;
-    };
+    auto tile_at = [&](int vb) -> GdtTile { return gdt_tile_at(vb, vblocks, ntm, ntn); };
     int vb = blockIdx.x;
-    TileAt cur = tile_at(vb);
+    GdtTile cur = tile_at(vb);
     if (!cur.valid) return;                   // (validity is monotone in vb)
 
     const int hw_g = d.OHg * d.OWg;
@@ -80,7 +65,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_rb_kernel(const Con
     const int q = (lane & 7) ^ ((lrow >> 1) & 7);              // source chunk of its 16-byte piece (XOR swizzle; 64 r keeps it)
     int s_pix0[AR], s_iy0[AR], s_ix0[AR]; unsigned s_valid = 0;
     int s_n = 0;                                               // image of the staged tile (NORM: whole tiles lie in one image)
-    auto seat = [&](const TileAt& ta) {                        // per-row output position of the tile being staged
+    auto seat = [&](const GdtTile& ta) {                        // per-row output position of the tile being staged
         s_valid = 0;
 #pragma unroll
         for (int r = 0; r < AR; ++r) {
@@ -103,9 +88,8 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_rb_kernel(const Con
 #pragma unroll
         for (int r = 0; r < AR; ++r) {
             const int iy = s_iy0[r] + dy, ix = s_ix0[r] + dx;
-            int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-            int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
-            ry = min(max(ry, 0), d.H - 1); rx = min(max(rx, 0), d.W - 1);           // always a valid address
+            int ry, rx;
+            GDT_REFLECT_CLAMP(iy, ix, d.H, d.W, ry, rx)           // always a valid address
             const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
             const bool ok = (((s_valid >> r) & 1u) != 0) & (inb | refl);
             p.ok |= (ok ? 1u : 0u) << r;
@@ -117,10 +101,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_rb_kernel(const Con
     float* nlds = (float*)(smem + 2 * A_BYTES);
     constexpr int ZERO_ENTRY = 2 * 512;                        // floats
     auto stage_norm = [&](int n, int slot) {
-        for (int i = tid; i < d.Cin / 2; i += NT) {            // float4 = 2 channels x (mean, rstd)
-            const float4 v = *(const float4*)(d.in_norm + (long)n * d.Cin * 2 + i * 4);
-            *(float4*)(nlds + slot * 512 + i * 4) = make_float4(v.y, -v.x * v.y, v.w, -v.z * v.w);
-        }
+        gdt_stage_norm(nlds, slot, d.in_norm, d.Cin, n, tid, NT);
         if (tid < 4) *(float4*)(nlds + ZERO_ENTRY + tid * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
     };
     auto store_pend = [&](const Pend& p, int stage_off) {
@@ -138,7 +119,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_rb_kernel(const Con
                 const u32x4 rawu = __builtin_bit_cast(u32x4, p.v[r]);
                 u32x4 ou;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { const float4 v = np4[k]; ou[k] = norm_pair(rawu[k], v.x, v.y, v.z, v.w); }
+                for (int k = 0; k < 4; ++k) { const float4 v = np4[k]; ou[k] = gdt_norm_pair(rawu[k], v.x, v.y, v.z, v.w); }
                 o = __builtin_bit_cast(f16x8, ou);
                 f16x8 lo8;
 #pragma unroll
@@ -150,13 +131,13 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_rb_kernel(const Con
     };
     // advance the cursor by one K-step; past the end of a tile it moves to the next tile of this workgroup (or, when there is
     // none, parks on the current tile's first step: harmless re-reads, never consumed)
-    TileAt s_tile = cur; int s_vb = vb;
+    GdtTile s_tile = cur; int s_vb = vb;
     auto advance = [&]() {
         ++s_step; ++s_chunk;
         if (s_chunk == cpt) { s_chunk = 0; ++s_tap; }
         if (s_step == nk) {
             s_step = 0; s_chunk = 0; s_tap = 0;
-            const TileAt nx = tile_at(s_vb + gridDim.x);
+            const GdtTile nx = tile_at(s_vb + gridDim.x);
             if (nx.valid) {
                 s_tile = nx; s_vb += gridDim.x;
                 seat(s_tile);
@@ -200,7 +181,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_igemm_rb_kernel(const Con
 
     int so = 0;                                   // LDS offset of the current step's A stage
     for (;;) {
-        const TileAt nxt = tile_at(vb + gridDim.x);
+        const GdtTile nxt = tile_at(vb + gridDim.x);
         f32x16 acc[TM][TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i)

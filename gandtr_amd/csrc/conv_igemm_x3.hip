@@ -13,20 +13,13 @@
 // from the accumulators (one half-wave writes 128 contiguous bytes).
 #include <cstdlib>
 
-#include "gdt_common.h"
-
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
+#include "conv_device.h"
 
 namespace {
 
 constexpr int BK = 32;
 constexpr int ROWB = 64;                 // bytes per LDS row (32 halves)
 constexpr float LO_SCALE = 2048.f, LO_INV = 1.f / 2048.f;
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gsrc, (LDS_AS void*)lds_dst, 16, 0, 0);
-}
 
 template <int BN, int WGM, int WGN>
 __global__ __launch_bounds__(256) void conv_igemm_x3_kernel(const ConvLaunch d) {
@@ -79,8 +72,8 @@ __global__ __launch_bounds__(256) void conv_igemm_x3_kernel(const ConvLaunch d) 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int iy = a_iy0[r] + dy, ix = a_ix0[r] + dx;
-            const int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-            const int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
+            int ry, rx;
+            GDT_REFLECT(iy, ix, d.H, d.W, ry, rx)
             const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
             const bool ok = tap_ok & (((a_valid >> r) & 1u) != 0) & (inb | refl);
             const int pix = a_base[r] + ry * d.W + rx;
@@ -122,8 +115,8 @@ __global__ __launch_bounds__(256) void conv_igemm_x3_kernel(const ConvLaunch d) 
 #pragma unroll
         for (int r = 0; r < BR; ++r) {
             if (r * 64 + wave * 16 >= BN) continue;            // wave-uniform (BN = 32: waves 0, 1 only)
-            glds16(bh_src + ((long)r * 64 * d.Kpad + ks * BK), Bh + (r * 64 + wave * 16) * ROWB);
-            glds16(bl_src + ((long)r * 64 * d.Kpad + ks * BK), Bl + (r * 64 + wave * 16) * ROWB);
+            gdt_glds16(bh_src + ((long)r * 64 * d.Kpad + ks * BK), Bh + (r * 64 + wave * 16) * ROWB);
+            gdt_glds16(bl_src + ((long)r * 64 * d.Kpad + ks * BK), Bl + (r * 64 + wave * 16) * ROWB);
         }
     };
 

@@ -20,10 +20,7 @@
 
 #include <type_traits>
 
-#include "gdt_common.h"
-
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
+#include "conv_device.h"
 
 namespace {
 
@@ -34,10 +31,6 @@ constexpr int TW = 32;                     // output tile width (one 32-pixel MF
 constexpr int NWAVE = 4, NT = NWAVE * 64;
 constexpr int CP = 72;                     // halves per pixel row of the wave-private transpose patch (64 + 8)
 constexpr int PATCH_BYTES = 32 * CP * 2;   // 4608 B per wave
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gsrc, (LDS_AS void*)lds_dst, 16, 0, 0);
-}
 
 template <int KS, int S>
 struct StemCfg {
@@ -99,12 +92,11 @@ __global__ __launch_bounds__(NT, 2) void conv_stem_kernel(const ConvLaunch d, co
             const int hp = min(hp0 + lane, C::HPIX - 1);
             const int hy = hp / HW, hx = hp - hy * HW;
             const int iy = y0 * S - PAD + hy, ix = x0 * S - PAD + hx;
-            int ry = iy < 0 ? -iy : (iy >= d.H ? 2 * d.H - 2 - iy : iy);
-            int rx = ix < 0 ? -ix : (ix >= d.W ? 2 * d.W - 2 - ix : ix);
-            ry = min(max(ry, 0), d.H - 1); rx = min(max(rx, 0), d.W - 1);
+            int ry, rx;
+            GDT_REFLECT_CLAMP(iy, ix, d.H, d.W, ry, rx)
             const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
             const f16* src = d.in + (long)((n * d.H + ry) * d.W + rx) * 8;
-            glds16((inb | refl) ? src : d.zeros, hbuf + hp0 * 16);
+            gdt_glds16((inb | refl) ? src : d.zeros, hbuf + hp0 * 16);
         }
         __syncthreads();                               // DMA landed (the barrier drains vmcnt) and visible
 
@@ -674,7 +666,6 @@ int gdt_launch_conv_stem_c(const ConvLaunch& d, hipStream_t stream) {
     if (d.ntaps == 9) return launch_stem<3, 1, true>(d, stream);
     return d.sy == 1 ? launch_stem<7, 1, true>(d, stream) : launch_stem<7, 2, true>(d, stream);
 }
-
 
 // Direct form of the ResNet stem (see conv_stem_pair_kernel): the descriptor is the stem conv's (H, W = the image, w_frag = the pair-packed weights of
 // net_build.hip, fp16 NHWC output), x the caller's fp32 NCHW image with at most 3 channels, perm / scale / shift the input op's per-channel transform.

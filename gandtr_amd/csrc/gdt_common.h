@@ -1,4 +1,5 @@
-// Shared declarations for the gandtr HIP library (gfx950 / MI355X only).
+// Shared declarations for the gandtr HIP library (gfx950 / MI355X only): errors, knobs, the kernel launcher, the conv launch descriptor, host tile
+// arithmetic.  The device-side helpers of the conv kernels live in conv_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -185,23 +186,6 @@ struct ConvLaunch {
 // (GANDTR_HIP_JOINT_LEVELS=1 selects this path).
 constexpr int GDT_MAX_LEVELS = 4;
 
-// ---- "f16c" correction operands, activation side (conv3x3_halo_c.hip, conv3x3_halo_c16.hip, conv_head7.hip) ----
-// A staged halo pixel's 64 channels are held 8 per lane by 8 consecutive lanes.  Its scale exponent e is the exponent of max|a| over them,
-// clamped to the fp16 normal range: a_hi is stored as fp4(a_hi * 2^(2 - e)) (|a_hi| <= 2^(e + 1): the e2m1 range, 6 saturating),
-// a_lo = a - fp16(a) as fp4(a_lo * 2^(13 - e)) (|a_lo| <= 2^(e - 11): <= 4).  The scale follows the data, so the correction holds at
-// any activation magnitude and scaling the input by 2^s scales the result by exactly 2^s.  The byte kept per pixel is the E8M0 scale
-// of the a_lo operand, 127 + e - 13; the a_hi operand's is 11 more.
-constexpr int GDT_C_HI_SCALE_OFF = 11;
-__device__ __forceinline__ int gdt_c_pixel_exp(const float (&a)[8]) {
-    const float m = fmaxf(fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))),
-                          fmaxf(fmaxf(fabsf(a[4]), fabsf(a[5])), fmaxf(fabsf(a[6]), fabsf(a[7]))));
-    int b = __float_as_int(m);                                             // (non-negative: orders as an integer)
-    b = max(b, __builtin_amdgcn_mov_dpp(b, 0xB1, 0xF, 0xF, false));     // quad_perm [1, 0, 3, 2]
-    b = max(b, __builtin_amdgcn_mov_dpp(b, 0x4E, 0xF, 0xF, false));     // quad_perm [2, 3, 0, 1]
-    b = max(b, __builtin_amdgcn_mov_dpp(b, 0x141, 0xF, 0xF, false));    // row_half_mirror: the other quad of the 8 lanes
-    return min(max((b >> 23) - 127, -14), 15);
-}
-__device__ __forceinline__ float gdt_exp2i(int e) { return __int_as_float((e + 127) << 23); }      // 2^e, -126 <= e <= 127
 struct MultiConv {
     int nlev;
     int prefix[GDT_MAX_LEVELS + 1];      // first workgroup of each level; prefix[nlev] = grid size
@@ -209,12 +193,6 @@ struct MultiConv {
     ConvLaunch lev[GDT_MAX_LEVELS];
 };
 static_assert(sizeof(MultiConv) <= 4096, "kernel arguments are limited to 4 KB");
-__device__ __forceinline__ int gdt_multi_level(const int nlev, const int* prefix, const int b) {
-    int l = 0;
-#pragma unroll
-    for (int k = 1; k < GDT_MAX_LEVELS; ++k) l += (k < nlev && b >= prefix[k]) ? 1 : 0;
-    return l;
-}
 // host: grid ranges per level -- every level all its virtual blocks when they fit `slots` together, else shares in proportion (multiples of 8, at least 8)
 inline int gdt_multi_partition(int* prefix, const int* vb, int L, int slots) {
     long total = 0;
@@ -232,20 +210,7 @@ inline int gdt_multi_partition(int* prefix, const int* vb, int L, int slots) {
     return prefix[L];
 }
 
-// variant (optional out): which kernel ran -- BM*1000+BN for conv_igemm_kernel<BM,BN,..>, 900000+BN for conv3x3_halo_kernel<BN,..>, 910000+BN for conv3x3_halo_rb_kernel<BN,..>
-// Workgroup -> (M tile, N tile).  Workgroups are dealt round-robin over the 8 XCDs (observed, MI355X_MICROARCH.md), each
-// with a private L2.  Every XCD therefore gets ONE contiguous span of M tiles: spatially adjacent tiles (which share input
-// rows through the kernel taps / halos) and the N tiles of one M tile (which share the whole A operand) meet in the same L2.
-// With tiles interleaved over the XCDs instead, the 7x1 head conv of the generator fetched its 537 MB input 6.7 times
-// (FETCH_SIZE 3.6 GB per launch).  Placement only affects speed, never results.  Grid size: 8 * ceil(ntm / 8) * ntn.
-__device__ __forceinline__ bool gdt_tile_of_block(int b, int ntm, int ntn, int& tile_m, int& tile_n) {
-    const int mchunk = (ntm + 7) >> 3;
-    const int xcd = b & 7, j = b >> 3;
-    tile_n = j % ntn;
-    const int lm = j / ntn;
-    tile_m = xcd * mchunk + lm;
-    return lm < mchunk && tile_m < ntm;
-}
+// grid of the XCD-chunked tile walk (conv_device.h gdt_tile_of_block): 8 XCD lanes x their share of the M tiles x the N tiles
 inline int gdt_grid_for_tiles(int ntm, int ntn) { return 8 * ((ntm + 7) / 8) * ntn; }
 
 // ---- tile arithmetic of the patch kernels (host: what the eligibility predicates and the launchers count) ----
@@ -270,6 +235,7 @@ inline int gdt_fold_refused(int mode) {
     GDT_REQUIRE(false, "fold mode " + std::to_string(mode) + " does not exist in this form of the kernel");
 }
 
+// variant (optional out): which kernel ran -- BM*1000+BN for conv_igemm_kernel<BM,BN,..>, 900000+BN for conv3x3_halo_kernel<BN,..>, 910000+BN for conv3x3_halo_rb_kernel<BN,..>
 int gdt_launch_conv(const ConvLaunch& d, hipStream_t stream, int* variant = nullptr);
 int gdt_conv_family(const ConvLaunch& d);                  // conv_igemm.hip: 1 conv1x1_rb, 2 conv3x3_halo_rb, 0 other (the families with a multi-geometry entry)
 bool gdt_conv_igemm_norm_eligible(const ConvLaunch& d);    // conv_igemm.hip: fused input InstanceNorm in the generic kernel

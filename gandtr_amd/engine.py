@@ -195,7 +195,7 @@ class HipNet:
         return int(math.floor(float(h * scale))), int(math.floor(float(w * scale)))
 
     def _geometry(self, n, rh, rw):
-        """(workspace bytes, output shapes) of a geometry, planned once: every query plans the whole graph (make_plan, csrc/net.hip: ~0.1 ms for ResNet-101), and a
+        """(workspace bytes, output shapes) of a geometry, planned once: every query plans the whole graph (make_plan, csrc/net_plan.hip: ~0.1 ms for ResNet-101), and a
         forward asks three times per pyramid level -- 1.2 ms of the 8.6 ms a synchronised multi-scale call took (round 5)."""
         # (the knobs the library reads every time it plans, A/B inside one process, are part of the key: the library names them itself)
         key = (n, rh, rw, getattr(self, "_group_factor", 1.0)) + tuple(os.environ.get(k) for k in _hip.plan_knobs())
