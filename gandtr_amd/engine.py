@@ -11,6 +11,7 @@
 PyTorch is used for device memory and streams only; no torch op runs on the data path.
 """
 import collections
+import contextlib
 import ctypes
 import math
 import os
@@ -52,6 +53,27 @@ def side_stream(device, k):
     return pool[k]
 
 
+def _stream(t):
+    """the caller's stream on ``t``'s device, as the handle the C ABI takes"""
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _out_ptrs(outs):
+    return (ctypes.c_void_p * max(1, len(outs)))(*[o.data_ptr() for o in outs])
+
+
+def _grow(slots, k, need, device):
+    """``slots[k]``: a scratch buffer of at least ``need`` bytes (the old one is dropped BEFORE the larger one is allocated)"""
+    if slots[k] is None or slots[k].numel() < need:
+        slots[k] = None
+        slots[k] = torch.empty(need, dtype=torch.uint8, device=device)
+    return slots[k]
+
+
+# one prepared level of a forward: the fp32 contiguous input on the net's device, its geometry, the resized geometry and the pack kernel's step
+_Level = collections.namedtuple("_Level", "x n h w rh rw rscale")
+
+
 class HipNet:
     """One layer graph living on one GPU.  Host calls are serialised per handle (one thread at a time; see forward_many for what may overlap on the device)."""
 
@@ -70,14 +92,22 @@ class HipNet:
         self.handle = ctypes.c_void_p()
         _hip.check(self.lib.gdt_net_create(ctypes.byref(self.handle)))
         _hip.check(self.lib.gdt_net_set_precision(self.handle, self.PRECISIONS[precision]))
-        self.in_channels = None
-        self._ws = None
-        self._finalized = False
+        self.in_channels = None                    # channels of the graph's input (input())
+        self.out_slot = None                       # external output of the model's result (set by the build_* functions)
+        self.tap_slots = {}                        # generator: tap index -> external output
+        self.feature_slot = None                   # embedder: external output of the feature map, if tapped
+        self._finalized = False                    # finalize() ran: weights are on the device, forwards allowed, geometries cached
+        self._profiling = False                    # set_profiling: per-op events; profiled forwards run eagerly, level by level
+        self._group_factor = 1.0                   # the planner hint the handle holds (set_group_factor)
+        self._geo_cache = {}                       # (n, rh, rw, group factor, live knobs) -> (workspace bytes, output shapes)
+        self._ws = [None]                          # scratch buffer of forward() (one slot, see _grow)
+        self._side = {"streams": [], "ws": []}     # per level of forward_many: side stream and scratch buffer
+        self.side_workspace_cap = 8 << 30          # bytes of side scratch kept between forward_many calls
         # hipGraph replay of whole forwards (launch-bound small batches: the reference's own operating point is batch 1)
         self.use_graphs = os.environ.get("GANDTR_HIP_GRAPHS", "0") == "1"   # measured: no gain (kernels, not launches, bound batch 1)
-        self.graph_max_workspace = 2 << 30      # geometries needing more scratch than this run eagerly
+        self.graph_max_workspace = 2 << 30         # geometries needing more scratch than this run eagerly
         self._graphs = collections.OrderedDict()   # key -> dict(graph, x, outs, ws) ; LRU of 8
-        self._seen = {}
+        self._seen = {}                            # key -> eager forwards so far (negative: capture failed, stay eager)
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -89,14 +119,19 @@ class HipNet:
             self.handle = None
 
     # ---- builder -------------------------------------------------------------------------------------------------
-    def input(self, channels, perm=None, scale=None, shift=None):
+    def _add(self, op, *args):
+        """call the adder ``gdt_net_<op>`` (handle first, new tensor id last) and return that id"""
         out = ctypes.c_int()
+        _hip.check(getattr(self.lib, "gdt_net_" + op)(self.handle, *args, ctypes.byref(out)))
+        return out.value
+
+    def input(self, channels, perm=None, scale=None, shift=None):
         perm_a = (ctypes.c_int * channels)(*perm) if perm is not None else None
         scale_a = (ctypes.c_float * channels)(*scale) if scale is not None else None
         shift_a = (ctypes.c_float * channels)(*shift) if shift is not None else None
-        _hip.check(self.lib.gdt_net_input(self.handle, channels, perm_a, scale_a, shift_a, ctypes.byref(out)))
+        out = self._add("input", channels, perm_a, scale_a, shift_a)
         self.in_channels = channels
-        return out.value
+        return out
 
     def conv(self, x, weight, bias=None, bn=None, stride=1, pad=0, reflect=False, transposed=False, relu=False,
              residual=-1, out_f32=False, act=0, dilation=1):
@@ -108,36 +143,24 @@ class HipNet:
         if dilation != 1:                 # gdt_net_conv_dilated: plain Conv2d + bias, no BN / residual
             if bn is not None or residual != -1:
                 raise ValueError("a dilated conv takes no BatchNorm and no residual")
-            out = ctypes.c_int()
-            _hip.check(self.lib.gdt_net_conv_dilated(self.handle, x, ctypes.byref(d), int(dilation), _ptr(w), _ptr(b), ctypes.byref(out)))
-            return out.value
+            return self._add("conv_dilated", x, ctypes.byref(d), int(dilation), _ptr(w), _ptr(b))
         g = be = m = v = None
         if bn is not None:
             g, be, m, v = (_f32(t) for t in bn)
-        out = ctypes.c_int()
-        _hip.check(self.lib.gdt_net_conv(self.handle, x, ctypes.byref(d), _ptr(w), _ptr(b), _ptr(g), _ptr(be), _ptr(m),
-                                         _ptr(v), residual, ctypes.byref(out)))
-        return out.value
+        return self._add("conv", x, ctypes.byref(d), _ptr(w), _ptr(b), _ptr(g), _ptr(be), _ptr(m), _ptr(v), residual)
 
     def instance_norm(self, x, relu=False, residual=-1, eps=1e-5):
-        out = ctypes.c_int()
-        _hip.check(self.lib.gdt_net_instance_norm(self.handle, x, eps, int(relu), residual, ctypes.byref(out)))
-        return out.value
+        return self._add("instance_norm", x, eps, int(relu), residual)
 
     def maxpool(self, x, kernel, stride, pad=0, ceil=False):
-        out = ctypes.c_int()
-        if ceil:
-            if pad:
-                raise ValueError("ceil-mode max-pooling takes no padding here")
-            _hip.check(self.lib.gdt_net_maxpool_ceil(self.handle, x, kernel, stride, ctypes.byref(out)))
-        else:
-            _hip.check(self.lib.gdt_net_maxpool(self.handle, x, kernel, stride, pad, ctypes.byref(out)))
-        return out.value
+        if not ceil:
+            return self._add("maxpool", x, kernel, stride, pad)
+        if pad:
+            raise ValueError("ceil-mode max-pooling takes no padding here")
+        return self._add("maxpool_ceil", x, kernel, stride)
 
     def gem_l2n(self, x, p, eps_gem=1e-6, eps_l2=1e-6):
-        out = ctypes.c_int()
-        _hip.check(self.lib.gdt_net_gem_l2n(self.handle, x, float(p), eps_gem, eps_l2, ctypes.byref(out)))
-        return out.value
+        return self._add("gem_l2n", x, float(p), eps_gem, eps_l2)
 
     POOL_KINDS = {"mac": 0, "spoc": 1, "gem": 2, "gemmp": 3}         # include/gandtr_hip.h, gdt_net_pool_head
 
@@ -147,26 +170,18 @@ class HipNet:
         pa = _f32(p).reshape(-1) if p is not None else None
         rw, rb = (_f32(rwhiten[0]), _f32(rwhiten[1])) if rwhiten is not None else (None, None)
         fw, fb = (_f32(whiten[0]), _f32(whiten[1])) if whiten is not None else (None, None)
-        out = ctypes.c_int()
-        _hip.check(self.lib.gdt_net_pool_head(self.handle, x, self.POOL_KINDS[kind], _ptr(pa), 0 if pa is None else pa.size, float(eps), int(aggregate),
-                                              int(levels), _ptr(rw), _ptr(rb), _ptr(fw), _ptr(fb), float(eps_l2), ctypes.byref(out)))
-        return out.value
+        return self._add("pool_head", x, self.POOL_KINDS[kind], _ptr(pa), 0 if pa is None else pa.size, float(eps), int(aggregate),
+                         int(levels), _ptr(rw), _ptr(rb), _ptr(fw), _ptr(fb), float(eps_l2))
 
     def output_nchw(self, x, bias=None):
-        out = ctypes.c_int()
         b = _f32(bias)
-        _hip.check(self.lib.gdt_net_output_nchw(self.handle, x, _ptr(b), ctypes.byref(out)))
-        return out.value
+        return self._add("output_nchw", x, _ptr(b))
 
     def hed_head(self, feats, score_w, score_b, fusion_w, fusion_b, sigmoid=True):
         ws = [_f32(w).reshape(-1) for w in score_w]
         wp = (ctypes.c_void_p * 5)(*[w.ctypes.data for w in ws])
-        out = ctypes.c_int()
-        _hip.check(self.lib.gdt_net_hed_head(self.handle, (ctypes.c_int * 5)(*feats), wp,
-                                             (ctypes.c_float * 5)(*[float(b) for b in score_b]),
-                                             (ctypes.c_float * 5)(*[float(w) for w in fusion_w]), float(fusion_b),
-                                             int(sigmoid), ctypes.byref(out)))
-        return out.value
+        return self._add("hed_head", (ctypes.c_int * 5)(*feats), wp, (ctypes.c_float * 5)(*[float(b) for b in score_b]),
+                         (ctypes.c_float * 5)(*[float(w) for w in fusion_w]), float(fusion_b), int(sigmoid))
 
     def rcf_head(self, feats, stage_of, side_w, stage_b, fuse_w, fuse_b, sigmoid=True):
         """gdt_net_rcf_head: 13 feature tensors, their stages, the folded side vectors (one per feature) and stage biases"""
@@ -174,11 +189,9 @@ class HipNet:
             raise ValueError("the RCF head takes 13 features (and stages / side vectors) and 5 stage biases / fusion weights")
         ws = [_f32(w).reshape(-1) for w in side_w]
         wp = (ctypes.c_void_p * 13)(*[w.ctypes.data for w in ws])
-        out = ctypes.c_int()
-        _hip.check(self.lib.gdt_net_rcf_head(self.handle, (ctypes.c_int * 13)(*feats), (ctypes.c_int * 13)(*stage_of), wp,
-                                             (ctypes.c_float * 5)(*[float(b) for b in stage_b]),
-                                             (ctypes.c_float * 5)(*[float(w) for w in fuse_w]), float(fuse_b), int(sigmoid), ctypes.byref(out)))
-        return out.value
+        return self._add("rcf_head", (ctypes.c_int * 13)(*feats), (ctypes.c_int * 13)(*stage_of), wp,
+                         (ctypes.c_float * 5)(*[float(b) for b in stage_b]), (ctypes.c_float * 5)(*[float(w) for w in fuse_w]), float(fuse_b),
+                         int(sigmoid))
 
     def finalize(self):
         with torch.cuda.device(self.device):
@@ -186,7 +199,7 @@ class HipNet:
         self._finalized = True
         return self
 
-    # ---- execution -----------------------------------------------------------------------------------------------
+    # ---- planning ------------------------------------------------------------------------------------------------
     @staticmethod
     def resized_size(h, w, scale):
         """Output size of F.interpolate(scale_factor=s): floor(float(in * s)) (torch/nn/functional.py)."""
@@ -198,9 +211,8 @@ class HipNet:
         """(workspace bytes, output shapes) of a geometry, planned once: every query plans the whole graph (make_plan, csrc/net_plan.hip: ~0.1 ms for ResNet-101), and a
         forward asks three times per pyramid level -- 1.2 ms of the 8.6 ms a synchronised multi-scale call took (round 5)."""
         # (the knobs the library reads every time it plans, A/B inside one process, are part of the key: the library names them itself)
-        key = (n, rh, rw, getattr(self, "_group_factor", 1.0)) + tuple(os.environ.get(k) for k in _hip.plan_knobs())
-        cache = self.__dict__.setdefault("_geo_cache", {})
-        hit = cache.get(key)
+        key = (n, rh, rw, self._group_factor) + tuple(os.environ.get(k) for k in _hip.plan_knobs())
+        hit = self._geo_cache.get(key)
         if hit is None:
             b = ctypes.c_size_t()
             _hip.check(self.lib.gdt_net_workspace_bytes(self.handle, n, rh, rw, ctypes.byref(b)))
@@ -209,12 +221,15 @@ class HipNet:
             for slot in range(self.lib.gdt_net_num_outputs(self.handle)):
                 _hip.check(self.lib.gdt_net_output_shape(self.handle, slot, n, rh, rw, dims, ctypes.byref(ndim)))
                 shapes.append(tuple(dims[i] for i in range(ndim.value)))
-            if len(cache) > 256:
-                cache.clear()
+            if len(self._geo_cache) > 256:
+                self._geo_cache.clear()
             hit = (b.value, shapes)
             if self._finalized:
-                cache[key] = hit
+                self._geo_cache[key] = hit
         return hit
+
+    def workspace_bytes(self, n, rh, rw):
+        return self._geometry(n, rh, rw)[0]
 
     def output_shapes(self, n, rh, rw):
         return list(self._geometry(n, rh, rw)[1])
@@ -222,102 +237,176 @@ class HipNet:
     PLAN_KEYS = ("conv_launches", "bottlenecks_fused", "conv3x3_expand", "chained_reduce", "shortcuts_folded", "norms_folded", "pools_fused", "direct_stem",
                  "transposed_fused", "stride2_shift", "dilated_convs", "dilated_special_forms")
 
+    def _plan_counts(self, n, rh, rw, resize, count):
+        """the first ``count`` counters of gdt_net_plan_summary for a geometry: host logic, no device call"""
+        c = (ctypes.c_int * count)()
+        _hip.check(self.lib.gdt_net_plan_summary(self.handle, n, rh, rw, int(bool(resize)), c, count))
+        return list(c)
+
     def plan_summary(self, n, rh, rw, resize=False):
-        """the planner's fusion decisions for a geometry as a dict of counts (gdt_net_plan_summary: host logic, no device call)"""
-        c = (ctypes.c_int * 12)()
-        _hip.check(self.lib.gdt_net_plan_summary(self.handle, n, rh, rw, int(bool(resize)), c, 12))
-        return dict(zip(self.PLAN_KEYS, list(c)))
+        """the planner's fusion decisions for a geometry as a dict of counts"""
+        return dict(zip(self.PLAN_KEYS, self._plan_counts(n, rh, rw, resize, 12)))
 
     def head_launches(self, n, rh, rw):
-        """(launches of the net's pool-head ops, launches among them that read the feature map) for a geometry -- the planner's count, no device call"""
-        c = (ctypes.c_int * 14)()
-        _hip.check(self.lib.gdt_net_plan_summary(self.handle, n, rh, rw, 0, c, 14))
-        return c[12], c[13]
+        """(launches of the net's pool-head ops, launches among them that read the feature map) for a geometry -- the planner's count"""
+        return tuple(self._plan_counts(n, rh, rw, False, 14)[12:])
 
     def flops(self, n, rh, rw):
         f = ctypes.c_double()
         _hip.check(self.lib.gdt_net_flops(self.handle, n, rh, rw, ctypes.byref(f)))
         return f.value
 
-    def set_profiling(self, enable):
-        self._profiling = bool(enable)          # profiled forwards run eagerly (events are recorded per op)
-        _hip.check(self.lib.gdt_net_set_profiling(self.handle, int(enable)))
-
-    def profile(self):
-        """per-op (kind, conv N-tile, ms, algorithmic flops) of the last profiled forward"""
-        cap = max(1, int(self.lib.gdt_net_num_ops(self.handle)))
-        n = ctypes.c_int()
-        kinds, tiles = (ctypes.c_int * cap)(), (ctypes.c_int * cap)()
-        ms, fl = (ctypes.c_double * cap)(), (ctypes.c_double * cap)()
-        _hip.check(self.lib.gdt_net_profile_read(self.handle, cap, ctypes.byref(n), kinds, tiles, ms, fl))
-        return [(kinds[i], tiles[i], ms[i], fl[i]) for i in range(n.value)]
-
-    def profile_bytes(self):
-        """per-op algorithmic HBM bytes of the last profiled forward (same op order as profile())"""
-        cap = max(1, int(self.lib.gdt_net_num_ops(self.handle)))
-        n = ctypes.c_int()
-        by = (ctypes.c_double * cap)()
-        _hip.check(self.lib.gdt_net_profile_read_bytes(self.handle, cap, ctypes.byref(n), by))
-        return [by[i] for i in range(n.value)]
-
-    def workspace_bytes(self, n, rh, rw):
-        return self._geometry(n, rh, rw)[0]
-
     def set_group_factor(self, factor):
         """planner hint for the geometry planned next: it runs concurrently with others of this net; factor = (pixels of all of them) / (its own), 1 = alone
         (gdt_net_set_group_factor).  forward_many sets it per level and resets it."""
         factor = max(1.0, float(factor))
-        if factor != getattr(self, "_group_factor", 1.0):
+        if factor != self._group_factor:
             _hip.check(self.lib.gdt_net_set_group_factor(self.handle, factor))
             self._group_factor = factor
 
+    # ---- profiling -----------------------------------------------------------------------------------------------
+    def set_profiling(self, enable):
+        self._profiling = bool(enable)          # profiled forwards run eagerly (events are recorded per op)
+        _hip.check(self.lib.gdt_net_set_profiling(self.handle, int(enable)))
+
+    def _profile_columns(self, read, *types):
+        """the per-op columns a gdt_net_profile_read* call fills, one list per ctypes type, cut to the ops of the last profiled forward"""
+        cap = max(1, int(self.lib.gdt_net_num_ops(self.handle)))
+        n = ctypes.c_int()
+        cols = [(t * cap)() for t in types]
+        _hip.check(read(self.handle, cap, ctypes.byref(n), *cols))
+        return [c[:n.value] for c in cols]
+
+    def profile(self):
+        """per-op (kind, conv N-tile, ms, algorithmic flops) of the last profiled forward"""
+        return list(zip(*self._profile_columns(self.lib.gdt_net_profile_read, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double)))
+
+    def profile_bytes(self):
+        """per-op algorithmic HBM bytes of the last profiled forward (same op order as profile())"""
+        return self._profile_columns(self.lib.gdt_net_profile_read_bytes, ctypes.c_double)[0]
+
+    # ---- execution -----------------------------------------------------------------------------------------------
+    def _level(self, x, scale):
+        """``(x, scale)`` checked and prepared: the input as fp32, contiguous, on this net's device, and the geometry gdt_net_forward takes"""
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError("expected an N x %s x H x W input, got %s" % (self.in_channels, tuple(x.shape)))
+        x = x.to(self.device).contiguous().float()
+        n, _, h, w = x.shape
+        rh, rw = self.resized_size(h, w, scale)
+        return _Level(x, n, h, w, rh, rw, float(np.float32(1.0 / scale)) if scale is not None else 1.0)
+
+    def _buffers(self, slots, k, lv):
+        """(scratch buffer ``slots[k]`` grown to the level's need, its freshly allocated outputs), on the current stream; the geometry comes from the cache"""
+        need, shapes = self._geometry(lv.n, lv.rh, lv.rw)
+        return _grow(slots, k, need, self.device), self._alloc_outputs(shapes)
+
+    def _alloc_outputs(self, shapes):
+        return [torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes]
+
     def _launch(self, x, n, h, w, rh, rw, rscale, ws, outs):
-        optrs = (ctypes.c_void_p * max(1, len(outs)))(*[o.data_ptr() for o in outs])
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _hip.check(self.lib.gdt_net_forward(self.handle, x.data_ptr(), n, h, w, rh, rw, rscale, optrs, len(outs),
-                                            ws.data_ptr(), ws.numel(), stream))
+        _hip.check(self.lib.gdt_net_forward(self.handle, x.data_ptr(), n, h, w, rh, rw, rscale, _out_ptrs(outs), len(outs),
+                                            ws.data_ptr(), ws.numel(), _stream(x)))
 
     def forward(self, x, scale=None):
         """x: fp32 NCHW tensor on this net's device.  ``scale``: optional F.interpolate scale_factor applied to the
-        input inside the pack kernel.  Returns the list of external outputs (torch tensors on the device).
-
-        A geometry seen for the second time is captured into a hipGraph (static input / output / scratch buffers) and
-        replayed from then on: one graph launch instead of ~100 kernel launches, which is what bounds small batches."""
+        input inside the pack kernel.  Returns the list of external outputs (torch tensors on the device)."""
         if not self._finalized:
             raise RuntimeError("HipNet.forward before finalize()")
-        if x.dim() != 4 or x.shape[1] != self.in_channels:
-            raise ValueError("expected an N x %s x H x W input, got %s" % (self.in_channels, tuple(x.shape)))
-        if x.device != self.device:
-            x = x.to(self.device)
-        x = x.contiguous().float()
-        n, _, h, w = x.shape
-        rh, rw = self.resized_size(h, w, scale)
-        rscale = float(np.float32(1.0 / scale)) if scale is not None else 1.0
-        key = (n, h, w, rh, rw, rscale)
-        with torch.cuda.device(x.device):
-            entry = self._graphs.get(key) if (self.use_graphs and not getattr(self, "_profiling", False)) else None      # (a profiled forward runs eagerly: events per op)
+        lv = self._level(x, scale)
+        with torch.cuda.device(self.device):
+            outs = self._replayed(lv)
+            if outs is None:
+                ws, outs = self._buffers(self._ws, 0, lv)
+                self._launch(*lv, ws, outs)
+        return outs
+
+    # hipGraph replay (opt-in: use_graphs).  A geometry seen for the second time is captured into a hipGraph (static input / output / scratch buffers) and replayed
+    # from then on: one graph launch instead of ~100 kernel launches, which is what bounds small batches.
+    def _replayed(self, lv):
+        """the outputs of ``lv`` from a replayed (or just captured) graph, or None: the caller launches eagerly, which is counted as a sighting of the geometry"""
+        key = lv[1:]
+        if self.use_graphs and not self._profiling:      # (a profiled forward runs eagerly: events per op)
+            entry = self._graphs.get(key)
             if entry is not None:
                 self._graphs.move_to_end(key)
-                entry["x"].copy_(x)
+                entry["x"].copy_(lv.x)
                 entry["graph"].replay()
+            elif self._seen.get(key, 0) >= 1 and not torch.cuda.is_current_stream_capturing():
+                need, shapes = self._geometry(lv.n, lv.rh, lv.rw)
+                if need <= self.graph_max_workspace:
+                    entry = self._capture(lv, need, shapes)
+            if entry is not None:
                 return [o.clone() for o in entry["outs"]]
-            need = self.workspace_bytes(n, rh, rw)
-            shapes = self.output_shapes(n, rh, rw)
-            profiling = getattr(self, "_profiling", False)
-            if self.use_graphs and not profiling and need <= self.graph_max_workspace and self._seen.get(key, 0) >= 1 \
-                    and not torch.cuda.is_current_stream_capturing():
-                entry = self._capture(x, key, need, shapes)
-                if entry is not None:
-                    return [o.clone() for o in entry["outs"]]
-            self._seen[key] = self._seen.get(key, 0) + 1
-            if len(self._seen) > 256:
-                self._seen.clear()
-            if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
-                self._ws = None
-                self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-            outs = [torch.empty(s, dtype=torch.float32, device=x.device) for s in shapes]
-            self._launch(x, n, h, w, rh, rw, rscale, self._ws, outs)
-        return outs
+        self._seen[key] = self._seen.get(key, 0) + 1
+        if len(self._seen) > 256:
+            self._seen.clear()
+        return None
+
+    def _capture(self, lv, need, shapes):
+        dev, geo = self.device, lv[1:]
+        try:
+            sx = lv.x.clone()
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            outs = self._alloc_outputs(shapes)
+            side = side_stream(dev, 0)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):           # warm-up outside capture (lazy function attributes etc.)
+                self._launch(sx, *geo, ws, outs)
+            torch.cuda.current_stream(dev).wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._launch(sx, *geo, ws, outs)
+            g.replay()
+        except Exception:               # capture is an optimisation only: fall back to eager launches for this geometry
+            self._seen[geo] = -(1 << 30)
+            return None
+        entry = {"graph": g, "x": sx, "outs": outs, "ws": ws}
+        self._graphs[geo] = entry
+        while len(self._graphs) > 8:
+            self._graphs.popitem(last=False)
+        return entry
+
+    # ---- several levels in flight --------------------------------------------------------------------------------
+    MAX_LEVELS = 4          # GDT_MAX_LEVELS (csrc/gdt_common.h): geometries per gdt_net_forward_levels call
+
+    def _group_px(self, inputs):
+        """resized pixels of a group of levels (what is not an image is refused later, level by level)"""
+        return float(sum(x.shape[0] * math.prod(self.resized_size(x.shape[2], x.shape[3], s)) for x, s in inputs if x.dim() == 4))
+
+    def _set_level_factor(self, group_px, lv, joint, alone=False):
+        """Tell the planner that ``lv`` runs together with its group: fusion thresholds count the group's patches."""
+        # The two paths differ, and are kept apart on purpose -- the factor feeds planner thresholds and the geometry-cache key, so unifying them would change
+        # plans: the side-stream path rounds to three decimals; the joint path does not round, and a group of one is alone (1.0).
+        f = group_px / float(lv.n * lv.rh * lv.rw)
+        self.set_group_factor((1.0 if alone else f) if joint else round(f, 3))
+
+    def _side_pools(self, count):
+        streams, slots = self._side["streams"], self._side["ws"]
+        while len(streams) < count:
+            streams.append(side_stream(self.device, len(streams)))
+            slots.append(None)
+
+    def _release_side_over_cap(self, cur):
+        slots = self._side["ws"]
+        if sum(w.numel() for w in slots if w is not None) > self.side_workspace_cap:
+            for k, w in enumerate(slots):
+                if w is not None:
+                    w.record_stream(cur)
+                    slots[k] = None
+
+    @contextlib.contextmanager
+    def _level_group(self, count):
+        """The frame of a forward_many call, yielding the caller's stream: ``count`` side streams and scratch slots exist; when the body is through, the side
+        scratch over ``side_workspace_cap`` is released (the caller's stream is the last to have used it); however it ends -- also when a level is refused
+        half-way -- the handle is back at group factor 1, so that the next plan is a single geometry's."""
+        cur = torch.cuda.current_stream(self.device)
+        self._side_pools(count)
+        try:
+            with torch.cuda.device(self.device):
+                yield cur
+                self._release_side_over_cap(cur)
+        finally:
+            self.set_group_factor(1.0)
 
     def forward_many(self, inputs):
         """Several independent forwards -- ``inputs`` = [(x, scale or None), ...], e.g. the levels of the multi-scale pyramid
@@ -336,66 +425,35 @@ class HipNet:
             return [self.forward(x, scale=s) for x, s in inputs]
         if os.environ.get("GANDTR_HIP_JOINT_LEVELS", "0") == "1":           # (opt-in: measured 5-12 % slower than the side streams, csrc/gdt_common.h MultiConv)
             return self._forward_levels(inputs)
-        if getattr(self, "_profiling", False):
+        if self._profiling:
             return [self.forward(x, scale=s) for x, s in inputs]
-        dev = self.device
-        cur = torch.cuda.current_stream(dev)
-        pools = self.__dict__.setdefault("_side", {"streams": [], "ws": []})
-        while len(pools["streams"]) < len(inputs):
-            pools["streams"].append(side_stream(dev, len(pools["streams"])))
-            pools["ws"].append(None)
-        group_px = float(sum(x.shape[0] * math.prod(self.resized_size(x.shape[2], x.shape[3], s)) for x, s in inputs if x.dim() == 4))
-        try:
-          with torch.cuda.device(dev):
-            # GANDTR_HIP_FIRST_ON_CURRENT=1 (experiment, off): the first input on the CALLER's stream, issued last, the others on side streams issued first -- one
-            # stream fewer, so that the default stream, two side streams and a collective's stream have a hardware queue each (the runtime has four).  Measured:
-            # 8 x 1024^2 6.68 -> 6.80 ms, 1 x 1024^2 2.87 -> 2.78 ms, one sharded rank 1127 -> 1100 descriptors/s: no
-            first_on_cur = os.environ.get("GANDTR_HIP_FIRST_ON_CURRENT", "0") == "1"
-            results = [None] * len(inputs)
-            order = (list(range(1, len(inputs))) + [0]) if first_on_cur else list(range(len(inputs)))
-            # (the order in which the host enqueues the levels -- as given, smallest first, largest first -- makes no difference: hub scales at 8 x 1024^2 6.36 / 6.56 /
-            # 6.43 ms, {1, 1/sqrt 2, sqrt 2} 13.68 / 13.64 / 13.67 ms)
+        # GANDTR_HIP_FIRST_ON_CURRENT=1 (experiment, off): the first input on the CALLER's stream, issued last, the others on side streams issued first -- one
+        # stream fewer, so that the default stream, two side streams and a collective's stream have a hardware queue each (the runtime has four).  Measured:
+        # 8 x 1024^2 6.68 -> 6.80 ms, 1 x 1024^2 2.87 -> 2.78 ms, one sharded rank 1127 -> 1100 descriptors/s: no
+        first_on_cur = os.environ.get("GANDTR_HIP_FIRST_ON_CURRENT", "0") == "1"
+        # (the order in which the host enqueues the levels -- as given, smallest first, largest first -- makes no difference: hub scales at 8 x 1024^2 6.36 / 6.56 /
+        # 6.43 ms, {1, 1/sqrt 2, sqrt 2} 13.68 / 13.64 / 13.67 ms)
+        order = (list(range(1, len(inputs))) + [0]) if first_on_cur else list(range(len(inputs)))
+        side = [k for k in range(len(inputs)) if not (first_on_cur and k == 0)]      # the levels that run on a side stream
+        results = [None] * len(inputs)
+        group_px = self._group_px(inputs)
+        with self._level_group(len(inputs)) as cur:
             for k in order:
-                x, scale = inputs[k]
-                if x.dim() != 4 or x.shape[1] != self.in_channels:
-                    raise ValueError("expected an N x %s x H x W input, got %s" % (self.in_channels, tuple(x.shape)))
-                x = x.to(dev).contiguous().float()
-                n, _, h, w = x.shape
-                rh, rw = self.resized_size(h, w, scale)
-                rscale = float(np.float32(1.0 / scale)) if scale is not None else 1.0
-                self.set_group_factor(round(group_px / float(n * rh * rw), 3))       # the levels run together: fusion thresholds count the group's patches
-                need = self.workspace_bytes(n, rh, rw)
-                shapes = self.output_shapes(n, rh, rw)
-                on_cur = first_on_cur and k == 0
-                st = cur if on_cur else pools["streams"][k]
-                if not on_cur:
+                lv = self._level(*inputs[k])
+                self._set_level_factor(group_px, lv, joint=False)
+                st = self._side["streams"][k] if k in side else cur
+                if k in side:
                     st.wait_stream(cur)
                 with torch.cuda.stream(st):
-                    if pools["ws"][k] is None or pools["ws"][k].numel() < need:
-                        pools["ws"][k] = None
-                        pools["ws"][k] = torch.empty(need, dtype=torch.uint8, device=dev)
-                    outs = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes]
-                    self._launch(x, n, h, w, rh, rw, rscale, pools["ws"][k], outs)
-                    if not on_cur:
-                        x.record_stream(st)
-                results[k] = outs
-            for k in range(len(inputs)):
-                if first_on_cur and k == 0:
-                    continue
-                cur.wait_stream(pools["streams"][k])
+                    ws, results[k] = self._buffers(self._side["ws"], k, lv)
+                    self._launch(*lv, ws, results[k])
+                    if k in side:
+                        lv.x.record_stream(st)
+            for k in side:
+                cur.wait_stream(self._side["streams"][k])
                 for o in results[k]:
                     o.record_stream(cur)
-            held = sum(w.numel() for w in pools["ws"] if w is not None)
-            if held > getattr(self, "side_workspace_cap", 8 << 30):
-                for k, w in enumerate(pools["ws"]):
-                    if w is not None:
-                        w.record_stream(cur)
-                        pools["ws"][k] = None
-        finally:
-            self.set_group_factor(1.0)
         return results
-
-    MAX_LEVELS = 4          # GDT_MAX_LEVELS (csrc/gdt_common.h): geometries per gdt_net_forward_levels call
 
     def levels_joined(self):
         """(ops whose levels shared one launch, launches the levels handed to the lock-step driver) of the last forward_many group"""
@@ -408,82 +466,41 @@ class HipNet:
         levels' launches of an op are one launch wherever the kernel has a multi-geometry entry (1x1 convs, 3x3 patch convs, fused Bottlenecks; round 5).  OPT-IN
         (GANDTR_HIP_JOINT_LEVELS=1): 120 launches instead of 300 for a three-level ResNet-101 pyramid, but 5-12 % slower than one side stream per level
         (csrc/gdt_common.h, MultiConv: measurements).  Every level has its own scratch buffer (kept between calls up to ``side_workspace_cap`` bytes in total); results are those of
-        ``forward`` level by level, bit for bit (tests/test_hip_f16c.py::test_forward_many_equals_level_by_level_forward)."""
-        dev = self.device
-        cur = torch.cuda.current_stream(dev)
-        pools = self.__dict__.setdefault("_side", {"streams": [], "ws": []})
-        while len(pools["ws"]) < min(len(inputs), self.MAX_LEVELS):
-            pools["streams"].append(side_stream(dev, len(pools["streams"])))
-            pools["ws"].append(None)
+        ``forward`` level by level, bit for bit (tests/test_hip_models.py::test_pyramid_levels_share_launches_bitwise)."""
         results = []
-        try:
-          with torch.cuda.device(dev):
+        with self._level_group(min(len(inputs), self.MAX_LEVELS)) as cur:
             for lo in range(0, len(inputs), self.MAX_LEVELS):
                 group = inputs[lo:lo + self.MAX_LEVELS]
                 levels = (_hip.Level * len(group))()
-                keep = []
-                group_px = float(sum(x.shape[0] * math.prod(self.resized_size(x.shape[2], x.shape[3], s)) for x, s in group if x.dim() == 4))
+                keep = []                   # what the struct array points into, alive until the call has returned
+                group_px = self._group_px(group)
                 for k, (x, scale) in enumerate(group):
-                    if x.dim() != 4 or x.shape[1] != self.in_channels:
-                        raise ValueError("expected an N x %s x H x W input, got %s" % (self.in_channels, tuple(x.shape)))
-                    x = x.to(dev).contiguous().float()
-                    n, _, h, w = x.shape
-                    rh, rw = self.resized_size(h, w, scale)
-                    self.set_group_factor(group_px / float(n * rh * rw) if len(group) > 1 else 1.0)      # (gdt_net_forward_levels plans each level with the same factor)
-                    need = self.workspace_bytes(n, rh, rw)
-                    if pools["ws"][k] is None or pools["ws"][k].numel() < need:
-                        pools["ws"][k] = None
-                        pools["ws"][k] = torch.empty(need, dtype=torch.uint8, device=dev)
-                    outs = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in self.output_shapes(n, rh, rw)]
-                    optrs = (ctypes.c_void_p * max(1, len(outs)))(*[o.data_ptr() for o in outs])
-                    lv = levels[k]
-                    lv.x, lv.n, lv.h, lv.w, lv.rh, lv.rw = x.data_ptr(), n, h, w, rh, rw
-                    lv.rscale = float(np.float32(1.0 / scale)) if scale is not None else 1.0
-                    lv.outputs, lv.n_outputs = optrs, len(outs)
-                    lv.workspace, lv.workspace_bytes = pools["ws"][k].data_ptr(), pools["ws"][k].numel()
-                    keep.append((x, optrs))
+                    lv = self._level(x, scale)
+                    self._set_level_factor(group_px, lv, joint=True, alone=len(group) == 1)      # (gdt_net_forward_levels plans each level with the same factor)
+                    ws, outs = self._buffers(self._side["ws"], k, lv)
+                    optrs = _out_ptrs(outs)
+                    c = levels[k]
+                    c.x, c.n, c.h, c.w, c.rh, c.rw, c.rscale = lv.x.data_ptr(), lv.n, lv.h, lv.w, lv.rh, lv.rw, lv.rscale
+                    c.outputs, c.n_outputs = optrs, len(outs)
+                    c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel()
+                    keep.append((lv.x, optrs))
                     results.append(outs)
                 self.set_group_factor(1.0)
                 _hip.check(self.lib.gdt_net_forward_levels(self.handle, levels, len(group), cur.cuda_stream))
                 del keep
-            held = sum(w.numel() for w in pools["ws"] if w is not None)
-            if held > getattr(self, "side_workspace_cap", 8 << 30):
-                for k, w in enumerate(pools["ws"]):
-                    if w is not None:
-                        w.record_stream(cur)
-                        pools["ws"][k] = None
-        finally:
-            self.set_group_factor(1.0)       # (also when a level of a group is refused half-way: the next plan is a single geometry's)
         return results
-
-    def _capture(self, x, key, need, shapes):
-        n, h, w, rh, rw, rscale = key
-        try:
-            sx = x.clone()
-            ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-            outs = [torch.empty(s, dtype=torch.float32, device=x.device) for s in shapes]
-            side = side_stream(x.device, 0)
-            side.wait_stream(torch.cuda.current_stream(x.device))
-            with torch.cuda.stream(side):           # warm-up outside capture (lazy function attributes etc.)
-                self._launch(sx, n, h, w, rh, rw, rscale, ws, outs)
-            torch.cuda.current_stream(x.device).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._launch(sx, n, h, w, rh, rw, rscale, ws, outs)
-            g.replay()
-        except Exception:               # capture is an optimisation only: fall back to eager launches for this geometry
-            self._seen[key] = -(1 << 30)
-            return None
-        entry = {"graph": g, "x": sx, "outs": outs, "ws": ws}
-        self._graphs[key] = entry
-        while len(self._graphs) > 8:
-            self._graphs.popitem(last=False)
-        return entry
 
 # ======================================================================================================= builders
 
 def _bn(sd, p):
     return (sd[p + ".weight"], sd[p + ".bias"], sd[p + ".running_mean"], sd[p + ".running_var"])
+
+
+def _open(device, precision, channels=3, perm=None, in_affine=None):
+    """(a new HipNet, its input tensor): ``perm`` / ``in_affine`` = (scale, shift) per channel are applied by the input pack kernel"""
+    net = HipNet(device, precision)
+    scale, shift = in_affine if in_affine is not None else (None, None)
+    return net, net.input(channels, perm=perm, scale=scale, shift=shift)
 
 
 def generator_layout(sd):
@@ -508,7 +525,7 @@ def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precisi
     if norm == "batch" and key_norm != "batch":
         raise NotImplementedError("BatchNorm without running statistics (track_running_stats=False) has no inference form on the HIP path")
     inorm = norm == "instance"
-    net = HipNet(device, precision)
+    net, x = _open(device, precision, in_nc, in_affine=in_affine)
     tap_slots = {}
 
     def tap(idx, t, bias=None):
@@ -528,10 +545,6 @@ def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precisi
             tap(idx, raw)
         return net.conv(x, sd[key + ".weight"], sd.get(key + ".bias"), bn=_bn(sd, nkey), relu=relu, residual=residual, **kw)
 
-    if in_affine is not None:
-        x = net.input(in_nc, scale=in_affine[0], shift=in_affine[1])
-    else:
-        x = net.input(in_nc)
     h = conv_norm_relu(x, "model.1", "model.2", 1, pad=3, reflect=True)
     tap(2, h); tap(3, h)
     i = 4
@@ -563,7 +576,6 @@ def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precisi
 
 
 VGG16_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512]
-RESNET101_BLOCKS = (3, 4, 23, 3)
 
 
 def _vgg16_trunk(net, x, sd, prefix="features."):
@@ -613,8 +625,7 @@ def build_embedder(sd, device, in_affine=None, feature_tap=False, precision="f16
     ``ImageRetrievalNet._hip_head`` gives: (pooling "mac" | "spoc" | "gem" | "gemmp" | "rmac", regional, L, eps of the pooling, local whitening, final
     whitening); the layers' weights are the reference's state-dict entries (``lwhiten.*``, ``pool.p`` / ``pool.rpool.p``, ``pool.whiten.*``,
     ``whiten.*``).  The local whitening is a 1x1 conv with bias and no ReLU in front of the pool; everything behind the map is one pool_head op."""
-    net = HipNet(device, precision)
-    x = net.input(3, scale=in_affine[0], shift=in_affine[1]) if in_affine is not None else net.input(3)
+    net, x = _open(device, precision, in_affine=in_affine)
     f = _resnet_trunk(net, x, sd) if embedder_arch(sd) == "resnet" else _vgg16_trunk(net, x, sd)
     if head is None:
         net.out_slot = net.gem_l2n(f, float(sd["pool.p"].reshape(-1)[0]))
@@ -636,15 +647,10 @@ def build_embedder(sd, device, in_affine=None, feature_tap=False, precision="f16
     return net
 
 
-HED_BLOCKS = ((64, 64), (128, 128), (256, 256, 256), (512, 512, 512), (512, 512, 512))
-
-
 def build_hed(sd, device, perm=None, in_affine=None, sigmoid=True, precision="f16", finalize=True):
     """HedInterpolation.forward (hed.py:60-83); ``perm``/``in_affine`` fold the RgbToBgrPre + MeanStdPre wrappers
     (wrapper.py:351-364, :182-194) into the input pack kernel."""
-    net = HipNet(device, precision)
-    x = net.input(3, perm=perm, scale=None if in_affine is None else in_affine[0],
-                  shift=None if in_affine is None else in_affine[1])
+    net, x = _open(device, precision, perm=perm, in_affine=in_affine)
     feats = []
     for bi in range(5):
         off = 0
@@ -690,9 +696,7 @@ def build_rcf(sd, device, perm=None, in_affine=None, sigmoid=True, precision="f1
     """RCF.forward (rcf.py:100-155): the VGG trunk with ceil-mode pools (pool4 at stride 1) and dilated conv5_x, then the RCF head.  ``perm`` /
     ``in_affine`` fold the rcfngan wrapper chain (MeanStdPre, RgbToBgrPre, MeanStdPre; wrapper.py:182-194, :351-364) into the input pack; with no
     resize, in the fp16 mode, the first conv reads the caller's fp32 image itself (conv_stem.hip pair form)."""
-    net = HipNet(device, precision)
-    x = net.input(3, perm=perm, scale=None if in_affine is None else in_affine[0],
-                  shift=None if in_affine is None else in_affine[1])
+    net, x = _open(device, precision, perm=perm, in_affine=in_affine)
     feats = []
     pools = ((2, 2), (2, 2), (2, 2), (2, 1))          # pool1-3: MaxPool2d(2, 2, ceil_mode=True); pool4: stride 1 (rcf.py:43-46)
     for bi, chans in enumerate(RCF_BLOCKS):
@@ -720,8 +724,7 @@ def ms_aggregate(x, msp):
     s, n, d = x.shape
     y = torch.empty((n, d), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _hip.check(lib.gdt_ms_aggregate(x.data_ptr(), y.data_ptr(), s, n, d, float(msp),
-                                        torch.cuda.current_stream(x.device).cuda_stream))
+        _hip.check(lib.gdt_ms_aggregate(x.data_ptr(), y.data_ptr(), s, n, d, float(msp), _stream(x)))
     return y
 
 
@@ -737,13 +740,9 @@ def whiten(v, P, m, dims=None, float64=False):
     dims = int(dims or P.shape[0])
     tmp = torch.empty((n, dims), dtype=dt, device=v.device)
     out = torch.empty((n, dims), dtype=dt, device=v.device)
+    fn = lib.gdt_whiten_f64 if float64 else lib.gdt_whiten
     with torch.cuda.device(v.device):
-        if float64:
-            _hip.check(lib.gdt_whiten_f64(P.data_ptr(), m.data_ptr(), v.data_ptr(), tmp.data_ptr(), out.data_ptr(), n, d, dims,
-                                          torch.cuda.current_stream(v.device).cuda_stream))
-            return out
-        _hip.check(lib.gdt_whiten(P.data_ptr(), m.data_ptr(), v.data_ptr(), tmp.data_ptr(), out.data_ptr(), n, d, dims,
-                                  torch.cuda.current_stream(v.device).cuda_stream))
+        _hip.check(fn(P.data_ptr(), m.data_ptr(), v.data_ptr(), tmp.data_ptr(), out.data_ptr(), n, d, dims, _stream(v)))
     return out
 
 
@@ -758,8 +757,7 @@ def gem_l2n(fmap, p=3.0, eps_gem=1e-6, eps_l2=1e-6):
     pooled = torch.empty((n, d), dtype=torch.float32, device=fmap.device)
     out = torch.empty((n, d), dtype=torch.float32, device=fmap.device)
     with torch.cuda.device(fmap.device):
-        _hip.check(lib.gdt_gem_l2n(fmap.data_ptr(), n, d, h, w, float(p), eps_gem, eps_l2, pooled.data_ptr(), out.data_ptr(),
-                                   torch.cuda.current_stream(fmap.device).cuda_stream))
+        _hip.check(lib.gdt_gem_l2n(fmap.data_ptr(), n, d, h, w, float(p), eps_gem, eps_l2, pooled.data_ptr(), out.data_ptr(), _stream(fmap)))
     return pooled.view(n, d, 1, 1), out.view(n, d, 1, 1)
 
 
@@ -768,6 +766,5 @@ def l2n_rows(x, eps=1e-6):
     x = x.contiguous().float()
     y = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _hip.check(lib.gdt_l2n_rows(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], eps,
-                                    torch.cuda.current_stream(x.device).cuda_stream))
+        _hip.check(lib.gdt_l2n_rows(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], eps, _stream(x)))
     return y

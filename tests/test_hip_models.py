@@ -461,3 +461,74 @@ def test_hipgraph_replay_equals_eager_launches(cuda_device):
         other = synth.synth_input(79, (1,) + shape[1:], 1.0).to(cuda_device)
         assert net.forward(other)[net.out_slot].shape[0] == 1                      # new geometry: eager again
         net.use_graphs = False
+
+
+def _r101_three_levels(cuda_device):
+    """(net, x, levels, want): a ResNet-101 embedder, the hub-default pyramid of one 2 x 3 x 160 x 128 input and what ``forward`` returns for it level by level"""
+    from gandtr_amd import engine
+    net = engine.build_embedder(synth.resnet101_state(0), cuda_device)
+    x = synth.synth_input(5, (2, 3, 160, 128)).to(cuda_device)
+    levels = [(x, None), (x, 2 ** -0.5), (x, 0.5)]
+    want = [[o.clone() for o in net.forward(xx, scale=s)] for xx, s in levels]
+    return net, x, levels, want
+
+
+def _same_levels(got, want):
+    torch.cuda.synchronize()
+    return len(got) == len(want) and all(len(g) == len(w) and all(torch.equal(a, b) for a, b in zip(g, w)) for g, w in zip(got, want))
+
+
+def test_first_level_on_the_callers_stream_equals_level_by_level(cuda_device):
+    """GANDTR_HIP_FIRST_ON_CURRENT=1 (the first level on the caller's stream, issued last): same bits as forward level by level, also on the second call (scratch
+    buffers reused), and a plain forward afterwards is undisturbed"""
+    import os
+    net, x, levels, want = _r101_three_levels(cuda_device)
+    os.environ["GANDTR_HIP_FIRST_ON_CURRENT"] = "1"
+    try:
+        for _ in range(2):
+            assert _same_levels(net.forward_many(levels), want)
+    finally:
+        del os.environ["GANDTR_HIP_FIRST_ON_CURRENT"]
+    assert torch.equal(net.forward(x)[net.out_slot], want[0][net.out_slot])
+
+
+def test_level_by_level_modes_of_forward_many_hold_no_side_workspace(cuda_device):
+    """GANDTR_HIP_CONCURRENT_LEVELS=0 and a profiled handle both run forward_many level by level on the caller's stream: same bits, no side workspace allocated, and
+    the profiled call leaves a per-op profile (that of its last level)"""
+    import os
+    net, x, levels, want = _r101_three_levels(cuda_device)
+
+    def side_workspaces():
+        side = vars(net).get("_side")
+        return [] if side is None else [w for w in side["ws"] if w is not None]
+
+    os.environ["GANDTR_HIP_CONCURRENT_LEVELS"] = "0"
+    try:
+        assert _same_levels(net.forward_many(levels), want)
+    finally:
+        del os.environ["GANDTR_HIP_CONCURRENT_LEVELS"]
+    assert side_workspaces() == []
+    net.set_profiling(True)
+    try:
+        assert _same_levels(net.forward_many(levels), want)
+        assert len(net.profile()) > 0
+    finally:
+        net.set_profiling(False)
+    assert side_workspaces() == []
+
+
+def test_forward_many_of_one_level_equals_forward(cuda_device):
+    net, x, levels, want = _r101_three_levels(cuda_device)
+    assert _same_levels(net.forward_many([(x, 0.5)]), [want[2]])
+
+
+def test_geometry_cache_is_not_stale_after_a_group(cuda_device):
+    """forward_many plans every level with the group's factor; the cached (workspace, shapes) and the plan of the same geometry asked for OUTSIDE the group are those of
+    a handle that never ran one"""
+    from gandtr_amd import engine
+    net, x, levels, want = _r101_three_levels(cuda_device)
+    fresh = engine.build_embedder(synth.resnet101_state(0), cuda_device)
+    ws, plan = net.workspace_bytes(2, 160, 128), net.plan_summary(2, 160, 128)
+    assert _same_levels(net.forward_many(levels), want)
+    assert net.workspace_bytes(2, 160, 128) == ws == fresh.workspace_bytes(2, 160, 128)
+    assert net.plan_summary(2, 160, 128) == plan == fresh.plan_summary(2, 160, 128)

@@ -185,3 +185,17 @@ def test_live_knob_changes_the_next_plan_and_a_latched_one_does_not(monkeypatch)
         monkeypatch.setenv(k, v)                                               # latched at their first read above: nothing changes
     assert gen.plan_summary(64, 256, 256) == g
     assert r101.plan_summary(32, 1024, 1024) == base
+
+
+def test_every_field_of_a_net_exists_from_construction():
+    """HipNet declares its state in __init__: planning, hinting and counting on a built graph create no attribute"""
+    net = engine.build_embedder(synth.resnet101_state(0), DEV, finalize=False)
+    fields = set(vars(net))
+    net.workspace_bytes(2, 160, 128)
+    net.output_shapes(2, 160, 128)
+    net.set_group_factor(1.75)
+    net.set_group_factor(1.0)
+    net.plan_summary(2, 160, 128)
+    net.head_launches(2, 160, 128)
+    net.flops(2, 160, 128)
+    assert set(vars(net)) == fields

@@ -1,6 +1,6 @@
-"""dev tool: aggregate a tools/dump_ops.py log by (kind, kernel variant)"""
+"""dev tool: aggregate a log of tools/net_probe.py in mean5 mode by (kind, kernel variant)"""
 import re, sys, collections
-rows = [l.split() for l in open(sys.argv[1]) if re.match(r'^\s*\d+ (conv|inorm|maxpool|gem|input)', l)]
+rows = [l.split() for l in open(sys.argv[1]) if re.match(r'^\s*\d+ (conv|inorm|maxpool|gem|input|tap|hed|rcf|poolhead)', l)]
 agg = collections.defaultdict(lambda: [0, 0.0, 0.0])
 for r in rows:
     key = (r[1], r[3]); agg[key][0] += 1; agg[key][1] += float(r[4]); agg[key][2] += float(r[7]) if len(r) > 7 else 0

@@ -25,7 +25,7 @@ ms = timed(lambda: net.forward_many([(c, None) for c in chunks]))
 print("%d forwards of %d on %d streams, no delay: %.3f ms = %.0f desc/s" % (parts, 32 // parts, parts, ms, 32e3 / ms))
 got = torch.cat([o[net.out_slot] for o in net.forward_many([(c, None) for c in chunks])])
 print("max |d| vs one forward: %.2e" % float((got - ref).abs().max()))
-pools = net.__dict__["_side"]
+pools = net._side
 cur = torch.cuda.current_stream(dev)
 for delay in [float(a) for a in sys.argv[1:]]:
     def run():
