@@ -97,6 +97,9 @@ SIGNATURES = {
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gdt_retrieval_diverse_anchors_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "gdt_retrieval_diverse_anchors": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gdt_tuple_loss_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "gdt_tuple_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
     "gdt_l2n_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "gdt_gem_l2n": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "gdt_rpool_regions": (c_int, [c_int, c_int, c_int, _IP, c_int, _IP]),

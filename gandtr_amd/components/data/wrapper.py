@@ -1,5 +1,5 @@
 """Inference wrappers around ``model(x)`` -- host mirror of mdir/components/data/wrapper.py:
-Compose :15-49, Wrapper :52-65, MeanStdPost/Pre :149-194, CirMultiscaleAggregation :197-263, FakeBatch :266-279,
+Compose :15-49, Wrapper :52-65, RandomPassThrough / CirRatioPassThrough :97-146, MeanStdPost/Pre :149-194, CirMultiscaleAggregation :197-263, FakeBatch :266-279,
 CirFakeTupleBatch :282-305, CirtorchWhiten :308-322, ClahePost :325-348, RgbToBgrPre :351-364, registry :367-396.
 
 Protocol (unchanged): ``preprocess(tensor, outputmodel) -> (tensor, meta)`` applied in list order,
@@ -11,7 +11,10 @@ MI355X-specific behaviour (same results, different place of execution):
   * the reference's aggregate / whiten code only works for batch size 1; here a batch of N images
     yields the stack of the N per-image reference results (D x N, one column per image; N = 1 keeps the (D,) shape).
 """
+import hashlib
 import json
+import random
+import re
 
 import numpy as np
 import torch
@@ -103,6 +106,137 @@ class Wrapper:
         """("perm", [..]) or ("affine", scale, shift) when the wrapper is a pure per-channel transform of the model INPUT with an
         identity postprocess (then a HIP model can apply it while packing its input, Compose._fold_input_wrappers); else None."""
         return None
+
+
+class RandomPassThrough(Wrapper):
+    """The input goes through the wrapped network with the given probability, otherwise it skips it (wrapper.py:97-117): ``preprocess``
+    hands on the input or None, ``postprocess`` puts a skipped input back in place of the missing output.  Wrappers listed BEFORE this one
+    post-process what it returns, the skipped inputs included (postprocess runs in reverse order), as in the reference.
+
+    A list input is the reference's per-item loop, decisions drawn in input order; the items that pass are handed to the network as
+    batches of equal-sized items (at most ``max_batch`` rows each) instead of one by one, and ``postprocess`` deals the outputs back to
+    the items' places: the same list the loop returns."""
+
+    max_batch = 32
+
+    def __init__(self, probability_through, device):
+        super().__init__(device)
+        self.probability = float(probability_through)
+
+    def _through(self, _tensor):
+        return random.random() < self.probability
+
+    def _row_decisions(self, _tensor):
+        """per-row decisions of ONE batched input, or None when the input is decided as a whole"""
+        return None
+
+    def preprocess(self, tensor, outputmodel):
+        if isinstance(tensor, list):
+            return self._preprocess_list(tensor)
+        rows = self._row_decisions(tensor)
+        if rows is None:
+            return (tensor, None) if self._through(tensor) else (None, tensor)
+        plain = tensors.as_tensor(tensor)
+        take = [i for i, through in enumerate(rows) if through]
+        if not take:
+            return None, ("rows", plain, take)
+        return (plain if len(take) == len(rows) else plain[take]), ("rows", plain, take)
+
+    def _preprocess_list(self, items):
+        through = [self._through(t) for t in items]                   # input order: the reference's loop
+        groups = {}
+        for i, t in enumerate(items):
+            if through[i]:
+                plain = tensors.as_tensor(t)
+                key = (i,) if plain.dim() != 4 else ("batch", tuple(plain.shape[1:]), plain.dtype, plain.device)
+                groups.setdefault(key, []).append(i)
+        batches, plan = [], []
+        for key, idx in groups.items():                               # dict order = first appearance: deterministic
+            if key[0] != "batch":
+                batches.append(tensors.as_tensor(items[idx[0]]))
+                plan.append((idx, None))
+                continue
+            at = 0
+            while at < len(idx):
+                part, rows = [], 0
+                while at < len(idx) and (not part or rows + tensors.as_tensor(items[idx[at]]).shape[0] <= self.max_batch):
+                    rows += tensors.as_tensor(items[idx[at]]).shape[0]
+                    part.append(idx[at])
+                    at += 1
+                counts = [tensors.as_tensor(items[i]).shape[0] for i in part]
+                batches.append(torch.cat([tensors.as_tensor(items[i]) for i in part], 0) if len(part) > 1 else tensors.as_tensor(items[part[0]]))
+                plan.append((part, counts))
+        skipped = {i: t for i, t in enumerate(items) if not through[i]}
+        return batches, ("list", len(items), plan, skipped)
+
+    def postprocess(self, tensor, outputmodel, meta):
+        if isinstance(meta, tuple) and meta and meta[0] == "list":
+            _, n, plan, skipped = meta
+            assert len(tensor) == len(plan), "%s outputs for %s batches" % (len(tensor), len(plan))
+            out = [None] * n
+            for y, (idx, counts) in zip(tensor, plan):
+                if counts is None:
+                    out[idx[0]] = y
+                    continue
+                at = 0
+                for i, rows in zip(idx, counts):
+                    out[i] = y[at:at + rows]
+                    at += rows
+            for i, t in skipped.items():
+                out[i] = tensors.as_tensor(t)
+            return out
+        if isinstance(meta, tuple) and meta and meta[0] == "rows":
+            _, plain, take = meta
+            if not take:
+                return plain
+            if len(take) == plain.shape[0]:
+                return tensor
+            out = plain.to(tensor.device).clone()
+            out[take] = tensor.to(out.dtype)
+            return out
+        return tensor if meta is None else tensors.as_tensor(meta)
+
+    def __repr__(self):
+        return "%s(probability=%s)" % (type(self).__name__, self.probability)
+
+
+class CirRatioPassThrough(RandomPassThrough):
+    """The images whose ``metadata['image_label']`` matches the regular expression go through the wrapped network when the md5 of their
+    ``metadata['name']`` says so (wrapper.py:120-146): the last four hex digits as a fraction of 16^4, below ``ratio_through`` -- a fixed
+    subset of the images, the same in every epoch.  Besides the reference's single image, a BATCH whose metadata lists carry one entry per
+    row (how a loader collates them) is decided row by row: the rows that pass go through the network as one batch and are written back
+    over a copy of the input, the other rows stay as they came."""
+
+    def __init__(self, ratio_through, image_label, *, device):
+        super().__init__(ratio_through, device)
+        self.image_label = re.compile(image_label)
+
+    def _decision(self, image_label, name):
+        return bool(self.image_label.match(image_label) and self._passthrough(name))
+
+    def _through(self, tensor):
+        image_label = tensor.metadata["image_label"]                  # image_label must be present - sanity check
+        if isinstance(image_label, list) and len(image_label) == 1:
+            image_label = image_label[0]
+        return self._decision(image_label, tensor.metadata["name"])
+
+    def _row_decisions(self, tensor):
+        labels, names = tensor.metadata["image_label"], tensor.metadata["name"]
+        if not (isinstance(labels, list) and isinstance(names, list)) or len(labels) == 1:
+            return None
+        plain = tensors.as_tensor(tensor)
+        assert plain.dim() == 4 and len(labels) == len(names) == plain.shape[0], "one image_label and one name per row of the batch"
+        return [self._decision(l, n) for l, n in zip(labels, names)]
+
+    def _passthrough(self, name):
+        if isinstance(name, list):
+            name, = name
+        digits = 4                                                    # 16 ** digits = precision
+        rand = int(hashlib.md5(name.encode("utf8")).hexdigest()[-digits:], 16) / (16 ** digits)
+        return rand < self.probability
+
+    def __repr__(self):
+        return "%s(probability=%s, train_label=%s)" % (type(self).__name__, self.probability, self.image_label)
 
 
 def _on_hip(t):
@@ -360,6 +494,8 @@ class RgbToBgrPre(Wrapper):
 
 
 WRAPPERS_LABELS = {
+    "random_pass_through": RandomPassThrough,
+    "cir_ratio_pass_through": CirRatioPassThrough,
     "meanstd_post": MeanStdPost,
     "meanstd_pre": MeanStdPre,
     "cirmultiscale": CirMultiscaleAggregation,

@@ -303,6 +303,28 @@ int gdt_retrieval_diverse_anchors(const float* vecs, int nq, int d, const int* t
                                   float* out_score, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Loss of retrieval tuples (the validation of the fine-tuning scenario: decisive criterion "val/learning/loss:total")
+ * Replaces, for all tuples of a validation set in one call,
+ *   the per-tuple loop                   mdir/learning/validation.py:93-107 (one criterion call and one .item() per tuple)
+ *   ContrastiveLoss / TripletLoss        mdir/components/optim/criterion/cirlosses.py:7-21, :51-61 (eps fixed at 1e-6, :10)
+ *   contrastive_loss / triplet_loss      mdir/external/cirtorch/layers/functional.py:141-157, :160-173
+ * vecs: [n_vec][d] fp32 descriptor rows (device).  tuples: int32 [n_tuples][s] (device): column 0 the anchor, 1 the positive, 2.. the
+ * negatives, each an index into vecs; an index may repeat within and across tuples.  The entry cannot read a device table: every index must
+ * lie in [0, n_vec) -- the binding checks a host table before it uploads it -- and the kernel clamps nothing.
+ *   kind 0, contrastive: D = sqrt(sum((a - b + eps)^2)), eps INSIDE the difference as in the reference; the positive pair gives 0.5 D^2, a
+ *           negative pair 0.5 max(margin - D, 0)^2; pair_dist holds D.
+ *   kind 1, triplet: squared distances without eps; every negative gives max(d_ap - d_an + margin, 0) (s == 2: no terms, loss 0);
+ *           pair_dist holds the squared distances.
+ * Outputs (device): pair_dist [n_tuples][s-1] (may be NULL), tuple_loss [n_tuples] = the pair terms added in index order, total (one
+ * double) = the tuple losses added in a fixed order in double.  No atomics: the results are bit-identical from run to run, and a tuple's
+ * loss does not depend on its position in the table.  workspace: device scratch of gdt_tuple_loss_workspace_bytes.  Two launches on
+ * `stream`, no synchronisation.  Bad sizes, a null buffer, an unknown kind or a short workspace return GDT_ERR_INVALID before any launch.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int gdt_tuple_loss_workspace_bytes(int n_tuples, int s, size_t* bytes);
+int gdt_tuple_loss(const float* vecs, const int* tuples, int n_vec, int d, int n_tuples, int s, int kind, float margin, float eps,
+                   float* pair_dist, float* tuple_loss, double* total, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * CLAHE post-processing ("next" row of SURVEY.md section 8f, rank 1: the step between generator and embedder)
  * Replaces the per-image device -> CPU -> cv2 -> device round trip of
  *   ClahePost.postprocess   mdir/components/data/wrapper.py:325-348

@@ -7,6 +7,7 @@
     mdir.learning / mdir.learning.network  -> gandtr_amd.learning(.network)         (NETWORKS, initialize_network, load_network)
     mdir.learning.validation               -> gandtr_amd.learning.validation        (initialize_validation, SingleValidation, ...)
     mdir.components.optim.score            -> gandtr_amd.components.optim.score     (SCORES, initialize_score: cirdatasetap)
+    mdir.components.optim.criterion        -> gandtr_amd.components.optim.criterion (CRITERIA, initialize_criterion: contrastive, triplet)
     mdir.stages.infer                      -> gandtr_amd.stages.infer               (infer(params, data))
     mdir.tools.tensors                     -> gandtr_amd.tools.tensors
 
@@ -38,6 +39,7 @@ _ALIASES = {
     "mdir.components.optim": "gandtr_amd.components.optim",
     "mdir.components.optim.score": "gandtr_amd.components.optim.score",
     "mdir.components.optim.score.cirscore": "gandtr_amd.components.optim.score.cirscore",
+    "mdir.components.optim.criterion": "gandtr_amd.components.optim.criterion",
     "mdir.stages": "gandtr_amd.stages",
     "mdir.stages.infer": "gandtr_amd.stages.infer",
     "mdir.stages.whiten": "gandtr_amd.stages.whiten",
