@@ -63,6 +63,8 @@ SIGNATURES = {
     "gdt_net_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _IP]),
     "gdt_net_maxpool_ceil": (c_int, [c_void_p, c_int, c_int, c_int, _IP]),
     "gdt_net_conv_dilated": (c_int, [c_void_p, c_int, POINTER(ConvDesc), c_int, c_void_p, c_void_p, _IP]),
+    "gdt_net_conv_leaky": (c_int, [c_void_p, c_int, POINTER(ConvDesc), c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _IP]),
+    "gdt_net_instance_norm_leaky": (c_int, [c_void_p, c_int, c_float, c_float, _IP]),
     "gdt_net_gem_l2n": (c_int, [c_void_p, c_int, c_float, c_float, c_float, _IP]),
     "gdt_net_pool_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, _IP]),
     "gdt_net_output_nchw": (c_int, [c_void_p, c_int, c_void_p, _IP]),
@@ -100,6 +102,7 @@ SIGNATURES = {
     "gdt_tuple_loss_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
     "gdt_tuple_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
+    "gdt_patch_score": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gdt_l2n_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "gdt_gem_l2n": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "gdt_rpool_regions": (c_int, [c_int, c_int, c_int, _IP, c_int, _IP]),

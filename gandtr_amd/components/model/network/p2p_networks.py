@@ -1,5 +1,5 @@
-"""CycleGAN / HED-N-GAN ResNet generator -- host mirror of mdir/components/model/network/p2p_networks.py
-(get_norm_layer :23-35, ResnetGenerator :239-337, ResnetBlock :454-506).
+"""CycleGAN / HED-N-GAN ResNet generator and PatchGAN discriminator -- host mirror of mdir/components/model/network/p2p_networks.py
+(get_norm_layer :23-35, ResnetGenerator :239-337, ResnetBlock :454-506, NLayerDiscriminator :509-571).
 
 The nn.Module tree is identical to the reference's (same nn.Sequential indices, same parameter names, same creation
 order), so reference checkpoints load unchanged and seeded initialisation reproduces the reference's weights.  On a
@@ -134,3 +134,60 @@ class ResnetGenerator(HipBacked, nn.Module):
         if encode_only and layers[-1] in net.tap_slots:
             return feats
         return out, feats
+
+
+class NLayerDiscriminator(HipBacked, nn.Module):
+    """PatchGAN discriminator: Conv(k4, s2, p1) + LeakyReLU(0.2), n_layers - 1 times Conv(k4, s2, p1) + norm + LeakyReLU(0.2) with widths
+    ndf * min(2^n, 8), one Conv(k4, s1, p1) + norm + LeakyReLU(0.2), Conv(k4, s1, p1) to ONE channel: a map of per-patch logits.  The nn.Sequential
+    tree is the reference's (``model.0.weight`` ..).  On a HIP device the forward is inference only (gandtr_amd.engine.build_discriminator); only the
+    ``no_antialias`` configuration with 4x4 kernels exists, on any device."""
+
+    #: single-pass fp16 like HED and the embedders; "f16x3" is the exact mode, the generator modes "f16c" / "f16ch" do not exist here
+    hip_default_precision = "f16"
+
+    def __init__(self, input_nc, ndf=64, n_layers=3, kw=4, norm_layer="batch", no_antialias=True, track_running_stats=True):
+        super().__init__()
+        if not no_antialias:
+            raise NotImplementedError("anti-aliased down-sampling (CUT) is outside the gandtr hot path")
+        if kw != 4:
+            raise NotImplementedError("PatchGAN kernel size [%s] is not implemented (4 only)" % (kw,))
+        self.meta = {"in_channels": input_nc, "out_channels": 1}
+        self._cfg = dict(norm=norm_layer if isinstance(norm_layer, str) else None, ndf=ndf)
+        norm_layer = get_norm_layer(norm_layer, track_running_stats)
+        base = norm_layer.func if isinstance(norm_layer, functools.partial) else norm_layer
+        use_bias = base == nn.InstanceNorm2d
+
+        padw = 1
+        sequence = [nn.Conv2d(input_nc, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
+        nf_mult = 1
+        for n in range(1, n_layers):
+            nf_mult_prev, nf_mult = nf_mult, min(2 ** n, 8)
+            sequence += [nn.Conv2d(ndf * nf_mult_prev, ndf * nf_mult, kernel_size=kw, stride=2, padding=padw, bias=use_bias),
+                         norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True)]
+        nf_mult_prev, nf_mult = nf_mult, min(2 ** n_layers, 8)
+        sequence += [nn.Conv2d(ndf * nf_mult_prev, ndf * nf_mult, kernel_size=kw, stride=1, padding=padw, bias=use_bias),
+                     norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True)]
+        sequence += [nn.Conv2d(ndf * nf_mult, 1, kernel_size=kw, stride=1, padding=padw)]
+        self.model = nn.Sequential(*sequence)
+
+    def forward(self, input):
+        if self._hip_device().type == "cuda":
+            return self._forward_hip(input)
+        return self.model(input)
+
+    def forward_multi(self, input):
+        return self.forward(input)
+
+    def _forward_hip(self, x):
+        from .... import engine
+        cfg = self._cfg
+        if cfg["norm"] not in ("instance", "batch"):
+            raise NotImplementedError("HIP discriminator supports norm instance|batch")
+        if self.training and cfg["norm"] == "batch":
+            raise NotImplementedError("HIP discriminator is inference-only: call .eval() (BatchNorm uses running statistics)")
+        self._hip_check_inference()
+        prec = self._hip_precision()
+        if prec not in ("f16", "f16x3"):
+            raise NotImplementedError("HIP discriminator runs in 'f16' or 'f16x3'; %r is a generator mode" % (prec,))
+        net = self._hip_net(("disc", prec), lambda sd, dev: engine.build_discriminator(sd, dev, precision=prec, norm=cfg["norm"]))
+        return net.forward(x)[net.out_slot]

@@ -10,7 +10,7 @@ int gdt_k_pack_input(const float* x, void* y, int f32, int N, int C, int H, int 
                      const int* perm, const float* scale, const float* shift, hipStream_t st);
 int gdt_in_stats_chunks(int HW);
 int gdt_k_instance_norm(const void* x, const void* res, void* y, int f32, float* partial, float* mean_rstd, int N, int HW, int C,
-                        float eps, int relu, hipStream_t st);
+                        float eps, int relu, hipStream_t st, float leaky = 0.f);      // leaky: LeakyReLU slope applied instead of ReLU (0: none)
 int gdt_k_instance_norm_fused(const void* x, const void* res, void* y, int f32, const float* tile_partials, int tiles_per_image,
                               int nphase, float* mean_rstd, int N, int HW, int C, float eps, int relu, hipStream_t st);
 int gdt_k_instance_norm_stats(const void* x, int f32, int fused, float* partial, int tiles_per_image, int nphase, float* mean_rstd,

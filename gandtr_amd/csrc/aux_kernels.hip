@@ -191,11 +191,11 @@ __global__ __launch_bounds__(1024) void in_finalize_tiles_kernel(const float* __
     }
 }
 
-// stage 3: y = relu?((x - mean) * rstd) (+ residual)
+// stage 3: y = relu?((x - mean) * rstd) (+ residual); leaky != 0: LeakyReLU(leaky) in place of the ReLU
 template <typename T>
 __global__ __launch_bounds__(256) void in_apply_kernel(const T* __restrict__ x, const float* __restrict__ mean_rstd,
                                                        const T* __restrict__ res, T* __restrict__ y,
-                                                       long HW, int C, int relu, long total8) {
+                                                       long HW, int C, int relu, long total8, float leaky) {
     const int c8n = C >> 3;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total8; i += (long)gridDim.x * 256) {
         const int c8 = (int)(i % c8n);
@@ -208,6 +208,7 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const T* __restrict__ x, 
         for (int e = 0; e < 8; ++e) {
             float f = (v[e] - mr[2 * e]) * mr[2 * e + 1];
             if (relu) f = fmaxf(f, 0.f);
+            else if (leaky != 0.f) f = f > 0.f ? f : f * leaky;
             if (res) f += r[e];
             v[e] = f;
         }
@@ -567,20 +568,20 @@ int gdt_k_pack_input(const float* x, void* y, int f32, int N, int C, int H, int 
 int gdt_in_stats_chunks(int HW) { int c = (HW + 1023) / 1024; return c < 1 ? 1 : c; }
 
 static int launch_apply(const void* x, const void* res, void* y, int f32, const float* mean_rstd, int N, int HW, int C, int relu,
-                        hipStream_t st) {
+                        hipStream_t st, float leaky = 0.f) {
     const long total8 = (long)N * HW * (C / 8);
     if (f32)
         hipLaunchKernelGGL(in_apply_kernel<float>, dim3(grid_for(total8)), dim3(256), 0, st, (const float*)x, mean_rstd,
-                           (const float*)res, (float*)y, (long)HW, C, relu, total8);
+                           (const float*)res, (float*)y, (long)HW, C, relu, total8, leaky);
     else
         hipLaunchKernelGGL(in_apply_kernel<f16>, dim3(grid_for(total8)), dim3(256), 0, st, (const f16*)x, mean_rstd, (const f16*)res,
-                           (f16*)y, (long)HW, C, relu, total8);
+                           (f16*)y, (long)HW, C, relu, total8, leaky);
     GDT_CHECK_HIP(hipGetLastError());
     return GDT_OK;
 }
 
 int gdt_k_instance_norm(const void* x, const void* res, void* y, int f32, float* partial, float* mean_rstd, int N, int HW, int C,
-                        float eps, int relu, hipStream_t st) {
+                        float eps, int relu, hipStream_t st, float leaky) {
     GDT_REQUIRE(C % 8 == 0 && C / 8 <= 256 && 256 % (C / 8) == 0, "InstanceNorm needs a power-of-two channel count <= 2048");
     const int nchunks = gdt_in_stats_chunks(HW);
     const int chunk_px = (HW + nchunks - 1) / nchunks;
@@ -590,7 +591,7 @@ int gdt_k_instance_norm(const void* x, const void* res, void* y, int f32, float*
     hipLaunchKernelGGL(in_finalize_kernel, dim3((N * C + 255) / 256), dim3(256), 0, st, (const float*)partial, mean_rstd, nchunks, C,
                        HW, eps, N * C);
     GDT_CHECK_HIP(hipGetLastError());
-    return launch_apply(x, res, y, f32, mean_rstd, N, HW, C, relu, st);
+    return launch_apply(x, res, y, f32, mean_rstd, N, HW, C, relu, st, leaky);
 }
 
 int gdt_k_instance_norm_fused(const void* x, const void* res, void* y, int f32, const float* tile_partials, int tiles_per_image,

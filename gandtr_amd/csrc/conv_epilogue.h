@@ -1,7 +1,7 @@
 // fp16 NHWC epilogue shared by conv_igemm.hip and conv3x3_halo.hip.
 //
 // Input: the wave's 32x32 MFMA accumulator tiles acc[TM][TN] (C layout of v_mfma_f32_32x32x16: column = lane & 31, row =
-// (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)).  Steps: + bias (folded BatchNorm shift), optional ReLU, fp16 -> LDS transpose
+// (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)).  Steps: + bias (folded BatchNorm shift), optional ReLU or LeakyReLU (d.leaky), fp16 -> LDS transpose
 // so that every lane stores 16 contiguous bytes; per-128-row InstanceNorm partial statistics (sum, sum of squares) from the
 // fp32 values with a fixed reduction order (deterministic); optional residual add (+ ReLU) in fp32 on the way out.
 // `pixel_of(row, ok)` maps a tile row to the output pixel index (n * OH * OW + y * OW + x) and says whether it exists.
@@ -25,6 +25,7 @@ __device__ __forceinline__ void conv_epilogue_f16(const ConvLaunch& d, const f32
     f16* Ct = (f16*)smem;
     float* sl = (float*)(smem + STATS_OFF);
     const bool relu_now = d.relu && !d.res;
+    const bool leaky_now = d.leaky != 0.f;                          // LeakyReLU (never together with ReLU or a residual: gdt_net_conv_leaky)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int col = wn * WTN + j * 32 + fr;
@@ -38,6 +39,7 @@ __device__ __forceinline__ void conv_epilogue_f16(const ConvLaunch& d, const f32
                 float v = acc[i][j][e] + bv;
                 s1 += v; s2 += v * v;
                 if (relu_now) v = fmaxf(v, 0.f);
+                else if (leaky_now) v = v > 0.f ? v : v * d.leaky;
                 Ct[row * CP + col] = (f16)v;
             }
         if (d.stats) {      // per-lane column sums over the wave's rows, the two half-waves combined

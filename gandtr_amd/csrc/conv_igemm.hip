@@ -299,6 +299,7 @@ int gdt_conv_bn(int Cout) { return Cout > 64 ? 128 : (Cout > 32 ? 64 : 32); }
 // 1 = conv1x1_rb.hip, 2 = conv3x3_halo_rb.hip, 0 = any other
 int gdt_conv_family(const ConvLaunch& d) {
     if (d.pool2 || d.stats || d.in_norm) return 0;
+    if (d.leaky != 0.f || gdt_conv4x4_halo_eligible(d)) return 0;
     if (gdt_conv_stem_eligible(d)) return 0;
     if (gdt_conv_1x1_rb_eligible(d)) return 1;
     if (!gdt_conv_halo_rb_eligible(d) && !gdt_conv_halo_eligible(d) && gdt_conv_igemm_rb_eligible(d)) return 0;
@@ -321,9 +322,13 @@ int gdt_launch_conv(const ConvLaunch& d_in, hipStream_t stream, int* variant) {
     const int bn = gdt_conv_bn(d.Cout);
     GDT_REQUIRE(d.CoutPad % bn == 0 && d.CoutPad >= d.Cout, "CoutPad must be a multiple of the N tile");
     if (d.pool2) GDT_REQUIRE(gdt_conv_halo_rb_eligible(d) || gdt_conv_halo_eligible(d), "fused max pool needs a patch kernel");
-    if (gdt_conv_stem_eligible(d)) { *variant = 950000 + d.ntaps; return gdt_launch_conv_stem(d, stream); }
-    if (gdt_conv_1x1_rb_eligible(d)) { *variant = 945128; return gdt_launch_conv_1x1_rb(d, stream); }
-    if (!gdt_conv_halo_rb_eligible(d) && !gdt_conv_halo_eligible(d) && gdt_conv_igemm_rb_eligible(d)) return gdt_launch_conv_igemm_rb(d, stream, variant);
+    if (gdt_conv4x4_halo_eligible(d)) return gdt_launch_conv4x4_halo(d, stream, variant);
+    // LeakyReLU (d.leaky): conv4x4_halo.hip above and the generic kernels at the end of this function (conv_epilogue.h) apply it; the families in between know ReLU only
+    const bool leaky = d.leaky != 0.f;
+    if (leaky) GDT_REQUIRE(!d.relu && !d.res && !d.in_norm && !d.pool2 && !d.stats && !d.out_f32, "a LeakyReLU conv is a plain launch with an fp16 output");
+    if (!leaky && gdt_conv_stem_eligible(d)) { *variant = 950000 + d.ntaps; return gdt_launch_conv_stem(d, stream); }
+    if (!leaky && gdt_conv_1x1_rb_eligible(d)) { *variant = 945128; return gdt_launch_conv_1x1_rb(d, stream); }
+    if (!leaky && !gdt_conv_halo_rb_eligible(d) && !gdt_conv_halo_eligible(d) && gdt_conv_igemm_rb_eligible(d)) return gdt_launch_conv_igemm_rb(d, stream, variant);
     if (d.in_norm && !gdt_conv_halo_eligible(d))
         GDT_REQUIRE(gdt_conv_igemm_norm_eligible(d), "fused input normalisation needs Cin == 64 and whole 256-row tiles per image here");
     if (d.in_norm && !gdt_conv_halo_eligible(d)) {      // generic kernel with the producer's InstanceNorm folded into the A staging
@@ -331,8 +336,8 @@ int gdt_launch_conv(const ConvLaunch& d_in, hipStream_t stream, int* variant) {
         if (bn == 64) { *variant = 128064; return launch_cfg<128, 64, 2, 2, true>(d, stream); }
         *variant = 128032; return launch_cfg<128, 32, 4, 1, true>(d, stream);
     }
-    if (gdt_conv_halo_rb_eligible(d)) { *variant = 910000 + (d.CoutPad < 256 ? d.CoutPad : 256); return gdt_launch_conv_halo_rb(d, stream); }
-    if (gdt_conv_halo_eligible(d)) { *variant = 900000 + (d.CoutPad % 256 == 0 ? 256 : (d.CoutPad % 128 == 0 ? 128 : 64)); return gdt_launch_conv_halo(d, stream); }
+    if (!leaky && gdt_conv_halo_rb_eligible(d)) { *variant = 910000 + (d.CoutPad < 256 ? d.CoutPad : 256); return gdt_launch_conv_halo_rb(d, stream); }
+    if (!leaky && gdt_conv_halo_eligible(d)) { *variant = 900000 + (d.CoutPad % 256 == 0 ? 256 : (d.CoutPad % 128 == 0 ? 128 : 64)); return gdt_launch_conv_halo(d, stream); }
     if (d.pad_reflect) {
         const int pady = d.dy0 < 0 ? -d.dy0 : 0, padx = d.dx0 < 0 ? -d.dx0 : 0;
         GDT_REQUIRE(pady < d.H && padx < d.W, "reflect padding needs pad < input size");

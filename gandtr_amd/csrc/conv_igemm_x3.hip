@@ -221,6 +221,7 @@ __global__ __launch_bounds__(256) void conv_igemm_x3_kernel(const ConvLaunch d) 
                     const long off = ((long)n * ohw + opix) * d.Cout + col;
                     if (resp) v += rr[i][e];
                     if (d.relu) v = fmaxf(v, 0.f);
+                    else if (d.leaky != 0.f) v = v > 0.f ? v : v * d.leaky;
                     outp[off] = v;
                 }
             }
@@ -273,8 +274,9 @@ int gdt_launch_conv_x3(const ConvLaunch& d, hipStream_t stream, int* variant) {
     }
     const int bn = gdt_conv_bn(d.Cout);
     GDT_REQUIRE(d.CoutPad % bn == 0 && d.CoutPad >= d.Cout, "CoutPad must be a multiple of the N tile");
-    if (d.x3_form == 0 && gdt_conv_halo_x3_eligible(d)) { if (variant) *variant = 930128; return gdt_launch_conv_halo_x3(d, stream); }
-    if (gdt_conv_halo_x3_taps_eligible(d)) { if (variant) *variant = d.x3_form == 2 ? 932128 : 931128; return gdt_launch_conv_halo_x3_taps(d, stream); }
+    // (LeakyReLU, d.leaky: this file's generic kernel only)
+    if (d.x3_form == 0 && d.leaky == 0.f && gdt_conv_halo_x3_eligible(d)) { if (variant) *variant = 930128; return gdt_launch_conv_halo_x3(d, stream); }
+    if (d.leaky == 0.f && gdt_conv_halo_x3_taps_eligible(d)) { if (variant) *variant = d.x3_form == 2 ? 932128 : 931128; return gdt_launch_conv_halo_x3_taps(d, stream); }
     GDT_REQUIRE(d.x3_form == 0, "the space-to-depth view exists in the patch kernel only");
     GDT_REQUIRE(d.in_norm == nullptr || gdt_conv_x3_norm_eligible(d), "fused input normalisation: plain norm (+ReLU), whole 128-row tiles per image");
     if (variant) *variant = 300000 + bn;

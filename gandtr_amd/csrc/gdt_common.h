@@ -63,6 +63,9 @@ enum GdtLiveKnob { GDT_LIVE_KNOBS(GDT_LIVE_KNOB_ID) GDT_LIVE_KNOB_COUNT };
 #define GDT_KNOB_LATCHED(fn, name, dflt) [[maybe_unused]] static int fn() { static const int v = gdt_env_int(name, dflt); return v; }
 #define GDT_KNOB_LATCHED_SET(fn, name) [[maybe_unused]] static bool fn() { static const bool v = gdt_env_set(name); return v; }      // presence, whatever the value
 #define GDT_KNOB_LIVE(fn, id, dflt) [[maybe_unused]] static int fn() { return gdt_env_int(GDT_LIVE_KNOB_NAMES[GDT_LIVE_##id], dflt); }
+// LAUNCH knobs are read whenever a launcher chooses between two kernels that compute the same layer on the same plan (same tensors, same workspace): one
+// process can A/B them, and nothing that caches a plan needs to know them.
+#define GDT_KNOB_LAUNCH(fn, name, dflt) [[maybe_unused]] static int fn() { return gdt_env_int(name, dflt); }
 
 // ---- a kernel's launcher: its dynamic-LDS set-up PER DEVICE, its cached CU figure, its launch ----
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the current device only, and a process may build nets on several GPUs and launch from
@@ -171,6 +174,9 @@ struct ConvLaunch {
     // planner hint: this geometry runs CONCURRENTLY with others of the same net (the levels of a pyramid on side streams): (pixels of all of them) / (its own), >= 1.
     // Fusions whose tile thresholds say "enough patches to fill the chip" count the group's patches (conv3x3_expand_rb.hip)
     float group_factor;
+    // LeakyReLU(leaky) after bias (and folded BatchNorm) instead of ReLU, 0 = none (NLayerDiscriminator, p2p_networks.py:533-560): conv_epilogue.h,
+    // conv_igemm_x3.hip and conv4x4_halo.hip apply it; gdt_launch_conv hands such a launch to no other kernel
+    float leaky;
 };
 
 // ---- several independent geometries in ONE launch (round 5: the levels of a multi-scale pyramid, wrapper.py:221-233 / network.py:139-140) ----
@@ -241,6 +247,8 @@ int gdt_conv_family(const ConvLaunch& d);                  // conv_igemm.hip: 1 
 bool gdt_conv_igemm_norm_eligible(const ConvLaunch& d);    // conv_igemm.hip: fused input InstanceNorm in the generic kernel
 bool gdt_conv_halo_eligible(const ConvLaunch& d);          // conv3x3_halo.hip
 int gdt_launch_conv_halo(const ConvLaunch& d, hipStream_t stream);
+bool gdt_conv4x4_halo_eligible(const ConvLaunch& d);       // conv4x4_halo.hip (k4 / zero pad 1, stride 1 or 2: PatchGAN discriminator, variant 904000 + stride * 1000 + BN)
+int gdt_launch_conv4x4_halo(const ConvLaunch& d, hipStream_t stream, int* variant);
 bool gdt_conv_halo_rb_eligible(const ConvLaunch& d);       // conv3x3_halo_rb.hip (weights streamed into registers)
 bool gdt_conv3x3_expand_eligible(const ConvLaunch& d);     // conv3x3_expand_rb.hip (3x3 + expand 1x1 + residual of a Bottleneck, variant 939000 + x_cout / 8)
 int gdt_launch_conv3x3_expand(const ConvLaunch& d, hipStream_t stream);

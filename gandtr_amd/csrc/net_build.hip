@@ -465,10 +465,10 @@ static void pack_bias(ConvPack& cp) {
     }
 }
 
-// gdt_net_conv (dil == 1) and gdt_net_conv_dilated
+// gdt_net_conv (dil == 1), gdt_net_conv_dilated and gdt_net_conv_leaky (leaky != 0)
 static int add_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, int dil, const float* weight, const float* bias,
                     const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
-                    int residual_tensor, int* out_tensor) {
+                    int residual_tensor, int* out_tensor, float leaky = 0.f) {
     GDT_REQUIRE(net && !net->finalized && desc && weight && out_tensor, "net/desc/weight");
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "input tensor id");
     GDT_REQUIRE(residual_tensor < (int)net->tensors.size(), "residual tensor id");
@@ -484,7 +484,7 @@ static int add_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, int 
     if (!cd.out_f32_nchw) GDT_REQUIRE(cd.cout % 8 == 0, "internal conv outputs need cout % 8 == 0");
     if (residual_tensor >= 0) GDT_REQUIRE(net->tensors[residual_tensor].C == cd.cout && !cd.out_f32_nchw, "residual channels");
 
-    Op o; o.kind = OP_CONV; o.in = in_tensor; o.res = residual_tensor; o.cd = cd; o.cin_pad = cin_pad; o.dil = dil;
+    Op o; o.kind = OP_CONV; o.in = in_tensor; o.res = residual_tensor; o.cd = cd; o.cin_pad = cin_pad; o.dil = dil; o.leaky = leaky;
     o.rowsplit = dil == 1 && cd.out_f32_nchw && !cd.transposed && cd.stride == 1 && cd.kw >= 3 && cd.cout <= 4 && cd.cout * cd.kw <= 32 &&
                  cd.kw == 2 * cd.pad + 1 && !cd.relu && !bn_gamma;
     const int gemm_cout = o.rowsplit ? cd.cout * cd.kw : cd.cout;
@@ -559,7 +559,7 @@ void gdtn::build_kcat_weights(gdt_net* net) {
         for (size_t j = 0; j < i; ++j) if (ops[j].out == c.res) ids = (int)j;
         if (ids < 0) continue;
         const Op& ds = ops[ids];
-        if (!plain1x1(ds) || ds.cd.relu || ds.res >= 0 || ds.cd.stride < 1 || ds.cd.stride > 2 || ds.cout_pad != c.cout_pad || ds.cd.cout != c.cd.cout || consumers[ds.out] != 1) continue;
+        if (!plain1x1(ds) || ds.cd.relu || ds.leaky != 0.f || ds.res >= 0 || ds.cd.stride < 1 || ds.cd.stride > 2 || ds.cout_pad != c.cout_pad || ds.cd.cout != c.cd.cout || consumers[ds.out] != 1) continue;
         const int K1 = c.cin_pad, K2 = ds.cin_pad, K = K1 + K2, cp = c.cout_pad;
         if ((K / 64) % 2 != 0) continue;
         const f16* w1 = (const f16*)(net->host_blob.data() + c.phases[0].w_off);
@@ -637,15 +637,28 @@ int gdt_net_conv_dilated(gdt_net* net, int in_tensor, const gdt_conv_desc* desc,
     return add_conv(net, in_tensor, desc, dilation, weight, bias, nullptr, nullptr, nullptr, nullptr, -1, out_tensor);
 }
 
-int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, int residual_tensor, int* out_tensor) {
+// a LeakyReLU slope as the two leaky entries take it
+#define GDT_REQUIRE_SLOPE(slope) GDT_REQUIRE((slope) > 0.f && (slope) < 1.f, "LeakyReLU slope must lie in (0, 1)")
+
+int gdt_net_conv_leaky(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, float slope, const float* weight, const float* bias,
+                       const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor) {
+    GDT_REQUIRE(net && !net->finalized && desc && weight && out_tensor, "net/desc/weight");
+    GDT_REQUIRE_SLOPE(slope);
+    GDT_REQUIRE(net->precision != 2, "a LeakyReLU conv exists in the f16 and f16x3 modes");
+    GDT_REQUIRE(!desc->relu && !desc->transposed && !desc->out_f32_nchw, "a LeakyReLU conv is a plain Conv2d with an internal output and no ReLU");
+    return add_conv(net, in_tensor, desc, 1, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, -1, out_tensor, slope);
+}
+
+static int add_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, float leaky, int residual_tensor, int* out_tensor) {
     GDT_REQUIRE(net && !net->finalized && out_tensor, "net");
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size() && residual_tensor < (int)net->tensors.size(), "tensor id");
     const int C = net->tensors[in_tensor].C;
     GDT_REQUIRE((C & (C - 1)) == 0 && C >= 8 && C <= 2048, "InstanceNorm needs a power-of-two channel count in [8, 2048]");
     if (residual_tensor >= 0) GDT_REQUIRE(net->tensors[residual_tensor].C == C, "residual channels");
-    Op o; o.kind = OP_INORM; o.in = in_tensor; o.res = residual_tensor; o.eps = eps; o.relu = relu;
+    Op o; o.kind = OP_INORM; o.in = in_tensor; o.res = residual_tensor; o.eps = eps; o.relu = relu; o.leaky = leaky;
     o.out = net->new_tensor(C, net->tensors[in_tensor].Creal);
-    for (size_t k = 0; k < net->ops.size(); ++k)
+    // (a LeakyReLU norm stays a separate op with its own statistics pass: its producer delivers none, and no consumer's staging applies it)
+    for (size_t k = 0; k < net->ops.size() && leaky == 0.f; ++k)
         if (net->ops[k].kind == OP_CONV && net->ops[k].out == in_tensor && net->ops[k].stats_for < 0) {
             net->ops[k].stats_for = (int)net->ops.size();
             o.stats_from = (int)k;
@@ -653,6 +666,15 @@ int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, int 
     net->ops.push_back(o);
     *out_tensor = o.out;
     return GDT_OK;
+}
+
+int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, int residual_tensor, int* out_tensor) {
+    return add_instance_norm(net, in_tensor, eps, relu, 0.f, residual_tensor, out_tensor);
+}
+
+int gdt_net_instance_norm_leaky(gdt_net* net, int in_tensor, float eps, float slope, int* out_tensor) {
+    GDT_REQUIRE_SLOPE(slope);
+    return add_instance_norm(net, in_tensor, eps, 0, slope, -1, out_tensor);
 }
 
 static int add_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int ceil, int* out_tensor) {

@@ -245,7 +245,7 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                                                    ti.H * ti.W, ti.C, o.eps, o.relu, st);
                 else
                     rc = gdt_k_instance_norm(tptr(o.in), o.res >= 0 ? tptr(o.res) : nullptr, tptr(o.out), f32, (float*)(ws + stp.aux_off[0]),
-                                             (float*)(ws + stp.aux_off[1]), n, ti.H * ti.W, ti.C, o.eps, o.relu, st);
+                                             (float*)(ws + stp.aux_off[1]), n, ti.H * ti.W, ti.C, o.eps, o.relu, st, o.leaky);
                 break;
             }
             case OP_MAXPOOL: {

@@ -62,6 +62,7 @@ struct Op {
     // fp16 mode: a 1x1 expand conv whose residual is the output of a 1x1 projection conv (ResNet Bottleneck shortcut, stride 1 or 2) carries the two
     // weight matrices K-concatenated (conv1x1_rb.hip, CAT form): kcat_ds = index of the projection op
     int kcat_ds = -1; size_t kcat_frag_off = 0, kcat_bias_off = 0;
+    float leaky = 0.f;    // conv / inorm: LeakyReLU slope applied instead of ReLU, 0 = none (gdt_net_conv_leaky, gdt_net_instance_norm_leaky)
     int dil = 1;          // conv: dilation (gdt_net_conv_dilated); the taps are (dy0 + (t / TW) * dil, ...): only the generic implicit-GEMM kernels take it
     // maxpool
     int k = 0, s = 0, p = 0; int ceil = 0;
@@ -93,7 +94,7 @@ void op_inputs(const Op& o, F&& f) {
 // a Conv2d the fp16 fusions can take apart (Bottleneck forms, 3x3 + expand, K-concatenated shortcut): one packed phase in fragment order, a bias, an internal
 // output, no statistics to deliver
 inline bool plain_conv(const Op& o) {
-    return o.kind == OP_CONV && !o.cd.transposed && !o.cd.out_f32_nchw && !o.rowsplit && o.stats_for < 0 && o.phases.size() == 1 && o.phases[0].has_frag && o.has_bias;
+    return o.kind == OP_CONV && o.leaky == 0.f && !o.cd.transposed && !o.cd.out_f32_nchw && !o.rowsplit && o.stats_for < 0 && o.phases.size() == 1 && o.phases[0].has_frag && o.has_bias;
 }
 
 // RCF's upsampling of stages 2-5 (rcf.py:69-72, :139-148): ConvTranspose2d with the fixed bilinear kernel K = 2 S, stride S, then crop at (c, c)

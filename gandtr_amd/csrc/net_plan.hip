@@ -18,7 +18,7 @@ static void conv_geometry(const gdt_net* net, const Op& o, const PackedPhase& ph
     d.N = n; d.H = ti.H; d.W = ti.W; d.Cin = o.cin_pad; d.lc8 = ilog2(o.cin_pad / 8);
     d.Cout = o.cd.cout; d.CoutPad = o.cout_pad;
     d.OH = conv_out_dim(o, ti.H, o.cd.kh); d.OW = conv_out_dim(o, ti.W, o.cd.kw);
-    d.pad_reflect = o.cd.pad_reflect; d.relu = o.cd.relu; d.act = o.cd.act;
+    d.pad_reflect = o.cd.pad_reflect; d.relu = o.cd.relu; d.act = o.cd.act; d.leaky = o.leaky;
     d.Kpad = ph.Kpad; d.nk = ph.Kpad / (net->precision ? 32 : 64);
     d.ntaps = ph.ntaps; d.TW = ph.TW; d.invTW = (65536 + ph.TW - 1) / ph.TW;
     d.dy0 = ph.dy0; d.dys = ph.dys; d.dx0 = ph.dx0; d.dxs = ph.dxs;
@@ -347,7 +347,7 @@ void Planner::norm_folds() {
         // f16x3: the patch kernel folds InstanceNorm (+ReLU, + residual, + write-back) while it stages; GDT_X3_NORM_FOLD=0 switches that off, 1 keeps it to the plain
         // norm (+ReLU) without residual / write-back (the round-5 first form)
         const int x3_fold = knob_x3_norm_fold();
-        if (oj.kind != OP_INORM || (net->precision == 1 && !x3_fold)) continue;
+        if (oj.kind != OP_INORM || (net->precision == 1 && !x3_fold) || oj.leaky != 0.f) continue;      // (the staging passes apply ReLU only)
         // plain norm(+ReLU): exactly one consumer.  norm + residual (ResnetBlock output): the tensor itself is still needed
         // later (as the next block's residual), so the consuming conv also writes it out -- every other consumer must come
         // after that conv in program order.
@@ -364,7 +364,7 @@ void Planner::norm_folds() {
             if (k < 0) continue;
         }
         const Op& ok = ops[k];
-        if (ok.kind != OP_CONV || ok.in != oj.out || ok.res == oj.out) continue;
+        if (ok.kind != OP_CONV || ok.in != oj.out || ok.res == oj.out || ok.leaky != 0.f) continue;     // (a LeakyReLU conv is a plain launch: gdt_launch_conv)
         if (ok.cd.transposed && !plan.steps[k].ctf) {
             // f16x3: the four sub-pixel phase launches of a transposed conv read the same input; each applies the norm while it stages (conv_igemm_x3.hip)
             bool all = net->precision == 1 && x3_fold >= 2 && !wb && !res && !ok.phases.empty();
@@ -433,7 +433,7 @@ void Planner::pool_folds() {
         if (oj.ceil && ((T[oj.in].H & 1) || (T[oj.in].W & 1))) continue;        // ceil_mode: the epilogue pools whole 2 x 2 windows only (= floor mode on even sizes)
         int i = -1;
         for (int k = 0; k < j; ++k) if (ops[k].kind == OP_CONV && ops[k].out == oj.in) i = k;
-        if (i < 0 || ops[i].cd.transposed || ops[i].cd.out_f32_nchw || ops[i].res >= 0 || ops[i].dil != 1) continue;
+        if (i < 0 || ops[i].cd.transposed || ops[i].cd.out_f32_nchw || ops[i].res >= 0 || ops[i].dil != 1 || ops[i].leaky != 0.f) continue;
         if (plan.steps[i].norm_from >= 0 && plan.steps[plan.steps[i].norm_from].wb) continue;
         // (asked of the launch as it is without the pool: pool2 = 0)
         if (gdt_conv_pool2_eligible(conv_desc_phase(probe, i, ops[i].phases[0], 0, fold(i, plan.steps[i].norm_from)))) { plan.steps[i].pool_into = j; plan.steps[j].skip = true; }
@@ -531,7 +531,7 @@ void Planner::direct_stem() {
     if (!direct_ok || net->precision || nops < 2 || ops[0].kind != OP_INPUT || ops[0].in_c > 3 || consumers[ops[0].out] != 1) return;
     const int j = consumer_op[ops[0].out];
     const Op& o = ops[j];
-    if (o.kind != OP_CONV || o.in != ops[0].out || o.res >= 0 || o.phases.size() != 1 || !o.phases[0].has_pair || plan.steps[j].aug || o.stats_for >= 0 || taken(j)) return;
+    if (o.kind != OP_CONV || o.in != ops[0].out || o.res >= 0 || o.leaky != 0.f || o.phases.size() != 1 || !o.phases[0].has_pair || plan.steps[j].aug || o.stats_for >= 0 || taken(j)) return;
     if (!gdt_conv_stem_pair_eligible(conv_desc_stem_direct(probe, j, -1))) return;
     plan.steps[0].direct = true; plan.steps[j].direct = true;
     // ... and the MaxPool2d(3, 2, 1) behind it, when it is the stem's only consumer: the stem launch writes the pooled tensor
@@ -752,7 +752,8 @@ int gdt_net_workspace_bytes(gdt_net* net, int n, int rh, int rw, size_t* bytes) 
 // [3] of those with the next block's reduce conv chained in, [4] projection shortcuts folded into their expand conv (K-concatenated 1x1), [5] InstanceNorms applied by
 // their consumer's staging, [6] max-pools written by their producer, [7] 1 if the stem reads the caller's image itself (calls that do not resize),
 // [8] transposed convs as one fused-phase launch, [9] stride-2 convs as the shift form, [10] dilated convs, [11] of those on a special form; with n_counts >= 14:
-// [12] launches of the pool-head ops (gdt_net_pool_head), [13] of those the ones that read the feature map
+// [12] launches of the pool-head ops (gdt_net_pool_head), [13] of those the ones that read the feature map; with n_counts >= 15: [14] conv launches that
+// conv4x4_halo.hip takes (what gdt_launch_conv decides for the conv as its own plain launch; GDT_CONV4X4_HALO=0: none)
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts) {
     GDT_REQUIRE(net && counts && n_counts >= 10 && n >= 1 && rh >= 1 && rw >= 1, "plan summary arguments");
     if (!net->finalized && !net->precision) build_kcat_weights(net);       // (what finalize would add: the K-concatenated shortcut weights the planner may choose)
@@ -772,6 +773,9 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
             counts[13] += 1;                              // ... of which read the feature map: the pooling pass
         }
         if (o.kind == OP_INPUT) counts[7] += st.direct;
+        if (o.kind == OP_CONV && n_counts >= 15 && !net->precision && o.phases.size() == 1 && !o.rowsplit &&
+            !(st.skip || st.bneck || st.xexp || st.kcat || st.direct || st.ctf || st.s2 || st.ctp || st.aug))
+            counts[14] += gdt_conv4x4_halo_eligible(conv_desc_phase(DescCtx{net, &net->tensors, n, Ptrs{}}, (int)i, o.phases[0], 0, fold_of(net, plan, (int)i)));
         if (o.kind == OP_CONV && o.dil != 1 && n_counts >= 12) {
             ++counts[10];
             // what gdt_launch_conv / gdt_launch_conv_x3 would be handed for the conv as its own plain launch

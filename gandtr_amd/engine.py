@@ -134,7 +134,8 @@ class HipNet:
         return out
 
     def conv(self, x, weight, bias=None, bn=None, stride=1, pad=0, reflect=False, transposed=False, relu=False,
-             residual=-1, out_f32=False, act=0, dilation=1):
+             residual=-1, out_f32=False, act=0, dilation=1, leaky=0.0):
+        """``leaky``: slope of an nn.LeakyReLU applied after bias and BatchNorm in place of ``relu`` (gdt_net_conv_leaky)"""
         w = _f32(weight)
         cin, cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
         d = ConvDesc(cin, cout, w.shape[2], w.shape[3], stride, pad, int(reflect), int(transposed), int(relu),
@@ -147,9 +148,18 @@ class HipNet:
         g = be = m = v = None
         if bn is not None:
             g, be, m, v = (_f32(t) for t in bn)
+        if leaky:
+            if dilation != 1 or residual != -1 or relu:
+                raise ValueError("a LeakyReLU conv takes no dilation, no residual and no ReLU")
+            return self._add("conv_leaky", x, ctypes.byref(d), float(leaky), _ptr(w), _ptr(b), _ptr(g), _ptr(be), _ptr(m), _ptr(v))
         return self._add("conv", x, ctypes.byref(d), _ptr(w), _ptr(b), _ptr(g), _ptr(be), _ptr(m), _ptr(v), residual)
 
-    def instance_norm(self, x, relu=False, residual=-1, eps=1e-5):
+    def instance_norm(self, x, relu=False, residual=-1, eps=1e-5, leaky=0.0):
+        """``leaky``: slope of an nn.LeakyReLU behind the norm in place of ``relu`` (gdt_net_instance_norm_leaky)"""
+        if leaky:
+            if relu or residual != -1:
+                raise ValueError("a LeakyReLU InstanceNorm takes no ReLU and no residual")
+            return self._add("instance_norm_leaky", x, eps, float(leaky))
         return self._add("instance_norm", x, eps, int(relu), residual)
 
     def maxpool(self, x, kernel, stride, pad=0, ceil=False):
@@ -246,6 +256,10 @@ class HipNet:
     def plan_summary(self, n, rh, rw, resize=False):
         """the planner's fusion decisions for a geometry as a dict of counts"""
         return dict(zip(self.PLAN_KEYS, self._plan_counts(n, rh, rw, resize, 12)))
+
+    def conv4x4_launches(self, n, rh, rw):
+        """conv launches of a geometry that run on the 4x4 patch kernel (conv4x4_halo.hip; GDT_CONV4X4_HALO=0: none) -- the planner's count"""
+        return self._plan_counts(n, rh, rw, False, 15)[14]
 
     def head_launches(self, n, rh, rw):
         """(launches of the net's pool-head ops, launches among them that read the feature map) for a geometry -- the planner's count"""
@@ -710,6 +724,47 @@ def build_rcf(sd, device, perm=None, in_affine=None, sigmoid=True, precision="f1
     stage_of, side_w, stage_b = rcf_fold_side(sd)
     net.out_slot = net.rcf_head(feats, stage_of, side_w, stage_b, [float(v) for v in sd["score_fuse.weight"].reshape(-1)],
                                 float(sd["score_fuse.bias"].reshape(-1)[0]), sigmoid)
+    if finalize:
+        net.finalize()
+    return net
+
+
+def discriminator_layout(sd):
+    """(norm, ndf, n_layers, in_nc) of an NLayerDiscriminator state dict: BatchNorm iff ``model.3.running_mean`` is present; the convs sit at the
+    nn.Sequential indices 0, 2, 5, 8, .. (p2p_networks.py:533-563: conv + LeakyReLU, then conv + norm + LeakyReLU triples, then the 1-channel conv)"""
+    convs = sorted(int(k.split(".")[1]) for k in sd if k.endswith(".weight") and sd[k].dim() == 4)
+    norm = "batch" if "model.3.running_mean" in sd else "instance"
+    w0 = sd["model.0.weight"]
+    return norm, w0.shape[0], len(convs) - 2, w0.shape[1]
+
+
+def build_discriminator(sd, device, precision="f16", finalize=True, norm=None, slope=0.2):
+    """NLayerDiscriminator (p2p_networks.py:509-571, no_antialias) as a HIP graph: Conv(k4, s2, p1) + LeakyReLU, n_layers - 1 times Conv(k4, s2, p1) + norm +
+    LeakyReLU, Conv(k4, s1, p1) + norm + LeakyReLU, Conv(k4, s1, p1) -> the one-channel fp32 logit map (the external output).  BatchNorm (eval) is folded into
+    its conv, whose epilogue applies the LeakyReLU; InstanceNorm(affine=False) is its own op with the LeakyReLU fused (the conv's bias cancels in it)."""
+    if precision not in ("f16", "f16x3"):
+        raise NotImplementedError("the discriminator runs in 'f16' or 'f16x3'; %r is a generator mode" % (precision,))
+    key_norm, ndf, n_layers, in_nc = discriminator_layout(sd)
+    norm = norm or key_norm
+    if norm not in ("instance", "batch"):
+        raise NotImplementedError('normalization layer [%s] is not found' % norm)
+    if norm == "batch" and key_norm != "batch":
+        raise NotImplementedError("BatchNorm without running statistics (track_running_stats=False) has no inference form on the HIP path")
+    net, x = _open(device, precision, in_nc)
+    h = net.conv(x, sd["model.0.weight"], sd["model.0.bias"], stride=2, pad=1, leaky=slope)
+    i = 2
+    for layer in range(1, n_layers + 1):
+        key, nkey = "model.%d" % i, "model.%d" % (i + 1)
+        stride = 2 if layer < n_layers else 1
+        if norm == "instance":
+            width = sd[key + ".weight"].shape[0]
+            if width & (width - 1) or width > 2048:
+                raise NotImplementedError("InstanceNorm on the HIP path needs a power-of-two channel count <= 2048: ndf = %d gives a layer of %d channels" % (ndf, width))
+            h = net.instance_norm(net.conv(h, sd[key + ".weight"], None, stride=stride, pad=1), leaky=slope)
+        else:
+            h = net.conv(h, sd[key + ".weight"], sd.get(key + ".bias"), bn=_bn(sd, nkey), stride=stride, pad=1, leaky=slope)
+        i += 3
+    net.out_slot = net.conv(h, sd["model.%d.weight" % i], sd["model.%d.bias" % i], pad=1, out_f32=True, act=0)
     if finalize:
         net.finalize()
     return net

@@ -90,6 +90,24 @@ def generator_state(seed=0, norm="instance", ngf=64, n_blocks=9, in_nc=3, out_nc
     return sd
 
 
+def discriminator_state(seed=0, norm="instance", ndf=64, n_layers=3, in_nc=3, gain=0.02):
+    """NLayerDiscriminator state dict (p2p_networks.py:533-563): 4x4 convs at the nn.Sequential indices 0, 2, 5, .., the first and the last with a bias,
+    the others with one iff ``norm='instance'``; ``norm='batch'``: non-trivial BN running statistics"""
+    sd = {}
+    inorm = norm == "instance"
+    g = gain if inorm else None
+    _conv(sd, seed, "model.0", ndf, in_nc, 4, True, g)
+    i, c = 2, ndf
+    for n in range(1, n_layers + 1):
+        cn = ndf * min(2 ** n, 8)
+        _conv(sd, seed, "model.%d" % i, cn, c, 4, inorm, g)
+        if not inorm:
+            _bn(sd, seed, "model.%d" % (i + 1), cn)
+        i, c = i + 3, cn
+    _conv(sd, seed, "model.%d" % i, 1, c, 4, True, g)
+    return sd
+
+
 VGG16_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512]
 
 

@@ -93,9 +93,18 @@ int gdt_net_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, const f
  * it (conv_igemm / conv_igemm_rb, conv_igemm_x3 in the split modes); the 3x3 patch kernels, which stage a one-pixel halo, and every fused form
  * of the planner are not taken (gdt_net_plan_summary counts [10], [11]). */
 int gdt_net_conv_dilated(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, int dilation, const float* weight, const float* bias, int* out_tensor);
+/* Conv2d + bias (+ folded BatchNorm2d(eval), as gdt_net_conv) + nn.LeakyReLU(slope): the convs of NLayerDiscriminator
+ * (nn.Conv2d(.., kernel_size=4, stride=2 | 1, padding=1) .. nn.LeakyReLU(0.2, True), p2p_networks.py:533, :543-547, :557-561).  0 < slope < 1; the
+ * activation is applied in the epilogue after bias and BN.  desc->relu, transposed and out_f32_nchw must be 0; no residual; precision modes f16 and f16x3.
+ * k4 / pad 1 layers with cin % 64 == 0 run on conv4x4_halo.hip (f16), everything else on the generic implicit-GEMM kernels. */
+int gdt_net_conv_leaky(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, float slope, const float* weight, const float* bias,
+                       const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor);
 
 /* nn.InstanceNorm2d(affine=False, eps) (+ fused ReLU) (+ fused residual add AFTER the norm): p2p_networks.py:29,:272,:505 */
 int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, int residual_tensor, int* out_tensor);
+/* nn.InstanceNorm2d(affine=False, eps) + nn.LeakyReLU(slope): norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True) of NLayerDiscriminator
+ * (p2p_networks.py:545-546, :559-560).  Always its own statistics and apply passes: neither its producer nor its consumer takes part of it. */
+int gdt_net_instance_norm_leaky(gdt_net* net, int in_tensor, float eps, float slope, int* out_tensor);
 
 /* nn.MaxPool2d(kernel, stride, padding), floor mode */
 int gdt_net_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int* out_tensor);
@@ -198,7 +207,8 @@ int gdt_net_flops(gdt_net* net, int n, int rh, int rw, double* flops);
  * one fused-phase launch, [9] stride-2 convs as the shift form.  n_counts >= 10; with n_counts >= 12 also [10] dilated convs (gdt_net_conv_dilated) and
  * [11] of those on any special form (a patch kernel, a fused launch): 0 -- dilation runs on the generic implicit-GEMM kernels only; with n_counts >= 14 also
  * [12] the launches of the pool-head ops (gdt_net_pool_head: fixed by the layers present, whatever the batch and the number of regions) and [13] those
- * among them that read the feature map (one per op).  (Diagnostics / tests; no reference counterpart.) */
+ * among them that read the feature map (one per op); with n_counts >= 15 also [14] the conv launches that run on the 4x4 patch kernel (conv4x4_halo.hip;
+ * none with GDT_CONV4X4_HALO=0).  (Diagnostics / tests; no reference counterpart.) */
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts);
 
 /* Per-op timing for bench.py's roofline line: when enabled, gdt_net_forward records HIP events on the caller's stream
@@ -321,6 +331,18 @@ int gdt_retrieval_diverse_anchors(const float* vecs, int nq, int d, const int* t
  * `stream`, no synchronisation.  Bad sizes, a null buffer, an unknown kind or a short workspace return GDT_ERR_INVALID before any launch.
  * ------------------------------------------------------------------------------------------------------------------ */
 int gdt_tuple_loss_workspace_bytes(int n_tuples, int s, size_t* bytes);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Patch scores of a PatchGAN discriminator and the adversarial criterion over them
+ *   DiscriminatorLoss.forward            mdir/components/optim/criterion/compound_losses.py:33-45 (criterion(output, full_like(output, target)))
+ *   get_target_tensor                    compound_losses.py:47-50 (target = int(not is_target_real): real -> 0, fake -> 1)
+ *   MSELoss / BCEWithLogitsLoss          mdir/components/optim/criterion/__init__.py:6-8 (torch's, reduction "mean")
+ * logits: n maps of hw fp32 values each ([n][1][h][w], device).  kind 0: mse, term(x, t) = (x - t)^2; kind 1: bce_with_logits,
+ * term(x, t) = max(x, 0) - x t + log(1 + exp(-|x|)).  per_image (device, double [n][3]): the mean logit, the mean term against target 0 and the mean
+ * term against target 1 of every map; total (device, double [3]): the same three means over all n * hw values (what the reference's criterion
+ * returns for the batch).  Terms and sums in double, added in a fixed order: no atomics, bit-identical from run to run.  Two launches on
+ * `stream`, no synchronisation.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int gdt_patch_score(const float* logits, int n, int hw, int kind, double* per_image, double* total, void* stream);
 int gdt_tuple_loss(const float* vecs, const int* tuples, int n_vec, int d, int n_tuples, int s, int kind, float margin, float eps,
                    float* pair_dist, float* tuple_loss, double* total, void* workspace, size_t workspace_bytes, void* stream);
 

@@ -8,6 +8,7 @@
     mdir.learning.validation               -> gandtr_amd.learning.validation        (initialize_validation, SingleValidation, ...)
     mdir.components.optim.score            -> gandtr_amd.components.optim.score     (SCORES, initialize_score: cirdatasetap)
     mdir.components.optim.criterion        -> gandtr_amd.components.optim.criterion (CRITERIA, initialize_criterion: contrastive, triplet)
+    mdir.components.optim.criterion.adversarial -> gandtr_amd.components.optim.criterion.adversarial (DiscriminatorLoss, patch_scores)
     mdir.stages.infer                      -> gandtr_amd.stages.infer               (infer(params, data))
     mdir.tools.tensors                     -> gandtr_amd.tools.tensors
 
@@ -40,6 +41,7 @@ _ALIASES = {
     "mdir.components.optim.score": "gandtr_amd.components.optim.score",
     "mdir.components.optim.score.cirscore": "gandtr_amd.components.optim.score.cirscore",
     "mdir.components.optim.criterion": "gandtr_amd.components.optim.criterion",
+    "mdir.components.optim.criterion.adversarial": "gandtr_amd.components.optim.criterion.adversarial",
     "mdir.stages": "gandtr_amd.stages",
     "mdir.stages.infer": "gandtr_amd.stages.infer",
     "mdir.stages.whiten": "gandtr_amd.stages.whiten",

@@ -3,7 +3,7 @@
 
 usage: tools/net_probe.py MODEL [--precision P] --shape N,H,W [--shape ...] MODE [options]
 
-  MODEL  gen | genbn (ResnetGenerator, InstanceNorm / BatchNorm) | hed | rcf | r101 | vgg16 (GeM embedders)
+  MODEL  gen | genbn (ResnetGenerator, InstanceNorm / BatchNorm) | disc | discbn (NLayerDiscriminator, likewise) | hed | rcf | r101 | vgg16 (GeM embedders)
   MODE   ops       per-op table of one profiled forward: index, kind, kernel variant, ms, TFLOP/s (--bytes: and GB/s of the algorithmic HBM bytes);
                    --min-ms T shows the ops of at least T ms, --from-op I those from index I on; the total counts every op
          variants  the same forward summed by (kind, variant), largest first
@@ -51,6 +51,8 @@ def build(model, dev, precision):
     kw = {} if precision is None else {"precision": precision}      # None: the builder's own default (generator f16c, the others f16)
     if model in ("gen", "genbn"):
         return engine.build_generator(synth.generator_state(0, "instance" if model == "gen" else "batch"), dev, **kw), 1.0
+    if model in ("disc", "discbn"):
+        return engine.build_discriminator(synth.discriminator_state(0, "instance" if model == "disc" else "batch", gain=0.2 if model == "disc" else None), dev, **kw), 1.0
     if model == "hed":
         return engine.build_hed(synth.hed_state(0), dev, **CAFFE_INPUT, **kw), 1.0
     if model == "rcf":
@@ -75,7 +77,7 @@ def rate(amount, ms, unit):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter,
                                  epilog="the module docstring lists the command lines of the scripts this tool replaced")
-    ap.add_argument("model", choices=("gen", "genbn", "hed", "rcf", "r101", "vgg16"))
+    ap.add_argument("model", choices=("gen", "genbn", "disc", "discbn", "hed", "rcf", "r101", "vgg16"))
     ap.add_argument("mode", choices=("ops", "variants", "mean5", "time"))
     ap.add_argument("--precision", choices=sorted(engine.HipNet.PRECISIONS), default=None, help="default: the builder's own")
     ap.add_argument("--shape", action="append", required=True, metavar="N,H,W", help="batch, height, width; may be given several times")
