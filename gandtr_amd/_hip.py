@@ -46,6 +46,19 @@ class JpegItem(ctypes.Structure):
     _fields_ = [("info", POINTER(JpegInfo)), ("scan", c_void_p), ("seg_off", POINTER(ctypes.c_uint)), ("dst_hwc", c_void_p)]
 
 
+class PatchLayer(ctypes.Structure):
+    """struct gdt_patch_layer (include/gandtr_hip.h): one feature map of gdt_patch_sample."""
+    _fields_ = [("feat", c_void_p), ("ids", c_void_p), ("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p), ("out", c_void_p),
+                ("batch", c_int), ("channels", c_int), ("hw", c_int), ("patches", c_int)]
+
+
+class PatchNceLayer(ctypes.Structure):
+    """struct gdt_patchnce_layer (include/gandtr_hip.h): one layer of gdt_patchnce_loss."""
+    _fields_ = [("q", c_void_p), ("k", c_void_p), ("row_loss", c_void_p), ("rows", c_int), ("d", c_int), ("groups", c_int)]
+
+
+PATCH_MAX_LAYERS = 16                  # GDT_PATCH_MAX_LAYERS
+
 _FP = POINTER(c_float)
 _IP = POINTER(c_int)
 
@@ -103,6 +116,8 @@ SIGNATURES = {
     "gdt_tuple_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
     "gdt_patch_score": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gdt_patch_sample": (c_int, [POINTER(PatchLayer), c_int, c_int, c_int, c_void_p]),
+    "gdt_patchnce_loss": (c_int, [POINTER(PatchNceLayer), c_int, c_float, c_float, c_void_p, c_void_p]),
     "gdt_l2n_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "gdt_gem_l2n": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "gdt_rpool_regions": (c_int, [c_int, c_int, c_int, _IP, c_int, _IP]),

@@ -1,5 +1,5 @@
 """Model registry (plugin API) -- mirror of mdir/components/model/network/__init__.py:20-48 restricted to the
-architectures reachable from the hub entrypoints, the BASELINE configs and the published GAN scenarios' discriminators.  Unknown names raise KeyError like the
+architectures reachable from the hub entrypoints, the BASELINE configs and the published GAN scenarios' discriminators and CUT's ``featdown`` network.  Unknown names raise KeyError like the
 reference (:48)."""
 import torch.nn as nn
 
@@ -19,6 +19,7 @@ MODEL_LABELS = {
     "identity": Identity,
     "official_resnet_generator": p2p_networks.ResnetGenerator,
     "official_p2p_discriminator": p2p_networks.NLayerDiscriminator,
+    "official_p2p_mlp": p2p_networks.PatchSampleF,
     "cirnet": cirnet.init_cirnet,
     "hed_interpolation": hed.HedInterpolation,
     "rcf": rcf.RCF,

@@ -1,5 +1,5 @@
-"""CycleGAN / HED-N-GAN ResNet generator and PatchGAN discriminator -- host mirror of mdir/components/model/network/p2p_networks.py
-(get_norm_layer :23-35, ResnetGenerator :239-337, ResnetBlock :454-506, NLayerDiscriminator :509-571).
+"""CycleGAN / HED-N-GAN ResNet generator, PatchGAN discriminator and CUT's patch sampler -- host mirror of mdir/components/model/network/p2p_networks.py
+(get_norm_layer :23-35, ResnetGenerator :239-337, ResnetBlock :454-506, NLayerDiscriminator :509-571, Normalize / PatchSampleF :595-671).
 
 The nn.Module tree is identical to the reference's (same nn.Sequential indices, same parameter names, same creation
 order), so reference checkpoints load unchanged and seeded initialisation reproduces the reference's weights.  On a
@@ -8,6 +8,7 @@ torch modules (BASELINE config 0: "plumbing, no GPU").
 """
 import functools
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -64,6 +65,8 @@ class ResnetGenerator(HipBacked, nn.Module):
 
     #: the generators meet north_star's 1e-3 in the compensated mode only
     hip_default_precision = "f16c"
+    #: ``forward(.., encode_only=True)`` on the HIP path runs a graph that ends at the last requested tap; False: the full graph, later layers discarded
+    hip_encoder_graph = True
 
     def __init__(self, input_nc, output_nc, ngf=64, norm_layer="batch", use_dropout=False, n_blocks=9,
                  padding_type="reflect", no_antialias=True, no_antialias_up=True, track_running_stats=True):
@@ -125,6 +128,12 @@ class ResnetGenerator(HipBacked, nn.Module):
             raise NotImplementedError("feature taps %s (reflection-padded tensors) are not materialised on the HIP path" % unavailable)
         self._hip_check_inference()
         prec = self._hip_precision()
+        if encode_only and taps and layers[-1] == taps[-1] < last - 2 and self.hip_encoder_graph:
+            # the reference returns at the last requested layer (:328-329): a graph of its own that ends there, cached beside the full one
+            net = self._hip_net(("gen_enc", taps, prec), lambda sd, dev: engine.build_generator(sd, dev, taps=taps, precision=prec, norm=cfg["norm"],
+                                                                                               stop_after_taps=True))
+            outs = net.forward(x)
+            return [outs[net.tap_slots[t]] for t in layers if t in net.tap_slots]
         net = self._hip_net(("gen", taps, prec), lambda sd, dev: engine.build_generator(sd, dev, taps=taps, precision=prec, norm=cfg["norm"]))
         outs = net.forward(x)
         out = outs[net.out_slot]
@@ -191,3 +200,154 @@ class NLayerDiscriminator(HipBacked, nn.Module):
             raise NotImplementedError("HIP discriminator runs in 'f16' or 'f16x3'; %r is a generator mode" % (prec,))
         net = self._hip_net(("disc", prec), lambda sd, dev: engine.build_discriminator(sd, dev, precision=prec, norm=cfg["norm"]))
         return net.forward(x)[net.out_slot]
+
+
+class Normalize(nn.Module):
+    """x / (sum(x^power, dim 1)^(1 / power) + 1e-7)"""
+
+    def __init__(self, power=2):
+        super().__init__()
+        self.power = power
+
+    def forward(self, x):
+        norm = x.pow(self.power).sum(1, keepdim=True).pow(1. / self.power)
+        return x.div(norm + 1e-7)
+
+
+UNAVAILABLE_TAPS = "feature taps %s (reflection-padded tensors) are not materialised on the HIP path"
+
+
+def generator_tap_channels(layers, ngf=64, n_blocks=9, input_nc=3, output_nc=3):
+    """channel counts of the taps ``layers`` (nn.Sequential indices) of a ResnetGenerator, from its layout alone: no forward.  The two reflection-padded
+    tensors (index 0 and the pad before the head) are refused like ResnetGenerator refuses them on the HIP path."""
+    widths = [input_nc] + [ngf] * 3 + [2 * ngf] * 3 + [4 * ngf] * 3 + [4 * ngf] * n_blocks + [2 * ngf] * 3 + [ngf] * 3 + [ngf] + [output_nc] * 2
+    last = len(widths) - 1
+    bad = [l for l in layers if l in (0, last - 2)]
+    if bad:
+        raise NotImplementedError(UNAVAILABLE_TAPS % bad)
+    out = [l for l in layers if not 0 <= l <= last]
+    if out:
+        raise ValueError("a ResnetGenerator with %d blocks has the layers 0 .. %d, got %s" % (n_blocks, last, out))
+    return [widths[l] for l in layers]
+
+
+class PatchSampleF(HipBacked, nn.Module):
+    """CUT's ``featdown`` network: per feature map, ``num_patches`` positions (the same for every image of the batch) -> rows [B * P][C] -> optional
+    Linear(C, nc) -> ReLU -> Linear(nc, nc) -> l2 normalisation.  Attribute names and state-dict keys (``mlp_<i>.0.weight`` ..) are the reference's.
+
+    Unlike the reference's constructor this one runs no generator forward and needs no GPU: with ``input_nc`` and ``nce_layers`` given, the MLPs' input
+    widths come from the layout of the 9-block ResnetGenerator the reference assumes (generator_tap_channels) and the MLPs are created on the CPU; without
+    them the MLPs are created at the first forward on the features' device (``create_mlp``).  On HIP tensors all layers run in ONE launch of
+    gdt_patch_sample (gandtr_amd/csrc/patch_nce.hip), inference only; on CPU tensors the reference's torch ops run."""
+
+    def __init__(self, use_mlp=True, init_type="normal", init_gain=0.02, input_nc=3, nc=256, nce_layers="0,4,8,12,16"):
+        super().__init__()
+        self.meta = {"in_channels": input_nc, "out_channels": nc}
+        self._disable_graphviz = True
+        self.l2norm = Normalize(2)
+        self.use_mlp = use_mlp
+        self.nc = nc
+        self.mlp_init = False
+        self.init_type = init_type
+        self.init_gain = init_gain
+        if input_nc and nce_layers:
+            layers = [int(i) for i in nce_layers.split(",")] if isinstance(nce_layers, str) else [int(i) for i in nce_layers]
+            self._create_mlp_widths(generator_tap_channels(layers, input_nc=input_nc), "cpu")
+
+    def _create_mlp_widths(self, widths, device):
+        for mlp_id, width in enumerate(widths):
+            mlp = nn.Sequential(nn.Linear(width, self.nc), nn.ReLU(), nn.Linear(self.nc, self.nc))
+            setattr(self, "mlp_%d" % mlp_id, mlp.to(device))
+        self.mlp_init = True
+
+    def create_mlp(self, feats, device=None):
+        """one MLP per feature map, on ``device`` or else where the features are (the reference's ``.cuda()`` default, without requiring a GPU)"""
+        self._create_mlp_widths([feat.shape[1] for feat in feats], device if device else feats[0].device)
+
+    def forward(self, feats, num_patches=64, patch_ids=None, device=None):
+        if self.use_mlp and not self.mlp_init:
+            self.create_mlp(feats, device)
+        if feats and feats[0].is_cuda:
+            return self._forward_hip(feats, num_patches, patch_ids)
+        return_ids, return_feats = [], []
+        for feat_id, feat in enumerate(feats):
+            B, H, W = feat.shape[0], feat.shape[2], feat.shape[3]
+            feat_reshape = feat.permute(0, 2, 3, 1).flatten(1, 2)
+            if num_patches > 0:
+                if patch_ids is not None:
+                    patch_id = patch_ids[feat_id]
+                else:
+                    patch_id = np.random.permutation(feat_reshape.shape[1])
+                    patch_id = patch_id[:int(min(num_patches, patch_id.shape[0]))]
+                patch_id = torch.as_tensor(patch_id, dtype=torch.long, device=feat.device)
+                x_sample = feat_reshape[:, patch_id, :].flatten(0, 1)
+            else:
+                x_sample = feat_reshape
+                patch_id = []
+            if self.use_mlp:
+                x_sample = getattr(self, "mlp_%d" % feat_id)(x_sample)
+            return_ids.append(patch_id)
+            x_sample = self.l2norm(x_sample)
+            if num_patches == 0:
+                x_sample = x_sample.permute(0, 2, 1).reshape([B, x_sample.shape[-1], H, W])
+            return_feats.append(x_sample)
+        return return_feats, return_ids
+
+    def _forward_hip(self, feats, num_patches, patch_ids):
+        from .... import _hip
+        if num_patches == 0:
+            raise NotImplementedError("num_patches == 0 (whole-map output) is not provided on the HIP path")
+        if len(feats) > _hip.PATCH_MAX_LAYERS:
+            raise NotImplementedError("the HIP path samples at most %d feature maps per call" % _hip.PATCH_MAX_LAYERS)
+        self._hip_check_inference()
+        lib = _hip.load()
+        dev = feats[0].device
+        feats = [f.detach().contiguous().float() for f in feats]
+        # position ids: drawn like the reference draws them (per layer, in layer order), or taken; host ids are checked and uploaded as ONE table
+        ids, host = [None] * len(feats), {}
+        for i, f in enumerate(feats):
+            hw = f.shape[2] * f.shape[3]
+            if patch_ids is None:
+                pid = np.random.permutation(hw)
+                pid = pid[:int(min(num_patches, pid.shape[0]))]
+            else:
+                pid = patch_ids[i]
+            if torch.is_tensor(pid) and pid.is_cuda:
+                ids[i] = pid.to(dev).reshape(-1)                # a device table is trusted (gdt_patch_sample)
+            else:
+                pid = np.asarray(pid.cpu() if torch.is_tensor(pid) else pid).reshape(-1)
+                if pid.size < 1 or pid.size > hw or pid.min() < 0 or pid.max() >= hw:
+                    raise ValueError("patch ids of feature map %d: 1 .. %d ids in [0, %d)" % (i, hw, hw))
+                host[i] = pid.astype(np.int32)
+        with torch.cuda.device(dev):
+            if host:
+                table = torch.from_numpy(np.concatenate([host[i] for i in sorted(host)])).to(dev)
+                at = 0
+                for i in sorted(host):
+                    ids[i] = table[at:at + host[i].size]
+                    at += host[i].size
+            ids32 = [t if t.dtype == torch.int32 else t.to(torch.int32) for t in ids]
+            widths = [self.nc if self.use_mlp else f.shape[1] for f in feats]
+            rows = [f.shape[0] * t.numel() for f, t in zip(feats, ids32)]
+            flat = torch.empty(sum(r * w for r, w in zip(rows, widths)), dtype=torch.float32, device=dev)
+            outs, at = [], 0
+            for r, w in zip(rows, widths):
+                outs.append(flat[at:at + r * w].view(r, w))
+                at += r * w
+            table, keep = (_hip.PatchLayer * len(feats))(), []
+            for i, (f, t, o) in enumerate(zip(feats, ids32, outs)):
+                ptrs = [None] * 4
+                if self.use_mlp:
+                    mlp = getattr(self, "mlp_%d" % i)
+                    if mlp[0].in_features != f.shape[1]:
+                        raise ValueError("feature map %d has %d channels, mlp_%d takes %d" % (i, f.shape[1], i, mlp[0].in_features))
+                    ws = [p.detach().contiguous().float() for p in (mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias)]
+                    if any(w.device != dev for w in ws):
+                        raise ValueError("mlp_%d is on %s, the features on %s" % (i, ws[0].device, dev))
+                    keep.append(ws)
+                    ptrs = [w.data_ptr() for w in ws]
+                table[i] = _hip.PatchLayer(f.data_ptr(), t.data_ptr(), ptrs[0], ptrs[1], ptrs[2], ptrs[3], o.data_ptr(), f.shape[0], f.shape[1],
+                                           f.shape[2] * f.shape[3], t.numel())
+            _hip.check(lib.gdt_patch_sample(table, len(feats), int(self.nc) if self.use_mlp else 0, int(bool(self.use_mlp)),
+                                            torch.cuda.current_stream(dev).cuda_stream))
+        return outs, [t.long() for t in ids]

@@ -527,11 +527,15 @@ def generator_layout(sd):
     return norm, w0.shape[0], n_blocks, w0.shape[1], sd["model.%d.weight" % last].shape[0]
 
 
-def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precision="f16c", finalize=True, norm=None):
+def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precision="f16c", finalize=True, norm=None, stop_after_taps=False):
     """ResnetGenerator as a HIP graph.  External outputs: [generator output] + one per requested tap (in ``taps``
     order).  Taps follow the reference's nn.Sequential indices (p2p_networks.py:316-334); a norm-layer tap aliases the
     post-ReLU tensor because the reference's ReLUs are in-place (:272).  Tap 0 / the second reflection pad are not
-    materialised on the device (padding is resolved inside the conv loader) and are not available."""
+    materialised on the device (padding is resolved inside the conv loader) and are not available.
+
+    ``stop_after_taps``: the encoder-only graph (``forward(.., encode_only=True)``, p2p_networks.py:328-329) -- the graph ends with the op that
+    materialises the last requested tap; there is no generator output (``out_slot`` is None).  A tapped tensor is written by its own op before any later
+    layer reads it, so the ops up to there are planned as in the full graph and the taps are the full graph's, bit for bit."""
     key_norm, ngf, n_blocks, in_nc, out_nc = generator_layout(sd)
     norm = norm or key_norm          # the module's configured norm type when the caller knows it (get_norm_layer, p2p_networks.py:23-35)
     if norm not in ("instance", "batch"):
@@ -545,6 +549,17 @@ def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precisi
     def tap(idx, t, bias=None):
         if idx in taps and idx not in tap_slots:
             tap_slots[idx] = net.output_nchw(t, bias)
+
+    def close(out):
+        if finalize:
+            net.finalize()
+        net.out_slot = out
+        net.tap_slots = tap_slots
+        return net
+
+    if stop_after_taps and not taps:
+        raise ValueError("an encoder-only graph needs at least one tap")
+    encoded = lambda: stop_after_taps and all(t in tap_slots for t in taps)
 
     def conv_norm_relu(x, key, nkey, idx, relu=True, residual=-1, **kw):
         """conv -> norm -> (ReLU) (+ residual).  InstanceNorm: bias-free conv (the bias cancels in the norm) + separate
@@ -561,20 +576,28 @@ def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precisi
 
     h = conv_norm_relu(x, "model.1", "model.2", 1, pad=3, reflect=True)
     tap(2, h); tap(3, h)
+    if encoded():
+        return close(None)
     i = 4
     for _ in range(2):
         h = conv_norm_relu(h, "model.%d" % i, "model.%d" % (i + 1), i, stride=2, pad=1)
         tap(i + 1, h); tap(i + 2, h)
+        if encoded():
+            return close(None)
         i += 3
     for _ in range(n_blocks):
         p = "model.%d.conv_block." % i
         r = conv_norm_relu(h, p + "1", p + "2", None, pad=1, reflect=True)
         h = conv_norm_relu(r, p + "5", p + "6", None, relu=False, residual=h, pad=1, reflect=True)
         tap(i, h)
+        if encoded():
+            return close(None)
         i += 1
     for _ in range(2):
         h = conv_norm_relu(h, "model.%d" % i, "model.%d" % (i + 1), i, transposed=True, stride=2, pad=1)
         tap(i + 1, h); tap(i + 2, h)
+        if encoded():
+            return close(None)
         i += 3
     head = "model.%d" % (i + 1)
     if (i + 1) in taps and not pre_tanh:
@@ -582,11 +605,7 @@ def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precisi
     out = net.conv(h, sd[head + ".weight"], sd[head + ".bias"], pad=3, reflect=True, out_f32=True, act=0 if pre_tanh else 1)
     if (i + 2) in taps:
         tap_slots[i + 2] = out
-    if finalize:
-        net.finalize()
-    net.out_slot = out
-    net.tap_slots = tap_slots
-    return net
+    return close(out)
 
 
 VGG16_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512]

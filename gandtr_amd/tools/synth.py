@@ -11,6 +11,7 @@ State-dict key names follow the reference modules:
                 (``features.<i>...``) plus ``pool.p`` (layers/pooling.py:40)
   HED        -- mdir/components/model/network/hed.py:30-45
   RCF        -- mdir/components/model/network/rcf.py:28-66
+  PatchSampleF -- mdir/components/model/network/p2p_networks.py:628-636 (``mlp_<i>.{0,2}...``)
 """
 import math
 import zlib
@@ -106,6 +107,26 @@ def discriminator_state(seed=0, norm="instance", ndf=64, n_layers=3, in_nc=3, ga
         i, c = i + 3, cn
     _conv(sd, seed, "model.%d" % i, 1, c, 4, True, g)
     return sd
+
+
+def patchsample_state(seed=0, channels=(128, 256, 256, 256), nc=256, gain=1.0):
+    """PatchSampleF state dict (p2p_networks.py:628-636): per feature map i of ``channels[i]`` channels ``mlp_<i>.0`` Linear(channels[i], nc) and
+    ``mlp_<i>.2`` Linear(nc, nc), N(0, gain * sqrt(2 / fan_in)) weights and N(0, 0.1) biases: on O(1) features the hidden and the output rows are O(1)"""
+    sd = {}
+    for i, c in enumerate(channels):
+        for j, fan_in in ((0, c), (2, nc)):
+            name = "mlp_%d.%d" % (i, j)
+            sd[name + ".weight"] = _normal(seed, name + ".weight", (nc, fan_in), gain * math.sqrt(2.0 / fan_in))
+            sd[name + ".bias"] = _normal(seed, name + ".bias", (nc,), 0.1)
+    return sd
+
+
+def patchnce_maps(seed, shape, mix=0.5):
+    """a pair of seeded fp32 feature maps (q side, k side) of ``shape``: the k map is ``mix`` of the q map plus independent noise, so a patch and its
+    translation are related (positive logits above the negatives') without being equal -- the row losses spread over a range"""
+    q = _normal(seed, "nce.q", shape)
+    k = q * np.float32(mix) + _normal(seed, "nce.k", shape) * np.float32(math.sqrt(1.0 - mix * mix))
+    return q, k
 
 
 VGG16_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512]

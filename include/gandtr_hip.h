@@ -345,6 +345,37 @@ int gdt_tuple_loss_workspace_bytes(int n_tuples, int s, size_t* bytes);
 int gdt_patch_score(const float* logits, int n, int hw, int kind, double* per_image, double* total, void* stream);
 int gdt_tuple_loss(const float* vecs, const int* tuples, int n_vec, int d, int n_tuples, int s, int kind, float margin, float eps,
                    float* pair_dist, float* tuple_loss, double* total, void* workspace, size_t workspace_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------------------------------
+ * CUT's contrastive head: patch sampling + projection, and the multi-layer PatchNCE loss (the `nce` criterion of train_cut.yml), forward only
+ *   PatchSampleF / Normalize             mdir/components/model/network/p2p_networks.py:595-671
+ *   PatchNCELoss / MultilayerPatchNCELoss mdir/components/optim/criterion/compound_losses.py:113-173
+ * gdt_patch_sample, per layer of a table of n_layers <= GDT_PATCH_MAX_LAYERS descriptors (a HOST array; every pointer in it a device pointer):
+ *   feat fp32 NCHW [batch][channels][hw]; ids int32 [patches], each in [0, hw) -- the entry cannot read a device table, the kernel clamps nothing, the
+ *   binding checks ids that come from the host --, shared by all images; row b * patches + p of `out` is feat[b, :, ids[p]], through
+ *   Linear(channels, nc) -> ReLU -> Linear(nc, nc) (w1 [nc][channels], b1 [nc], w2 [nc][nc], b2 [nc], torch's layout) when use_mlp is set, divided by
+ *   sqrt(sum x^2) + 1e-7.  out: fp32 [batch * patches][nc], or [..][channels] with use_mlp 0 (nc and the weights are then not read).  fp32 throughout
+ *   (f32-input MFMAs); the hidden activations stay on chip.  1 <= nc <= 512.  ONE launch for all layers.
+ * gdt_patchnce_loss, per layer: q, k fp32 [rows][d] (d <= 512), groups = batch_dim_for_bmm (rows % groups == 0, n = rows / groups).  For row i of group g
+ *   out_0 = q_i . k_i / T, out_{1+j} = q_i . k_j / T over the n rows j of g with the entry j == i replaced by -10 / T, row_loss[i] = logsumexp(out) - out_0.
+ *   The logits are never written (running maximum and sum per row).  totals (device, double [n_layers + 1]): mean(row_loss) * weight per layer, then
+ *   their sum / n_layers.  TWO launches for all layers.
+ * Every sum has an order fixed by the shapes: no atomics, bit-identical from run to run, a row's result independent of the other layers of the call.
+ * No synchronisation.  A null pointer, non-positive sizes, patches > hw, rows % groups != 0 or too many layers return GDT_ERR_INVALID before any launch.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define GDT_PATCH_MAX_LAYERS 16
+typedef struct gdt_patch_layer {
+    const float* feat; const int* ids;
+    const float* w1; const float* b1; const float* w2; const float* b2;
+    float* out;
+    int batch, channels, hw, patches;
+} gdt_patch_layer;
+typedef struct gdt_patchnce_layer {
+    const float* q; const float* k;
+    float* row_loss;
+    int rows, d, groups;
+} gdt_patchnce_layer;
+int gdt_patch_sample(const gdt_patch_layer* layers, int n_layers, int nc, int use_mlp, void* stream);
+int gdt_patchnce_loss(const gdt_patchnce_layer* layers, int n_layers, float inv_temperature, float weight, double* totals, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * CLAHE post-processing ("next" row of SURVEY.md section 8f, rank 1: the step between generator and embedder)

@@ -9,6 +9,7 @@
     mdir.components.optim.score            -> gandtr_amd.components.optim.score     (SCORES, initialize_score: cirdatasetap)
     mdir.components.optim.criterion        -> gandtr_amd.components.optim.criterion (CRITERIA, initialize_criterion: contrastive, triplet)
     mdir.components.optim.criterion.adversarial -> gandtr_amd.components.optim.criterion.adversarial (DiscriminatorLoss, patch_scores)
+    mdir.components.optim.criterion.patchnce -> gandtr_amd.components.optim.criterion.patchnce (MultilayerPatchNCELoss, calculate_nce_loss)
     mdir.stages.infer                      -> gandtr_amd.stages.infer               (infer(params, data))
     mdir.tools.tensors                     -> gandtr_amd.tools.tensors
 
@@ -42,6 +43,7 @@ _ALIASES = {
     "mdir.components.optim.score.cirscore": "gandtr_amd.components.optim.score.cirscore",
     "mdir.components.optim.criterion": "gandtr_amd.components.optim.criterion",
     "mdir.components.optim.criterion.adversarial": "gandtr_amd.components.optim.criterion.adversarial",
+    "mdir.components.optim.criterion.patchnce": "gandtr_amd.components.optim.criterion.patchnce",
     "mdir.stages": "gandtr_amd.stages",
     "mdir.stages.infer": "gandtr_amd.stages.infer",
     "mdir.stages.whiten": "gandtr_amd.stages.whiten",
