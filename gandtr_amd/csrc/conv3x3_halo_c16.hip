@@ -39,8 +39,9 @@
 #include "conv_device.h"
 
 #ifndef GDT_C16_SCHED
-#define GDT_C16_SCHED 1         // 1: sched_group_barrier interleave (per MFMA: at most one LDS read, two VALU; a memory operation every fourth)
-#endif
+#define GDT_C16_SCHED 2         // layout of the chunk body (the kernel comment "PHASES"): 1 = per patch row (four MFMAs, then the row's companion work in
+#endif                          // one piece), 2 = per MFMA (behind each MFMA at most about three instructions of it)
+static_assert(GDT_C16_SCHED == 1 || GDT_C16_SCHED == 2, "GDT_C16_SCHED: 1 (row layout) or 2 (per-MFMA layout)");
 #ifndef GDT_C16_RING
 #define GDT_C16_RING 3
 #endif
@@ -85,6 +86,28 @@ __device__ __forceinline__ void mfma16(f32x4& acc, const f16x8& a, const f16x8& 
 }
 __device__ __forceinline__ void mfma16_mx(f32x4& acc, const v6i& a6, const v4i& b4, int sa, int sb) {      // A: 32 e2m3 values per lane, B: 32 e2m1
     asm("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:2 blgp:4" : "+a"(acc) : "v"(a6), "v"(b4), "v"(sa), "v"(sb));
+}
+
+// ... of layout 2, volatile and with a memory clobber: each keeps its place between the sched_barrier fences, ahead of the (volatile) pins of the
+// work laid behind it and ahead of the loads and LDS reads laid behind it
+__device__ __forceinline__ void mfma16_at(f32x4& acc, const f16x8& a, const f16x8& b) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b) : "memory");
+}
+__device__ __forceinline__ void mfma16_mx_at(f32x4& acc, const v6i& a6, const v4i& b4, int sa, int sb) {
+    asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:2 blgp:4" : "+a"(acc) : "v"(a6), "v"(b4), "v"(sa), "v"(sb) : "memory");
+}
+// max(|a|, |b|, |c|) / max(|a|, |b|) in one instruction each (the C expression canonicalises every pinned input first: two instructions more per
+// maximum).  Same value as fmaxf of the absolute values for every input but a signalling NaN, which no kernel of the path produces and which the
+// MFMAs would turn into NaN outputs either way.
+__device__ __forceinline__ float gdt_max3_abs(float a, float b, float c) {
+    float m;
+    asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(m) : "v"(a), "v"(b), "v"(c));
+    return m;
+}
+__device__ __forceinline__ float gdt_max_abs(float a, float b) {
+    float m;
+    asm("v_max_f32_e64 %0, |%1|, |%2|" : "=v"(m) : "v"(a), "v"(b));
+    return m;
 }
 
 // MODE bits: 1 = the producer's InstanceNorm (+ReLU) is applied while staging; 2 = ... plus a residual; 4 = the transformed tensor is written back
@@ -211,8 +234,19 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
 
     // The same work in PHASES for the main loop: the MFMAs there are inline asm, which the compiler neither schedules around nor sees as long
     // operations -- left alone it sinks every LDS read to just in front of its MFMA and runs the ~100 staging instructions of a round in one
-    // piece.  So the loop body is laid out by hand: after the four MFMAs of a patch row comes one phase (<= 8 instructions) of the staging,
-    // fenced by sched_barrier; a round's store (phases 0-9) and the next round's load (10, 11) share a slot of 16 patch rows.
+    // piece.  So the loop body is laid out by hand, fenced by sched_barrier, in one of two layouts (GDT_C16_SCHED):
+    //   1  per patch row: the row's four MFMAs back to back, then its fragment read, its weight load and one of 14 phases of the staging; a
+    //      round's store (phases 0-9) and the next round's load (10-13) share ONE slot of 16 patch rows, every second slot.  With one wave per
+    //      SIMD and in-order issue the second to fourth MFMA of a row each wait ~12 cycles for the pipe with nothing to issue, and only the
+    //      fourth one's shadow covers the row's work, which is 9-41 instructions (tools/mfma_gaps.py: a quarter of the chunk's non-MFMA issue
+    //      cycles sit under an MFMA, 5.4-6.1 k cycles per chunk do not);
+    //   2  per MFMA: behind the row's first MFMA its vector-memory instruction (a weight load), behind the second and third one MICRO-PHASE
+    //      of the staging each (stage_micro: <= 3 VALU instructions, or one load / store / LDS write), behind the fourth its LDS reads (the
+    //      window slot they refill is read by all four MFMAs).  A round spreads over both slots of its pair: 64 micro-phase positions, of
+    //      which a round uses 47-57; no gap holds 12 instructions, 0.5-0.7 k issue cycles per chunk stay uncovered (tests/test_c16_layout_cpu.py).
+    // Both issue the same MFMAs into every accumulator in the same order (the output is the same bit for bit), a step's weights ahead of the halo
+    // loads consumed after them, a round's loads SDIST rounds ahead of its store and its LDS writes ahead of the chunk barrier.  Measured:
+    // DESIGN.md section 4, "per-MFMA layout".
     float sa[8];
     unsigned sou[4], sqlo = 0, sqhi = 0;
     int sex = 0;                      // the pixel's scale exponent (gdt_c_pixel_exp) and the converts' scales
@@ -276,6 +310,243 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
 #undef GDT_PIN4
 #undef GDT_PIN8
     };
+    // Layout 2: the same work in MICRO-PHASES, two per patch row (behind the row's second and third MFMA) over the 32 rows of the round's slot
+    // pair; position mp = 2 * (row of the pair) + g.  Every micro-phase pins its inputs AND its results (empty asm volatile), so that its
+    // instructions stay between the two sched_barrier fences around it.  The arithmetic is store_piece's, value for value; what differs is
+    // integer bookkeeping with the same result: the scale exponent is carried biased (e + 127), and the reflected coordinate is
+    // min(|i|, 2 (H - 1) - |i|) -- |i| reflects i = -1, the other operand i >= H, in bounds the minimum is i itself -- clamped like before.
+    int mh = 0, mt = 0, my = 0, mx = 0, ma = 0, mb = 0;      // load side: halo row, its coordinates
+    int wrow = 0, wx = 0, wa = 0, wq = 0;                    // store side: LDS addresses
+    float mu = 0.f, ml0 = 0.f, ml1 = 0.f;
+    int mbits = 0;
+    int gy0 = 0, gx0 = 0;                // first halo pixel of the patch being loaded (set per chunk, in front of its first MFMA)
+    int wes = E_OFF + HROWS_PAD;         // scale bytes of the stage being WRITTEN (the other one than `ve`'s), flipped with it (flip_stage)
+    auto stage_micro = [&](const GdtPatch& ta, int chunk, int stage_off, int sl, int row, int g) {
+        if (GDT_C16_ABL & 1) return;
+        const int r = sl / SPR, mp = ((sl % SPR) * 16 + row) * 2 + g;
+        const bool st = r >= SDIST && r - SDIST < NR, ld = r < NR;
+        Pend& pend = pendv[r % SDIST];      // (the round stored now and the round loaded behind it share a buffer)
+        constexpr int P_NORM = 0, P_RES = P_NORM + (NORM ? 8 : 1), P_WB = P_RES + (NORM && RES ? 3 : 0), P_MASK = P_WB + (WB ? 2 : 0), P_MAX = P_MASK + 3,
+                      P_DPP = P_MAX + 2, P_EXP = P_DPP + 3, P_SPLIT = P_EXP + 2, P_ADDR = P_SPLIT + 10, P_WRITE = P_ADDR + 7, P_GADDR = P_WRITE + 4,
+                      P_LOAD = P_GADDR + 9, P_END = P_LOAD + (RES ? 4 : 2);
+        static_assert(P_END <= SPR * 16 * 2, "a round's micro-phases fit the positions of its slot pair");
+#define GDT_PIN1(a) asm volatile("" : "+v"(a))
+#define GDT_PIN2(a, b) asm volatile("" : "+v"(a), "+v"(b))
+#define GDT_PIN3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
+#define GDT_PIN4(a, b, c, e) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(e))
+        auto f4 = [](float4& v, int i) -> float& { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); };
+        auto pr = [&](int e) -> float& { return e < 4 ? f4(pend.r0, e) : f4(pend.r1, e - 4); };
+        auto ps = [&](int e) -> float& { return e < 4 ? f4(pend.s0, e) : f4(pend.s1, e - 4); };
+        // ---- the round stored now
+        if (st && !NORM && mp == P_NORM) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sa[e] = pr(e);
+            GDT_PIN4(sa[0], sa[1], sa[2], sa[3]); GDT_PIN4(sa[4], sa[5], sa[6], sa[7]);
+        }
+        if (st && NORM && mp >= P_NORM && mp < P_NORM + 8) {        // normalise: one channel per micro-phase
+            const int e = mp - P_NORM;
+            const float lo = d.in_relu ? 0.f : -3.0e38f;
+            const float4 v = nf[e >> 1];
+            float x = pr(e);
+            GDT_PIN1(x);
+            x = fmaxf(fmaf(x, (e & 1) ? v.z : v.x, (e & 1) ? v.w : v.y), lo);
+            GDT_PIN1(x);
+            sa[e] = x;
+        }
+        if (st && NORM && RES && mp >= P_RES && mp < P_RES + 3) {     // residual: three channels
+            const int e = 3 * (mp - P_RES);
+            float y0 = ps(e), y1 = ps(e + 1), y2 = ps(e + 2 < 8 ? e + 2 : e);
+            if (e + 2 < 8) { GDT_PIN3(sa[e], sa[e + 1], sa[e + 2]); GDT_PIN3(y0, y1, y2); } else { GDT_PIN2(sa[e], sa[e + 1]); GDT_PIN2(y0, y1); }
+            sa[e] += y0; sa[e + 1] += y1;
+            if (e + 2 < 8) { sa[e + 2] += y2; GDT_PIN3(sa[e], sa[e + 1], sa[e + 2]); } else GDT_PIN2(sa[e], sa[e + 1]);
+        }
+        if (st && WB && mp == P_WB) {
+            GDT_PIN4(sa[0], sa[1], sa[2], sa[3]);
+            *(float4*)((char*)wbf + pend.goff) = make_float4(sa[0], sa[1], sa[2], sa[3]);
+        }
+        if (st && WB && mp == P_WB + 1) {
+            GDT_PIN4(sa[4], sa[5], sa[6], sa[7]);
+            *(float4*)((char*)wbf + pend.goff + 16) = make_float4(sa[4], sa[5], sa[6], sa[7]);
+        }
+        if (st && mp >= P_MASK && mp < P_MASK + 3) {                  // rows beyond the halo / zero padding: three channels
+            const int e = 3 * (mp - P_MASK);
+            if (e + 2 < 8) GDT_PIN3(sa[e], sa[e + 1], sa[e + 2]); else GDT_PIN2(sa[e], sa[e + 1]);
+            sa[e] = pend.ok ? sa[e] : 0.f; sa[e + 1] = pend.ok ? sa[e + 1] : 0.f;
+            if (e + 2 < 8) { sa[e + 2] = pend.ok ? sa[e + 2] : 0.f; GDT_PIN3(sa[e], sa[e + 1], sa[e + 2]); } else GDT_PIN2(sa[e], sa[e + 1]);
+        }
+        // gdt_c_pixel_exp in pieces: max |a| over the lane's 8 channels (any order gives the same value), then the three DPP steps one per
+        // micro-phase (the MFMA between two of them stands where the DPP wait states would)
+        if (st && mp == P_MAX) {
+            GDT_PIN4(sa[0], sa[1], sa[2], sa[3]); GDT_PIN1(sa[4]);
+            mu = gdt_max3_abs(gdt_max3_abs(sa[0], sa[1], sa[2]), sa[3], sa[4]);
+            GDT_PIN1(mu);
+        }
+        if (st && mp == P_MAX + 1) {
+            GDT_PIN4(mu, sa[5], sa[6], sa[7]);
+            mu = gdt_max_abs(gdt_max3_abs(mu, sa[5], sa[6]), sa[7]);
+            mbits = __float_as_int(mu);
+            sqlo = 0; sqhi = 0;
+            GDT_PIN3(mbits, sqlo, sqhi);
+        }
+        if (st && mp >= P_DPP && mp < P_DPP + 3) {
+            GDT_PIN1(mbits);
+            if (mp == P_DPP) mbits = max(mbits, __builtin_amdgcn_mov_dpp(mbits, 0xB1, 0xF, 0xF, false));         // quad_perm [1, 0, 3, 2]
+            if (mp == P_DPP + 1) mbits = max(mbits, __builtin_amdgcn_mov_dpp(mbits, 0x4E, 0xF, 0xF, false));     // quad_perm [2, 3, 0, 1]
+            if (mp == P_DPP + 2) mbits = max(mbits, __builtin_amdgcn_mov_dpp(mbits, 0x141, 0xF, 0xF, false));    // row_half_mirror
+            GDT_PIN1(mbits);
+        }
+        if (st && mp == P_EXP) {
+            GDT_PIN1(mbits);
+            sex = min(max(mbits >> 23, 127 - 14), 127 + 15);      // biased
+            GDT_PIN1(sex);
+        }
+        if (st && mp == P_EXP + 1) {
+            GDT_PIN1(sex);
+            slo_scale = __int_as_float((sex - 13) << 23); shi_scale = __int_as_float((sex - 2) << 23);
+            GDT_PIN2(slo_scale, shi_scale);
+        }
+        // gdt_c_split of the four channel pairs, two instructions per micro-phase: instruction i of pair K = 0 the fp16 pair, 1 / 2 the two
+        // remainders a - fp16(a), 3 / 4 the fp4 converts of the fp16 pair and of the remainders
+        if (st && mp >= P_SPLIT && mp < P_SPLIT + 10) {
+            GDT_PIN4(sqlo, sqhi, ml0, ml1);
+#pragma unroll
+            for (int i = 2 * (mp - P_SPLIT); i < 2 * (mp - P_SPLIT) + 2; ++i) {
+                const int K = i / 5, w = i - 5 * K;
+                GDT_PIN2(sa[2 * K], sa[2 * K + 1]);
+                if (w > 0) GDT_PIN1(sou[K]);
+                if (w == 0) sou[K] = gdt_pk_f16(sa[2 * K], sa[2 * K + 1]);
+                if (w == 1) asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(ml0) : "v"(sou[K]), "v"(sa[2 * K]));
+                if (w == 2) asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ml1) : "v"(sou[K]), "v"(sa[2 * K + 1]));
+                if (w == 3) {
+                    GDT_PIN1(shi_scale);
+                    if (K == 0) sqhi = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(sqhi, __builtin_bit_cast(f16x2, sou[K]), shi_scale, 0);
+                    if (K == 1) sqhi = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(sqhi, __builtin_bit_cast(f16x2, sou[K]), shi_scale, 1);
+                    if (K == 2) sqhi = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(sqhi, __builtin_bit_cast(f16x2, sou[K]), shi_scale, 2);
+                    if (K == 3) sqhi = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(sqhi, __builtin_bit_cast(f16x2, sou[K]), shi_scale, 3);
+                }
+                if (w == 4) {
+                    GDT_PIN1(slo_scale);
+                    if (K == 0) sqlo = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(sqlo, ml0, ml1, slo_scale, 0);
+                    if (K == 1) sqlo = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(sqlo, ml0, ml1, slo_scale, 1);
+                    if (K == 2) sqlo = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(sqlo, ml0, ml1, slo_scale, 2);
+                    if (K == 3) sqlo = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(sqlo, ml0, ml1, slo_scale, 3);
+                }
+                GDT_PIN1(sou[K]);
+            }
+            GDT_PIN4(sqlo, sqhi, ml0, ml1);
+        }
+        // the LDS addresses (store_piece explains the planes), then the four writes
+        const int q = lane & 7;
+        if (st && mp == P_ADDR) {
+            int lr = lrow;
+            GDT_PIN1(lr);
+            wrow = min((r - SDIST) * RPR + lr, HROWS_PAD - 1);
+            GDT_PIN1(wrow);
+        }
+        if (st && mp == P_ADDR + 1) {
+            GDT_PIN1(wrow);
+            wx = wrow - ((wrow * (65536 / HW_ + 1)) >> 16) * HW_;
+            GDT_PIN1(wx);
+        }
+        if (st && mp == P_ADDR + 2) {
+            GDT_PIN1(wx);
+            wa = q ^ ((wx >> 1) & 7);
+            GDT_PIN1(wa);
+        }
+        if (st && mp == P_ADDR + 3) {
+            GDT_PIN2(wrow, wa);
+            wa = stage_off + wrow * ROWB + (wa << 4);
+            GDT_PIN1(wa);
+        }
+        if (st && mp == P_ADDR + 4) {
+            GDT_PIN1(wx);
+            wx = ((q >> 2) << 1) ^ ((wx >> 2) & 3);
+            GDT_PIN1(wx);
+        }
+        if (st && mp == P_ADDR + 5) {
+            GDT_PIN1(wx);
+            wq = (wx << 4) + ((q & 3) << 2);
+            GDT_PIN1(wq);
+        }
+        if (st && mp == P_ADDR + 6) {
+            GDT_PIN2(wrow, wq);
+            wq = stage_off + A_BYTES + wrow * QROWB + wq;
+            GDT_PIN1(wq);
+        }
+        if (st && mp == P_WRITE) {
+            GDT_PIN1(wa); GDT_PIN4(sou[0], sou[1], sou[2], sou[3]);
+            const u32x4 ov = {sou[0], sou[1], sou[2], sou[3]};
+            *(f16x8*)(smem + wa) = __builtin_bit_cast(f16x8, ov);
+        }
+        if (st && mp == P_WRITE + 1) {
+            GDT_PIN2(wq, sqlo);
+            *(unsigned*)(smem + wq) = sqlo;
+        }
+        if (st && mp == P_WRITE + 2) {
+            GDT_PIN2(wq, sqhi);
+            *(unsigned*)(smem + (wq ^ 16)) = sqhi;
+        }
+        if (st && mp == P_WRITE + 3) {
+            GDT_PIN2(wrow, sex);
+            smem[wes + wrow] = (char)(sex - 13);      // (the row's 8 lanes store the same byte)
+        }
+        // ---- the round loaded now: load_piece_part's address in pieces, then one load per micro-phase
+        if (ld && mp == P_GADDR) {
+            int lr = lrow;
+            GDT_PIN1(lr);
+            mh = min(r * RPR + lr, HROWS_PAD - 1);
+            GDT_PIN1(mh);
+        }
+        if (ld && mp == P_GADDR + 1) {
+            GDT_PIN1(mh);
+            mt = (mh * (65536 / HW_ + 1)) >> 16;
+            GDT_PIN2(mh, mt);
+        }
+        if (ld && mp == P_GADDR + 2) {
+            GDT_PIN2(mh, mt);
+            my = gy0 + mt; mx = gx0 + (mh - mt * HW_);
+            GDT_PIN3(mh, my, mx);
+        }
+        if (ld && mp == P_GADDR + 3) {
+            GDT_PIN3(mh, my, mx);
+            const bool inb = ((unsigned)my < (unsigned)d.H) & ((unsigned)mx < (unsigned)d.W);
+            pend.ok = (mh < HROWS) & (inb | refl);
+        }
+        if (ld && mp == P_GADDR + 4) {
+            GDT_PIN1(my);
+            ma = max(my, -my); mb = 2 * d.H - 2 - ma;
+            GDT_PIN2(ma, mb);
+        }
+        if (ld && mp == P_GADDR + 5) {
+            GDT_PIN2(ma, mb);
+            my = min(max(min(ma, mb), 0), d.H - 1);
+            GDT_PIN1(my);
+        }
+        if (ld && mp == P_GADDR + 6) {
+            GDT_PIN1(mx);
+            ma = max(mx, -mx); mb = 2 * d.W - 2 - ma;
+            GDT_PIN2(ma, mb);
+        }
+        if (ld && mp == P_GADDR + 7) {
+            GDT_PIN2(ma, mb);
+            mx = min(max(min(ma, mb), 0), d.W - 1);
+            GDT_PIN1(mx);
+        }
+        if (ld && mp == P_GADDR + 8) {
+            GDT_PIN2(my, mx);
+            pend.goff = (((unsigned)((ta.n * d.H + my) * d.W + mx) << (d.lc8 + 5)) + (chunk * 8 + q) * 32);      // byte offset (< 2^32, checked on the host)
+            GDT_PIN1(pend.goff);
+        }
+        if (ld && mp == P_LOAD) pend.r0 = *(const float4*)((const char*)inf + pend.goff);
+        if (ld && mp == P_LOAD + 1) pend.r1 = *(const float4*)((const char*)inf + pend.goff + 16);
+        if (ld && RES && mp == P_LOAD + 2) pend.s0 = *(const float4*)((const char*)resf + pend.goff);
+        if (ld && RES && mp == P_LOAD + 3) pend.s1 = *(const float4*)((const char*)resf + pend.goff + 16);
+#undef GDT_PIN1
+#undef GDT_PIN2
+#undef GDT_PIN3
+#undef GDT_PIN4
+    };
+    (void)stage_phase; (void)stage_micro;       // (one of them per layout)
 
     // ---- weights, streamed L2 -> registers in fragment order (net_build.hip pack_mx16): per 64 output channels (a wave's slice)
     //   w_c16 [cout/64][K/32][4 blocks][64 lanes][16 B]: lane (n, g) = W[cout block * 16 + n][k = 32 step + 8 g ..+7]
@@ -301,6 +572,11 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     // [scales: 1 KB] -- a wave's whole weight stream is one sequential region
     constexpr long WREC = 15360;
     auto load_bw = [&](int rs, int cb, int tile_n, long ks) {        // ks: uniform index of the 32-k step
+        if (GDT_C16_SCHED == 2) {       // (the record's offset in 32 bits -- gdt_conv_halo_c16_eligible -- : half the scalar address work)
+            const char* wb = (const char*)d.w_c16 + (unsigned)(((tile_n * 4 + wave) * nms + (int)(ks >> 1)) * (int)WREC + (int)(ks & 1) * 4096);
+            bw[rs][cb] = *(const f16x8*)(wb + lo16 + cb * 1024);
+            return;
+        }
         const char* wb = (const char*)d.w_c16 + (wgrp(tile_n) * nms + (ks >> 1)) * WREC + (ks & 1) * 4096;
         bw[rs][cb] = *(const f16x8*)(wb + lo16 + cb * 1024);
     };
@@ -309,7 +585,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     // operand tuple, 2 cb + 1 = its last 8 (both loaded INTO the tuple), part 8 = the four blocks' scales
     auto load_bq_part = [&](int set, int part, int tile_n, long ms) {          // ms: uniform index of the 64-k group
         const long f0 = (GDT_C16_ABL & 128) ? 0 : wgrp(tile_n) * nms + ms;      // (ablation 128: every fetch from the same 7 KB)
-        const char* rec = (const char*)d.w_c16 + f0 * WREC;
+        const char* rec = GDT_C16_SCHED == 2 ? (const char*)d.w_c16 + (unsigned)((int)f0 * (int)WREC) : (const char*)d.w_c16 + f0 * WREC;
         const int cb = part >> 1;
         if (part == 8) bqs[set] = *(const v4i*)(rec + 14336 + lo16);
         else if ((part & 1) == 0) {
@@ -343,11 +619,13 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     };
     auto flip_stage = [&](int delta) {
         ve += delta > 0 ? HROWS_PAD : -HROWS_PAD;
+        if (GDT_C16_SCHED == 2) wes -= delta > 0 ? HROWS_PAD : -HROWS_PAD;
 #pragma unroll
         for (int k = 0; k < 3; ++k) { vt[k] += delta; vq[k] += delta; }
     };
     // E8M0 scales of the activation side: blocks 0 / 2 carry a_lo, 1 / 3 a_hi, of their pixel (scale byte + this)
     const int a_scale_off = (fg & 1) ? GDT_C_HI_SCALE_OFF : 0;
+    constexpr bool AE_PRE = GDT_C16_SCHED == 2 && !(GDT_C16_ABL & (2 | 8));      // layout 2 adds it a row ahead of the MFMAs, in a gap of its own
 
     const int nchunks = d.Cin >> 6;
     // ---- prologue
@@ -402,6 +680,11 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
             // last chunk this fetches the first slices again: unconditional loads keep the code straight-line)
             auto ks_of = [&](int u) -> long { return u < 18 ? (long)(((u >> 1) * cin64 + c) * 2 + (u & 1)) : (long)(sc * 2 + (u - 18)); };
             auto tn_of = [&](int u) -> int { return (u >= 18 && last) ? nxt.tile_n : cur.tile_n; };
+            if (GDT_C16_SCHED == 2) {       // (the chunk's set-up stays in front of its first MFMA)
+                gy0 = sta.y0 - 1; gx0 = sta.x0 - 1;
+                asm volatile("" : "+s"(gy0), "+s"(gx0));
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int t = 0; t < NTAP; ++t) {
                 const int ty = t / 3, tx = t - ty * 3;
@@ -411,6 +694,32 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
                     const int u = 2 * t + s;
 #pragma unroll
                     for (int pb = 0; pb < 16; ++pb) {
+                        if (GDT_C16_SCHED == 2) {
+                            // per MFMA: (cb 0) the row's weight load, (1, 2) a staging micro-phase each, (3) the row's LDS reads -- what each
+                            // of them is, and why there, is written at the row layout below
+#pragma unroll
+                            for (int cb = 0; cb < 4; ++cb) {
+                                mfma16_at(acc[pb][cb], bw[u % RING][cb], afr[pb % AW]);     // D[cout][pixel]
+                                if (cb == 0) {
+                                    if (AE_PRE && s == 1 && pb == 15) { asm volatile("" : "+v"(ae[0])); ae[0] += a_scale_off; asm volatile("" : "+v"(ae[0])); }
+                                    if (!(GDT_C16_ABL & 4) && (pb & 3) == 2) load_bw((u + RING - 1) % RING, pb >> 2, tn_of(u + RING - 1), ks_of(u + RING - 1));
+                                    if (!(GDT_C16_ABL & (2 | 16)) && BQS == 2) {
+                                        if (t == 0 && s == 0 && pb < 9) load_bq_part(0, pb, cur.tile_n, (long)c);
+                                        if (t + 1 < NTAP && s == 1 && (pb & 1) == 1) load_bq_part((t + 1) & 1, pb >> 1, cur.tile_n, (long)((t + 1) * cin64 + c));
+                                    }
+                                    if (!(GDT_C16_ABL & (2 | 16)) && BQS == 1 && (pb & 1) == 1 && (s == 0 || pb == 1)) load_bq_part(0, s == 0 ? pb >> 1 : 8, cur.tile_n, (long)(t * cin64 + c));
+                                } else if (cb < 3) {
+                                    stage_micro(sta, sc, STAGE_BYTES - so, 3 * t + s, pb, cb - 1);
+                                } else {
+                                    if (pb + AW < 16) afr[pb % AW] = a_frag(pb + AW, ty, tx, s);
+                                    else if (s == 0) afr[pb % AW] = a_frag(pb + AW - 16, ty, tx, 1);
+                                    else if (t < NTAP - 1) afr[pb % AW] = a_frag(pb + AW - 16, nty, ntx, 0);
+                                    if (!(GDT_C16_ABL & (2 | 8)) && s == 1 && pb >= 16 - QW) { aq[pb - (16 - QW)] = a_qfrag(pb - (16 - QW), ty, tx); ae[pb - (16 - QW)] = a_efrag(pb - (16 - QW), ty, tx); }
+                                }
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                            continue;
+                        }
 #pragma unroll
                         for (int cb = 0; cb < 4; ++cb)
                             mfma16(acc[pb][cb], bw[u % RING][cb], afr[pb % AW]);     // D[cout][pixel]
@@ -438,6 +747,21 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
                 // the correction product of the tap's 64 k-values
 #pragma unroll
                 for (int pb = 0; pb < 16; ++pb) {
+                    if (GDT_C16_SCHED == 2) {
+#pragma unroll
+                        for (int cb = 0; cb < 4; ++cb) {
+                            if (!(GDT_C16_ABL & 2)) {
+                                mfma16_mx_at(acc[pb][cb], bq[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], aq[pb % QW], bqs[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], AE_PRE ? ae[pb % QW] : ae[pb % QW] + a_scale_off);
+                                // (the next row's scale byte gets its a_hi offset here, off the gap of the LDS reads)
+                                if (cb == 0 && AE_PRE && pb + 1 < 16) { asm volatile("" : "+v"(ae[(pb + 1) % QW])); ae[(pb + 1) % QW] += a_scale_off; asm volatile("" : "+v"(ae[(pb + 1) % QW])); }
+                                if (cb == 0 && !(GDT_C16_ABL & 16) && BQS == 2 && t + 1 < NTAP && pb == 1) load_bq_part((t + 1) & 1, 8, cur.tile_n, (long)((t + 1) * cin64 + c));
+                                if (cb == 3 && !(GDT_C16_ABL & 8) && pb + QW < 16) { aq[pb % QW] = a_qfrag(pb + QW, ty, tx); ae[pb % QW] = a_efrag(pb + QW, ty, tx); }
+                            }
+                            if (cb == 1 || cb == 2) stage_micro(sta, sc, STAGE_BYTES - so, 3 * t + 2, pb, cb - 1);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        continue;
+                    }
                     if (!(GDT_C16_ABL & 2)) {
 #pragma unroll
                         for (int cb = 0; cb < 4; ++cb) mfma16_mx(acc[pb][cb], bq[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], aq[pb % QW], bqs[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], ae[pb % QW] + a_scale_off);
@@ -641,6 +965,7 @@ bool gdt_conv_halo_c16_eligible(const ConvLaunch& d) {
     if (!gdt_conv_halo_c_eligible(d) || gdt_conv_halo_c_columns(d) != 256) return false;
     if ((d.H & 15) || (d.W & 15) || d.Cout != d.CoutPad || (d.Cout & 255)) return false;
     if (d.res && d.in_norm) return false;
+    if ((unsigned long long)(d.CoutPad >> 6) * (unsigned long long)(d.Kpad >> 6) * 15360ull >= (1ull << 32)) return false;      // weight records are addressed in 32 bits (WREC)
     return true;
 }
 
