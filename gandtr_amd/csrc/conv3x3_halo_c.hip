@@ -16,9 +16,8 @@
 //     operands, D[cout][pixel] = W . A^T;
 //   * FOUR waves, one per SIMD, 512 registers each (256 accumulator AGPRs + 256 VGPRs), laid out 1 x 4 in the 3x3 and stride-2 forms: every wave
 //     owns all 256 pixels x 64 output channels, so a weight fragment feeds 8 MFMAs (half the L1 weight bytes per MFMA of a 2 x 2 layout, twice its LDS
-//     fragment bytes); the transposed form and the 128-column tiles keep 2 x 2 waves (its phase-per-block map needs four blocks per wave); an
-//     experimental 1 x 8 layout -- two waves per SIMD at 256 registers, each 256 pixels x 32 channels -- exists behind GDT_C_WAVES=8 (same cycles,
-//     lower clock: off);
+//     fragment bytes); the transposed form and the 128-column tiles keep 2 x 2 waves (its phase-per-block map needs four blocks per wave); the
+//     128-column stride-2 form runs EIGHT waves, 2 x 4, two per SIMD at 256 registers;
 //   * the halo (18 x 18 per 64-channel chunk; 17 x 17 in the shift forms) is read as fp32 through registers, branch-free, one loader round in flight per
 //     thread, normalised / ReLU'd / residual-added in fp32 (the producer's InstanceNorm folded in: MODE bits 1 norm, 2 + residual, 4 + write-back of
 //     the transformed tensor), then split by v_cvt_pk_f16_f32 / v_fma_mix_f32 / v_cvt_scalef32_pk_fp4_*: fp16 hi plane (128-byte rows, XOR swizzle) and
@@ -51,8 +50,6 @@
 #ifndef GDT_C_ABL
 #define GDT_C_ABL 0
 #endif
-// transposed form: skip the all-zero (shift, phase) weight blocks under a run-time (wave-uniform) mask?  Measured: the branches around
-// the MFMAs of a one-wave-per-SIMD loop cost ~190 spilled registers; issuing the zero blocks (16/9 of the MFMAs) is faster.
 #ifndef GDT_C_DEPTH
 #define GDT_C_DEPTH 1           // loader rounds in flight per thread, 3x3 form (modes without / with residual + write-back)
 #endif
@@ -67,23 +64,6 @@
 #endif
 #ifndef GDT_C_DEPTH_SHIFT_RES
 #define GDT_C_DEPTH_SHIFT_RES 2
-#endif
-// cache policy of the streamed loads: bit 1 = weight fragments, bit 2 = halo pieces are fetched non-temporal (the line is not kept in the
-// CU's 32 KB L1: with two substeps of weights per wave in flight the outstanding lines alone fill it)
-#ifndef GDT_C_NT
-#define GDT_C_NT 0
-#endif
-#ifndef GDT_C_WB_INTERIOR
-#define GDT_C_WB_INTERIOR 0     // 1: write-back stores of the folded norm only for the patch's interior pixels (exec-masked stores)
-#endif
-#ifndef GDT_C_SCHED
-#define GDT_C_SCHED 2          // 1: loads after each column's MFMAs (clumped)   2: one load per two MFMAs (+0.3 % images/s)
-#endif
-#ifndef GDT_C_WSTAG
-#define GDT_C_WSTAG 0           // s_sleep units (64 cycles) of start offset between consecutive waves after each chunk barrier
-#endif
-#ifndef GDT_C_CT_SKIP
-#define GDT_C_CT_SKIP 1
 #endif
 
 namespace {
@@ -129,7 +109,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
     static_assert((TM == 4 || TM == 8) && (TN == 1 || TN == 2 || TN == 4) && TM * TN <= 16, "tile shape (128-row statistics records: one or two per wave)");
     constexpr int NWAVES = WGM * WGN;
     constexpr bool PIPE2 = NWAVES <= 4;             // two epilogue patches per wave
-    // TN == 1 (eight waves of 256 pixels x 32 channels, two per SIMD at 256 registers): an activation fragment feeds ONE MFMA, so the
+    // TN == 1 (eight waves of 128 pixels x 32 channels, two per SIMD at 256 registers): an activation fragment feeds ONE MFMA, so the
     // fragments rotate through a window of AW registers sets, each re-loaded AW MFMAs ahead of its use (TN >= 2: AW = TM, the fragment
     // of row block i is re-loaded in place for the next substep)
     constexpr int AW = TN == 1 ? 4 : TM;
@@ -195,12 +175,8 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
         Pend p;
         p.goff = (((unsigned)((ta.n * d.H + ry) * d.W + rx) << (d.lc8 + (S2 ? 3 : 5))) + cbyte);      // byte offset (< 2^32, checked on the host)
         p.ok = (h < HROWS) & (inb | refl);
-        auto ldh = [](const float4* q) -> float4 {
-            if constexpr ((GDT_C_NT & 2) != 0) { const f32x4 v = __builtin_nontemporal_load((const f32x4*)q); return make_float4(v[0], v[1], v[2], v[3]); }
-            else return *q;
-        };
-        p.r0 = ldh((const float4*)((const char*)inf + p.goff)); p.r1 = ldh((const float4*)((const char*)inf + p.goff + 16));
-        if (RES && !(GDT_C_ABL & 32)) { p.s0 = ldh((const float4*)((const char*)resf + p.goff)); p.s1 = ldh((const float4*)((const char*)resf + p.goff + 16)); }
+        p.r0 = *(const float4*)((const char*)inf + p.goff); p.r1 = *(const float4*)((const char*)inf + p.goff + 16);
+        if (RES && !(GDT_C_ABL & 32)) { p.s0 = *(const float4*)((const char*)resf + p.goff); p.s1 = *(const float4*)((const char*)resf + p.goff + 16); }
         return p;
     };
     float* nlds = (float*)(smem + 2 * STAGE_BYTES);
@@ -247,16 +223,8 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
         // write-back of the transformed tensor (every piece stores the value of its clamped source pixel: identical bits from
         // neighbouring patches, no branch)
         if (WB && !(GDT_C_ABL & 16)) {
-#if GDT_C_WB_INTERIOR
-            // only the patch's own 16 x 16 pixels: the halo ring belongs to the neighbours, who write identical bits (27 % of the stores)
-            if ((unsigned)(phy - 1) < 16u && (unsigned)(phx - 1) < 16u) {
-                *(float4*)((char*)wbf + p.goff) = make_float4(a[0], a[1], a[2], a[3]);
-                *(float4*)((char*)wbf + p.goff + 16) = make_float4(a[4], a[5], a[6], a[7]);
-            }
-#else
             *(float4*)((char*)wbf + p.goff) = make_float4(a[0], a[1], a[2], a[3]);
             *(float4*)((char*)wbf + p.goff + 16) = make_float4(a[4], a[5], a[6], a[7]);
-#endif
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] = p.ok ? a[e] : 0.f;
@@ -296,10 +264,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
     // RING substep slices and substep u re-loads the slot that substep u - 1 has just finished with (slice u + RING - 1); the MX
     // fragments of group g (32 k-values, MFMAs at the end of substep 2g + 1) are re-loaded with group g + 1 early in substep 2g + 2.
     // Each substep issues its loads row by row between its MFMAs.
-#ifndef GDT_C_RING
-#define GDT_C_RING 3
-#endif
-    constexpr int RING = SHIFT ? 4 : GDT_C_RING;
+    constexpr int RING = SHIFT ? 4 : 3;
     static_assert(SLOTS % RING == 0, "ring / buffer positions of a substep must not depend on the chunk");
     static_assert(TN == 4 || TN == 2 || TN == 1, "the weight streams are grouped per 128 output channels");
     const int wgrp_of_wave = (wn * WTN) >> 7, wblk = ((wn * WTN) >> 5) & 3;      // the wave's 128-column weight group within the tile, its first 32-column block in it
@@ -313,17 +278,16 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
         return v;
     };
     unsigned lo16 = lane_bytes(16), lo8 = lane_bytes(8), lo4 = lane_bytes(4);        // (refreshed at the top of every chunk body)
-    auto ldw = [](const auto* p) { if constexpr ((GDT_C_NT & 1) != 0) return __builtin_nontemporal_load(p); else return *p; };
     auto load_b = [&](int rs, int j, int tile_n, long ks) {       // ks: uniform k-substep index (16 k-values each)
         const char* wb = (const char*)d.w_cfrag + ((long)(tile_n * (BN / 128) + wgrp_of_wave) * nks + ks) * 4096;
-        b[rs][j] = ldw((const f16x8*)(wb + lo16 + (wblk + j) * 1024));
+        b[rs][j] = *(const f16x8*)(wb + lo16 + (wblk + j) * 1024);
     };
     auto load_bq = [&](int j, int tile_n, long ks) {     // MX fragment j of the 32-k group starting at substep ks (even)
         const long f0 = (long)(tile_n * (BN / 128) + wgrp_of_wave) * nms + (ks >> 1);
-        const v4i qa = ldw((const v4i*)((const char*)d.wmx_a + f0 * 4096 + lo16 + (wblk + j) * 1024));
-        const v2i qb = ldw((const v2i*)((const char*)d.wmx_b + f0 * 2048 + lo8 + (wblk + j) * 512));
+        const v4i qa = *(const v4i*)((const char*)d.wmx_a + f0 * 4096 + lo16 + (wblk + j) * 1024);
+        const v2i qb = *(const v2i*)((const char*)d.wmx_b + f0 * 2048 + lo8 + (wblk + j) * 512);
         bq[j] = __builtin_shufflevector(__builtin_shufflevector(qa, qa, 0, 1, 2, 3, -1, -1), __builtin_shufflevector(qb, qb, 0, 1, -1, -1, -1, -1), 0, 1, 2, 3, 6, 7);
-        bqs[j] = ldw((const int*)((const char*)d.wmx_s + f0 * 1024 + lo4 + (wblk + j) * 256));
+        bqs[j] = *(const int*)((const char*)d.wmx_s + f0 * 1024 + lo4 + (wblk + j) * 256);
     };
 
     // A fragment addresses (see conv3x3_halo_rb.hip); fp4 plane: per-lane base per tap column (+ tap row for CT) with the swizzle key
@@ -393,14 +357,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
 #pragma unroll
     for (int i = 0; i < AW; ++i) afr[i] = a_frag(i, 0, 0, 0);
 
-    // The four waves run the same code and leave every barrier together, so their vector-memory instructions reach the CU's one address
-    // unit in the same cycles and queue behind each other (measured: ~50 cycles of blocked issue per load, three of four waves waiting).
-    // Wave w idles w * GDT_C_WSTAG * 64 cycles after each chunk barrier: the load clusters of the waves no longer coincide.
-    auto wave_stagger = [&]() {
-#if GDT_C_WSTAG > 0
-        for (int k = 0; k < wave; ++k) __builtin_amdgcn_s_sleep(GDT_C_WSTAG);
-#endif
-    };
     int so = 0;                   // LDS offset of the halo stage of the current chunk (0 or STAGE_BYTES)
     int slot = 0;                 // (scale, shift) slot of the current tile
 #ifdef GDT_C_STAMP                 // diagnostic build (tools/build_variant.sh stamp): per-wave s_memtime totals, written to d.stamp_out only
@@ -439,7 +395,9 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
             // slices pair a cheap phase with an expensive one)
             // -- with gdt_ctc_column() column block j of EVERY wave is sub-pixel phase j of 32 output channels: the masks are
             // compile-time constants (phase 0: shift 0; 1: + dx; 2: + dy; 3: all four), the zero blocks cost neither MFMAs nor loads
-            auto ct_on = [](int t, int j) -> bool { return !CT || !GDT_C_CT_SKIP || (((0xF531u >> (4 * j)) >> t) & 1u) != 0; };
+            // (skipping them under a run-time, wave-uniform mask instead: the branches around the MFMAs of a one-wave-per-SIMD loop cost
+            //  ~190 spilled registers; issuing the zero blocks, 16/9 of the MFMAs, is faster than that)
+            auto ct_on = [](int t, int j) -> bool { return !CT || (((0xF531u >> (4 * j)) >> t) & 1u) != 0; };
             // tap of substep u (u >= SLOTS: the first substeps of the chunk staged now)
             auto t_of = [](int u) -> int { return u < SLOTS ? (u >> 2) : ((u - SLOTS) >> 2); };
             // (within the chunk: u < SLOTS; slices of the next chunk are always fetched -- its parity is another instantiation's business)
@@ -467,20 +425,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
 #pragma unroll
                         for (int j = 0; j < TN; ++j)
                             if (!(GDT_C_ABL & 8) && ct_on(t, j) && s2_on(t))
-#ifdef GDT_C_SHAPE16_TIMING      // timing only (results are wrong): the same FLOPs, operand loads and accumulator registers on the 16 x 16 x 32 shape
-                            {
-                                typedef float f32x4_ __attribute__((ext_vector_type(4)));
-#pragma unroll
-                                for (int qq = 0; qq < 2; ++qq) {
-                                    const int q4 = 4 * (2 * (u & 1) + qq);
-                                    f32x4_ tq = {acc[i][j][q4], acc[i][j][q4 + 1], acc[i][j][q4 + 2], acc[i][j][q4 + 3]};
-                                    tq = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[u % RING][j], afr[i % AW], tq, 0, 0, 0);
-                                    acc[i][j][q4] = tq[0]; acc[i][j][q4 + 1] = tq[1]; acc[i][j][q4 + 2] = tq[2]; acc[i][j][q4 + 3] = tq[3];
-                                }
-                            }
-#else
                                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b[u % RING][j], afr[i % AW], acc[i][j], 0, 0, 0);     // D[cout][pixel]
-#endif
                         // this row's share of the substep's loads: column i of the ring slot substep u - 1 has finished with, (even
                         // substeps) the fp4 fragment and column i of the MX weights two groups ahead
                         if (!(GDT_C_ABL & 4) && i < TN && ct_on(t_of(u + RING - 1), i) && s2_on_u(u + RING - 1)) load_b((u + RING - 1) % RING, i, tn_of(u + RING - 1), ks_of(u + RING - 1));
@@ -504,26 +449,13 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
                             const int a_scale = ae[i % AW] + a_scale_off;
 #pragma unroll
                             for (int j = 0; j < TN; ++j)
-                                if (ct_on(t, j) && s2_on(t)) {
-#ifdef GDT_C_SHAPE16_TIMING
-                                    typedef float f32x4_ __attribute__((ext_vector_type(4)));
-#pragma unroll
-                                    for (int qq = 0; qq < 2; ++qq) {
-                                        const int q4 = 4 * (2 * ((u >> 1) & 1) + qq);
-                                        f32x4_ tq = {acc[i][j][q4], acc[i][j][q4 + 1], acc[i][j][q4 + 2], acc[i][j][q4 + 3]};
-                                        tq = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(__builtin_shufflevector(bq[j], bq[j], 0, 1, 2, 3, 4, 5, -1, -1), av, tq, 2, 4, 0, bqs[j], 0, a_scale);
-                                        acc[i][j][q4] = tq[0]; acc[i][j][q4 + 1] = tq[1]; acc[i][j][q4 + 2] = tq[2]; acc[i][j][q4 + 3] = tq[3];
-                                    }
-#else
+                                if (ct_on(t, j) && s2_on(t))
                                     acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(__builtin_shufflevector(bq[j], bq[j], 0, 1, 2, 3, 4, 5, -1, -1), av, acc[i][j], 2, 4, 0, bqs[j], 0, a_scale);
-#endif
-                                }
                             if (!(GDT_C_ABL & 64) && i + AW < TM && s2_ld(t)) { aq[i % AW] = a_qfrag(i + AW, ty, tx, kk >> 1); ae[i % AW] = a_efrag(i + AW, ty, tx); }      // (AW < TM)
                         }
                     }
                     // in-order issue: lay the substep out as MFMA, a few VALU (the halo staging), MFMA, ... with the memory operations
                     // of a column behind its MFMAs
-#if GDT_C_SCHED == 2
                     // one vector-memory instruction at a time: the L2 -> CU path takes ~1 KB per 30 cycles; a clump of loads backs
                     // the address unit up and the in-order wave cannot issue its next MFMA until the last of them is accepted
 #pragma unroll
@@ -545,29 +477,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
                             if ((m & 3) == 3) __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
                         }
                     }
-#elif !defined(GDT_C_NOSCHED)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-#pragma unroll
-                        for (int i = 0; i < TM; ++i) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // 1 MFMA
-                            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);      // VALU
-                        }
-                        if (cu == 0 && j < 2) { __builtin_amdgcn_sched_group_barrier(0x020, 5, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); }   // global loads, LDS reads
-                        else if (cu == 0) { __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); }
-                        else { __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-                        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);      // LDS write
-                        __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);      // global store
-                    }
-                    if (cu == 1) {
-#pragma unroll
-                        for (int m = 0; m < TM * TN; ++m) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                        }
-                    }
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -576,7 +485,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv3x3_halo_c_kernel(const Co
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                wave_stagger();
                 GDT_STAMP(st_cbar)
                 flip_stage(STAGE_BYTES - 2 * so);
                 so = STAGE_BYTES - so;
@@ -824,32 +732,28 @@ GDT_KNOB_LATCHED(knob_narrow_below, "GDT_C_NARROW_BELOW", 192)
 GDT_KNOB_LATCHED(knob_rb_dbg, "GDT_RB_DBG", 0)               // timing-only ablation, the 3x3 form
 GDT_KNOB_LATCHED(knob_c_dbg, "GDT_C_DBG", 0)                 // ... the transposed and stride-2 forms: 4 skips the epilogue
 GDT_KNOB_LATCHED(knob_stagger_us, "GDT_C_STAGGER_US", 0)
-GDT_KNOB_LATCHED(knob_tall, "GDT_C_TALL", 1)                 // 0: the 2 x 2 wave layout
-GDT_KNOB_LATCHED(knob_waves, "GDT_C_WAVES", 0)               // 8: the 1 x 8 layout, two waves per SIMD
 GDT_KNOB_LATCHED(knob_s2_waves, "GDT_C_S2_WAVES", 8)         // two waves per SIMD (2 x 4): 0.55 -> 0.51 ms; 4: back to four
-GDT_KNOB_LATCHED(knob_tall_s2, "GDT_C_TALL_S2", 1)           // 0: the 2 x 2 wave layout
 
-// Four waves, one per SIMD (512 registers each: 256 accumulator AGPRs + 256 VGPRs).  TALL = false: 2 x 2 waves of 128 pixels x 128
-// channels; TALL = true: 1 x 4 waves of 256 pixels x 64 channels -- every wave reads all 256 pixels' fragments from LDS (twice the
-// LDS bytes per MFMA) and streams a quarter of the weights from L1 (half the L1 bytes per MFMA: the L1 weight stream is the scarcer
-// of the two, ~60 % of its bandwidth in the square shape).  Measured on the resblock conv: 0.422 -> 0.408 ms plain, 0.518 -> 0.485
-// with the residual + write-back staging.  (An eight-wave form, two waves of 128 x 64 per SIMD at 256 registers, runs its fp16
-// core faster -- 0.185 vs 0.243 ms -- but pays 0.09 ms for the weight stream and 0.07 for the staging: 0.443 ms complete.)
-// BN_ = 128 (output channel counts that are not a multiple of 256: the 64 -> 128 stride-2 layer): 2 x 2 waves of 128 pixels x 64 channels.
-// W8 (with TALL): eight waves, two per SIMD at 256 registers each, 1 x 8: every wave owns all 256 pixels x 32 channels.  The same
-// weight bytes per MFMA as 1 x 4 (a weight fragment still feeds 8 MFMAs), twice its LDS fragment bytes (an activation fragment feeds one
-// MFMA); what it buys is a second wave per SIMD: while one waits -- for a weight fragment behind older halo loads (vmcnt retires in
-// order), for an LDS fragment, at the address unit -- the other issues.
-// W8 with BN_ = 128 (the 64 -> 128 stride-2 layer): eight waves as 2 x 4, a wave = 128 pixels x 32 channels.  That layer has little matrix work per halo byte and its
-// four-wave form spends a tile adding up what ONE wave per SIMD must issue in order: staging arithmetic, loads, fragment reads, MFMAs.
+// Four waves, one per SIMD (512 registers each: 256 accumulator AGPRs + 256 VGPRs).  TALL = true (the 256-column 3x3 and stride-2
+// forms): 1 x 4 waves of 256 pixels x 64 channels -- every wave reads all 256 pixels' fragments from LDS (twice the LDS bytes per MFMA of
+// a 2 x 2 layout) and streams a quarter of the weights from L1 (half the L1 bytes per MFMA: the L1 weight stream is the scarcer of the
+// two, ~60 % of its bandwidth in the square shape).  Measured on the resblock conv against 2 x 2: 0.422 -> 0.408 ms plain, 0.518 -> 0.485
+// with the residual + write-back staging.  TALL = false: 2 x 2 waves -- the transposed form (128 pixels x 128 channels: its phase-per-block
+// map needs four blocks per wave) and BN_ = 128 (128 pixels x 64 channels: few patches, and output channel counts that are not a
+// multiple of 256, the 64 -> 128 stride-2 layer).
+// W8 (BN_ = 128, stride-2, MODE 1 only): eight waves as 2 x 4, two per SIMD at 256 registers, a wave = 128 pixels x 32 channels.  That layer
+// has little matrix work per halo byte and its four-wave form spends a tile adding up what ONE wave per SIMD must issue in order: staging
+// arithmetic, loads, fragment reads, MFMAs; with a second wave per SIMD one issues while the other waits.
+// (The 2 x 2 layout of the 256-column 3x3 and stride-2 forms and a 1 x 8 eight-wave 3x3 form -- same cycles, lower clock -- were measured
+// and removed; commit `2b4e7c4` holds them.)
 template <int MODE, int FORM = 0, bool TALL = false, int BN_ = 256, bool W8 = false>
 int launch_c(const ConvLaunch& d, hipStream_t stream) {
-    constexpr int BN = BN_, WGM = TALL ? 1 : 2, WGN = TALL ? (W8 ? 8 : 4) : (W8 ? 4 : 2);
+    constexpr int BN = BN_, WGM = TALL ? 1 : 2, WGN = TALL ? 4 : (W8 ? 4 : 2);
     constexpr size_t LDS_BYTES = lds_bytes(WGM * WGN);
-    static_assert(BN == 256 || (BN == 128 && !TALL), "tile width");
+    static_assert(BN == 256 ? TALL == (FORM != 1) : (BN == 128 && !TALL && FORM != 1), "256 columns: 1 x 4 waves (transposed form: 2 x 2); 128 columns: 2 x 2");
     // (the transposed form's compile-time skipping of zero weight blocks assumes that a wave's column blocks ARE the four sub-pixel phases, i.e. four blocks per wave:
     //  with 2 x 4 waves the phases of a wave depend on its column -- not instantiated; the 256-column stride-2 form spills at 256 registers: 0.35 -> 0.61 ms)
-    static_assert(!W8 || (TALL && FORM == 0) || (!TALL && MODE == 1 && FORM == 2 && BN == 128), "the eight-wave layouts: 1 x 8 for the 3x3 form; 2 x 4 for the 128-column stride-2 form");
+    static_assert(!W8 || (MODE == 1 && FORM == 2 && BN == 128), "the eight-wave layout: 2 x 4, the 128-column stride-2 form");
     const int gh = FORM == 2 ? d.OH : d.H, gw = FORM == 2 ? d.OW : d.W;
     using K = GdtKernel<conv3x3_halo_c_kernel<BN, WGM, WGN, MODE, FORM>, (int)LDS_BYTES>;
     int cus = 0;
@@ -882,19 +786,19 @@ int launch_c(const ConvLaunch& d, hipStream_t stream) {
 }
 
 // the fold modes this file instantiates -- 3x3 form (FORM 0): all five; transposed (1): no write-back; stride-2 (2): no residual
-template <int FORM, bool TALL = false, int BN = 256, bool W8 = false>
+template <int FORM, bool TALL = false, int BN = 256>
 int launch_c_fold(const ConvLaunch& d, hipStream_t stream) {
     const int mode = gdt_fold_mode(d);
-    if (mode == 0) return launch_c<0, FORM, TALL, BN, W8>(d, stream);
-    if (mode == 1) return launch_c<1, FORM, TALL, BN, W8>(d, stream);
+    if (mode == 0) return launch_c<0, FORM, TALL, BN>(d, stream);
+    if (mode == 1) return launch_c<1, FORM, TALL, BN>(d, stream);
     if constexpr (FORM != 2) {
-        if (mode == 3) return launch_c<3, FORM, TALL, BN, W8>(d, stream);
+        if (mode == 3) return launch_c<3, FORM, TALL, BN>(d, stream);
     }
     if constexpr (FORM != 1) {
-        if (mode == 5) return launch_c<5, FORM, TALL, BN, W8>(d, stream);
+        if (mode == 5) return launch_c<5, FORM, TALL, BN>(d, stream);
     }
     if constexpr (FORM == 0) {
-        if (mode == 7) return launch_c<7, FORM, TALL, BN, W8>(d, stream);
+        if (mode == 7) return launch_c<7, FORM, TALL, BN>(d, stream);
     }
     return gdt_fold_refused(mode);
 }
@@ -932,13 +836,8 @@ int gdt_launch_conv_halo_c(const ConvLaunch& d_in, hipStream_t stream) {
     ConvLaunch d = d_in;
     d.dbg = knob_rb_dbg();
     d.stagger_us = knob_stagger_us();
-#ifdef GDT_C_DEV_W8_ONLY      // dev builds (resource reports, asm): only the eight-wave instantiations are compiled
-    return launch_c_fold<0, true, 256, true>(d, stream);
-#else
     if (gdt_conv_halo_c_columns(d) == 128) return launch_c_fold<0, false, 128>(d, stream);
-    if (knob_tall() && knob_waves() == 8) return launch_c_fold<0, true, 256, true>(d, stream);
-    return knob_tall() ? launch_c_fold<0, true>(d, stream) : launch_c_fold<0>(d, stream);
-#endif
+    return launch_c_fold<0, true>(d, stream);
 }
 
 // Transposed form (CT): ConvTranspose2d(k3,s2,p1,op1) as one launch (phase_cout > 0, weights of Op::ctf packed by pack_mx), 64 or 128
@@ -956,13 +855,9 @@ bool gdt_conv_halo_c_ct_eligible(const ConvLaunch& d) {
 }
 
 int gdt_launch_conv_halo_c_ct(const ConvLaunch& d_in, hipStream_t stream) {
-#ifdef GDT_C_DEV_W8_ONLY
-    return GDT_ERR_INVALID;
-#else
     ConvLaunch d = d_in;
     d.dbg = knob_c_dbg();
     return launch_c_fold<1>(d, stream);
-#endif
 }
 
 // Stride-2 form (S2): Conv2d(k3, s2, p1, zero padding) over the virtual space-to-depth view of its input.  The launch descriptor carries
@@ -981,15 +876,11 @@ bool gdt_conv_halo_c_s2_eligible(const ConvLaunch& d) {
 }
 
 int gdt_launch_conv_halo_c_s2(const ConvLaunch& d_in, hipStream_t stream) {
-#ifdef GDT_C_DEV_W8_ONLY
-    return GDT_ERR_INVALID;
-#else
     ConvLaunch d = d_in;
     d.dbg = knob_c_dbg();
     if (d.CoutPad % 256 != 0) {
         if (knob_s2_waves() == 8 && gdt_fold_mode(d) == GDT_FOLD_NORM) return launch_c<1, 2, false, 128, true>(d, stream);      // (the only eight-wave instantiation of this form)
         return launch_c_fold<2, false, 128>(d, stream);
     }
-    return knob_tall_s2() ? launch_c_fold<2, true>(d, stream) : launch_c_fold<2>(d, stream);
-#endif
+    return launch_c_fold<2, true>(d, stream);
 }

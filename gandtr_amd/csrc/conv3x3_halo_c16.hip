@@ -38,19 +38,6 @@
 #endif
 #include "conv_device.h"
 
-#ifndef GDT_C16_SCHED
-#define GDT_C16_SCHED 2         // layout of the chunk body (the kernel comment "PHASES"): 1 = per patch row (four MFMAs, then the row's companion work in
-#endif                          // one piece), 2 = per MFMA (behind each MFMA at most about three instructions of it)
-static_assert(GDT_C16_SCHED == 1 || GDT_C16_SCHED == 2, "GDT_C16_SCHED: 1 (row layout) or 2 (per-MFMA layout)");
-#ifndef GDT_C16_RING
-#define GDT_C16_RING 3
-#endif
-#ifndef GDT_C16_FULL_LINES
-#define GDT_C16_FULL_LINES 1    // epilogue: pixel halves exchange a channel block (DPP row_ror:8) so that every store instruction writes whole 128-byte lines
-#endif
-#ifndef GDT_C16_BQ_SETS
-#define GDT_C16_BQ_SETS 1       // register sets of the MX weights: 2 = the set of tap t + 1 is fetched during tap t (measured: no faster -- the weight stream is
-#endif                          // throughput-, not latency-bound -- and 28 registers that the second halo round in flight needs more)
 #ifndef GDT_C16_ABL
 #define GDT_C16_ABL 0           // timing-only ablations: 1 no halo staging   2 no MX MFMAs / loads   4 no fp16 weight re-loads   8 no fp4 fragment re-loads   16 no MX weight re-loads   64 MX weights fetched into an unused set   128 every weight fetch from one hot 7 KB window   256 no output stores
 #endif
@@ -81,19 +68,12 @@ static_assert((NR + SDIST) * SPR <= SLOTS, "halo rounds are spread over the slot
 // around every MFMA (first build: 1580 v_accvgpr_read + 1520 v_accvgpr_write + 250 scratch operations per chunk).  Operands arrive from LDS /
 // global loads (the compiler's s_waitcnt covers asm operands); the accumulators are read by VALU only behind the tile-end barrier, far
 // beyond the MFMA -> VALU wait states nothing pads inside asm.
+// Volatile and with a memory clobber: each keeps its place between the sched_barrier fences, ahead of the (volatile) pins of the work laid
+// behind it and ahead of the loads and LDS reads laid behind it.
 __device__ __forceinline__ void mfma16(f32x4& acc, const f16x8& a, const f16x8& b) {
-    asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma16_mx(f32x4& acc, const v6i& a6, const v4i& b4, int sa, int sb) {      // A: 32 e2m3 values per lane, B: 32 e2m1
-    asm("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:2 blgp:4" : "+a"(acc) : "v"(a6), "v"(b4), "v"(sa), "v"(sb));
-}
-
-// ... of layout 2, volatile and with a memory clobber: each keeps its place between the sched_barrier fences, ahead of the (volatile) pins of the
-// work laid behind it and ahead of the loads and LDS reads laid behind it
-__device__ __forceinline__ void mfma16_at(f32x4& acc, const f16x8& a, const f16x8& b) {
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b) : "memory");
 }
-__device__ __forceinline__ void mfma16_mx_at(f32x4& acc, const v6i& a6, const v4i& b4, int sa, int sb) {
+__device__ __forceinline__ void mfma16_mx(f32x4& acc, const v6i& a6, const v4i& b4, int sa, int sb) {      // A: 32 e2m3 values per lane, B: 32 e2m1
     asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:2 blgp:4" : "+a"(acc) : "v"(a6), "v"(b4), "v"(sa), "v"(sb) : "memory");
 }
 // max(|a|, |b|, |c|) / max(|a|, |b|) in one instruction each (the C expression canonicalises every pinned input first: two instructions more per
@@ -114,7 +94,7 @@ __device__ __forceinline__ float gdt_max_abs(float a, float b) {
 template <int MODE>
 __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d, const int vblocks) {
     constexpr bool NORM = (MODE & 1) != 0, RES = (MODE & 2) != 0, WB = (MODE & 4) != 0;
-    constexpr int RING = GDT_C16_RING;
+    constexpr int RING = 3;                  // ring of fp16 weight fragments: half-step u + RING - 1 is fetched during half-step u
     static_assert(18 % RING == 0, "ring slot of a half-step must not depend on the chunk");
     constexpr int AW = 8, QW = 4;            // activation fragment windows (fp16 plane / fp4 plane): register sets re-loaded AW / QW pixel blocks ahead
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -155,28 +135,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
         if (RES) { p.s0 = *(const float4*)((const char*)resf + p.goff); p.s1 = *(const float4*)((const char*)resf + p.goff + 16); }
         return p;
     };
-    // ... one load instruction per call (main loop): part 0 computes the address and fetches the first 16 bytes
-    Pend pendv[SDIST];
-    auto load_piece_part = [&](const GdtPatch& ta, int chunk, int r, int part) {
-        Pend& pend = pendv[r % SDIST];
-        if (part == 0) {
-            int lr = lrow;
-            asm volatile("" : "+v"(lr));
-            const int h = min(r * RPR + lr, HROWS_PAD - 1);
-            int hy, hx;
-            gdt_halo_yx<HW_>(h, hy, hx);
-            const int iy = ta.y0 - 1 + hy, ix = ta.x0 - 1 + hx;
-            int ry, rx;
-            GDT_REFLECT_CLAMP(iy, ix, d.H, d.W, ry, rx)
-            const bool inb = ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);
-            pend.goff = (((unsigned)((ta.n * d.H + ry) * d.W + rx) << (d.lc8 + 5)) + (chunk * 8 + (lane & 7)) * 32);
-            pend.ok = (h < HROWS) & (inb | refl);
-            pend.r0 = *(const float4*)((const char*)inf + pend.goff);
-        }
-        if (part == 1) pend.r1 = *(const float4*)((const char*)inf + pend.goff + 16);
-        if (RES && part == 2) pend.s0 = *(const float4*)((const char*)resf + pend.goff);
-        if (RES && part == 3) pend.s1 = *(const float4*)((const char*)resf + pend.goff + 16);
-    };
+    Pend pendv[SDIST];            // main loop: the rounds in flight
     float* nlds = (float*)(smem + 2 * STAGE_BYTES);
     auto stage_norm = [&](const GdtPatch& ta, int slot) {
         gdt_stage_norm(nlds, slot, d.in_norm, d.Cin, ta.n, tid, NT);
@@ -232,89 +191,26 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
         smem[E_OFF + (stage_off ? HROWS_PAD : 0) + row] = (char)(127 + ex - 13);      // (the row's 8 lanes store the same byte)
     };
 
-    // The same work in PHASES for the main loop: the MFMAs there are inline asm, which the compiler neither schedules around nor sees as long
-    // operations -- left alone it sinks every LDS read to just in front of its MFMA and runs the ~100 staging instructions of a round in one
-    // piece.  So the loop body is laid out by hand, fenced by sched_barrier, in one of two layouts (GDT_C16_SCHED):
-    //   1  per patch row: the row's four MFMAs back to back, then its fragment read, its weight load and one of 14 phases of the staging; a
-    //      round's store (phases 0-9) and the next round's load (10-13) share ONE slot of 16 patch rows, every second slot.  With one wave per
-    //      SIMD and in-order issue the second to fourth MFMA of a row each wait ~12 cycles for the pipe with nothing to issue, and only the
-    //      fourth one's shadow covers the row's work, which is 9-41 instructions (tools/mfma_gaps.py: a quarter of the chunk's non-MFMA issue
-    //      cycles sit under an MFMA, 5.4-6.1 k cycles per chunk do not);
-    //   2  per MFMA: behind the row's first MFMA its vector-memory instruction (a weight load), behind the second and third one MICRO-PHASE
-    //      of the staging each (stage_micro: <= 3 VALU instructions, or one load / store / LDS write), behind the fourth its LDS reads (the
-    //      window slot they refill is read by all four MFMAs).  A round spreads over both slots of its pair: 64 micro-phase positions, of
-    //      which a round uses 47-57; no gap holds 12 instructions, 0.5-0.7 k issue cycles per chunk stay uncovered (tests/test_c16_layout_cpu.py).
-    // Both issue the same MFMAs into every accumulator in the same order (the output is the same bit for bit), a step's weights ahead of the halo
-    // loads consumed after them, a round's loads SDIST rounds ahead of its store and its LDS writes ahead of the chunk barrier.  Measured:
-    // DESIGN.md section 4, "per-MFMA layout".
+    // The same work in MICRO-PHASES for the main loop: the MFMAs there are inline asm, which the compiler neither schedules around nor sees as
+    // long operations -- left alone it sinks every LDS read to just in front of its MFMA and runs the ~100 staging instructions of a round in one
+    // piece.  So the loop body is laid out by hand, per MFMA, fenced by sched_barrier: with one wave per SIMD and in-order issue every MFMA
+    // but the first of a patch row waits ~12 cycles for the pipe with nothing to issue, so each of the row's four gets a little work behind it:
+    // the first the row's vector-memory instruction (a weight load), the second and third one micro-phase of the staging each (stage_micro:
+    // <= 3 VALU instructions, or one load / store / LDS write), the fourth the row's LDS reads (the window slot they refill is read by all
+    // four MFMAs).  A round spreads over both slots of its pair: 64 micro-phase positions, position mp = 2 * (row of the pair) + g, of which
+    // a round uses 47-57; no gap holds 12 instructions, 0.5-0.7 k issue cycles per chunk stay uncovered (tests/test_c16_layout_cpu.py).  A step's
+    // weights are loaded ahead of the halo loads consumed after them, a round's loads SDIST rounds ahead of its store, its LDS writes ahead
+    // of the chunk barrier.  Predecessor: the row layout (a row's four MFMAs back to back, then its companion work in one piece; 5.4-6.1 k
+    // cycles per chunk uncovered, the same output bit for bit); commit `2b4e7c4` holds it.  Measured: DESIGN.md section 4, "per-MFMA layout".
+    // Every micro-phase pins its inputs AND its results (empty asm volatile), so that its instructions stay between the two sched_barrier
+    // fences around it: pure VALU instructions carry no ordering against the fences when the block is linearised, and the compiler otherwise
+    // runs the normalisation right behind the loads -- with the wait for them.  The arithmetic is store_piece's, value for value; what differs
+    // is integer bookkeeping with the same result: the scale exponent is carried biased (e + 127), and the reflected coordinate is
+    // min(|i|, 2 (H - 1) - |i|) -- |i| reflects i = -1, the other operand i >= H, in bounds the minimum is i itself -- clamped like before.
     float sa[8];
     unsigned sou[4], sqlo = 0, sqhi = 0;
-    int sex = 0;                      // the pixel's scale exponent (gdt_c_pixel_exp) and the converts' scales
+    int sex = 0;                      // the pixel's scale exponent (gdt_c_pixel_exp), biased, and the converts' scales
     float slo_scale = 1.f, shi_scale = 1.f;
-    auto stage_phase = [&](const GdtPatch& ta, int chunk, int stage_off, int sl, int ph) {
-        if ((GDT_C16_ABL & 1) || sl % SPR != 0) return;
-        const int r = sl / SPR;
-        const bool st = r >= SDIST && r - SDIST < NR, ld = r < NR;
-        Pend& pend = pendv[r % SDIST];      // (the round stored now and the round loaded behind it share a buffer)
-        // (an empty asm volatile on a phase's inputs pins its arithmetic to the phase: pure VALU instructions carry no ordering against the
-        //  sched_barrier fences when the block is linearised, and the compiler otherwise runs the normalisation right behind the loads -- with
-        //  the wait for them)
-#define GDT_PIN4(v) asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w))
-#define GDT_PIN8(a) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]))
-        if (st && ph == 0) {
-            GDT_PIN4(pend.r0); GDT_PIN4(pend.r1);
-            sa[0] = pend.r0.x; sa[1] = pend.r0.y; sa[2] = pend.r0.z; sa[3] = pend.r0.w; sa[4] = pend.r1.x; sa[5] = pend.r1.y; sa[6] = pend.r1.z; sa[7] = pend.r1.w;
-        }
-        if (st && ph >= 1 && ph <= 9) GDT_PIN8(sa);
-        if (st && NORM && (ph == 0 || ph == 1)) {
-            const float lo = d.in_relu ? 0.f : -3.0e38f;
-#pragma unroll
-            for (int k = 2 * ph; k < 2 * ph + 2; ++k) {
-                const float4 v = nf[k];
-                sa[2 * k] = fmaxf(fmaf(sa[2 * k], v.x, v.y), lo);
-                sa[2 * k + 1] = fmaxf(fmaf(sa[2 * k + 1], v.z, v.w), lo);
-            }
-        }
-        if (st && NORM && RES && ph == 2) {
-            GDT_PIN4(pend.s0); GDT_PIN4(pend.s1);
-            sa[0] += pend.s0.x; sa[1] += pend.s0.y; sa[2] += pend.s0.z; sa[3] += pend.s0.w;
-            sa[4] += pend.s1.x; sa[5] += pend.s1.y; sa[6] += pend.s1.z; sa[7] += pend.s1.w;
-        }
-        if (st && WB && ph == 3) *(float4*)((char*)wbf + pend.goff) = make_float4(sa[0], sa[1], sa[2], sa[3]);
-        if (st && WB && ph == 4) *(float4*)((char*)wbf + pend.goff + 16) = make_float4(sa[4], sa[5], sa[6], sa[7]);
-        if (st && ph == 4) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) sa[e] = pend.ok ? sa[e] : 0.f;
-            sqlo = 0; sqhi = 0;
-            sex = gdt_c_pixel_exp(sa);
-            slo_scale = gdt_exp2i(sex - 13); shi_scale = gdt_exp2i(sex - 2);
-        }
-        if (st && ph == 5) gdt_c_split<0>(sa[0], sa[1], slo_scale, shi_scale, sou[0], sqlo, sqhi);
-        if (st && ph == 6) gdt_c_split<1>(sa[2], sa[3], slo_scale, shi_scale, sou[1], sqlo, sqhi);
-        if (st && ph == 7) gdt_c_split<2>(sa[4], sa[5], slo_scale, shi_scale, sou[2], sqlo, sqhi);
-        if (st && ph == 8) gdt_c_split<3>(sa[6], sa[7], slo_scale, shi_scale, sou[3], sqlo, sqhi);
-        if (st && ph == 9) {
-            const int row = min((r - SDIST) * RPR + lrow, HROWS_PAD - 1);
-            int phy, phx;
-            gdt_halo_yx<HW_>(row, phy, phx);
-            const u32x4 ov = {sou[0], sou[1], sou[2], sou[3]};
-            const int q = lane & 7;
-            *(f16x8*)(smem + stage_off + row * ROWB + ((q ^ ((phx >> 1) & 7)) << 4)) = __builtin_bit_cast(f16x8, ov);
-            const int key2 = (phx >> 2) & 3;
-            const int qo = stage_off + A_BYTES + row * QROWB + ((((q >> 2) << 1) ^ key2) << 4) + ((q & 3) << 2);
-            *(unsigned*)(smem + qo) = sqlo;
-            *(unsigned*)(smem + (qo ^ 16)) = sqhi;
-            smem[E_OFF + (stage_off ? HROWS_PAD : 0) + row] = (char)(127 + sex - 13);
-        }
-        if (ld && ph >= 10 && ph <= 13) load_piece_part(ta, chunk, r, ph - 10);
-#undef GDT_PIN4
-#undef GDT_PIN8
-    };
-    // Layout 2: the same work in MICRO-PHASES, two per patch row (behind the row's second and third MFMA) over the 32 rows of the round's slot
-    // pair; position mp = 2 * (row of the pair) + g.  Every micro-phase pins its inputs AND its results (empty asm volatile), so that its
-    // instructions stay between the two sched_barrier fences around it.  The arithmetic is store_piece's, value for value; what differs is
-    // integer bookkeeping with the same result: the scale exponent is carried biased (e + 127), and the reflected coordinate is
-    // min(|i|, 2 (H - 1) - |i|) -- |i| reflects i = -1, the other operand i >= H, in bounds the minimum is i itself -- clamped like before.
     int mh = 0, mt = 0, my = 0, mx = 0, ma = 0, mb = 0;      // load side: halo row, its coordinates
     int wrow = 0, wx = 0, wa = 0, wq = 0;                    // store side: LDS addresses
     float mu = 0.f, ml0 = 0.f, ml1 = 0.f;
@@ -490,7 +386,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
             GDT_PIN2(wrow, sex);
             smem[wes + wrow] = (char)(sex - 13);      // (the row's 8 lanes store the same byte)
         }
-        // ---- the round loaded now: load_piece_part's address in pieces, then one load per micro-phase
+        // ---- the round loaded now: load_piece's address in pieces, then one load per micro-phase
         if (ld && mp == P_GADDR) {
             int lr = lrow;
             GDT_PIN1(lr);
@@ -546,7 +442,6 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
 #undef GDT_PIN3
 #undef GDT_PIN4
     };
-    (void)stage_phase; (void)stage_micro;       // (one of them per layout)
 
     // ---- weights, streamed L2 -> registers in fragment order (net_build.hip pack_mx16): per 64 output channels (a wave's slice)
     //   w_c16 [cout/64][K/32][4 blocks][64 lanes][16 B]: lane (n, g) = W[cout block * 16 + n][k = 32 step + 8 g ..+7]
@@ -555,13 +450,12 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     auto wgrp = [&](int tile_n) -> long { return (long)tile_n * 4 + wave; };
     const int nms = d.Kpad >> 6, cin64 = d.Cin >> 6;
     f16x8 bw[RING][4];
-    // two sets, used by alternate taps: the set of tap t + 1 is fetched during tap t (its second half-step and its MX run: >= 3000 cycles before the
-    // first use).  With one set the loads can only follow the previous tap's MX run, 1000-2000 cycles ahead of their own -- and the weights come
-    // from beyond L2 (the activation stream evicts them): every MX run started with a ~440-cycle wait, 16 k cycles per tile (stamped ablations).
-    // Tap 0 of a chunk (its set is still in use by tap 8 of the previous chunk: 9 taps, two sets) is fetched in its own first half-step.
-    constexpr int BQS = GDT_C16_BQ_SETS;
-    v6i bq[BQS + ((GDT_C16_ABL & 64) ? 1 : 0)][4];            // (extra set: ablation 64 only)
-    v4i bqs[BQS + ((GDT_C16_ABL & 64) ? 1 : 0)];              // E8M0 scales of the four channel blocks (one dwordx4 per lane)
+    // MX weights: ONE register set, fetched behind the previous tap's MX run (a second set, fetched a tap ahead, measured no faster -- the weight
+    // stream is throughput-, not latency-bound -- and costs 28 registers that the second halo round in flight needs more).  Ablation 64 adds a
+    // set that nothing loads in the loop and lets the MFMAs read that one.
+    constexpr int BQ_MFMA = (GDT_C16_ABL & 64) ? 1 : 0;        // the set the MX MFMAs read
+    v6i bq[1 + BQ_MFMA][4];
+    v4i bqs[1 + BQ_MFMA];                                      // E8M0 scales of the four channel blocks (one dwordx4 per lane)
     auto lane_bytes = [&](int per_lane) -> unsigned {
         unsigned v = lane * per_lane;
         asm volatile("" : "+v"(v));
@@ -572,12 +466,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     // [scales: 1 KB] -- a wave's whole weight stream is one sequential region
     constexpr long WREC = 15360;
     auto load_bw = [&](int rs, int cb, int tile_n, long ks) {        // ks: uniform index of the 32-k step
-        if (GDT_C16_SCHED == 2) {       // (the record's offset in 32 bits -- gdt_conv_halo_c16_eligible -- : half the scalar address work)
-            const char* wb = (const char*)d.w_c16 + (unsigned)(((tile_n * 4 + wave) * nms + (int)(ks >> 1)) * (int)WREC + (int)(ks & 1) * 4096);
-            bw[rs][cb] = *(const f16x8*)(wb + lo16 + cb * 1024);
-            return;
-        }
-        const char* wb = (const char*)d.w_c16 + (wgrp(tile_n) * nms + (ks >> 1)) * WREC + (ks & 1) * 4096;
+        // (the record's offset in 32 bits -- gdt_conv_halo_c16_eligible -- : half the scalar address work)
+        const char* wb = (const char*)d.w_c16 + (unsigned)(((tile_n * 4 + wave) * nms + (int)(ks >> 1)) * (int)WREC + (int)(ks & 1) * 4096);
         bw[rs][cb] = *(const f16x8*)(wb + lo16 + cb * 1024);
     };
     // MX weights of a (tap, chunk): nine loads, ONE per patch row of MFMAs (a vector-memory instruction takes the wave ~16-20 issue cycles, a patch
@@ -585,7 +475,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     // operand tuple, 2 cb + 1 = its last 8 (both loaded INTO the tuple), part 8 = the four blocks' scales
     auto load_bq_part = [&](int set, int part, int tile_n, long ms) {          // ms: uniform index of the 64-k group
         const long f0 = (GDT_C16_ABL & 128) ? 0 : wgrp(tile_n) * nms + ms;      // (ablation 128: every fetch from the same 7 KB)
-        const char* rec = GDT_C16_SCHED == 2 ? (const char*)d.w_c16 + (unsigned)((int)f0 * (int)WREC) : (const char*)d.w_c16 + f0 * WREC;
+        const char* rec = (const char*)d.w_c16 + (unsigned)((int)f0 * (int)WREC);
         const int cb = part >> 1;
         if (part == 8) bqs[set] = *(const v4i*)(rec + 14336 + lo16);
         else if ((part & 1) == 0) {
@@ -619,13 +509,13 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     };
     auto flip_stage = [&](int delta) {
         ve += delta > 0 ? HROWS_PAD : -HROWS_PAD;
-        if (GDT_C16_SCHED == 2) wes -= delta > 0 ? HROWS_PAD : -HROWS_PAD;
+        wes -= delta > 0 ? HROWS_PAD : -HROWS_PAD;
 #pragma unroll
         for (int k = 0; k < 3; ++k) { vt[k] += delta; vq[k] += delta; }
     };
     // E8M0 scales of the activation side: blocks 0 / 2 carry a_lo, 1 / 3 a_hi, of their pixel (scale byte + this)
     const int a_scale_off = (fg & 1) ? GDT_C_HI_SCALE_OFF : 0;
-    constexpr bool AE_PRE = GDT_C16_SCHED == 2 && !(GDT_C16_ABL & (2 | 8));      // layout 2 adds it a row ahead of the MFMAs, in a gap of its own
+    constexpr bool AE_PRE = !(GDT_C16_ABL & (2 | 8));      // added a row ahead of the MFMAs, in a gap of its own
 
     const int nchunks = d.Cin >> 6;
     // ---- prologue
@@ -648,7 +538,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
     v4i aq[QW];
     int ae[QW];                   // their scale bytes
     if (GDT_C16_ABL & 8) { for (int i = 0; i < QW; ++i) { aq[i] = a_qfrag(i, 0, 0); ae[i] = a_efrag(i, 0, 0); } }
-    if (GDT_C16_ABL & (16 | 64)) { for (int st = 0; st < BQS + ((GDT_C16_ABL & 64) ? 1 : 0); ++st) for (int part = 0; part < 9; ++part) load_bq_part(st, part, cur.tile_n, 0); }
+    if (GDT_C16_ABL & (16 | 64)) { for (int st = 0; st < 1 + BQ_MFMA; ++st) for (int part = 0; part < 9; ++part) load_bq_part(st, part, cur.tile_n, 0); }
 #pragma unroll
     for (int i = 0; i < AW; ++i) afr[i] = a_frag(i, 0, 0, 0);
 
@@ -680,11 +570,9 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
             // last chunk this fetches the first slices again: unconditional loads keep the code straight-line)
             auto ks_of = [&](int u) -> long { return u < 18 ? (long)(((u >> 1) * cin64 + c) * 2 + (u & 1)) : (long)(sc * 2 + (u - 18)); };
             auto tn_of = [&](int u) -> int { return (u >= 18 && last) ? nxt.tile_n : cur.tile_n; };
-            if (GDT_C16_SCHED == 2) {       // (the chunk's set-up stays in front of its first MFMA)
-                gy0 = sta.y0 - 1; gx0 = sta.x0 - 1;
-                asm volatile("" : "+s"(gy0), "+s"(gx0));
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            gy0 = sta.y0 - 1; gx0 = sta.x0 - 1;       // (the chunk's set-up stays in front of its first MFMA)
+            asm volatile("" : "+s"(gy0), "+s"(gx0));
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int t = 0; t < NTAP; ++t) {
                 const int ty = t / 3, tx = t - ty * 3;
@@ -694,91 +582,51 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
                     const int u = 2 * t + s;
 #pragma unroll
                     for (int pb = 0; pb < 16; ++pb) {
-                        if (GDT_C16_SCHED == 2) {
-                            // per MFMA: (cb 0) the row's weight load, (1, 2) a staging micro-phase each, (3) the row's LDS reads -- what each
-                            // of them is, and why there, is written at the row layout below
+                        // behind the row's MFMA cb: (0) its weight load, (1, 2) a staging micro-phase each, (3) its LDS reads
 #pragma unroll
-                            for (int cb = 0; cb < 4; ++cb) {
-                                mfma16_at(acc[pb][cb], bw[u % RING][cb], afr[pb % AW]);     // D[cout][pixel]
-                                if (cb == 0) {
-                                    if (AE_PRE && s == 1 && pb == 15) { asm volatile("" : "+v"(ae[0])); ae[0] += a_scale_off; asm volatile("" : "+v"(ae[0])); }
-                                    if (!(GDT_C16_ABL & 4) && (pb & 3) == 2) load_bw((u + RING - 1) % RING, pb >> 2, tn_of(u + RING - 1), ks_of(u + RING - 1));
-                                    if (!(GDT_C16_ABL & (2 | 16)) && BQS == 2) {
-                                        if (t == 0 && s == 0 && pb < 9) load_bq_part(0, pb, cur.tile_n, (long)c);
-                                        if (t + 1 < NTAP && s == 1 && (pb & 1) == 1) load_bq_part((t + 1) & 1, pb >> 1, cur.tile_n, (long)((t + 1) * cin64 + c));
-                                    }
-                                    if (!(GDT_C16_ABL & (2 | 16)) && BQS == 1 && (pb & 1) == 1 && (s == 0 || pb == 1)) load_bq_part(0, s == 0 ? pb >> 1 : 8, cur.tile_n, (long)(t * cin64 + c));
-                                } else if (cb < 3) {
-                                    stage_micro(sta, sc, STAGE_BYTES - so, 3 * t + s, pb, cb - 1);
-                                } else {
-                                    if (pb + AW < 16) afr[pb % AW] = a_frag(pb + AW, ty, tx, s);
-                                    else if (s == 0) afr[pb % AW] = a_frag(pb + AW - 16, ty, tx, 1);
-                                    else if (t < NTAP - 1) afr[pb % AW] = a_frag(pb + AW - 16, nty, ntx, 0);
-                                    if (!(GDT_C16_ABL & (2 | 8)) && s == 1 && pb >= 16 - QW) { aq[pb - (16 - QW)] = a_qfrag(pb - (16 - QW), ty, tx); ae[pb - (16 - QW)] = a_efrag(pb - (16 - QW), ty, tx); }
-                                }
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                            continue;
-                        }
-#pragma unroll
-                        for (int cb = 0; cb < 4; ++cb)
+                        for (int cb = 0; cb < 4; ++cb) {
                             mfma16(acc[pb][cb], bw[u % RING][cb], afr[pb % AW]);     // D[cout][pixel]
-                        // the window slot just used takes the fragment AW patch rows on: of this half-step or of the next one
-                        if (pb + AW < 16) afr[pb % AW] = a_frag(pb + AW, ty, tx, s);
-                        else if (s == 0) afr[pb % AW] = a_frag(pb + AW - 16, ty, tx, 1);
-                        else if (t < NTAP - 1) afr[pb % AW] = a_frag(pb + AW - 16, nty, ntx, 0);
-                        // weights of half-step u + RING - 1 into the ring slot half-step u - 1 has finished with
-                        if (!(GDT_C16_ABL & 4) && (pb & 3) == 2) load_bw((u + RING - 1) % RING, pb >> 2, tn_of(u + RING - 1), ks_of(u + RING - 1));
-                        // MX weights of this tap (read by the MX run behind the second half-step; the previous run has finished with them)
-                        // MX weights: tap 0's own set in the first nine patch rows of its first half-step; the set of tap t + 1 during the second
-                        // half-step of tap t (parts 0-7) and its MX run (the scales)
-                        if (!(GDT_C16_ABL & (2 | 16)) && BQS == 2) {
-                            if (t == 0 && s == 0 && pb < 9) load_bq_part(0, pb, cur.tile_n, (long)c);
-                            if (t + 1 < NTAP && s == 1 && (pb & 1) == 1) load_bq_part((t + 1) & 1, pb >> 1, cur.tile_n, (long)((t + 1) * cin64 + c));
+                            if (cb == 0) {       // the row's weight load: at most one per patch row (load_bq_part says why)
+                                if (AE_PRE && s == 1 && pb == 15) { asm volatile("" : "+v"(ae[0])); ae[0] += a_scale_off; asm volatile("" : "+v"(ae[0])); }
+                                // weights of half-step u + RING - 1 into the ring slot half-step u - 1 has finished with
+                                if (!(GDT_C16_ABL & 4) && (pb & 3) == 2) load_bw((u + RING - 1) % RING, pb >> 2, tn_of(u + RING - 1), ks_of(u + RING - 1));
+                                // MX weights of this tap (read by the MX run behind the second half-step; the previous run has finished with them):
+                                // one part per second patch row of the first half-step, the scales in the second
+                                if (!(GDT_C16_ABL & (2 | 16)) && (pb & 1) == 1 && (s == 0 || pb == 1)) load_bq_part(0, s == 0 ? pb >> 1 : 8, cur.tile_n, (long)(t * cin64 + c));
+                            } else if (cb < 3) {
+                                stage_micro(sta, sc, STAGE_BYTES - so, 3 * t + s, pb, cb - 1);
+                            } else {
+                                // the window slot just used takes the fragment AW patch rows on: of this half-step or of the next one
+                                if (pb + AW < 16) afr[pb % AW] = a_frag(pb + AW, ty, tx, s);
+                                else if (s == 0) afr[pb % AW] = a_frag(pb + AW - 16, ty, tx, 1);
+                                else if (t < NTAP - 1) afr[pb % AW] = a_frag(pb + AW - 16, nty, ntx, 0);
+                                // the first fp4 fragments of the MX run
+                                if (!(GDT_C16_ABL & (2 | 8)) && s == 1 && pb >= 16 - QW) { aq[pb - (16 - QW)] = a_qfrag(pb - (16 - QW), ty, tx); ae[pb - (16 - QW)] = a_efrag(pb - (16 - QW), ty, tx); }
+                            }
+                            __builtin_amdgcn_sched_barrier(0);
                         }
-                        // (one set: behind the previous tap's MX run, one part per second patch row of the first half-step, the scales in the second)
-                        if (!(GDT_C16_ABL & (2 | 16)) && BQS == 1 && (pb & 1) == 1 && (s == 0 || pb == 1)) load_bq_part(0, s == 0 ? pb >> 1 : 8, cur.tile_n, (long)(t * cin64 + c));
-                        // the first fp4 fragments of the MX run
-                        if (!(GDT_C16_ABL & (2 | 8)) && s == 1 && pb >= 16 - QW) { aq[pb - (16 - QW)] = a_qfrag(pb - (16 - QW), ty, tx); ae[pb - (16 - QW)] = a_efrag(pb - (16 - QW), ty, tx); }
-                        stage_phase(sta, sc, STAGE_BYTES - so, 3 * t + s, pb);
-                        __builtin_amdgcn_sched_barrier(0);
                     }
                 }
                 // the correction product of the tap's 64 k-values
 #pragma unroll
                 for (int pb = 0; pb < 16; ++pb) {
-                    if (GDT_C16_SCHED == 2) {
 #pragma unroll
-                        for (int cb = 0; cb < 4; ++cb) {
-                            if (!(GDT_C16_ABL & 2)) {
-                                mfma16_mx_at(acc[pb][cb], bq[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], aq[pb % QW], bqs[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], AE_PRE ? ae[pb % QW] : ae[pb % QW] + a_scale_off);
-                                // (the next row's scale byte gets its a_hi offset here, off the gap of the LDS reads)
-                                if (cb == 0 && AE_PRE && pb + 1 < 16) { asm volatile("" : "+v"(ae[(pb + 1) % QW])); ae[(pb + 1) % QW] += a_scale_off; asm volatile("" : "+v"(ae[(pb + 1) % QW])); }
-                                if (cb == 0 && !(GDT_C16_ABL & 16) && BQS == 2 && t + 1 < NTAP && pb == 1) load_bq_part((t + 1) & 1, 8, cur.tile_n, (long)((t + 1) * cin64 + c));
-                                if (cb == 3 && !(GDT_C16_ABL & 8) && pb + QW < 16) { aq[pb % QW] = a_qfrag(pb + QW, ty, tx); ae[pb % QW] = a_efrag(pb + QW, ty, tx); }
-                            }
-                            if (cb == 1 || cb == 2) stage_micro(sta, sc, STAGE_BYTES - so, 3 * t + 2, pb, cb - 1);
-                            __builtin_amdgcn_sched_barrier(0);
+                    for (int cb = 0; cb < 4; ++cb) {
+                        if (!(GDT_C16_ABL & 2)) {
+                            mfma16_mx(acc[pb][cb], bq[BQ_MFMA][cb], aq[pb % QW], bqs[BQ_MFMA][cb], AE_PRE ? ae[pb % QW] : ae[pb % QW] + a_scale_off);
+                            // (the next row's scale byte gets its a_hi offset here, off the gap of the LDS reads)
+                            if (cb == 0 && AE_PRE && pb + 1 < 16) { asm volatile("" : "+v"(ae[(pb + 1) % QW])); ae[(pb + 1) % QW] += a_scale_off; asm volatile("" : "+v"(ae[(pb + 1) % QW])); }
+                            if (cb == 3 && !(GDT_C16_ABL & 8) && pb + QW < 16) { aq[pb % QW] = a_qfrag(pb + QW, ty, tx); ae[pb % QW] = a_efrag(pb + QW, ty, tx); }
                         }
-                        continue;
+                        if (cb == 1 || cb == 2) stage_micro(sta, sc, STAGE_BYTES - so, 3 * t + 2, pb, cb - 1);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
-                    if (!(GDT_C16_ABL & 2)) {
-#pragma unroll
-                        for (int cb = 0; cb < 4; ++cb) mfma16_mx(acc[pb][cb], bq[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], aq[pb % QW], bqs[(GDT_C16_ABL & 64) ? BQS : (t % BQS)][cb], ae[pb % QW] + a_scale_off);
-                        if (!(GDT_C16_ABL & 8) && pb + QW < 16) { aq[pb % QW] = a_qfrag(pb + QW, ty, tx); ae[pb % QW] = a_efrag(pb + QW, ty, tx); }
-                        if (!(GDT_C16_ABL & 16) && BQS == 2 && t + 1 < NTAP && pb == 1) load_bq_part((t + 1) & 1, 8, cur.tile_n, (long)((t + 1) * cin64 + c));
-                    }
-                    stage_phase(sta, sc, STAGE_BYTES - so, 3 * t + 2, pb);
-                    __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            if (GDT_C16_ABL & 64) {       // keep the (unused) loads of the two working sets alive
+            if (GDT_C16_ABL & 64) {       // keep the (unused) loads of the working set alive
 #pragma unroll
-                for (int st = 0; st < BQS; ++st) {
-#pragma unroll
-                    for (int cb = 0; cb < 4; ++cb) asm volatile("" :: "v"(bq[st][cb]));
-                    asm volatile("" :: "v"(bqs[st]));
-                }
+                for (int cb = 0; cb < 4; ++cb) asm volatile("" :: "v"(bq[0][cb]));
+                asm volatile("" :: "v"(bqs[0]));
             }
             GDT_STAMP(st_body)
             if (!last) {
@@ -852,9 +700,6 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_c16_kernel(const ConvLaunch d
                 if (GDT_C16_ABL & 256) {      // (ablation 256: no output stores)
 #pragma unroll
                     for (int cb = 0; cb < 4; ++cb) asm volatile("" :: "v"(tv[cb].x), "v"(tv[cb].y), "v"(tv[cb].z), "v"(tv[cb].w));
-                } else if (!GDT_C16_FULL_LINES) {
-#pragma unroll
-                    for (int cb = 0; cb < 4; ++cb) *(float4*)(outp + o + cb * 16) = tv[cb];      // 16 pixels x 64 bytes per instruction
                 } else {
                     // Whole lines: as the registers stand an instruction writes 64 bytes (the four lane groups) of each of its 16 pixels.  The pixel
                     // lanes n and n ^ 8 swap one block of a pair (2p, 2p + 1): lanes n < 8 hand over block 2p + 1 and receive block 2p of the partner,
