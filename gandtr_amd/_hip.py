@@ -57,7 +57,14 @@ class PatchNceLayer(ctypes.Structure):
     _fields_ = [("q", c_void_p), ("k", c_void_p), ("row_loss", c_void_p), ("rows", c_int), ("d", c_int), ("groups", c_int)]
 
 
+class MapLossPair(ctypes.Structure):
+    """struct gdt_map_loss_pair (include/gandtr_hip.h): one pair of maps of gdt_map_loss."""
+    _fields_ = [("a", c_void_p), ("b", c_void_p), ("target", c_float), ("kind", c_int), ("flags", c_int), ("n_images", c_int),
+                ("count", ctypes.c_long), ("weight", c_double)]
+
+
 PATCH_MAX_LAYERS = 16                  # GDT_PATCH_MAX_LAYERS
+MAP_LOSS_MAX_PAIRS = 16                # GDT_MAP_LOSS_MAX_PAIRS
 
 _FP = POINTER(c_float)
 _IP = POINTER(c_int)
@@ -118,6 +125,8 @@ SIGNATURES = {
     "gdt_patch_score": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gdt_patch_sample": (c_int, [POINTER(PatchLayer), c_int, c_int, c_int, c_void_p]),
     "gdt_patchnce_loss": (c_int, [POINTER(PatchNceLayer), c_int, c_float, c_float, c_void_p, c_void_p]),
+    "gdt_map_loss_workspace_bytes": (c_int, [POINTER(MapLossPair), c_int, POINTER(c_size_t)]),
+    "gdt_map_loss": (c_int, [POINTER(MapLossPair), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gdt_l2n_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "gdt_gem_l2n": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "gdt_rpool_regions": (c_int, [c_int, c_int, c_int, _IP, c_int, _IP]),

@@ -378,6 +378,33 @@ int gdt_patch_sample(const gdt_patch_layer* layers, int n_layers, int nc, int us
 int gdt_patchnce_loss(const gdt_patchnce_layer* layers, int n_layers, float inv_temperature, float weight, double* totals, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * L1 / MSE terms over pairs of maps: the `l1` / `mse` heads of the GAN scenarios' objectives, forward only
+ *   L1Loss / MSELoss                     mdir/components/optim/criterion/base_losses.py:5-14 (torch's, reduction "mean")
+ *   MultiheadLoss / CombinationLoss      mdir/components/optim/criterion/compound_losses.py:65-108 (total = sum_k weight_k * loss_k)
+ * A call takes a table of n_pairs <= GDT_MAP_LOSS_MAX_PAIRS descriptors (a HOST array; a, b device pointers).  Per pair: a, b fp32 [count] (4-byte
+ * alignment is enough), seen as n_images maps of count / n_images values; b may be NULL: every value of b is then `target`.  kind 0: |a - b|, kind 1:
+ * (a - b)^2; flags bit 0: sigmoid applied to a and to b (never to `target`) before the term.  per_image (device, double [sum of n_images], the pairs'
+ * images in table order): the mean term of every map; per_pair (device, double [n_pairs]): the mean over all count values; total (device, double [1]):
+ * sum_k weight_k * per_pair[k].  Terms, sigmoid and sums in double.  An image is summed in chunks of 8192 values that restart at every image, the chunks
+ * of an image, the images and the pairs are added in index order: the order of additions depends on (count, n_images) alone -- no atomics, bit-identical
+ * from run to run, independent of the other pairs of the call and of the 16-byte alignment of a / b (aligned chunks are read with 16-byte loads).
+ * TWO launches for all pairs on `stream`, no synchronisation.  workspace: gdt_map_loss_workspace_bytes, 8-byte aligned device memory.
+ * n_pairs outside 1 .. 16, a null a or output, count < 1, count % n_images != 0, an unknown kind or flag or a workspace that is too small return
+ * GDT_ERR_INVALID before any launch.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define GDT_MAP_LOSS_MAX_PAIRS 16
+typedef struct gdt_map_loss_pair {
+    const float* a; const float* b;
+    float target;
+    int kind, flags, n_images;
+    long count;
+    double weight;
+} gdt_map_loss_pair;
+int gdt_map_loss_workspace_bytes(const gdt_map_loss_pair* pairs, int n_pairs, size_t* bytes);
+int gdt_map_loss(const gdt_map_loss_pair* pairs, int n_pairs, double* per_image, double* per_pair, double* total, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * CLAHE post-processing ("next" row of SURVEY.md section 8f, rank 1: the step between generator and embedder)
  * Replaces the per-image device -> CPU -> cv2 -> device round trip of
  *   ClahePost.postprocess   mdir/components/data/wrapper.py:325-348

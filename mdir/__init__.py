@@ -10,6 +10,8 @@
     mdir.components.optim.criterion        -> gandtr_amd.components.optim.criterion (CRITERIA, initialize_criterion: contrastive, triplet)
     mdir.components.optim.criterion.adversarial -> gandtr_amd.components.optim.criterion.adversarial (DiscriminatorLoss, patch_scores)
     mdir.components.optim.criterion.patchnce -> gandtr_amd.components.optim.criterion.patchnce (MultilayerPatchNCELoss, calculate_nce_loss)
+    mdir.components.optim.criterion.compound -> gandtr_amd.components.optim.criterion.compound (GAN_CRITERIA, initialize_gan_criterion: l1, mse, multihead_loss, ..)
+    mdir.learning.epoch_iteration          -> gandtr_amd.learning.epoch_iteration   (EPOCH_ITERATIONS: the GAN scenarios' step_losses; gan_epochs, edges_epochs, cut_epochs)
     mdir.stages.infer                      -> gandtr_amd.stages.infer               (infer(params, data))
     mdir.tools.tensors                     -> gandtr_amd.tools.tensors
 
@@ -44,6 +46,11 @@ _ALIASES = {
     "mdir.components.optim.criterion": "gandtr_amd.components.optim.criterion",
     "mdir.components.optim.criterion.adversarial": "gandtr_amd.components.optim.criterion.adversarial",
     "mdir.components.optim.criterion.patchnce": "gandtr_amd.components.optim.criterion.patchnce",
+    "mdir.components.optim.criterion.compound": "gandtr_amd.components.optim.criterion.compound",
+    "mdir.learning.epoch_iteration": "gandtr_amd.learning.epoch_iteration",
+    "mdir.learning.epoch_iteration.gan_epochs": "gandtr_amd.learning.epoch_iteration.gan_epochs",
+    "mdir.learning.epoch_iteration.edges_epochs": "gandtr_amd.learning.epoch_iteration.edges_epochs",
+    "mdir.learning.epoch_iteration.cut_epochs": "gandtr_amd.learning.epoch_iteration.cut_epochs",
     "mdir.stages": "gandtr_amd.stages",
     "mdir.stages.infer": "gandtr_amd.stages.infer",
     "mdir.stages.whiten": "gandtr_amd.stages.whiten",
