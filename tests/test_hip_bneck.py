@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_bound as cb
 from gandtr_amd.engine import HipNet
 from gandtr_amd.tools import synth
 
@@ -41,6 +42,15 @@ def _ref_block(x, w):
     return F.relu(F.conv2d(t, we, be) + x)
 
 
+def _block_bound(x, w):
+    """float64 reference and per-output bound of one fused block on the fp16 input ``x``: the reduce and 3x3 outputs live in LDS as fp16, so each layer's bound (its
+    accumulation and its fp16 rounding) is the input perturbation of the next (tests/conv_bound.py, in_delta); the expand conv rounds before it adds x"""
+    wr, br, w3, b3, we, be = w
+    r = cb.layer(x, *cb.fold(wr, br), act="relu")
+    t = cb.layer(r.ref, *cb.fold(w3, b3), pad=1, act="relu", in_delta=r.bound)
+    return cb.layer(t.ref, *cb.fold(we, be), act="relu", residual=x, in_delta=t.bound)
+
+
 @pytest.mark.parametrize("C,mid,n,h,w", [(256, 64, 4, 128, 128), (512, 128, 4, 64, 128), (256, 64, 1, 256, 256),
                                           (256, 64, 4, 120, 136), (512, 128, 4, 68, 136), (256, 64, 3, 171, 250)])     # ragged maps: the last patch row / column hangs over the image
 def test_fused_bottleneck(cuda_device, C, mid, n, h, w, monkeypatch):
@@ -60,6 +70,9 @@ def test_fused_bottleneck(cuda_device, C, mid, n, h, w, monkeypatch):
     err2 = float((got2 - ref2).abs().max() / ref2.abs().max())
     print("fused bottleneck C %d mid %d: %.2e, %.2e of fp64 (fp16 output rounding 4.9e-4)" % (C, mid, err1, err2))
     assert err1 < 1.5e-3 and err2 < 1.5e-3, (err1, err2)
+    for i in (0, n - 1):
+        cb.assert_within(got1[i:i + 1], _block_bound(xin[i:i + 1], ws[0]), "935%03d block 1 %s image %d" % (C, (n, h, w), i))
+        cb.assert_within(got2[i:i + 1], _block_bound(got1[i:i + 1], ws[1]), "935%03d block 2 %s image %d" % (C, (n, h, w), i))
     # the image border rows / columns, where the r halo is zero padding
     for sl in ((slice(None), slice(None), 0), (slice(None), slice(None), h - 1), (slice(None), slice(None), slice(None), 0),
                (slice(None), slice(None), slice(None), w - 1)):

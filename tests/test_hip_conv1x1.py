@@ -5,6 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_bound as cb
 from gandtr_amd.engine import HipNet
 from gandtr_amd.tools import synth
 
@@ -48,5 +49,10 @@ def test_conv1x1_streaming(cuda_device, cin, cout, hw, n, res, relu):
     assert got.shape == ref.shape
     err = float((got - ref).abs().max() / ref.abs().max())
     assert err < 1.5e-3, err                                      # one fp16 rounding of the output (+ of the pre-residual value)
+    # ... and every output within its own bound (tests/conv_bound.py; the kernel rounds to fp16 before it adds the residual, like conv_epilogue.h)
+    wp, shift = cb.fold(w, bias)
+    for i in (0, n - 1):
+        cb.assert_within(got[i:i + 1], cb.layer(ain[i:i + 1], wp, shift, act="relu" if relu else None, residual=outs[taps[2]][i:i + 1].cpu() if res else None),
+                         "945128 %d -> %d %d^2 image %d" % (cin, cout, hw, i))
     # run-to-run determinism
     assert torch.equal(outs[taps[0]], net.forward(x.to(cuda_device))[taps[0]])

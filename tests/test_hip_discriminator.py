@@ -70,7 +70,13 @@ def test_layer_against_float64(cuda_device, monkeypatch, layer, leaky, with_bn):
     assert net.output_shapes(n, ih, iw)[tap] == (n, cout, oh, ow)
     assert net.conv4x4_launches(n, ih, iw) == 1
     x = synth.synth_input(4, (n, 3, ih, iw)).to(cuda_device)
+    net.set_profiling(True)
     outs = net.forward(x)
+    torch.cuda.synchronize()
+    variants = [v for k, v, ms, fl in net.profile() if k == 1]
+    assert variants[-1] == (905256 if stride == 1 else (906256 if cout % 256 == 0 else 906128)), variants       # conv4x4_halo.hip: stride 1, stride 2 in 256 / 128 columns
+    net.set_profiling(False)
+    assert torch.equal(outs[tap], net.forward(x)[tap])
     xin, got = outs[tap_in].cpu(), outs[tap].cpu().double()
     monkeypatch.setenv("GDT_CONV4X4_HALO", "0")
     assert net.conv4x4_launches(n, ih, iw) == 0
