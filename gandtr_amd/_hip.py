@@ -153,6 +153,12 @@ SIGNATURES = {
     "gdt_whiten_learn_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "gdt_whiten_learn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int),
                                  c_void_p, c_size_t, c_void_p]),
+    "gdt_pca_whiten_learn_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "gdt_pca_whiten_learn": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int), c_void_p, c_size_t, c_void_p]),
+    "gdt_pca_project_normalize_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "gdt_pca_project_normalize": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_int), c_void_p, c_size_t, c_void_p]),
+    "gdt_pca_covariance": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "gdt_l2n_rows_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "gdt_clahe_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "gdt_clahe_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "gdt_clahe_lab_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), POINTER(c_float),

@@ -11,6 +11,10 @@
 // Jacobi with both columns of a pair in LDS (one pass over the matrix per round, HBM-bound at 5.9 TB/s); a two-sided cyclic Jacobi
 // on P0 C P0^T is the fallback when C is singular.  Cholesky and the triangular inverse run as d short launches each (d <= 2048: a
 // few tens of ms).  Eigenvectors are defined up to sign, so P's rows are too.
+// PCA whitening and the PCA projection of pasted descriptors (second half of the file) reuse the same pieces:
+//   pcawhitenlearn              mdir/external/cirtorch/utils/whiten.py:14-35
+//   learn_pca_whitening, paste_pca_normalize, l2_normalize      mdir/stages/whiten.py:78-135
+// their covariance / Gram product launches only the 64 x 64 tiles on and below the diagonal and mirrors them.
 #include <math.h>
 #include <string.h>
 
@@ -21,34 +25,46 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------------------------- GEMM
 // C[m][n] = scale * sum_k A(k, m) * B(k, n)   (both operands K-major), 64 x 64 tile per workgroup, 4 x 4 per lane, K-step 16.
-// Operand sources: MAT  = double matrix [K][ld];  DIFF = float rows X[q[k]] - X[p[k]];  CENT = float row X[k] - mean.
-enum { SRC_MAT = 0, SRC_DIFF = 1, SRC_CENT = 2 };
+// Operand sources: MAT  = double matrix [K][ld];  DIFF = float rows X[q[k]] - X[p[k]];  CENT = float row X[k] - mean;
+// DCENT = double rows V[k] - mean[0] (a scalar), columns >= xd read as zero (the padding column of an odd width);
+// DROWS = the same matrix taken row-major on the OUTPUT side, A(k, m) = V[m][k] - mean[0] (operand a of gemm_rows_kernel only).
+enum { SRC_MAT = 0, SRC_DIFF = 1, SRC_CENT = 2, SRC_DCENT = 3, SRC_DROWS = 4 };
 struct Operand {
     int kind;
-    const double* mat; int ld;          // SRC_MAT
-    const float* x; int xd;             // SRC_DIFF / SRC_CENT: rows of xd floats
+    const double* mat; int ld;          // SRC_MAT / SRC_DCENT / SRC_DROWS
+    const float* x; int xd;             // SRC_DIFF / SRC_CENT: rows of xd floats;  SRC_DCENT / SRC_DROWS: valid columns
     const int* q; const int* p;         // SRC_DIFF
-    const double* mean;                 // SRC_CENT
+    const double* mean;                 // SRC_CENT (per column), SRC_DCENT / SRC_DROWS (one scalar)
 };
 
 __device__ __forceinline__ double fetch(const Operand& o, int k, int m) {
     if (o.kind == SRC_MAT) return o.mat[(size_t)k * o.ld + m];
     if (o.kind == SRC_DIFF) return (double)o.x[(size_t)o.q[k] * o.xd + m] - (double)o.x[(size_t)o.p[k] * o.xd + m];
+    if (o.kind == SRC_DCENT) return m < o.xd ? o.mat[(size_t)k * o.ld + m] - o.mean[0] : 0.0;
+    if (o.kind == SRC_DROWS) return k < o.xd ? o.mat[(size_t)m * o.ld + k] - o.mean[0] : 0.0;
     return (double)o.x[(size_t)k * o.xd + m] - o.mean[m];
 }
 
-__global__ __launch_bounds__(256) void gemm_kk_kernel(Operand a, Operand b, double* __restrict__ c, int M, int N, int K, double scale) {
+// one 64 x 64 tile at (m0, n0).  ROWS_A: operand a is row-major on the output side (SRC_DROWS), so its 16 x 64 stage is read with k
+// fastest across lanes.  mirror: also store the transposed tile (lower-triangle launches of a symmetric product, M = N = ldc).
+template <bool ROWS_A>
+__device__ __forceinline__ void gemm_tile(const Operand& a, const Operand& b, double* __restrict__ c, int M, int N, int K, int ldc, double scale,
+                                          int m0, int n0, bool mirror) {
     __shared__ double as[16][64 + 1];
     __shared__ double bs[16][64 + 1];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
     double acc[4][4] = {};
     for (int k0 = 0; k0 < K; k0 += 16) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {                       // 16 x 64 elements per operand, 4 per lane
             const int e = tid + i * 256, kk = e >> 6, mm = e & 63;
             const bool ok = k0 + kk < K;
-            as[kk][mm] = (ok && m0 + mm < M) ? fetch(a, k0 + kk, m0 + mm) : 0.0;
+            if (ROWS_A) {
+                const int ka = e & 15, ma = e >> 4;
+                as[ka][ma] = (k0 + ka < K && m0 + ma < M) ? fetch(a, k0 + ka, m0 + ma) : 0.0;
+            } else {
+                as[kk][mm] = (ok && m0 + mm < M) ? fetch(a, k0 + kk, m0 + mm) : 0.0;
+            }
             bs[kk][mm] = (ok && n0 + mm < N) ? fetch(b, k0 + kk, n0 + mm) : 0.0;
         }
         __syncthreads();
@@ -69,8 +85,29 @@ __global__ __launch_bounds__(256) void gemm_kk_kernel(Operand a, Operand b, doub
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int m = m0 + ty * 4 + i, n = n0 + tx * 4 + j;
-            if (m < M && n < N) c[(size_t)m * N + n] = acc[i][j] * scale;
+            if (m < M && n < N) {
+                c[(size_t)m * ldc + n] = acc[i][j] * scale;
+                if (mirror) c[(size_t)n * ldc + m] = acc[i][j] * scale;
+            }
         }
+}
+
+__global__ __launch_bounds__(256) void gemm_kk_kernel(Operand a, Operand b, double* __restrict__ c, int M, int N, int K, double scale) {
+    gemm_tile<false>(a, b, c, M, N, K, N, scale, blockIdx.y * 64, blockIdx.x * 64, false);
+}
+// symmetric product A^T A (both operands the same, M x M): workgroup t computes tile (r, c) of the lower triangle, c <= r, t = r (r + 1) / 2 + c,
+// and stores it at both places; a diagonal tile is computed whole (element (m, n) and (n, m) run the same fma chain, so they are equal bits).
+__global__ __launch_bounds__(256) void gemm_lower_kernel(Operand a, double* __restrict__ c, int M, int K, double scale) {
+    const int t = blockIdx.x;
+    int r = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+    while ((r + 1) * (r + 2) / 2 <= t) ++r;
+    while (r * (r + 1) / 2 > t) --r;
+    const int col = t - r * (r + 1) / 2;
+    gemm_tile<false>(a, a, c, M, M, K, M, scale, r * 64, col * 64, col != r);
+}
+// out[m][n] = sum_k A(k, m) B(k, n) with operand a row-major on the output side (SRC_DROWS); row stride of c: ldc
+__global__ __launch_bounds__(256) void gemm_rows_kernel(Operand a, Operand b, double* __restrict__ c, int M, int N, int K, int ldc) {
+    gemm_tile<true>(a, b, c, M, N, K, ldc, 1.0, blockIdx.y * 64, blockIdx.x * 64, false);
 }
 
 __global__ __launch_bounds__(256) void transpose_kernel(const double* __restrict__ a, double* __restrict__ t, int d) {
@@ -354,6 +391,188 @@ void gemm(hipStream_t st, const Operand& a, const Operand& b, double* c, int M, 
     hipLaunchKernelGGL(gemm_kk_kernel, dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, st, a, b, c, M, N, K, scale);
 }
 
+// Hestenes sweeps over the rows of gt until a sweep rotates nothing (at most 60); synchronises the stream once per sweep
+int hestenes_sweeps(hipStream_t st, double* gt, int d, int* flag, int& sweeps, bool& converged) {
+    for (; sweeps < 60; ++sweeps) {
+        GDT_CHECK_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
+        for (int r = 0; r < d - 1; ++r)
+            hipLaunchKernelGGL(hestenes_round_kernel, dim3(d / 2), dim3(256), (size_t)2 * d * sizeof(double), st, gt, d, r, flag, 1e-28);
+        int changed = 0;
+        GDT_CHECK_HIP(hipMemcpyAsync(&changed, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+        GDT_CHECK_HIP(hipStreamSynchronize(st));
+        if (!changed) { ++sweeps; converged = true; break; }
+    }
+    return GDT_OK;
+}
+// two-sided cyclic Jacobi sweeps on the symmetric A, V accumulating the rotations, until the off-diagonal norm is below 1e-13 of the diagonal's (at most 40)
+int jacobi_sweeps(hipStream_t st, double* A, double* V, int d, double* cs, double* red, int& sweeps, bool& converged) {
+    for (; sweeps < 40; ++sweeps) {
+        hipLaunchKernelGGL(offdiag_kernel, dim3(1), dim3(1024), 0, st, A, d, red);
+        double h[2];
+        GDT_CHECK_HIP(hipMemcpyAsync(h, red, sizeof(h), hipMemcpyDeviceToHost, st));
+        GDT_CHECK_HIP(hipStreamSynchronize(st));
+        if (!(h[0] > 1e-26 * h[1])) { converged = true; break; }
+        for (int r = 0; r < d - 1; ++r) {
+            hipLaunchKernelGGL(jacobi_angles_kernel, dim3((d / 2 + 255) / 256), dim3(256), 0, st, A, d, r, cs);
+            hipLaunchKernelGGL(jacobi_rows_kernel, dim3((d + 255) / 256, d / 2), dim3(256), 0, st, A, d, r, cs);
+            hipLaunchKernelGGL(jacobi_cols_kernel, dim3(2 * d), dim3(256), (size_t)d * sizeof(double), st, A, V, d, r, cs);
+        }
+    }
+    return GDT_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------- PCA whitening
+// column sums of rows [c * len, (c + 1) * len) of x (MEAN_PARTS fixed chunks, one lane per column), combined in chunk order below
+constexpr int MEAN_PARTS = 64;
+__global__ __launch_bounds__(256) void mean_all_partial_kernel(const float* __restrict__ x, int n, int d, double* __restrict__ part) {
+    const int c = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (c >= d) return;
+    const int len = (n + MEAN_PARTS - 1) / MEAN_PARTS, i0 = min(k * len, n), i1 = min(i0 + len, n);
+    double s = 0.0;
+    for (int i = i0; i < i1; ++i) s += (double)x[(size_t)i * d + c];
+    part[(size_t)k * d + c] = s;
+}
+__global__ __launch_bounds__(256) void mean_all_finish_kernel(const double* __restrict__ part, int n, int d, double* __restrict__ m) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= d) return;
+    double s = 0.0;
+    for (int k = 0; k < MEAN_PARTS; ++k) s += part[(size_t)k * d + c];
+    m[c] = s / (double)n;
+}
+// sum of all entries of v in two fixed stages: SUM_BLOCKS workgroups of strided partial sums, then one workgroup; out[0] = sum / count
+constexpr int SUM_BLOCKS = 256;
+__device__ __forceinline__ double block_sum_256(double a, double* part) {      // part: 4 doubles of LDS; result valid in every lane
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) a += __shfl_xor(a, m);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
+    __syncthreads();
+    return (part[0] + part[1]) + (part[2] + part[3]);
+}
+__global__ __launch_bounds__(256) void sum_partial_kernel(const double* __restrict__ v, size_t count, double* __restrict__ part) {
+    __shared__ double red[4];
+    double a = 0.0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)SUM_BLOCKS * 256) a += v[i];
+    a = block_sum_256(a, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+__global__ __launch_bounds__(256) void sum_finish_kernel(const double* __restrict__ part, size_t count, double* __restrict__ out) {
+    __shared__ double red[4];
+    const double a = block_sum_256(threadIdx.x < SUM_BLOCKS ? part[threadIdx.x] : 0.0, red);
+    if (threadIdx.x == 0) out[0] = a / (double)count;
+}
+// out[i] = v[i] / |v[i]|_2, no epsilon (one workgroup per row, fixed reduction order; in place allowed)
+__global__ __launch_bounds__(256) void l2n_rows_f64_kernel(const double* v, double* out, int d) {
+    __shared__ double red[4];
+    const double* row = v + (size_t)blockIdx.x * d;
+    double* dst = out + (size_t)blockIdx.x * d;
+    double a = 0.0;
+    for (int j = threadIdx.x; j < d; j += 256) a = fma(row[j], row[j], a);
+    const double norm = sqrt(block_sum_256(a, red));
+    for (int j = threadIdx.x; j < d; j += 256) dst[j] = row[j] / norm;
+}
+// rows[i][k] = gt[order[i]][k] / sqrt(lam[order[i]]): the unit left singular vectors as ROWS, in eigenvalue order
+__global__ __launch_bounds__(256) void unit_rows_kernel(const double* __restrict__ gt, const double* __restrict__ lam, const int* __restrict__ order,
+                                                        double* __restrict__ rows, int d) {
+    const int src = order[blockIdx.x];
+    const double s = sqrt(lam[src]);
+    for (int j = threadIdx.x; j < d; j += 256) rows[(size_t)blockIdx.x * d + j] = gt[(size_t)src * d + j] / s;
+}
+__global__ void set_value_kernel(double* __restrict__ a, double value) { a[0] = value; }
+// Arun's shrinkage (cirtorch/utils/whiten.py:28-31): lamp[i] = (1 - b) eig[i] + b with b = eig[shrink - 1] (shrink = 0: lamp = eig).  bad[0] = the first
+// index whose value is not above d 2^-52 lamp[0] (or is not finite), -1 when there is none; bad_value[0] = that value.  One lane: d <= 8192.
+__global__ void pca_shrink_kernel(const double* __restrict__ eig, int d, int shrink, double* __restrict__ lamp, int* __restrict__ bad, double* __restrict__ bad_value) {
+    const double b = shrink ? eig[shrink - 1] : 0.0;
+    int first = -1;
+    double thr = 0.0;
+    for (int i = 0; i < d; ++i) {
+        const double l = shrink ? (1.0 - b) * eig[i] + b : eig[i];
+        lamp[i] = l;
+        if (i == 0) thr = (double)d * 2.220446049250313e-16 * l;
+        if (first < 0 && !(l > thr && isfinite(l))) { first = i; bad_value[0] = l; }
+    }
+    bad[0] = first;
+}
+// P[i][j] = rows[i][j] / sqrt(lamp[i])
+__global__ __launch_bounds__(256) void pca_scale_rows_kernel(const double* __restrict__ rows, const double* __restrict__ lamp, double* __restrict__ p, int d) {
+    const double s = sqrt(lamp[blockIdx.x]);
+    for (int j = threadIdx.x; j < d; j += 256) p[(size_t)blockIdx.x * d + j] = rows[(size_t)blockIdx.x * d + j] / s;
+}
+
+void gemm_lower(hipStream_t st, const Operand& a, double* c, int M, int K, double scale) {
+    const int t = (M + 63) / 64;
+    hipLaunchKernelGGL(gemm_lower_kernel, dim3(t * (t + 1) / 2), dim3(256), 0, st, a, c, M, K, scale);
+}
+
+// Eigenpairs of the symmetric d x d matrix C (d even): unit eigenvectors as the ROWS of *rows_out (one of the buffers below), eigenvalues decreasing in
+// eig.  Cholesky C = Lc Lc^T and Hestenes on Lc when C is positive definite and two columns fit in LDS, else the two-sided cyclic Jacobi on C.  padded:
+// the last row / column of C is zero padding (its eigenvalue 0 is made to rank last whatever the rounding of the other zero eigenvalues).
+struct EigBuffers { double *A, *V, *T1, *cs, *red, *eig; int *flag, *order; };
+int sym_eig(hipStream_t st, const double* C, int d, bool padded, const EigBuffers& w, double** rows_out, int& sweeps, bool& one_sided, bool& converged) {
+    const unsigned dd_blocks = (unsigned)(((size_t)d * d + 255) / 256);
+    const dim3 tgrid((d + 31) / 32, (d + 31) / 32);
+    int rc, c_failed = 1;
+    sweeps = 0; converged = false;
+    hipLaunchKernelGGL(add_diag_copy_kernel, dim3(dd_blocks), dim3(256), 0, st, C, w.A, d, 0.0);
+    if (!padded && (size_t)2 * d * sizeof(double) <= 64 * 1024) {
+        rc = cholesky_inplace(st, w.A, d, w.flag, c_failed);
+        if (rc != GDT_OK) return rc;
+        if (c_failed) hipLaunchKernelGGL(add_diag_copy_kernel, dim3(dd_blocks), dim3(256), 0, st, C, w.A, d, 0.0);
+    }
+    one_sided = !c_failed;
+    if (one_sided) {
+        hipLaunchKernelGGL(zero_upper_kernel, dim3(dd_blocks), dim3(256), 0, st, w.A, d);                       // A = Lc
+        hipLaunchKernelGGL(transpose_kernel, tgrid, dim3(256), 0, st, w.A, w.V, d);                              // V = Lc^T: row i = column i of Lc
+        rc = hestenes_sweeps(st, w.V, d, w.flag, sweeps, converged);
+        if (rc != GDT_OK) return rc;
+        hipLaunchKernelGGL(row_norm2_kernel, dim3(d), dim3(256), 0, st, w.V, d, w.cs);
+        hipLaunchKernelGGL(rank_desc_kernel, dim3((d + 255) / 256), dim3(256), 0, st, w.cs, (size_t)1, d, w.order, w.eig);
+        hipLaunchKernelGGL(unit_rows_kernel, dim3(d), dim3(256), 0, st, w.V, w.cs, w.order, w.T1, d);
+        *rows_out = w.T1;
+    } else {
+        hipLaunchKernelGGL(identity_kernel, dim3(dd_blocks), dim3(256), 0, st, w.V, d);
+        rc = jacobi_sweeps(st, w.A, w.V, d, w.cs, w.red, sweeps, converged);
+        if (rc != GDT_OK) return rc;
+        // the padding column never rotates (its off-diagonal entries are exact zeros): it is still eigenvector d - 1
+        if (padded) hipLaunchKernelGGL(set_value_kernel, dim3(1), dim3(1), 0, st, w.A + (size_t)(d - 1) * (d + 1), -1.7976931348623157e308);
+        hipLaunchKernelGGL(rank_desc_kernel, dim3((d + 255) / 256), dim3(256), 0, st, w.A, (size_t)d + 1, d, w.order, w.eig);
+        hipLaunchKernelGGL(gather_cols_kernel, dim3(dd_blocks), dim3(256), 0, st, w.V, w.order, w.T1, d);       // T1[k][i] = V[k][order[i]]
+        hipLaunchKernelGGL(transpose_kernel, tgrid, dim3(256), 0, st, w.T1, w.A, d);                             // A[i][k]: eigenvectors as rows
+        *rows_out = w.A;
+    }
+    return GDT_OK;
+}
+
+struct PcaLayout { size_t c, a, v, t1, m2, cs, eig, lamp, part, flag, red, order, total; };
+int pca_plan(int n, int d, bool pad_odd, const char* what, PcaLayout& L, int& dp) {
+    if (n < 1) { gdt_set_error(std::string(what) + ": empty input"); return GDT_ERR_INVALID; }
+    dp = d + ((pad_odd && d % 2) ? 1 : 0);
+    if (d < 1 || dp < 2 || dp % 2 != 0 || dp > 8192) {
+        gdt_set_error(std::string(what) + (pad_odd ? ": width must be 1..8191" : ": descriptor size must be even and <= 8192"));
+        return GDT_ERR_INVALID;
+    }
+    const size_t dd = align_up((size_t)dp * dp * sizeof(double)), dv = align_up((size_t)dp * sizeof(double));
+    size_t off = 0;
+    L.c = off; off += dd; L.a = off; off += dd; L.v = off; off += dd; L.t1 = off; off += dd;
+    L.m2 = off; off += pad_odd ? dd : 0;                                          // the projector V_k V_k^T
+    L.cs = off; off += dv; L.eig = off; off += dv; L.lamp = off; off += dv;
+    L.part = off; off += align_up(((size_t)MEAN_PARTS * dp > (size_t)SUM_BLOCKS ? (size_t)MEAN_PARTS * dp : (size_t)SUM_BLOCKS) * sizeof(double));
+    L.flag = off; off += ALIGN; L.red = off; off += ALIGN;
+    L.order = off; off += align_up((size_t)dp * sizeof(int));
+    L.total = off + ALIGN;
+    return GDT_OK;
+}
+EigBuffers eig_buffers(char* ws, const PcaLayout& L) {
+    EigBuffers w;
+    w.A = (double*)(ws + L.a); w.V = (double*)(ws + L.v); w.T1 = (double*)(ws + L.t1); w.cs = (double*)(ws + L.cs);
+    w.red = (double*)(ws + L.red); w.eig = (double*)(ws + L.eig); w.flag = (int*)(ws + L.flag); w.order = (int*)(ws + L.order);
+    return w;
+}
+int not_converged(const char* what, int sweeps) {
+    gdt_set_error(std::string(what) + ": the Jacobi eigensolver stopped at its sweep cap (" + std::to_string(sweeps) + " sweeps) without converging");
+    return GDT_ERR_NOT_CONVERGED;
+}
+
 }  // namespace
 
 extern "C" {
@@ -423,15 +642,8 @@ int gdt_whiten_learn(const float* x, const int* qidx, const int* pidx, int n_vec
     if (!c_failed) {
         hipLaunchKernelGGL(zero_upper_kernel, dim3(dd_blocks), dim3(256), 0, st, A, d);                        // A = Lc
         gemm(st, mat(A, d), mat(T2, d), V, d, d, d, 1.0);                 // V = G^T: V[i][k] = sum_j Lc[j][i] P0[k][j]
-        for (; sweeps < 60; ++sweeps) {
-            GDT_CHECK_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
-            for (int r = 0; r < d - 1; ++r)
-                hipLaunchKernelGGL(hestenes_round_kernel, dim3(d / 2), dim3(256), (size_t)2 * d * sizeof(double), st, V, d, r, flag, 1e-28);
-            int changed = 0;
-            GDT_CHECK_HIP(hipMemcpyAsync(&changed, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-            GDT_CHECK_HIP(hipStreamSynchronize(st));
-            if (!changed) { ++sweeps; converged = true; break; }
-        }
+        rc = hestenes_sweeps(st, V, d, flag, sweeps, converged);
+        if (rc != GDT_OK) return rc;
         hipLaunchKernelGGL(row_norm2_kernel, dim3(d), dim3(256), 0, st, V, d, cs);                              // cs = eigenvalues (unordered)
         hipLaunchKernelGGL(rank_desc_kernel, dim3((d + 255) / 256), dim3(256), 0, st, cs, (size_t)1, d, order, eig_out);
         hipLaunchKernelGGL(unit_columns_kernel, dim3((d + 31) / 32, (d + 31) / 32), dim3(256), 0, st, V, cs, order, T1, d);
@@ -442,18 +654,8 @@ int gdt_whiten_learn(const float* x, const int* qidx, const int* pidx, int n_vec
         gemm(st, mat(T1, d), mat(T2, d), A, d, d, d, 1.0);                                         // A = (P0 C) P0^T (sum_k (P0C)[i][k] P0[j][k])
         hipLaunchKernelGGL(symmetrise_kernel, dim3(dd_blocks), dim3(256), 0, st, A, d);
         hipLaunchKernelGGL(identity_kernel, dim3(dd_blocks), dim3(256), 0, st, V, d);
-        for (; sweeps < 40; ++sweeps) {
-            hipLaunchKernelGGL(offdiag_kernel, dim3(1), dim3(1024), 0, st, A, d, red);
-            double h[2];
-            GDT_CHECK_HIP(hipMemcpyAsync(h, red, sizeof(h), hipMemcpyDeviceToHost, st));
-            GDT_CHECK_HIP(hipStreamSynchronize(st));
-            if (!(h[0] > 1e-26 * h[1])) { converged = true; break; }                               // off-diagonal norm below 1e-13 of the diagonal's
-            for (int r = 0; r < d - 1; ++r) {
-                hipLaunchKernelGGL(jacobi_angles_kernel, dim3((d / 2 + 255) / 256), dim3(256), 0, st, A, d, r, cs);
-                hipLaunchKernelGGL(jacobi_rows_kernel, dim3((d + 255) / 256, d / 2), dim3(256), 0, st, A, d, r, cs);
-                hipLaunchKernelGGL(jacobi_cols_kernel, dim3(2 * d), dim3(256), (size_t)d * sizeof(double), st, A, V, d, r, cs);
-            }
-        }
+        rc = jacobi_sweeps(st, A, V, d, cs, red, sweeps, converged);
+        if (rc != GDT_OK) return rc;
         hipLaunchKernelGGL(rank_desc_kernel, dim3((d + 255) / 256), dim3(256), 0, st, A, (size_t)d + 1, d, order, eig_out);
         hipLaunchKernelGGL(gather_cols_kernel, dim3(dd_blocks), dim3(256), 0, st, V, order, T1, d);            // T1[k][i] = V[k][order[i]]
     }
@@ -466,6 +668,131 @@ int gdt_whiten_learn(const float* x, const int* qidx, const int* pidx, int n_vec
         gdt_set_error("whiten_learn: the Jacobi eigensolver stopped at its sweep cap (" + std::to_string(sweeps) + " sweeps) without converging");
         return GDT_ERR_NOT_CONVERGED;
     }
+    return GDT_OK;
+}
+
+int gdt_pca_whiten_learn_workspace_bytes(int n_vec, int d, size_t* bytes) {
+    GDT_REQUIRE(bytes != nullptr, "bytes");
+    PcaLayout L; int dp;
+    int rc = pca_plan(n_vec, d, false, "pca_whiten_learn", L, dp);
+    if (rc != GDT_OK) return rc;
+    *bytes = L.total;
+    return GDT_OK;
+}
+
+int gdt_pca_whiten_learn(const float* x, int n_vec, int d, int shrink, double* m_out, double* p_out, double* eig_out, int* info, void* workspace,
+                         size_t workspace_bytes, void* stream_) {
+    PcaLayout L; int dp;
+    int rc = pca_plan(n_vec, d, false, "pca_whiten_learn", L, dp);
+    if (rc != GDT_OK) return rc;
+    GDT_REQUIRE(shrink >= 0 && shrink <= d, "pca_whiten_learn: shrink must be 0 (none) or 1..d");
+    GDT_REQUIRE(x && m_out && p_out && workspace, "pca_whiten_learn: null buffer");
+    if (workspace_bytes < L.total) { gdt_set_error("pca_whiten_learn: workspace too small"); return GDT_ERR_WORKSPACE; }
+    hipStream_t st = (hipStream_t)stream_;
+    char* ws = (char*)(((uintptr_t)workspace + ALIGN - 1) / ALIGN * ALIGN);
+    double *C = (double*)(ws + L.c), *part = (double*)(ws + L.part), *lamp = (double*)(ws + L.lamp);
+    const EigBuffers w = eig_buffers(ws, L);
+
+    // m = mean over ALL vectors; C = sum (x - m)(x - m)^T / n: the tiles on and below the diagonal, mirrored
+    hipLaunchKernelGGL(mean_all_partial_kernel, dim3((d + 255) / 256, MEAN_PARTS), dim3(256), 0, st, x, n_vec, d, part);
+    hipLaunchKernelGGL(mean_all_finish_kernel, dim3((d + 255) / 256), dim3(256), 0, st, part, n_vec, d, m_out);
+    Operand ce = {}; ce.kind = SRC_CENT; ce.x = x; ce.xd = d; ce.mean = m_out;
+    gemm_lower(st, ce, C, d, n_vec, 1.0 / (double)n_vec);
+
+    double* rows = nullptr;
+    int sweeps = 0;
+    bool one_sided = false, converged = false;
+    rc = sym_eig(st, C, d, false, w, &rows, sweeps, one_sided, converged);
+    if (rc != GDT_OK) return rc;
+    if (eig_out) GDT_CHECK_HIP(hipMemcpyAsync(eig_out, w.eig, (size_t)d * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (info) info[0] = one_sided ? sweeps : -sweeps;                               // negative: the two-sided form ran
+    if (!converged) { GDT_CHECK_HIP(hipStreamSynchronize(st)); return not_converged("pca_whiten_learn", sweeps); }
+
+    // shrinkage, the positive-definiteness test on the (shrunk) eigenvalues, P[i] = v_i^T / sqrt(lambda'_i)
+    hipLaunchKernelGGL(pca_shrink_kernel, dim3(1), dim3(1), 0, st, w.eig, d, shrink, lamp, w.flag, w.red);
+    int bad = -1;
+    double bad_value = 0.0;
+    GDT_CHECK_HIP(hipMemcpyAsync(&bad, w.flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    GDT_CHECK_HIP(hipMemcpyAsync(&bad_value, w.red, sizeof(double), hipMemcpyDeviceToHost, st));
+    GDT_CHECK_HIP(hipStreamSynchronize(st));
+    if (bad >= 0) {
+        char value[64];
+        snprintf(value, sizeof(value), "%.6g", bad_value);
+        gdt_set_error("pca_whiten_learn: the covariance is numerically not positive definite: eigenvalue " + std::to_string(bad) + " of " +
+                      std::to_string(d) + (shrink ? " (after shrinkage) is " : " is ") + value +
+                      ", not above d * 2^-52 times the largest; its whitening row would be infinite or NaN -- pass shrink (1..d) to regularise");
+        return GDT_ERR_INVALID;
+    }
+    hipLaunchKernelGGL(pca_scale_rows_kernel, dim3(d), dim3(256), 0, st, rows, lamp, p_out, d);
+    GDT_CHECK_HIP(hipGetLastError());
+    GDT_CHECK_HIP(hipStreamSynchronize(st));
+    return GDT_OK;
+}
+
+int gdt_pca_project_normalize_workspace_bytes(int n, int d, size_t* bytes) {
+    GDT_REQUIRE(bytes != nullptr, "bytes");
+    PcaLayout L; int dp;
+    int rc = pca_plan(n, d, true, "pca_project_normalize", L, dp);
+    if (rc != GDT_OK) return rc;
+    *bytes = L.total;
+    return GDT_OK;
+}
+
+int gdt_pca_project_normalize(const double* v, int n, int d, int dims, double* out, int* info, void* workspace, size_t workspace_bytes, void* stream_) {
+    PcaLayout L; int dp;
+    int rc = pca_plan(n, d, true, "pca_project_normalize", L, dp);
+    if (rc != GDT_OK) return rc;
+    GDT_REQUIRE(dims >= 1 && dims <= d, "pca_project_normalize: dims must be 1..d");
+    GDT_REQUIRE(v && out && workspace, "pca_project_normalize: null buffer");
+    if (workspace_bytes < L.total) { gdt_set_error("pca_project_normalize: workspace too small"); return GDT_ERR_WORKSPACE; }
+    hipStream_t st = (hipStream_t)stream_;
+    char* ws = (char*)(((uintptr_t)workspace + ALIGN - 1) / ALIGN * ALIGN);
+    double *C = (double*)(ws + L.c), *M2 = (double*)(ws + L.m2), *part = (double*)(ws + L.part), *mean = (double*)(ws + L.lamp);
+    const EigBuffers w = eig_buffers(ws, L);
+
+    // the scalar mean of all entries; Gram matrix of the centred rows (dp x dp: an odd width gets one zero column)
+    const size_t count = (size_t)n * d;
+    hipLaunchKernelGGL(sum_partial_kernel, dim3(SUM_BLOCKS), dim3(256), 0, st, v, count, part);
+    hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(256), 0, st, part, count, mean);
+    Operand ce = {}; ce.kind = SRC_DCENT; ce.mat = v; ce.ld = d; ce.xd = d; ce.mean = mean;
+    gemm_lower(st, ce, C, dp, n, 1.0);
+
+    double* rows = nullptr;
+    int sweeps = 0;
+    bool one_sided = false, converged = false;
+    rc = sym_eig(st, C, dp, dp != d, w, &rows, sweeps, one_sided, converged);
+    if (rc != GDT_OK) return rc;
+    if (info) info[0] = one_sided ? sweeps : -sweeps;
+    if (!converged) { GDT_CHECK_HIP(hipStreamSynchronize(st)); return not_converged("pca_project_normalize", sweeps); }
+
+    // M = V_k V_k^T from the dims leading eigenvector rows; out = (v - mean) M; rows to unit length
+    gemm_lower(st, mat(rows, dp), M2, dp, dims, 1.0);
+    Operand vr = {}; vr.kind = SRC_DROWS; vr.mat = v; vr.ld = d; vr.xd = d; vr.mean = mean;
+    hipLaunchKernelGGL(gemm_rows_kernel, dim3((d + 63) / 64, (n + 63) / 64), dim3(256), 0, st, vr, mat(M2, dp), out, n, d, dp, d);
+    hipLaunchKernelGGL(l2n_rows_f64_kernel, dim3(n), dim3(256), 0, st, out, out, d);
+    GDT_CHECK_HIP(hipGetLastError());
+    GDT_CHECK_HIP(hipStreamSynchronize(st));
+    return GDT_OK;
+}
+
+int gdt_l2n_rows_f64(const double* v, double* out, int n, int d, void* stream_) {
+    GDT_REQUIRE(n >= 0 && d >= 1, "l2n_rows_f64: n >= 0 and d >= 1");
+    if (n == 0) return GDT_OK;
+    GDT_REQUIRE(v && out, "l2n_rows_f64: null buffer");
+    hipLaunchKernelGGL(l2n_rows_f64_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream_, v, out, d);
+    GDT_CHECK_HIP(hipGetLastError());
+    return GDT_OK;
+}
+
+// measurement aid: the covariance product of gdt_pca_whiten_learn on its own, as the lower-tile launch or as the full grid gdt_whiten_learn uses
+int gdt_pca_covariance(const float* x, int n_vec, int d, const double* mean, double* c, int lower, void* stream_) {
+    GDT_REQUIRE(n_vec >= 1 && d >= 1 && d <= 8192, "pca_covariance: n_vec >= 1 and d in 1..8192");
+    GDT_REQUIRE(x && mean && c, "pca_covariance: null buffer");
+    hipStream_t st = (hipStream_t)stream_;
+    Operand ce = {}; ce.kind = SRC_CENT; ce.x = x; ce.xd = d; ce.mean = mean;
+    if (lower) gemm_lower(st, ce, c, d, n_vec, 1.0 / (double)n_vec);
+    else gemm(st, ce, ce, c, d, d, n_vec, 1.0 / (double)n_vec);
+    GDT_CHECK_HIP(hipGetLastError());
     return GDT_OK;
 }
 

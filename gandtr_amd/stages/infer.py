@@ -14,6 +14,14 @@ descriptors |d| <= 1e-3 / cosine >= 0.9999 against the fp32 oracle either way, D
 embedding item that is a batch already (N > 1) sends the whole call through the item-by-item loop, as the reference would run it.  Outputs:
     "embedding" -> one (N x D) float32 numpy array   (EmbeddingOutput, mdir/components/data/output.py:118-156)
     "rgb"       -> a list of H x W x 3 float arrays in [0, 1] (un-normalised with the network's mean_std; RgbImageSaver :75-84)
+
+The file route is the reference's own data contract for embeddings: ``data[0]`` is a list of image identifiers (strings),
+``params["data"]["test"]["dataset"]`` a ``CirImageList`` section (``image_dir``, ``image_size``; cir_image_list_dataset,
+components/data/dataset/cirtorch_datasets.py:33-50) and the output ``embedding``.  Paths are ``path_join(image_dir, name)``; ``mean_std`` and the
+``apply_clahe`` step come from the network's ``runtime.data`` merged with ``data.test`` (infer.py:31); decoding, resizing, normalisation and the
+descriptors run on the device (``extract_vectors_from_files``).  The return value is then the reference's triple ``(metadata, images, vecs)`` with
+``vecs`` an N x D float64 array (EmbeddingOutput allocates ``np.zeros``).  A file that does not exist raises ``FileNotFoundError`` naming it: the
+reference's convention of a NaN row for an item its loader could not read (output.py:144-146) is not mirrored.
 """
 import copy
 import os
@@ -30,7 +38,12 @@ def infer(params, data):
     np.random.seed(0)
     torch.manual_seed(0)
     if not len(data[0]):
+        if _is_file_route(params, data):
+            return ({"status": "skipped"}, data[0], [])             # EmbeddingOutput.postprocess() without vectors (output.py:156)
         return ({"status": "skipped"},)
+    if _is_file_route(params, data):
+        metadata, vecs = embed_files(params, list(data[0]))
+        return (metadata, data[0], vecs.t().contiguous().double().cpu().numpy())
     network = load_network(copy.deepcopy(params["network"]), device).eval()
     kind = params["output"]["inference"]["name"]
     if kind not in ("embedding", "rgb"):
@@ -63,6 +76,44 @@ def infer(params, data):
     if kind == "embedding":
         return (metadata, np.stack(outputs))
     return (metadata, outputs)
+
+
+def _is_file_route(params, data):
+    dataset = ((params.get("data") or {}).get("test") or {}).get("dataset") or {}
+    return (isinstance(dataset, dict) and dataset.get("name") == "CirImageList" and params["output"]["inference"]["name"] == "embedding"
+            and all(isinstance(x, str) for x in data[0]))
+
+
+def embed_files(params, names):
+    """The file route of ``infer`` up to the host copy: ``(metadata, D x N float32 descriptors on the device)`` for the image identifiers
+    ``names`` (see the module docstring).  ``infer_and_learn_whitening`` hands the device tensor to the whitening learner."""
+    from ..components.optim.score.cirscore import path_join
+    from ..ingest import DeviceTransform
+    from .validate import extract_vectors_from_files
+    if not _is_file_route(params, (names,)):
+        raise NotImplementedError("embeddings from image identifiers need data.test.dataset.name = CirImageList and output.inference.name = embedding")
+    if not torch.cuda.is_available():
+        raise RuntimeError("the file route of infer decodes and describes on a HIP device; none is available")
+    device = torch.device("cuda")
+    dataset = dict(params["data"]["test"]["dataset"])
+    unknown = set(dataset) - {"name", "image_dir", "image_size"}
+    if unknown:
+        raise NotImplementedError("CirImageList: options %s are not mirrored" % sorted(unknown))
+    files = [path_join(dataset["image_dir"], x) for x in names]
+    for f in files:
+        if not os.path.exists(f):
+            raise FileNotFoundError("infer: image file %s does not exist" % f)
+    t0 = time.time()
+    network = load_network(copy.deepcopy(params["network"]), device).eval()
+    data_params = {**network.network_params.runtime.get("data", {}), **{k: v for k, v in params["data"]["test"].items() if k != "dataset"}}
+    if data_params.get("mean_std") is None:
+        raise ValueError("image files need runtime.data.mean_std in the network parameters (the transform the reference builds its dataset with)")
+    transform = DeviceTransform(data_params.get("transforms") or "totensor | normalize", data_params["mean_std"])
+    if transform.clahe_grid != 8:
+        raise NotImplementedError("apply_clahe with a grid other than 8 is not mirrored on the file route")
+    mean_std = (transform.mean, transform.std) if transform.normalize else ([0.0] * 3, [1.0] * 3)
+    vecs = extract_vectors_from_files(network, files, dataset["image_size"], mean_std, device, clahe_clip=transform.clahe_clip)
+    return {"stats": {"items": len(files), "seconds": time.time() - t0}}, vecs
 
 
 def _pixel_budget(kind):

@@ -539,6 +539,43 @@ int gdt_whiten_learn(const float* x, const int* qidx, const int* pidx, int n_vec
                      double* eig_out, int* info, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * PCA whitening: the {m, P} of  pcawhitenlearn(X, shrink)  (mdir/external/cirtorch/utils/whiten.py:14-35; called with float64 D x N
+ * values by the learn_pca_whitening stage, mdir/stages/whiten.py:78-96).  x: [n_vec][d] fp32 descriptor rows (device); shrink: 0 for
+ * none, else 1..d (whiten.py:28-31: b = eigval[shrink-1], eigval = (1-b) eigval + b).  All arithmetic in float64, fixed summation
+ * orders (two calls give the same bits).  m = mean over ALL rows; C = sum (x-m)(x-m)^T / n_vec, computed as the 64 x 64 tiles on and
+ * below the diagonal and mirrored (exactly symmetric: stands in for (Xcov + Xcov^T) / 2N); eigenpairs by Cholesky + one-sided Jacobi,
+ * or the two-sided cyclic Jacobi when C is singular or d > 4096.  Outputs (device): m [d], P [d][d] row-major with
+ * P[i] = eigvec_i^T / sqrt(eigval'_i), eig [d] (may be NULL) = the RAW eigenvalues in decreasing order, before shrinkage.  info (host,
+ * one int, may be NULL): Jacobi sweeps, negative when the two-sided form ran.  The call synchronises the stream.  d even, <= 8192.
+ * GDT_ERR_NOT_CONVERGED as for gdt_whiten_learn.  GDT_ERR_INVALID when a (shrunk) eigenvalue i is not above d * 2^-52 times the
+ * largest or is not finite -- the covariance is numerically not positive definite; the reference would return infinite / NaN rows
+ * silently there -- the message names the index and the value.  With shrink the test is on the shrunk values, so a singular
+ * covariance (n_vec <= d) is accepted then.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int gdt_pca_whiten_learn_workspace_bytes(int n_vec, int d, size_t* bytes);
+int gdt_pca_whiten_learn(const float* x, int n_vec, int d, int shrink, double* m_out, double* p_out, double* eig_out, int* info,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* The `dimensions` branch of the paste_pca_normalize stage (mdir/stages/whiten.py:108-125): v float64 [n][d] (device), dims in 1..d.
+ *   value -= np.mean(value) (ONE scalar over all n*d entries);  eigenpairs of value^T value;  M = V_k V_k^T from the dims largest;
+ *   out = value M;  every row divided by its 2-norm, no epsilon.
+ * out float64 [n][d] (the projection keeps the width).  Any d in 1..8191: an odd width gets one zero column internally, whose
+ * eigenvalue 0 ranks last.  The Gram matrix uses the lower-tile product and the solver choice of gdt_pca_whiten_learn (a singular
+ * Gram matrix takes the two-sided form).  info (host, one int, may be NULL): sweeps, negative for two-sided.  Synchronises the stream. */
+int gdt_pca_project_normalize_workspace_bytes(int n, int d, size_t* bytes);
+int gdt_pca_project_normalize(const double* v, int n, int d, int dims, double* out, int* info, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
+/* out[i] = v[i] / ||v[i]||_2 in float64, no epsilon: the l2_normalize stage (mdir/stages/whiten.py:130-135) and the last line of
+ * paste_pca_normalize (:125).  v, out: [n][d] on the device, in place allowed.  (gdt_l2n_rows is cirtorch's float32 form with its epsilon.) */
+int gdt_l2n_rows_f64(const double* v, double* out, int n, int d, void* stream);
+
+/* Measurement aid (tools/pca_whiten_bench.py): the covariance product of gdt_pca_whiten_learn alone, c [d][d] = sum (x - mean)(x - mean)^T / n_vec
+ * from fp32 rows x [n_vec][d] and a float64 mean [d] (device), lower = 1: the tiles on and below the diagonal, mirrored (what gdt_pca_whiten_learn
+ * launches); lower = 0: the full tile grid that gdt_whiten_learn launches.  Both give the same bits.  Asynchronous on `stream`. */
+int gdt_pca_covariance(const float* x, int n_vec, int d, const double* mean, double* c, int lower, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): sustained rate of the matrix pipe alone on this device -- a kernel of nothing
  * but v_mfma_f32_32x32x16_f16 on random fp16 operands (8 independent accumulators per wave, 8 waves per CU) run for about
  * `millis` milliseconds.  bench.py reports it next to the 2.5 PFLOP/s datasheet peak: these boxes throttle to 1.5-1.7 PFLOP/s

@@ -13,6 +13,7 @@
     mdir.components.optim.criterion.compound -> gandtr_amd.components.optim.criterion.compound (GAN_CRITERIA, initialize_gan_criterion: l1, mse, multihead_loss, ..)
     mdir.learning.epoch_iteration          -> gandtr_amd.learning.epoch_iteration   (EPOCH_ITERATIONS: the GAN scenarios' step_losses; gan_epochs, edges_epochs, cut_epochs)
     mdir.stages.infer                      -> gandtr_amd.stages.infer               (infer(params, data))
+    mdir.stages.multistep                  -> gandtr_amd.stages.multistep           (infer_and_learn_whitening(params, data))
     mdir.tools.tensors                     -> gandtr_amd.tools.tensors
 
 Unlike the reference's ``mdir/__init__.py`` this does NOT call ``torch.set_num_threads(3)`` (mdir/stages/infer.py:12-15)
@@ -54,6 +55,7 @@ _ALIASES = {
     "mdir.stages": "gandtr_amd.stages",
     "mdir.stages.infer": "gandtr_amd.stages.infer",
     "mdir.stages.whiten": "gandtr_amd.stages.whiten",
+    "mdir.stages.multistep": "gandtr_amd.stages.multistep",
     "mdir.stages.validate": "gandtr_amd.stages.validate",
     "mdir.tools": "gandtr_amd.tools",
     "mdir.tools.tensors": "gandtr_amd.tools.tensors",
