@@ -1,5 +1,5 @@
 """Inference wrappers around ``model(x)`` -- host mirror of mdir/components/data/wrapper.py:
-Compose :15-49, Wrapper :52-65, RandomPassThrough / CirRatioPassThrough :97-146, MeanStdPost/Pre :149-194, CirMultiscaleAggregation :197-263, FakeBatch :266-279,
+Compose :15-49, Wrapper :52-65, ReflectPadMakeDivisible :68-94, RandomPassThrough / CirRatioPassThrough :97-146, MeanStdPost/Pre :149-194, CirMultiscaleAggregation :197-263, FakeBatch :266-279,
 CirFakeTupleBatch :282-305, CirtorchWhiten :308-322, ClahePost :325-348, RgbToBgrPre :351-364, registry :367-396.
 
 Protocol (unchanged): ``preprocess(tensor, outputmodel) -> (tensor, meta)`` applied in list order,
@@ -106,6 +106,35 @@ class Wrapper:
         """("perm", [..]) or ("affine", scale, shift) when the wrapper is a pure per-channel transform of the model INPUT with an
         identity postprocess (then a HIP model can apply it while packing its input, Compose._fold_input_wrappers); else None."""
         return None
+
+
+class ReflectPadMakeDivisible(Wrapper):
+    """Pad H and W up to the next multiple of ``divisible_by`` and crop the model's output back (wrapper.py:68-94) -- what a U-Net needs.
+    As in the reference, and despite the name, the padding REPLICATES the border.  An axis' deficit is split floor (top / left) and ceil
+    (bottom / right); the metadata is the tuple F.pad takes, (left, right, top, bottom).  A list is handled item by item.
+    Pad and crop are index copies: F.pad and slicing on the tensor's own device (a HIP tensor stays on the GPU); no kernel of this project is needed."""
+
+    def __init__(self, divisible_by, device):
+        super().__init__(device)
+        self.divisible_by = int(divisible_by)
+
+    def preprocess(self, tensor, outputmodel):
+        if isinstance(tensor, list):
+            done = [self.preprocess(t, outputmodel) for t in tensor]
+            return [t for t, _ in done], [p for _, p in done]
+        d = self.divisible_by
+        short_h, short_w = (-tensor.shape[2]) % d, (-tensor.shape[3]) % d
+        padding = (short_w // 2, short_w - short_w // 2, short_h // 2, short_h - short_h // 2)
+        return F.pad(tensor, padding, "replicate"), padding
+
+    def postprocess(self, tensor, outputmodel, padding):
+        if isinstance(tensor, list):
+            return [self.postprocess(t, outputmodel, p) for t, p in zip(tensor, padding)]
+        left, right, top, bottom = padding
+        return tensor[:, :, top:-bottom or None, left:-right or None]
+
+    def __repr__(self):
+        return "%s (divisible_by=%s)" % (type(self).__name__, self.divisible_by)
 
 
 class RandomPassThrough(Wrapper):
@@ -494,6 +523,7 @@ class RgbToBgrPre(Wrapper):
 
 
 WRAPPERS_LABELS = {
+    "reflectpad_divisible": ReflectPadMakeDivisible,
     "random_pass_through": RandomPassThrough,
     "cir_ratio_pass_through": CirRatioPassThrough,
     "meanstd_post": MeanStdPost,

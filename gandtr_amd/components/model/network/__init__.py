@@ -1,5 +1,5 @@
 """Model registry (plugin API) -- mirror of mdir/components/model/network/__init__.py:20-48 restricted to the
-architectures reachable from the hub entrypoints, the BASELINE configs and the published GAN scenarios' discriminators and CUT's ``featdown`` network.  Unknown names raise KeyError like the
+architectures reachable from the hub entrypoints, the BASELINE configs, the published GAN scenarios' discriminators, CUT's ``featdown`` network and the pix2pix U-Net generator.  Unknown names raise KeyError like the
 reference (:48)."""
 import torch.nn as nn
 
@@ -18,6 +18,7 @@ class Identity(nn.Module):
 MODEL_LABELS = {
     "identity": Identity,
     "official_resnet_generator": p2p_networks.ResnetGenerator,
+    "official_p2p_unet_generator": p2p_networks.UnetGenerator,
     "official_p2p_discriminator": p2p_networks.NLayerDiscriminator,
     "official_p2p_mlp": p2p_networks.PatchSampleF,
     "cirnet": cirnet.init_cirnet,

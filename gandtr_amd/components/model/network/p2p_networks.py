@@ -1,5 +1,5 @@
-"""CycleGAN / HED-N-GAN ResNet generator, PatchGAN discriminator and CUT's patch sampler -- host mirror of mdir/components/model/network/p2p_networks.py
-(get_norm_layer :23-35, ResnetGenerator :239-337, ResnetBlock :454-506, NLayerDiscriminator :509-571, Normalize / PatchSampleF :595-671).
+"""CycleGAN / HED-N-GAN ResNet generator, pix2pix U-Net generator, PatchGAN discriminator and CUT's patch sampler -- host mirror of
+mdir/components/model/network/p2p_networks.py (get_norm_layer :23-35, UnetGenerator / UnetSkipConnectionBlock :132-236, ResnetGenerator :239-337, ResnetBlock :454-506, NLayerDiscriminator :509-571, Normalize / PatchSampleF :595-671).
 
 The nn.Module tree is identical to the reference's (same nn.Sequential indices, same parameter names, same creation
 order), so reference checkpoints load unchanged and seeded initialisation reproduces the reference's weights.  On a
@@ -143,6 +143,99 @@ class ResnetGenerator(HipBacked, nn.Module):
         if encode_only and layers[-1] in net.tap_slots:
             return feats
         return out, feats
+
+
+class UnetSkipConnectionBlock(nn.Module):
+    """One level of the U-Net: ``cat([x, up(submodule(down(x)))], 1)`` (the outermost level returns ``up(..)`` alone).  down = [LeakyReLU(0.2, inplace)]
+    Conv2d(k4, s2, p1) [norm]; up = ReLU ConvTranspose2d(k4, s2, p1) [norm] -- outermost: no down activation, no norms, Tanh last, a biased
+    up-convolution; innermost: no down norm, an up-convolution of one tensor.  The LeakyReLU is IN PLACE, as in the reference: it alters ``x``
+    before the concatenation, so the skip half of what a block returns is ``leaky(x)`` (p2p_networks.py:199, :236)."""
+
+    def __init__(self, outer_nc, inner_nc, input_nc=None, submodule=None, outermost=False, innermost=False, norm_layer="batch", use_dropout=False,
+                 track_running_stats=True):
+        super().__init__()
+        self.outermost = outermost
+        norm_layer = get_norm_layer(norm_layer, track_running_stats)
+        base = norm_layer.func if isinstance(norm_layer, functools.partial) else norm_layer
+        use_bias = base == nn.InstanceNorm2d
+        if input_nc is None:
+            input_nc = outer_nc
+        downconv = nn.Conv2d(input_nc, inner_nc, kernel_size=4, stride=2, padding=1, bias=use_bias)
+        downrelu = nn.LeakyReLU(0.2, True)
+        downnorm = norm_layer(inner_nc)
+        uprelu = nn.ReLU(True)
+        upnorm = norm_layer(outer_nc)
+        if outermost:
+            upconv = nn.ConvTranspose2d(inner_nc * 2, outer_nc, kernel_size=4, stride=2, padding=1)
+            model = [downconv] + [submodule] + [uprelu, upconv, nn.Tanh()]
+        elif innermost:
+            upconv = nn.ConvTranspose2d(inner_nc, outer_nc, kernel_size=4, stride=2, padding=1, bias=use_bias)
+            model = [downrelu, downconv] + [uprelu, upconv, upnorm]
+        else:
+            upconv = nn.ConvTranspose2d(inner_nc * 2, outer_nc, kernel_size=4, stride=2, padding=1, bias=use_bias)
+            model = [downrelu, downconv, downnorm] + [submodule] + [uprelu, upconv, upnorm]
+            if use_dropout:
+                model = model + [nn.Dropout(0.5)]
+        self.model = nn.Sequential(*model)
+
+    def forward(self, x):
+        if self.outermost:
+            return self.model(x)
+        return torch.cat([x, self.model(x)], 1)
+
+
+class UnetGenerator(HipBacked, nn.Module):
+    """pix2pix U-Net generator: ``num_downs`` levels of UnetSkipConnectionBlock, widths ngf, 2 ngf, 4 ngf, 8 ngf, 8 ngf, ..; the module tree (and so
+    every state-dict key, ``model.model.0.weight`` ..) is the reference's.  H and W must be divisible by 2^num_downs (the reference fails in torch.cat
+    otherwise; the ``reflectpad_divisible`` wrapper pads to that).  On a HIP device the forward is inference only
+    (gandtr_amd.engine.build_unet_generator); Dropout is the identity there, as in eval mode."""
+
+    #: single-pass fp16; NOT covered by the generators' 1e-3 contract (DESIGN.md section 4, "The U-Net generator"): "f16x3" is the exact mode that is;
+    #: the compensated generator modes "f16c" / "f16ch" do not exist here
+    hip_default_precision = "f16"
+
+    def __init__(self, input_nc, output_nc, num_downs, ngf=64, norm_layer="batch", use_dropout=False, track_running_stats=True):
+        super().__init__()
+        if num_downs < 5:
+            raise ValueError("a UnetGenerator has at least 5 levels, got num_downs = %s" % (num_downs,))
+        self.meta = {"in_channels": input_nc, "out_channels": output_nc}
+        self._cfg = dict(norm=norm_layer if isinstance(norm_layer, str) else None, num_downs=num_downs, ngf=ngf)
+        kw = dict(norm_layer=norm_layer, track_running_stats=track_running_stats)
+        block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, innermost=True, **kw)
+        for _ in range(num_downs - 5):
+            block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, submodule=block, use_dropout=use_dropout, **kw)
+        block = UnetSkipConnectionBlock(ngf * 4, ngf * 8, submodule=block, **kw)
+        block = UnetSkipConnectionBlock(ngf * 2, ngf * 4, submodule=block, **kw)
+        block = UnetSkipConnectionBlock(ngf, ngf * 2, submodule=block, **kw)
+        self.model = UnetSkipConnectionBlock(output_nc, ngf, input_nc=input_nc, submodule=block, outermost=True, **kw)
+
+    def forward(self, input):
+        if self._hip_device().type == "cuda":
+            return self._forward_hip(input)
+        return self.model(input)
+
+    def _hip_modes(self):
+        """the precision of the HIP forward, checked: the U-Net runs in 'f16' or 'f16x3'"""
+        prec = self._hip_precision()
+        if prec not in ("f16", "f16x3"):
+            raise NotImplementedError("HIP U-Net generator runs in 'f16' or 'f16x3'; %r is a ResnetGenerator mode" % (prec,))
+        return prec
+
+    def _forward_hip(self, x):
+        from .... import engine
+        cfg = self._cfg
+        if cfg["norm"] not in ("instance", "batch"):
+            raise NotImplementedError("HIP U-Net generator supports norm instance|batch")
+        if self.training and cfg["norm"] == "batch":
+            raise NotImplementedError("HIP U-Net generator is inference-only: call .eval() (BatchNorm uses running statistics)")
+        prec = self._hip_modes()
+        div = 2 ** cfg["num_downs"]
+        if x.dim() != 4 or x.shape[2] % div or x.shape[3] % div:
+            raise ValueError("a UnetGenerator with num_downs = %d needs H and W divisible by %d, got %s: pad the input with the "
+                             "'reflectpad_divisible:%d' wrapper" % (cfg["num_downs"], div, tuple(x.shape), div))
+        self._hip_check_inference()
+        net = self._hip_net(("unet", prec), lambda sd, dev: engine.build_unet_generator(sd, dev, precision=prec, norm=cfg["norm"]))
+        return net.forward(x)[net.out_slot]
 
 
 class NLayerDiscriminator(HipBacked, nn.Module):

@@ -246,6 +246,34 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const T* __restrict__ x, T
     }
 }
 
+// ------------------------------------------------------------------------------------------------ channel concatenation
+// torch.cat([a, b], 1) of two NHWC tensors (+ ReLU on the `a` part) into a tensor of C channels, zero behind the real ones: the skip connection of
+// UnetSkipConnectionBlock (p2p_networks.py:236) as the generic transposed-conv route reads it.  Ca / Cb: channel strides, ca / cb: channels copied
+// (multiples of 8; cb = 0: one input).
+template <typename T>
+__global__ __launch_bounds__(256) void concat_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ y, long NP, int Ca, int ca,
+                                                     int Cb, int cb, int C, int relu_a) {
+    const int c8n = C >> 3;
+    const long total = NP * c8n;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % c8n) * 8;
+        const long pix = i / c8n;
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = 0.f;
+        if (c < ca) {
+            load8(a + pix * Ca + c, v);
+            if (relu_a) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+            }
+        } else if (c < ca + cb) {
+            load8(b + pix * Cb + (c - ca), v);
+        }
+        store8(y + i * 8, v);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ GeM + L2N
 // grid (D/64, N); 8 lanes cover 64 channels (16 B each), 32 pixel rows per pass; fixed-order LDS reduction.
 template <typename T>
@@ -628,6 +656,16 @@ int gdt_k_maxpool(const void* x, void* y, int f32, int N, int H, int W, int C, i
     const dim3 grid(grid_for((long)N * OH * OW * (C / 8)));
     if (f32) hipLaunchKernelGGL(maxpool_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (float*)y, N, H, W, C, OH, OW, k, s, p);
     else hipLaunchKernelGGL(maxpool_kernel<f16>, grid, dim3(256), 0, st, (const f16*)x, (f16*)y, N, H, W, C, OH, OW, k, s, p);
+    GDT_CHECK_HIP(hipGetLastError());
+    return GDT_OK;
+}
+
+int gdt_k_concat(const void* a, const void* b, void* y, int f32, long NP, int Ca, int ca, int Cb, int cb, int C, int relu_a, hipStream_t st) {
+    GDT_REQUIRE(a && y && (b || cb == 0), "concat tensors");
+    GDT_REQUIRE(C % 8 == 0 && ca % 8 == 0 && cb % 8 == 0 && ca >= 8 && ca <= Ca && cb >= 0 && cb <= Cb && ca + cb <= C, "concat needs channel counts % 8 == 0");
+    const dim3 grid(grid_for(NP * (C / 8)));
+    if (f32) hipLaunchKernelGGL(concat_kernel<float>, grid, dim3(256), 0, st, (const float*)a, (const float*)b, (float*)y, NP, Ca, ca, Cb, cb, C, relu_a);
+    else hipLaunchKernelGGL(concat_kernel<f16>, grid, dim3(256), 0, st, (const f16*)a, (const f16*)b, (f16*)y, NP, Ca, ca, Cb, cb, C, relu_a);
     GDT_CHECK_HIP(hipGetLastError());
     return GDT_OK;
 }

@@ -249,6 +249,22 @@ bool gdt_conv_halo_eligible(const ConvLaunch& d);          // conv3x3_halo.hip
 int gdt_launch_conv_halo(const ConvLaunch& d, hipStream_t stream);
 bool gdt_conv4x4_halo_eligible(const ConvLaunch& d);       // conv4x4_halo.hip (k4 / zero pad 1, stride 1 or 2: PatchGAN discriminator, variant 904000 + stride * 1000 + BN)
 int gdt_launch_conv4x4_halo(const ConvLaunch& d, hipStream_t stream, int* variant);
+// conv4x4t_halo.hip: ConvTranspose2d(k4, s2, p1) of the channel concatenation of `in` (Cin channels, ReLU while read when in_relu) and `in2` (in2_cin channels, or
+// none), variant 907064.  A chunk of 64 input channels meets the 16 kernel taps as 16 steps: step s = gdt_t4_step -- the halo shift (sy, sx) of the input
+// pixel (y - 1 + sy, x - 1 + sx) and the output parity (py, px) it feeds, through kernel tap (gdt_t4_tap(sy, py), gdt_t4_tap(sx, px)); the fragment-ordered weights
+// have k = (chunk * 16 + s) * 64 + channel
+bool gdt_conv4x4t_halo_eligible(const ConvLaunch& d);
+int gdt_launch_conv4x4t_halo(const ConvLaunch& d, hipStream_t stream, int* variant);
+inline __host__ __device__ constexpr bool gdt_t4_meets(int s, int par) { return s == 1 || s == 2 * par; }          // shift s (0..2) of a row / column feeds output parity par
+inline __host__ __device__ constexpr int gdt_t4_tap(int s, int par) { return par ? (s == 1 ? 2 : 0) : (s == 1 ? 1 : 3); }
+inline void gdt_t4_step(int step, int& sy, int& sx, int& py, int& px) {
+    int s = 0;
+    for (sy = 0; sy < 3; ++sy)
+        for (sx = 0; sx < 3; ++sx)
+            for (py = 0; py < 2; ++py)
+                for (px = 0; px < 2; ++px)
+                    if (gdt_t4_meets(sy, py) && gdt_t4_meets(sx, px) && s++ == step) return;
+}
 bool gdt_conv_halo_rb_eligible(const ConvLaunch& d);       // conv3x3_halo_rb.hip (weights streamed into registers)
 bool gdt_conv3x3_expand_eligible(const ConvLaunch& d);     // conv3x3_expand_rb.hip (3x3 + expand 1x1 + residual of a Bottleneck, variant 939000 + x_cout / 8)
 int gdt_launch_conv3x3_expand(const ConvLaunch& d, hipStream_t stream);

@@ -538,6 +538,76 @@ static int add_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, int 
     return GDT_OK;
 }
 
+// conv4x4t_halo.hip: [cout_pad][16 cin] with k = (chunk * 16 + step) * 64 + channel (gdt_t4_step), in fragment order; cin counts the channels of both inputs
+static void pack_t4(ConvPack& cp) {
+    gdt_net* net = cp.net; Op& o = cp.o;
+    const gdt_conv_desc& cd = o.cd;
+    const int K = 16 * cd.cin;
+    std::vector<f16> pk((size_t)o.cout_pad * K, (f16)0.f);
+    for (int s = 0; s < 16; ++s) {
+        int sy, sx, py, px;
+        gdt_t4_step(s, sy, sx, py, px);
+        const int ky = gdt_t4_tap(sy, py), kx = gdt_t4_tap(sx, px);
+        for (int co = 0; co < cd.cout; ++co)
+            for (int c = 0; c < cd.cin; ++c)
+                pk[(size_t)co * K + ((size_t)(c >> 6) * 16 + s) * 64 + (c & 63)] = (f16)(cp.weight[(((size_t)c * cd.cout + co) * 4 + ky) * 4 + kx] * cp.scale[co]);
+    }
+    const std::vector<f16> pf = frag_order(pk, o.cout_pad, K);
+    o.t4_frag_off = net->blob_append(pf.data(), pf.size() * sizeof(f16));
+    o.has_t4 = true;
+}
+
+// gdt_net_conv_transposed4
+static int add_conv_t4(gdt_net* net, int in_a, int in_b, int relu_a, const gdt_conv_desc& cd, const float* weight, const float* bias,
+                       const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor) {
+    const int ca = net->tensors[in_a].Creal, cb = in_b >= 0 ? net->tensors[in_b].Creal : 0;
+    int in = in_a, cat_op = -1;
+    if (in_b >= 0 || relu_a) {          // the generic route's input: the concatenation (+ ReLU on the first part) as a tensor of its own
+        Op c; c.kind = OP_CONCAT; c.in = in_a; c.res = in_b; c.relu = relu_a ? 1 : 0;
+        c.out = net->new_tensor(next_pow2(cd.cin), cd.cin);
+        c.cat_for = (int)net->ops.size() + 1;
+        cat_op = (int)net->ops.size();
+        in = c.out;
+        net->ops.push_back(c);
+    }
+    Op o; o.kind = OP_CONV; o.in = in; o.cd = cd; o.cin_pad = next_pow2(cd.cin); o.cat_op = cat_op;
+    o.t4_a = in_a; o.t4_b = in_b; o.t4_relu = relu_a ? 1 : 0;
+    const int bn_tile = gdt_conv_bn(cd.cout);
+    o.cout_pad = (cd.cout + bn_tile - 1) / bn_tile * bn_tile;
+    ConvPack cp{net, o, weight, 1};
+    fold_bn(cd, bias, bn_gamma, bn_beta, bn_mean, bn_var, cp.scale, cp.shift, cp.has_shift);
+    pack_bias(cp);
+    // four sub-pixel phases of 2 x 2 taps: output parity 0 meets kernel rows 1 (input row y) and 3 (y - 1), parity 1 rows 0 (y + 1) and 2 (y); columns alike
+    for (int py = 0; py < 2; ++py)
+        for (int px = 0; px < 2; ++px) {
+            PackedPhase ph;
+            ph.ntaps = 4; ph.TW = 2;
+            ph.dy0 = py; ph.dys = -1; ph.dx0 = px; ph.dxs = -1;
+            ph.ooy = py; ph.oox = px;
+            pack_phase(cp, ph, [&](int co, int c, int t) {
+                const int ty = t >> 1, tx = t & 1;
+                const int ky = py ? (ty == 0 ? 0 : 2) : (ty == 0 ? 1 : 3), kx = px ? (tx == 0 ? 0 : 2) : (tx == 0 ? 1 : 3);
+                return weight[(((size_t)c * cd.cout + co) * 4 + ky) * 4 + kx];
+            });
+            o.phases.push_back(ph);
+        }
+    if (!net->precision && !cd.out_f32_nchw && ca % 64 == 0 && cb % 64 == 0 && cd.cout % 64 == 0) {
+        pack_t4(cp);
+        o.feats.push_back(in_a);                  // (read by the patch kernel itself: alive until this op)
+        if (in_b >= 0) o.feats.push_back(in_b);
+    }
+    if (cd.out_f32_nchw) {
+        o.slot = (int)net->out_ops.size();
+        net->out_ops.push_back((int)net->ops.size());
+        *out_tensor = o.slot;
+    } else {
+        o.out = net->new_tensor(cd.cout, cd.cout);
+        *out_tensor = o.out;
+    }
+    net->ops.push_back(std::move(o));
+    return GDT_OK;
+}
+
 }  // namespace
 
 // fp16 mode: for every 1x1 conv c (stride 1, ReLU) whose residual is the output of a 1x1 projection conv ds (no ReLU, stride 1 or 2, no other consumer),
@@ -647,6 +717,24 @@ int gdt_net_conv_leaky(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, f
     GDT_REQUIRE(net->precision != 2, "a LeakyReLU conv exists in the f16 and f16x3 modes");
     GDT_REQUIRE(!desc->relu && !desc->transposed && !desc->out_f32_nchw, "a LeakyReLU conv is a plain Conv2d with an internal output and no ReLU");
     return add_conv(net, in_tensor, desc, 1, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, -1, out_tensor, slope);
+}
+
+int gdt_net_conv_transposed4(gdt_net* net, int in_a, int in_b, int relu_a, int cout, const float* weight, const float* bias, const float* bn_gamma,
+                             const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps, int relu, int out_f32_nchw, int act, int* out_tensor) {
+    GDT_REQUIRE(net && !net->finalized && weight && out_tensor, "net/weight");
+    GDT_REQUIRE(net->precision == 0 || net->precision == 1, "ConvTranspose2d(k4,s2,p1) exists in the f16 and f16x3 modes");
+    GDT_REQUIRE(in_a >= 0 && in_a < (int)net->tensors.size() && in_b >= -1 && in_b < (int)net->tensors.size(), "input tensor id");
+    GDT_REQUIRE((bn_gamma && bn_beta && bn_mean && bn_var) || (!bn_gamma && !bn_beta && !bn_mean && !bn_var), "BN vectors");
+    const int ca = net->tensors[in_a].Creal, cb = in_b >= 0 ? net->tensors[in_b].Creal : 0;
+    GDT_REQUIRE(cout >= 1 && ca + cb <= 4096, "conv geometry");
+    if (in_b >= 0 || relu_a) GDT_REQUIRE(ca % 8 == 0 && cb % 8 == 0, "a concatenated or ReLU-on-read input needs channel counts % 8 == 0");
+    else GDT_REQUIRE(net->tensors[in_a].C == next_pow2(ca), "a single input read as stored needs a power-of-two channel count");
+    if (!out_f32_nchw) GDT_REQUIRE(cout % 8 == 0 && act == 0, "internal conv outputs need cout % 8 == 0 and take no activation but ReLU");
+    GDT_REQUIRE(act >= 0 && act <= 2 && !(out_f32_nchw && relu), "output activation");
+    gdt_conv_desc cd{};
+    cd.cin = ca + cb; cd.cout = cout; cd.kh = cd.kw = 4; cd.stride = 2; cd.pad = 1; cd.transposed = 1; cd.relu = relu ? 1 : 0;
+    cd.out_f32_nchw = out_f32_nchw ? 1 : 0; cd.act = act; cd.bn_eps = bn_eps;
+    return add_conv_t4(net, in_a, in_b, relu_a, cd, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, out_tensor);
 }
 
 static int add_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, float leaky, int residual_tensor, int* out_tensor) {

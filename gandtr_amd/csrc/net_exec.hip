@@ -202,6 +202,20 @@ int exec_conv(const ConvStep& s) {
     if (stp.direct) return exec_stem_direct(s);
     if (stp.xexp) return exec_xexp(s);
     if (stp.kcat) return exec_kcat(s);
+    if (s.o.has_t4) {                      // ConvTranspose2d(k4,s2,p1) from its own inputs (conv4x4t_halo.hip) -- else the phase launches below, over the concatenation
+        const ConvLaunch d = conv_desc_t4(s.x, stp.op);
+        if (gdt_conv4x4t_halo_eligible(d)) {
+            int variant = 0;
+            const int rc = gdt_launch_conv4x4t_halo(d, s.st, &variant);
+            s.variant(variant);
+            if (net->profiling && s.book && s.o.cat_op >= 0) {      // bytes: the concatenation is neither written nor read; its two sources are read once
+                const Op& oc = net->ops[s.o.cat_op];
+                const double src = s.tbytes(oc.in) + (oc.res >= 0 ? s.tbytes(oc.res) : 0.0);
+                net->last_bytes[stp.op] += src - s.tbytes(s.o.in);
+            }
+            return rc;
+        }
+    }
     const ConvFold f = fold_of(net, s.c.plan, stp.op);      // InstanceNorm(+ReLU) of the producer applied while staging the input, statistics, pool
     if (f.norm >= 0 && net->profiling)        // bytes the folded form must move on top of the conv's own: the residual tensor read, the normalised tensor written back
         net->last_bytes[stp.op] += s.tbytes(net->ops[f.norm].in) * ((f.res ? 1.0 : 0.0) + (f.wb ? 1.0 : 0.0));
@@ -246,6 +260,14 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                 else
                     rc = gdt_k_instance_norm(tptr(o.in), o.res >= 0 ? tptr(o.res) : nullptr, tptr(o.out), f32, (float*)(ws + stp.aux_off[0]),
                                              (float*)(ws + stp.aux_off[1]), n, ti.H * ti.W, ti.C, o.eps, o.relu, st, o.leaky);
+                break;
+            }
+            case OP_CONCAT: {
+                const Op& oc = net->ops[o.cat_for];
+                if (oc.has_t4 && gdt_conv4x4t_halo_eligible(conv_desc_t4(DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}, o.cat_for))) break;   // the conv reads the sources itself
+                const Tensor& ta = T[o.in]; const Tensor& to = T[o.out];
+                rc = gdt_k_concat(tptr(o.in), o.res >= 0 ? tptr(o.res) : nullptr, tptr(o.out), f32, (long)n * ta.H * ta.W, ta.C, ta.Creal,
+                                  o.res >= 0 ? T[o.res].C : 0, o.res >= 0 ? T[o.res].Creal : 0, to.C, o.relu, st);
                 break;
             }
             case OP_MAXPOOL: {

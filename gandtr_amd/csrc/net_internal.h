@@ -19,7 +19,7 @@ inline size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
 inline int next_pow2(int v) { int p = 8; while (p < v) p <<= 1; return p; }
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF, OP_POOL_HEAD };
+enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF, OP_POOL_HEAD, OP_CONCAT };
 
 struct PackedPhase {
     size_t w_off = 0;                 // byte offset in the device weight blob
@@ -63,6 +63,12 @@ struct Op {
     // weight matrices K-concatenated (conv1x1_rb.hip, CAT form): kcat_ds = index of the projection op
     int kcat_ds = -1; size_t kcat_frag_off = 0, kcat_bias_off = 0;
     float leaky = 0.f;    // conv / inorm: LeakyReLU slope applied instead of ReLU, 0 = none (gdt_net_conv_leaky, gdt_net_instance_norm_leaky)
+    // ConvTranspose2d(k4,s2,p1) (gdt_net_conv_transposed4): `in` is what the four generic phase launches read -- the first input itself, or the output of the OP_CONCAT
+    // op `cat_op` (channel concatenation of t4_a and t4_b, ReLU on the t4_a part when t4_relu); has_t4: the fragment-ordered weights of conv4x4t_halo.hip, which
+    // reads t4_a / t4_b itself (they are also in `feats`, so that they live until this op) -- then the concatenation is never written
+    bool has_t4 = false; size_t t4_frag_off = 0; int t4_a = -1, t4_b = -1, t4_relu = 0, cat_op = -1;
+    // concat (OP_CONCAT): in / res = the two tensors (res < 0: one), relu = ReLU on the first; cat_for = the conv op that reads the output
+    int cat_for = -1;
     int dil = 1;          // conv: dilation (gdt_net_conv_dilated); the taps are (dy0 + (t / TW) * dil, ...): only the generic implicit-GEMM kernels take it
     // maxpool
     int k = 0, s = 0, p = 0; int ceil = 0;
@@ -257,5 +263,6 @@ ConvLaunch conv_desc_pair(const DescCtx& x, int i, int pair_idx, const ConvFold&
 ConvLaunch conv_desc_xexp(const DescCtx& x, int i, int chain, float group_factor);       // 3x3 + expand (op i + 1) (+ the next reduce conv, op `chain`)
 ConvLaunch conv_desc_kcat(const DescCtx& x, int i);                                      // expand conv + its projection shortcut, K-concatenated
 ConvLaunch conv_desc_stem_direct(const DescCtx& x, int i, int pool_into);                // ResNet stem from the caller's image (+ the 3 x 3 max-pool behind it)
+ConvLaunch conv_desc_t4(const DescCtx& x, int i);                                        // ConvTranspose2d(k4,s2,p1) from its one or two inputs (Op::has_t4, conv4x4t_halo.hip)
 
 }  // namespace gdtn

@@ -32,6 +32,7 @@ static void conv_geometry(const gdt_net* net, const Op& o, const PackedPhase& ph
 
 bool conv_fuses_stats(const Op& o, const Tensor& ti) {      // InstanceNorm partial statistics from the conv epilogue
     if (o.stats_for < 0 || o.cd.relu || o.res >= 0) return false;
+    if (o.cd.transposed && o.cd.kh == 4) return false;      // (ConvTranspose2d(k4,s2,p1): its two routes are a launch-time choice on ONE plan, and conv4x4t_halo.hip delivers no statistics)
     const int hwg = o.cd.transposed ? ti.H * ti.W : conv_out_dim(o, ti.H, o.cd.kh) * conv_out_dim(o, ti.W, o.cd.kw);
     return hwg % 128 == 0;
 }
@@ -208,6 +209,23 @@ ConvLaunch conv_desc_stem_direct(const DescCtx& x, int i, int pool_into) {
     return d;
 }
 
+ConvLaunch conv_desc_t4(const DescCtx& x, int i) {
+    const Op& o = x.net->ops[i];
+    const auto& T = *x.T;
+    const Tensor& ta = T[o.t4_a];
+    ConvLaunch d{};
+    d.in = x.p.act(T, o.t4_a); d.Cin = ta.C; d.in_relu = o.t4_relu;
+    if (o.t4_b >= 0) { d.in2 = x.p.act(T, o.t4_b); d.in2_cin = T[o.t4_b].C; d.in2_h = ta.H; d.in2_w = ta.W; d.in2_stride = 1; }
+    d.N = x.n; d.H = ta.H; d.W = ta.W; d.OH = d.H * 2; d.OW = d.W * 2; d.OHg = d.H; d.OWg = d.W; d.M = x.n * d.H * d.W;
+    d.Cout = o.cd.cout; d.CoutPad = o.cout_pad; d.Kpad = 16 * o.cd.cin; d.nk = d.Kpad / 64;
+    d.ntaps = 16; d.TW = 4; d.invTW = 65536 / 4; d.sy = d.sx = 1; d.osy = d.osx = 2; d.relu = o.cd.relu;
+    d.w_frag = o.has_t4 ? x.p.w<const f16*>(o.t4_frag_off) : nullptr;
+    d.bias = o.has_bias ? x.p.w<const float*>(o.bias_off) : nullptr;
+    d.out = x.p.act(T, o.out);
+    d.zeros = x.p.w<const f16*>(x.net->zeros_off);
+    return d;
+}
+
 // ---- make_plan, pass by pass ------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -256,6 +274,10 @@ int Planner::shapes() {
                 break;
             }
             case OP_INORM: h = T[o.in].H; w = T[o.in].W; break;
+            case OP_CONCAT:
+                h = T[o.in].H; w = T[o.in].W;
+                if (o.res >= 0) GDT_REQUIRE(T[o.res].H == h && T[o.res].W == w, "the two inputs of a concatenation differ in size");
+                break;
             case OP_MAXPOOL:
                 h = pool_out_dim(o, T[o.in].H); w = pool_out_dim(o, T[o.in].W);
                 break;
@@ -614,6 +636,7 @@ int Planner::layout() {
                 break;
             }
             case OP_MAXPOOL: if (!st.skip) alloc_tensor(o.out); break;
+            case OP_CONCAT: alloc_tensor(o.out); break;       // (laid out on either route of its conv: which one runs is decided at launch time)
             case OP_GEM: st.aux_off[0] = arena.scratch((size_t)N * T[o.in].C * sizeof(float)); break;
             case OP_POOL_HEAD: {                        // the [N][R][D] pooled vectors and their normalised copy, two [N][D] rows (gdt_k_pool_head)
                 const Tensor& ti = T[o.in];
@@ -753,7 +776,8 @@ int gdt_net_workspace_bytes(gdt_net* net, int n, int rh, int rw, size_t* bytes) 
 // their consumer's staging, [6] max-pools written by their producer, [7] 1 if the stem reads the caller's image itself (calls that do not resize),
 // [8] transposed convs as one fused-phase launch, [9] stride-2 convs as the shift form, [10] dilated convs, [11] of those on a special form; with n_counts >= 14:
 // [12] launches of the pool-head ops (gdt_net_pool_head), [13] of those the ones that read the feature map; with n_counts >= 15: [14] conv launches that
-// conv4x4_halo.hip takes (what gdt_launch_conv decides for the conv as its own plain launch; GDT_CONV4X4_HALO=0: none)
+// conv4x4_halo.hip takes (what gdt_launch_conv decides for the conv as its own plain launch; GDT_CONV4X4_HALO=0: none); with n_counts >= 16: [15] transposed 4x4 convs
+// that conv4x4t_halo.hip takes (one launch each, the concatenation in front never written; GDT_CONV4X4T_HALO=0: none -- then four phase launches each)
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts) {
     GDT_REQUIRE(net && counts && n_counts >= 10 && n >= 1 && rh >= 1 && rw >= 1, "plan summary arguments");
     if (!net->finalized && !net->precision) build_kcat_weights(net);       // (what finalize would add: the K-concatenated shortcut weights the planner may choose)
@@ -776,6 +800,8 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
         if (o.kind == OP_CONV && n_counts >= 15 && !net->precision && o.phases.size() == 1 && !o.rowsplit &&
             !(st.skip || st.bneck || st.xexp || st.kcat || st.direct || st.ctf || st.s2 || st.ctp || st.aug))
             counts[14] += gdt_conv4x4_halo_eligible(conv_desc_phase(DescCtx{net, &net->tensors, n, Ptrs{}}, (int)i, o.phases[0], 0, fold_of(net, plan, (int)i)));
+        if (o.kind == OP_CONV && n_counts >= 16 && o.has_t4 && !st.skip)
+            counts[15] += gdt_conv4x4t_halo_eligible(conv_desc_t4(DescCtx{net, &net->tensors, n, Ptrs{}}, (int)i));
         if (o.kind == OP_CONV && o.dil != 1 && n_counts >= 12) {
             ++counts[10];
             // what gdt_launch_conv / gdt_launch_conv_x3 would be handed for the conv as its own plain launch

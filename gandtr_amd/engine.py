@@ -154,6 +154,19 @@ class HipNet:
             return self._add("conv_leaky", x, ctypes.byref(d), float(leaky), _ptr(w), _ptr(b), _ptr(g), _ptr(be), _ptr(m), _ptr(v))
         return self._add("conv", x, ctypes.byref(d), _ptr(w), _ptr(b), _ptr(g), _ptr(be), _ptr(m), _ptr(v), residual)
 
+    def conv_transposed4(self, a, weight, b=-1, relu_a=False, bias=None, bn=None, relu=False, out_f32=False, act=0):
+        """nn.ConvTranspose2d(k4, s2, p1) of ``torch.cat([a, b], 1)`` (``b`` = -1: of ``a`` alone) with ReLU applied to ``a`` as it is read when ``relu_a``
+        (gdt_net_conv_transposed4); ``weight`` [cin_a + cin_b][cout][4][4]"""
+        w = _f32(weight)
+        if w.ndim != 4 or w.shape[2:] != (4, 4):
+            raise ValueError("conv_transposed4 takes a [cin][cout][4][4] weight, got %s" % (tuple(w.shape),))
+        g = be = m = v = None
+        if bn is not None:
+            g, be, m, v = (_f32(t) for t in bn)
+        bias = _f32(bias)
+        return self._add("conv_transposed4", a, b, int(relu_a), w.shape[1], _ptr(w), _ptr(bias), _ptr(g), _ptr(be), _ptr(m), _ptr(v), 1e-5, int(relu),
+                         int(out_f32), act)
+
     def instance_norm(self, x, relu=False, residual=-1, eps=1e-5, leaky=0.0):
         """``leaky``: slope of an nn.LeakyReLU behind the norm in place of ``relu`` (gdt_net_instance_norm_leaky)"""
         if leaky:
@@ -260,6 +273,10 @@ class HipNet:
     def conv4x4_launches(self, n, rh, rw):
         """conv launches of a geometry that run on the 4x4 patch kernel (conv4x4_halo.hip; GDT_CONV4X4_HALO=0: none) -- the planner's count"""
         return self._plan_counts(n, rh, rw, False, 15)[14]
+
+    def conv4x4t_launches(self, n, rh, rw):
+        """transposed 4x4 convs of a geometry that run as one launch of conv4x4t_halo.hip (GDT_CONV4X4T_HALO=0: none) -- the planner's count"""
+        return self._plan_counts(n, rh, rw, False, 16)[15]
 
     def head_launches(self, n, rh, rw):
         """(launches of the net's pool-head ops, launches among them that read the feature map) for a geometry -- the planner's count"""
@@ -784,6 +801,75 @@ def build_discriminator(sd, device, precision="f16", finalize=True, norm=None, s
             h = net.conv(h, sd[key + ".weight"], sd.get(key + ".bias"), bn=_bn(sd, nkey), stride=stride, pad=1, leaky=slope)
         i += 3
     net.out_slot = net.conv(h, sd["model.%d.weight" % i], sd["model.%d.bias" % i], pad=1, out_f32=True, act=0)
+    if finalize:
+        net.finalize()
+    return net
+
+
+def unet_block_prefix(i):
+    """state-dict prefix of the nn.Sequential of level i of a UnetGenerator: the outermost block keeps its submodule at index 1, every other block at
+    index 3 (behind LeakyReLU, conv, norm).  Inside: outermost -- down conv 0, up conv 3; middle -- down conv 1, down norm 2, up conv 5, up norm 6;
+    innermost -- down conv 1, up conv 3, up norm 4 (p2p_networks.py:204-230)"""
+    return "model.model." + ("1.model." + "3.model." * (i - 1) if i else "")
+
+
+def unet_layout(sd):
+    """(norm, ngf, num_downs, in_nc, out_nc) of a UnetGenerator state dict: a level exists while its down conv does; BatchNorm iff the second level's down
+    norm carries running statistics"""
+    depth = 0
+    while unet_block_prefix(depth + 1) + "1.weight" in sd:
+        depth += 1
+    w0 = sd["model.model.0.weight"]
+    norm = "batch" if unet_block_prefix(1) + "2.running_mean" in sd else "instance"
+    return norm, w0.shape[0], depth + 1, w0.shape[1], sd["model.model.3.weight"].shape[1]
+
+
+def build_unet_generator(sd, device, precision="f16", pre_tanh=False, finalize=True, norm=None):
+    """UnetGenerator (p2p_networks.py:132-236) as a HIP graph; the external output is the tanh map (``pre_tanh``: the map in front of it).
+
+    Stored tensors.  The reference's LeakyReLU is in place, so a block hands ``cat([leaky(x), up], 1)`` to its parent, whose ReLU acts on both halves;
+    relu(leaky(x)) = relu(x).  Per level i the graph therefore stores ONE down tensor s_i = leaky(d_i) (d_i the normalised down output; the next down
+    conv reads it as it is, the up conv of level i reads it through ReLU-on-read) and ONE up tensor relu(u_i), which is only ever read through that ReLU.
+    Down convs: BatchNorm folded + LeakyReLU in the conv epilogue, or conv + instance_norm(leaky) (the conv's bias cancels in the norm); the innermost
+    has no norm and a fused ReLU (its only reader is the ReLU in front of the up conv).  Up convs: gdt_net_conv_transposed4 of [relu(s_i), relu(u_(i+1))]
+    -- BatchNorm folded + fused ReLU, or followed by instance_norm(relu).  The outermost up conv has a bias and writes the external fp32 NCHW output.
+    Dropout (eval) is the identity."""
+    if precision not in ("f16", "f16x3"):
+        raise NotImplementedError("the U-Net generator runs in 'f16' or 'f16x3'; %r is a ResnetGenerator mode" % (precision,))
+    key_norm, ngf, num_downs, in_nc, out_nc = unet_layout(sd)
+    norm = norm or key_norm
+    if norm not in ("instance", "batch"):
+        raise NotImplementedError('normalization layer [%s] is not found' % norm)
+    if norm == "batch" and key_norm != "batch":
+        raise NotImplementedError("BatchNorm without running statistics (track_running_stats=False) has no inference form on the HIP path")
+    inorm = norm == "instance"
+    if inorm:
+        for width in (ngf, 2 * ngf, 4 * ngf, 8 * ngf):
+            if width & (width - 1) or width > 2048:
+                raise NotImplementedError("InstanceNorm on the HIP path needs a power-of-two channel count <= 2048: ngf = %d gives a layer of %d channels" % (ngf, width))
+    net, x = _open(device, precision, in_nc)
+    block = unet_block_prefix
+    last = num_downs - 1
+    # ---- down path: s[i] = the stored down tensor of level i
+    s = [net.conv(x, sd[block(0) + "0.weight"], sd.get(block(0) + "0.bias"), stride=2, pad=1, leaky=0.2)]
+    for i in range(1, num_downs):
+        key = block(i) + "1"
+        if i == last:
+            s.append(net.conv(s[-1], sd[key + ".weight"], sd.get(key + ".bias"), stride=2, pad=1, relu=True))
+        elif inorm:
+            s.append(net.instance_norm(net.conv(s[-1], sd[key + ".weight"], None, stride=2, pad=1), leaky=0.2))
+        else:
+            s.append(net.conv(s[-1], sd[key + ".weight"], sd.get(key + ".bias"), bn=_bn(sd, block(i) + "2"), stride=2, pad=1, leaky=0.2))
+    # ---- up path
+    u = -1
+    for i in range(last, 0, -1):
+        key, nkey = (block(i) + "3", block(i) + "4") if i == last else (block(i) + "5", block(i) + "6")
+        relu_a = i != last                       # (the innermost down tensor is stored with its ReLU applied)
+        if inorm:
+            u = net.instance_norm(net.conv_transposed4(s[i], sd[key + ".weight"], u, relu_a=relu_a), relu=True)
+        else:
+            u = net.conv_transposed4(s[i], sd[key + ".weight"], u, relu_a=relu_a, bias=sd.get(key + ".bias"), bn=_bn(sd, nkey), relu=True)
+    net.out_slot = net.conv_transposed4(s[0], sd[block(0) + "3.weight"], u, relu_a=True, bias=sd[block(0) + "3.bias"], out_f32=True, act=0 if pre_tanh else 1)
     if finalize:
         net.finalize()
     return net

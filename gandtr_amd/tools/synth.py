@@ -11,6 +11,7 @@ State-dict key names follow the reference modules:
                 (``features.<i>...``) plus ``pool.p`` (layers/pooling.py:40)
   HED        -- mdir/components/model/network/hed.py:30-45
   RCF        -- mdir/components/model/network/rcf.py:28-66
+  U-Net      -- mdir/components/model/network/p2p_networks.py:154-161, :197-230 (``model.model.<i>..``, nested through ``model.1`` / ``model.3``)
   PatchSampleF -- mdir/components/model/network/p2p_networks.py:628-636 (``mlp_<i>.{0,2}...``)
 """
 import math
@@ -106,6 +107,35 @@ def discriminator_state(seed=0, norm="instance", ndf=64, n_layers=3, in_nc=3, ga
             _bn(sd, seed, "model.%d" % (i + 1), cn)
         i, c = i + 3, cn
     _conv(sd, seed, "model.%d" % i, 1, c, 4, True, g)
+    return sd
+
+
+def unet_state(seed=0, norm="instance", ngf=64, num_downs=8, in_nc=3, out_nc=3, gain=0.2, up_gain=1.0, out_gain=1.0):
+    """UnetGenerator state dict (p2p_networks.py:132-236).  Level i's nn.Sequential is at ``model.model.`` (outermost; submodule at index 1) or
+    ``model.model.1.model.`` + (i - 1) times ``3.model.``; down conv at index 0 (outermost) or 1, up conv at 3 (outermost, innermost) or 5, norms at
+    2 / 6 (innermost: 4).  ``norm='instance'``: N(0, gain) conv weights, biases on every conv
+    (use_bias); ``norm='batch'``: kaiming-scaled weights (an up conv's fan-in counted as the 4 taps x cin that meet one output pixel, times ``up_gain``), no
+    conv bias but on the outermost up conv, non-trivial BatchNorm running statistics and affine parameters.  The outermost up conv (no norm behind it) is
+    N(0, out_gain * sqrt(2 / (4 cin))) in both cases, so that the pre-tanh map is O(1)."""
+    sd = {}
+    inorm = norm == "instance"
+    widths = [ngf * min(2 ** i, 8) for i in range(num_downs)]          # inner_nc of level i
+    block = lambda i: "model.model." + ("1.model." + "3.model." * (i - 1) if i else "")
+    for i in range(num_downs):
+        last, outer = i == num_downs - 1, i == 0
+        cin_down = in_nc if outer else widths[i - 1]
+        cout_up = out_nc if outer else widths[i - 1]
+        cin_up = widths[i] if last else 2 * widths[i]
+        down, up = block(i) + ("0" if outer else "1"), block(i) + ("3" if outer or last else "5")
+        _conv(sd, seed, down, widths[i], cin_down, 4, inorm, gain if inorm else None)
+        if outer:
+            _conv(sd, seed, up, cout_up, cin_up, 4, True, out_gain * math.sqrt(2.0 / (4 * cin_up)), transposed=True)
+        else:
+            _conv(sd, seed, up, cout_up, cin_up, 4, inorm, gain if inorm else up_gain * math.sqrt(2.0 / (4 * cin_up)), transposed=True)
+        if not inorm and not outer:
+            if not last:
+                _bn(sd, seed, block(i) + "2", widths[i])
+            _bn(sd, seed, block(i) + ("4" if last else "6"), cout_up)
     return sd
 
 

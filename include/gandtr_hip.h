@@ -99,6 +99,16 @@ int gdt_net_conv_dilated(gdt_net* net, int in_tensor, const gdt_conv_desc* desc,
  * k4 / pad 1 layers with cin % 64 == 0 run on conv4x4_halo.hip (f16), everything else on the generic implicit-GEMM kernels. */
 int gdt_net_conv_leaky(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, float slope, const float* weight, const float* bias,
                        const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor);
+/* [nn.ReLU] nn.ConvTranspose2d(cin_a + cin_b, cout, kernel_size=4, stride=2, padding=1) (+ folded BatchNorm2d(eval), as gdt_net_conv) (+ ReLU: relu) of the
+ * channel concatenation torch.cat([a, b], 1): the up-convolutions of UnetSkipConnectionBlock (p2p_networks.py:205-221, :236).  in_b = -1: one input (the
+ * innermost block).  relu_a: ReLU applied to in_a as it is read (in_b is read as stored).  weight: host fp32 [cin_a + cin_b][cout][4][4], in_a's channels
+ * first; bias and the four BatchNorm vectors may be NULL.  out_f32_nchw = 0: internal output tensor of 2H x 2W (cout % 8 == 0, act 0); 1: external fp32 NCHW
+ * output with `act` (0 none, 1 tanh, 2 sigmoid), out_tensor receives the slot.  Precision modes f16 and f16x3.  In f16, layers with cin_a % 64 == 0,
+ * cin_b % 64 == 0, cout % 64 == 0 and an internal output run as ONE launch of conv4x4t_halo.hip, which reads both inputs itself; everything else (and
+ * everything with GDT_CONV4X4T_HALO=0) runs as a copy that writes the concatenation (+ ReLU) once and the four sub-pixel phases of 2 x 2 taps on the
+ * generic implicit-GEMM kernels (gdt_net_plan_summary count [15]). */
+int gdt_net_conv_transposed4(gdt_net* net, int in_a, int in_b, int relu_a, int cout, const float* weight, const float* bias, const float* bn_gamma,
+                             const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps, int relu, int out_f32_nchw, int act, int* out_tensor);
 
 /* nn.InstanceNorm2d(affine=False, eps) (+ fused ReLU) (+ fused residual add AFTER the norm): p2p_networks.py:29,:272,:505 */
 int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, int residual_tensor, int* out_tensor);
@@ -208,12 +218,13 @@ int gdt_net_flops(gdt_net* net, int n, int rh, int rw, double* flops);
  * [11] of those on any special form (a patch kernel, a fused launch): 0 -- dilation runs on the generic implicit-GEMM kernels only; with n_counts >= 14 also
  * [12] the launches of the pool-head ops (gdt_net_pool_head: fixed by the layers present, whatever the batch and the number of regions) and [13] those
  * among them that read the feature map (one per op); with n_counts >= 15 also [14] the conv launches that run on the 4x4 patch kernel (conv4x4_halo.hip;
- * none with GDT_CONV4X4_HALO=0).  (Diagnostics / tests; no reference counterpart.) */
+ * none with GDT_CONV4X4_HALO=0); with n_counts >= 16 also [15] the transposed 4x4 convs (gdt_net_conv_transposed4) that run as one launch of
+ * conv4x4t_halo.hip (none with GDT_CONV4X4T_HALO=0).  (Diagnostics / tests; no reference counterpart.) */
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts);
 
 /* Per-op timing for bench.py's roofline line: when enabled, gdt_net_forward records HIP events on the caller's stream
  * around every op.  gdt_net_profile_read (after the forward) returns per op: kind (0 input, 1 conv, 2 instance-norm,
- * 3 maxpool, 4 gem, 5 tap, 6 hed, 7 rcf head), the conv kernel variant (BM*1000+BN: conv_igemm_kernel<BM,BN>; 900000+BN:
+ * 3 maxpool, 4 gem, 5 tap, 6 hed, 7 rcf head, 8 pool head, 9 channel concatenation), the conv kernel variant (BM*1000+BN: conv_igemm_kernel<BM,BN>; 900000+BN:
  * conv3x3_halo_kernel<BN>), elapsed ms and the algorithmic FLOPs.  No reference counterpart (the reference has wall-clock StopWatch only, mdir/tools/stats.py:48-68). */
 int gdt_net_set_profiling(gdt_net* net, int enable);
 int gdt_net_profile_read(gdt_net* net, int max_ops, int* n_ops, int* kinds, int* tile_n, double* ms, double* flops);
