@@ -26,6 +26,12 @@ class IngestItem(ctypes.Structure):
                 ("out_w", c_int), ("out_h", c_int), ("dst_hwc", c_void_p), ("dst_chw", c_void_p)]
 
 
+class CropItem(ctypes.Structure):
+    """struct gdt_crop_item (include/gandtr_hip.h)."""
+    _fields_ = [("src", c_void_p), ("h", c_int), ("w", c_int), ("x0", c_int), ("y0", c_int), ("cw", c_int), ("ch", c_int),
+                ("flip_src", c_int), ("flip_dst", c_int), ("dst_chw", c_void_p)]
+
+
 class JpegInfo(ctypes.Structure):
     """struct gdt_jpeg_info (include/gandtr_hip.h)."""
     _fields_ = [("width", c_int), ("height", c_int), ("ncomp", c_int), ("hs", c_int * 4), ("vs", c_int * 4), ("tq", c_int * 4),
@@ -140,6 +146,9 @@ SIGNATURES = {
     "gdt_ingest_batch_workspace_bytes": (c_int, [POINTER(IngestItem), c_int, c_int, POINTER(c_size_t)]),
     "gdt_ingest_resize_u8_batch": (c_int, [POINTER(IngestItem), c_int, c_int, POINTER(c_float), POINTER(c_float), c_void_p, c_size_t,
                                            c_void_p]),
+    "gdt_crop_resize_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "gdt_crop_resize_u8_batch": (c_int, [POINTER(CropItem), c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_void_p, c_size_t,
+                                         c_void_p]),
     "gdt_jpeg_parse": (c_int, [c_void_p, c_size_t, POINTER(JpegInfo)]),
     "gdt_jpeg_extract_scan": (c_int, [c_void_p, c_size_t, POINTER(JpegInfo), c_void_p, POINTER(ctypes.c_uint)]),
     "gdt_jpeg_parse_batch": (c_int, [POINTER(c_void_p), POINTER(c_size_t), c_int, POINTER(JpegInfo), _IP, c_int]),

@@ -1,7 +1,12 @@
 """CPU image preprocessing attached to hub models as ``.transform`` -- host mirror of
 mdir/components/data/transform/__init__.py:37-46 (initialize_transforms), core_transforms.py:25-100
 (Compose, ToTensor, Normalize, Pil2Numpy) and photometric_transforms.py:28-36 / functional.py:140-161 (ApplyClahe).
-Host-side only (out of the HIP scope); CLAHE needs opencv and raises ImportError without it."""
+Host-side only (out of the HIP scope); CLAHE needs opencv and raises ImportError without it.
+The geometric steps of the GAN scenarios' data (augmentation_transforms.py:24-164: mirror, center_crop, square_crop, downscale, scalecrop,
+centerscalecrop) run without opencv: the bilinear step is a numpy restatement of cv2's INTER_LINEAR float path."""
+import math
+import random
+
 import numpy as np
 import torch
 
@@ -116,7 +121,191 @@ class Normalize(GenericTransform):
         return out
 
 
-TRANSFORMS = {"totensor": ToTensor, "normalize": Normalize, "pil2np": Pil2Numpy, "apply_clahe": ApplyClahe}
+#
+# Crop, scale and flip: the steps ``mirror``, ``center_crop``, ``square_crop``, ``downscale``, ``scalecrop`` and ``centerscalecrop`` of the reference's
+# chains, written from the behaviour tests/golden/gan_data.npz records of its classes.  Every class states its geometry ONCE, in ``ops(shapes, rng)``:
+# per pic one of None (unchanged), ("crop", y0, x0, ch, cw), ("flip",), ("bilinear", y0, x0, ch, cw, ow, oh) or ("lanczos", n), asking ``rng`` for
+# exactly the numbers the reference asks ``random`` for, in its order, so that ``random.seed(s)`` reproduces its crops.  ``__call__`` applies the ops to
+# numpy pics; gandtr_amd.ingest.DeviceTransform.plan composes the same ops into one source box + flips + resampler per pic for the device.
+#
+
+def parse_tuple(text, dtype=int):
+    """"256_256" -> (256, 256); anything that is not a string is taken as the tuple it already is"""
+    return tuple(dtype(part) for part in text.split("_")) if isinstance(text, str) else tuple(text)
+
+
+def linear_taps(n_in, n_out):
+    """cv2's INTER_LINEAR float path for one axis (what ``cv2.resize`` of a float32 image computes): per output index the two source taps and the fp32
+    weight of the second.  The coordinate is formed in double and CAST TO float32 before the floor, the clamps are to the source extent."""
+    d = np.arange(n_out, dtype=np.float64)
+    f = ((d + 0.5) * (n_in / float(n_out)) - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int64)
+    f = f - s.astype(np.float32)
+    low, high = s < 0, s >= n_in - 1
+    s[low], f[low] = 0, 0
+    s[high], f[high] = n_in - 1, 0
+    return s, np.minimum(s + 1, n_in - 1), f.astype(np.float32)
+
+
+def bilinear_resize(pic, out_w, out_h):
+    """``cv2.resize(pic, (out_w, out_h))`` for a float32 H x W [x C] array, restated in numpy (cv2 is not a dependency): the horizontal blend first, then
+    the vertical one, in fp32 with the weights ``1.f - f`` and ``f``"""
+    pic = np.asarray(pic, dtype=np.float32)
+    sx0, sx1, fx = linear_taps(pic.shape[1], out_w)
+    sy0, sy1, fy = linear_taps(pic.shape[0], out_h)
+    tail = (1,) * (pic.ndim - 2)
+    fx, fy = fx.reshape((1, -1) + tail), fy.reshape((-1, 1) + tail)
+    rows = pic[:, sx0] * (np.float32(1) - fx) + pic[:, sx1] * fx
+    return rows[sy0] * (np.float32(1) - fy) + rows[sy1] * fy
+
+
+class GeometricTransform(GenericTransform):
+    def __init__(self, **params):
+        super().__init__(params)
+
+    def ops(self, shapes, rng):
+        raise NotImplementedError
+
+    def __call__(self, *pics):
+        if not all(isinstance(p, np.ndarray) for p in pics):
+            raise RuntimeError("%s works on numpy pics (put pil2np first), got %s" % (type(self).__name__, [type(p).__name__ for p in pics]))
+        ops = self.ops([p.shape[:2] for p in pics], random)
+        if all(op is None for op in ops):
+            return pics
+        return [apply_op(p, op) for p, op in zip(pics, ops)]
+
+
+def _thumbnail(pic, n):
+    """Pillow's LANCZOS thumbnail of a float [0, 1] pic: quantised to 8 bits by truncation on the way in, back to float32 / 255 on the way out"""
+    from PIL import Image
+    image = Image.fromarray((pic * 255).astype(np.uint8))
+    image.thumbnail((n, n), Image.LANCZOS)
+    return np.asarray(image).astype(np.float32) / 255.0
+
+
+def apply_op(pic, op):
+    if op is None:
+        return pic
+    kind, args = op[0], op[1:]
+    if kind == "flip":
+        return np.ascontiguousarray(pic[:, ::-1])
+    if kind == "lanczos":
+        return _thumbnail(pic, args[0])
+    y0, x0, ch, cw = args[:4]
+    crop = pic[y0:y0 + ch, x0:x0 + cw]
+    if kind == "crop":
+        return crop
+    if kind == "bilinear":
+        return bilinear_resize(crop, args[4], args[5])
+    raise ValueError(op)
+
+
+class RandomHorizontalFlip(GeometricTransform):
+    """with probability ``p`` (one ``rng.random()`` per item) all pics of the item are mirrored left-right"""
+
+    def __init__(self, p=0.5):
+        super().__init__(p=float(p))
+
+    def ops(self, shapes, rng):
+        flip = rng.random() < self.params["p"]
+        return [("flip",) if flip else None for _ in shapes]
+
+
+def _centred(extent, wanted):
+    """first index of ``wanted`` centred pixels out of ``extent``: an odd surplus leaves the extra pixel at the far end"""
+    return (extent - wanted) // 2
+
+
+class CenterCrop(GeometricTransform):
+    """``center_crop:W_H``: the middle H x W pixels of every pic"""
+
+    def __init__(self, size):
+        w, h = parse_tuple(size, int)
+        super().__init__(size=np.array([h, w]))
+
+    def ops(self, shapes, rng):
+        h, w = (int(v) for v in self.params["size"])
+        for shape in shapes:
+            if shape[0] < h or shape[1] < w:
+                raise ValueError("center_crop: a %d x %d pic is smaller than the %d x %d crop" % (shape[0], shape[1], h, w))
+        return [("crop", _centred(shape[0], h), _centred(shape[1], w), h, w) for shape in shapes]
+
+
+class SquareCrop(GeometricTransform):
+    """``square_crop``: the middle square of every pic, its side the pic's shorter one"""
+
+    def ops(self, shapes, rng):
+        acc = []
+        for h, w in shapes:
+            side = min(h, w)
+            acc.append(("crop", _centred(h, side), _centred(w, side), side, side))
+        return acc
+
+
+class Downscale(GeometricTransform):
+    """``downscale:N``: pics whose longer side exceeds N are shrunk to fit N x N, aspect kept (Pillow's LANCZOS thumbnail, as the reference does it)"""
+
+    def __init__(self, size):
+        super().__init__(size=int(size))
+
+    def ops(self, shapes, rng):
+        n = self.params["size"]
+        return [("lanczos", n) if max(shape) > n else None for shape in shapes]
+
+
+class RandomScaleCrop(GeometricTransform):
+    """``scalecrop:W_H[:lo_hi]``: a random crop of a randomly scaled pic, done as ONE crop of H / s x W / s pixels (rounded up) resized to W x H, with
+    s = lowest + u * (hi - lowest), u = ``rng.random()``, and lowest = the larger of ``lo`` and the scale at which the crop still fits.  The crop is
+    placed by ``rng.randint`` (row first, then column) within the SMALLEST extents over the item's pics and shared by all of them.  Kept as the reference
+    behaves: when the first two pics (or the only one) have equal shapes and that shape is the target, the item passes unchanged and nothing is drawn;
+    the fit test and ``lowest`` compare W with the pics' height and H with their width."""
+
+    def __init__(self, size, scale=(0.5, 0.8)):
+        w, h = parse_tuple(size, int)
+        low, high = parse_tuple(scale, float)
+        super().__init__(size=np.array([w, h]), scale=(float(low), float(high)))
+
+    def _untouched(self, shapes):
+        w, h = (int(v) for v in self.params["size"])
+        alike = len(shapes) == 1 or tuple(shapes[0]) == tuple(shapes[1])
+        return alike and tuple(shapes[0]) == (h, w)
+
+    def _scale(self, low, rng):
+        return rng.random() * (self.params["scale"][1] - low) + low
+
+    def _place(self, slack, rng):
+        return rng.randint(0, slack)
+
+    def ops(self, shapes, rng):
+        if self._untouched(shapes):
+            return [None] * len(shapes)
+        w, h = (int(v) for v in self.params["size"])
+        rows, cols = min(int(s[0]) for s in shapes), min(int(s[1]) for s in shapes)
+        assert w <= rows and h <= cols, "target (%d, %d) against the smallest pic (%d, %d)" % (w, h, rows, cols)
+        scale = self._scale(max(w / rows, h / cols, self.params["scale"][0]), rng)
+        ch, cw = math.ceil(h / scale), math.ceil(w / scale)
+        assert ch <= rows and cw <= cols, "a %d x %d crop does not fit %d x %d" % (ch, cw, rows, cols)
+        y0 = self._place(rows - ch, rng)
+        x0 = self._place(cols - cw, rng)
+        return [("bilinear", y0, x0, ch, cw, w, h) for _ in shapes]
+
+
+class CenterScaleCrop(RandomScaleCrop):
+    """``centerscalecrop:W_H[:s]``: the same crop-and-resize at the fixed scale s, centred in the smallest extents; draws nothing"""
+
+    def __init__(self, size, scale=0.6):
+        super().__init__(size, (float(scale), float(scale)))
+
+    def _scale(self, low, rng):
+        return self.params["scale"][0]
+
+    def _place(self, slack, rng):
+        return slack // 2
+
+
+TRANSFORMS = {"totensor": ToTensor, "normalize": Normalize, "pil2np": Pil2Numpy, "apply_clahe": ApplyClahe,
+              "mirror": RandomHorizontalFlip, "center_crop": CenterCrop, "square_crop": SquareCrop, "downscale": Downscale,
+              "scalecrop": RandomScaleCrop, "centerscalecrop": CenterScaleCrop}
 
 
 def initialize_transforms(augmentations, mean_std):

@@ -6,12 +6,15 @@ Reference (per image, on the CPU through Pillow / numpy): ``imresize`` = ``img.t
 Here the decoded uint8 H x W x 3 image is uploaded once; resize (bit-identical to Pillow), [0, 1] scaling, optional CLAHE and
 normalisation run as HIP launches (gandtr_amd/csrc/ingest.hip, clahe.hip).  The size / reducing-gap plan below mirrors Pillow's
 Python layer (PIL/Image.py: thumbnail, resize); JPEG decoding stays on the host.  No CPU fallback."""
+import collections
 import ctypes
 import math
+import random
 
 import torch
 
 from . import _hip
+from .components.data import transform as host
 
 
 def thumbnail_size(width, height, imsize):
@@ -164,16 +167,69 @@ def ingest_many(images, imsize, mean, std, clahe_clip=None, clahe_grid=8, stream
     return [clahe.clahe_lab(u[None], clahe_clip, clahe_grid, None, (mean, std))[0] for u in unit]
 
 
+def crop_resize(images, boxes, out_w, out_h, flips=None, mean_std=None, out=None):
+    """``cv2.resize(pic[y0:y0 + ch, x0:x0 + cw], (out_w, out_h))`` + ``totensor | normalize`` for a list of decoded uint8 H x W x 3 device tensors of
+    different sizes in ONE launch (gdt_crop_resize_u8_batch, gandtr_amd/csrc/crop_resize.hip).  ``boxes``: per image ``(y0, x0, ch, cw)``; ``flips``:
+    per image ``(flip_src, flip_dst)`` -- mirror the box before / the output after the resample; ``mean_std`` None = the unit image.  A box of the
+    output's size is a crop + convert, bit-identical to ``((u8 / 255) - mean) / std``.  ``out``: an fp32 N x 3 x out_h x out_w tensor or a list of N
+    contiguous fp32 3 x out_h x out_w views (slices of several tensors: the call takes one destination per image); default a new tensor.  Returns it."""
+    lib = _hip.load()
+    n = len(images)
+    if n == 0:
+        raise ValueError("crop_resize needs at least one image")
+    dev = images[0].device
+    images = [img.contiguous() for img in images]
+    for img in images:
+        if not img.is_cuda or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or img.device != dev:
+            raise ValueError("crop_resize needs uint8 H x W x 3 tensors on one HIP device")
+    if out is None:
+        out = torch.empty((n, 3, out_h, out_w), dtype=torch.float32, device=dev)
+    dsts = list(out)                                                     # (a tensor's rows, or the caller's list of views)
+    if len(dsts) != n or any(d.shape != (3, out_h, out_w) or d.dtype != torch.float32 or d.device != dev or not d.is_contiguous() for d in dsts):
+        raise ValueError("crop_resize: out must be %d contiguous fp32 3 x %d x %d tensors on the images' device" % (n, out_h, out_w))
+    items = (_hip.CropItem * n)()
+    for i, (img, (y0, x0, ch, cw)) in enumerate(zip(images, boxes)):
+        it = items[i]
+        it.src, it.h, it.w = img.data_ptr(), img.shape[0], img.shape[1]
+        it.x0, it.y0, it.cw, it.ch = int(x0), int(y0), int(cw), int(ch)
+        if flips is not None:
+            it.flip_src, it.flip_dst = int(bool(flips[i][0])), int(bool(flips[i][1]))
+        it.dst_chw = dsts[i].data_ptr()
+    mean, std = mean_std if mean_std is not None else (None, None)
+    need = ctypes.c_size_t()
+    with torch.cuda.device(dev):
+        _hip.check(lib.gdt_crop_resize_workspace_bytes(n, out_w, out_h, ctypes.byref(need)))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        _hip.check(lib.gdt_crop_resize_u8_batch(items, n, out_w, out_h, _f(mean, 3), _f(std, 3), ws.data_ptr(), ws.numel(),
+                                                torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+Geometry = collections.namedtuple("Geometry", "box flip_src resample flip_dst out")
+Geometry.__doc__ = """What a chain's geometric steps do to one pic: the source ``box`` (y0, x0, ch, cw) in the decoded image, ``flip_src`` (mirror the box),
+``resample`` -- ("none",), ("bilinear", ow, oh) or ("lanczos", n) (Pillow's thumbnail to n) --, ``flip_dst`` (mirror the result), ``out`` = (h, w) of it."""
+
+_RESAMPLERS = ("scalecrop", "centerscalecrop", "downscale")
+_CROPS = ("center_crop", "square_crop")
+
+
 class DeviceTransform:
     """Device-side counterpart of the ``.transform`` the hub attaches to a network (mdir/hub/model.py:38-42 builds it from
-    ``runtime.data.transforms``, e.g. ``pil2np | apply_clahe:1.0 | totensor | normalize``): takes the DECODED image as a uint8
-    H x W x 3 tensor on the device (optionally the ``imsize`` of the dataset's ``imresize``) and returns the fp32 3 x h x w tensor
-    the network expects.  Supported steps: pil2np, apply_clahe[:clip[:grid[:lab]]], totensor, normalize."""
+    ``runtime.data.transforms``, e.g. ``pil2np | apply_clahe:1.0 | totensor | normalize``) and of the ``transforms:`` chain of a dataset
+    (mdir/components/data/dataset/__init__.py:35-41, e.g. ``pil2np | scalecrop:256_256:0.8_1 | totensor | normalize``): takes DECODED images as uint8
+    H x W x 3 tensors on the device and returns the fp32 3 x h x w tensors the network expects.  Supported steps: pil2np, apply_clahe[:clip[:grid[:lab]]],
+    totensor, normalize and the geometric steps scalecrop:W_H[:lo_hi], centerscalecrop:W_H[:s], downscale:N, center_crop:W_H, square_crop, mirror[:p]
+    (augmentation_transforms.py:24-164) in the chain shape ``crops / mirrors, at most one resampling step, mirrors``; apply_clahe comes after them.
+
+    ``__call__(img, imsize=None)`` serves chains without geometric steps (the hub's).  A chain with them runs as ``plan`` (host, draws the random numbers
+    the reference draws) + ``apply_many`` (device, one crop-resize launch for a whole batch)."""
 
     def __init__(self, augmentations, mean_std):
         self.mean, self.std = [float(v) for v in mean_std[0]], [float(v) for v in mean_std[1]]
         self.clahe_clip, self.clahe_grid, self.normalize = None, 8, False
         self.spec = augmentations
+        self.geometric = []                                                # (name, host transform): the one statement of each step's geometry
+        resampled = False
         for step in [t.strip() for t in augmentations.split("|") if t.strip()]:
             name, *args = step.split(":")
             if name in ("pil2np", "totensor"):
@@ -185,12 +241,90 @@ class DeviceTransform:
                 self.clahe_grid = int(args[1]) if len(args) > 1 else 8
                 if len(args) > 2 and args[2].lower() != "lab":
                     raise NotImplementedError("Colorspace %s is not supported on the HIP path" % args[2])
+            elif name in _RESAMPLERS + _CROPS + ("mirror",):
+                if self.clahe_clip is not None:
+                    raise NotImplementedError("apply_clahe before a geometric step is not supported on the HIP path: '%s'" % augmentations)
+                if resampled and name != "mirror":
+                    raise NotImplementedError("only mirrors may follow a resampling step on the HIP path: '%s'" % augmentations)
+                resampled = resampled or name in _RESAMPLERS
+                self.geometric.append((name, host.TRANSFORMS[name](*args)))
             else:
                 raise KeyError("transform '%s' has no device implementation" % name)
 
+    def _mean_std(self):
+        return (self.mean, self.std) if self.normalize else ([0.0] * 3, [1.0] * 3)
+
     def __call__(self, img, imsize=None):
-        mean, std = (self.mean, self.std) if self.normalize else ([0.0] * 3, [1.0] * 3)
+        if self.geometric:
+            raise NotImplementedError("a chain with geometric steps runs through plan() + apply_many(): '%s'" % self.spec)
+        mean, std = self._mean_std()
         return ingest(img, imsize, mean, std, self.clahe_clip, self.clahe_grid)
+
+    def plan(self, shapes, rng=random):
+        """One ``Geometry`` per pic of ONE item (``shapes``: their decoded (h, w)).  Pure host code; draws from ``rng`` exactly what the reference's
+        transforms draw on the same pics, in their order, so ``random.seed(s)`` reproduces its crops and flips."""
+        state = [dict(box=(0, 0, int(h), int(w)), flip_src=False, resample=("none",), flip_dst=False, out=(int(h), int(w))) for h, w in shapes]
+        for _, step in self.geometric:
+            for st, op in zip(state, step.ops([st["out"] for st in state], rng)):
+                if op is None:
+                    continue
+                if op[0] == "flip":
+                    key = "flip_src" if st["resample"] == ("none",) else "flip_dst"
+                    st[key] = not st[key]
+                    continue
+                assert st["resample"] == ("none",), self.spec               # (the constructor refused such a chain)
+                if op[0] == "lanczos":
+                    size = thumbnail_size(st["out"][1], st["out"][0], op[1])
+                    if size is not None:
+                        st["resample"], st["out"] = ("lanczos", op[1]), (size[1], size[0])
+                    continue
+                y0, x0, ch, cw = op[1:5]
+                by, bx, _, bw = st["box"]
+                st["box"] = (by + y0, bx + (bw - x0 - cw if st["flip_src"] else x0), ch, cw)       # (a crop of the mirrored box, in unmirrored columns)
+                st["out"] = (ch, cw)
+                if op[0] == "bilinear":
+                    st["resample"], st["out"] = ("bilinear", op[5], op[6]), (op[6], op[5])
+        return [Geometry(**st) for st in state]
+
+    def apply_many(self, decoded_items, plans):
+        """``decoded_items``: per item its pics as decoded uint8 H x W x 3 device tensors; ``plans``: per item what ``plan`` returned for it.  Returns the
+        collated batch: one fp32 N x 3 x h x w tensor per column.  Every pic without a LANCZOS step goes through ONE gdt_crop_resize_u8_batch launch
+        per distinct output size (one for the whole batch when the columns agree, as in every published scenario); LANCZOS pics go through
+        ``resize_many`` on the cropped view (Pillow's integer arithmetic: the reference's ``(pic * 255).astype(uint8)`` round trip is the identity
+        on decoded 8-bit data).  Items that end with different sizes raise RuntimeError, as ``default_collate`` does."""
+        n, ncols = len(decoded_items), len(decoded_items[0])
+        dev = decoded_items[0][0].device
+        mean_std = self._mean_std() if self.clahe_clip is None else None         # (CLAHE takes the unit image and normalises itself)
+        columns = []
+        for c in range(ncols):
+            sizes = [plans[i][c].out for i in range(n)]
+            if any(s != sizes[0] for s in sizes):
+                raise RuntimeError("stack expects each tensor to be equal size, but got %s at entry 0 and %s at entry %d" % (
+                    [3, *sizes[0]], [3, *next(s for s in sizes if s != sizes[0])], next(i for i, s in enumerate(sizes) if s != sizes[0])))
+            columns.append(torch.empty((n, 3, sizes[0][0], sizes[0][1]), dtype=torch.float32, device=dev))
+        direct, lanczos = {}, []
+        for i in range(n):
+            for c in range(ncols):
+                g = plans[i][c]
+                (lanczos if g.resample[0] == "lanczos" else direct.setdefault(g.out, [])).append((i, c))
+        for (oh, ow), where in direct.items():                              # straight into the columns: one destination view per pic
+            crop_resize([decoded_items[i][c] for i, c in where], [plans[i][c].box for i, c in where], ow, oh,
+                        [(plans[i][c].flip_src, plans[i][c].flip_dst) for i, c in where], mean_std, [columns[c][i] for i, c in where])
+        if lanczos:
+            views = []
+            for i, c in lanczos:
+                g = plans[i][c]
+                y0, x0, ch, cw = g.box
+                view = decoded_items[i][c][y0:y0 + ch, x0:x0 + cw]
+                views.append((view.flip(1) if g.flip_src else view).contiguous())
+            outs = resize_many(views, [_plan(v, plans[i][c].resample[1]) for v, (i, c) in zip(views, lanczos)], want_u8=False, mean_std=mean_std,
+                               want_chw=True)[1]
+            for o, (i, c) in zip(outs, lanczos):
+                columns[c][i].copy_(o.flip(2) if plans[i][c].flip_dst else o)
+        if self.clahe_clip is not None:
+            from . import clahe
+            columns = [clahe.clahe_lab(col, self.clahe_clip, self.clahe_grid, None, self._mean_std()) for col in columns]
+        return columns
 
     def __repr__(self):
         return "%s(%s, mean=%s, std=%s)" % (type(self).__name__, self.spec, self.mean, self.std)

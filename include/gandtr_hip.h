@@ -466,6 +466,30 @@ int gdt_ingest_batch_workspace_bytes(const gdt_ingest_item* items, int n, int c,
 int gdt_ingest_resize_u8_batch(const gdt_ingest_item* items, int n, int c, const float* mean, const float* std, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* Crop + bilinear resize + normalise of a LIST of decoded RGB images in one launch: the geometric steps of the GAN scenarios' data
+ * (mdir/examples/iccv23/parameters/_gan_data.yml: pil2np | scalecrop:256_256:0.8_1 | totensor | normalize).
+ * Replaces  cv2.resize(pic[y0:y1, x0:x1], (ow, oh))  of RandomScaleCrop._crop_downscale / CenterScaleCrop
+ * (mdir/components/data/transform/augmentation_transforms.py:100-164), the slices of CenterCrop / SquareCrop (:35-76),
+ * RandomHorizontalFlip (:24-32) and the  totensor | normalize  that follow (core_transforms.py:35-100).
+ * Arithmetic: cv2's INTER_LINEAR float path per axis -- scale = n_in / (double) n_out, f = (float)((d + 0.5) * scale - 0.5),
+ * s = floor(f), f -= s, s clamped to the CROP BOX (never the image: the reference slices first), taps s and min(s + 1, n_in - 1) with
+ * fp32 weights 1.f - f and f, horizontal blend then vertical blend in fp32 on u8 / 255.f.  The tap tables are built on the host in
+ * doubles by the call itself (the float32 cast of the coordinate is part of the result) and uploaded with the descriptors into the
+ * workspace.  flip_src mirrors the box before the resample, flip_dst the output after it.  A box of the output's size makes the call a
+ * crop + convert, bit-identical to ((u8 / 255.f) - mean[c]) / std[c].  Every item writes [3][out_h][out_w] fp32 (normally a slice of
+ * one N x 3 x out_h x out_w tensor); mean / std: host float[3], NULL = 0 / 1.  items: host array.  All argument checks precede the
+ * first HIP call. */
+typedef struct gdt_crop_item {
+    const unsigned char* src;      /* device [h][w][3] uint8, the whole decoded image */
+    int h, w;
+    int x0, y0, cw, ch;            /* crop box inside it */
+    int flip_src, flip_dst;
+    float* dst_chw;                /* device [3][out_h][out_w] fp32 */
+} gdt_crop_item;
+int gdt_crop_resize_workspace_bytes(int n, int out_w, int out_h, size_t* bytes);
+int gdt_crop_resize_u8_batch(const gdt_crop_item* items, int n, int out_w, int out_h, const float* mean, const float* std,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * JPEG decoding on the device (the first half of the ingest row)
  * Replaces  pil_loader: Image.open(f).convert('RGB')  (mdir/external/cirtorch/datasets/datahelpers.py:39-47, called per image from

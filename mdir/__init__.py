@@ -4,6 +4,7 @@
     mdir.components.model.network          -> gandtr_amd.components.model.network   (MODEL_LABELS, initialize_model)
     mdir.components.data.wrapper           -> gandtr_amd.components.data.wrapper    (WRAPPERS_LABELS, initialize_wrappers)
     mdir.components.data.transform         -> gandtr_amd.components.data.transform  (initialize_transforms)
+    mdir.components.data.dataset           -> gandtr_amd.components.data.dataset    (DATASET_LABELS, initialize_dataset_loader: the GAN scenarios' data)
     mdir.learning / mdir.learning.network  -> gandtr_amd.learning(.network)         (NETWORKS, initialize_network, load_network)
     mdir.learning.validation               -> gandtr_amd.learning.validation        (initialize_validation, SingleValidation, ...)
     mdir.components.optim.score            -> gandtr_amd.components.optim.score     (SCORES, initialize_score: cirdatasetap)
@@ -37,6 +38,7 @@ _ALIASES = {
     "mdir.components.data": "gandtr_amd.components.data",
     "mdir.components.data.wrapper": "gandtr_amd.components.data.wrapper",
     "mdir.components.data.transform": "gandtr_amd.components.data.transform",
+    "mdir.components.data.dataset": "gandtr_amd.components.data.dataset",
     "mdir.learning": "gandtr_amd.learning",
     "mdir.learning.network": "gandtr_amd.learning.network",
     "mdir.learning.checkpoints": "gandtr_amd.learning.checkpoints",

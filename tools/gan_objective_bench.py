@@ -8,7 +8,10 @@ is compared inside this process, alternating, after a warm-up of every variant:
       the terms.
 Each timed sample is a burst of calls between two events divided by the burst length.  Event-timed bursts run at higher clocks than a sustained run: they
 rank variants; bench.py quotes speed.  Prints one JSON line and writes it to the path given (default profiles/gan_objective_1gpu.json).
-usage: tools/gan_objective_bench.py [iters] [out.json]      (default 10 timed bursts per variant)"""
+With ``--data DIR`` the inputs of (b) are one batch of the scenarios' own training data instead of synthetic tensors: DIR/train_day.txt and DIR/train_night.txt
+(one file name per line) over the images in DIR/ims, read through the ``train`` block of parameters/_gan_data.yml (RandomDomainsPair,
+``pil2np | scalecrop:256_256:0.8_1 | totensor | normalize``) by gandtr_amd.components.data.dataset.initialize_dataset_loader -- decode, crop and resize on the device.
+usage: tools/gan_objective_bench.py [iters] [out.json] [--data DIR]      (default 10 timed bursts per variant)"""
 import ctypes
 import json
 import os
@@ -24,6 +27,11 @@ from gandtr_amd.components.optim.criterion import compound       # noqa: E402
 from gandtr_amd.learning import epoch_iteration                  # noqa: E402
 from gandtr_amd.tools import synth                               # noqa: E402
 
+data_dir = None
+if "--data" in sys.argv:
+    at = sys.argv.index("--data")
+    data_dir = sys.argv[at + 1]
+    del sys.argv[at:at + 2]
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gan_objective_1gpu.json")
 dev = torch.device("cuda:0")
@@ -131,9 +139,28 @@ def naive_cyclegan(nets, X, Y):
     return loss_G_X + loss_G_Y + loss_D_X + loss_D_Y
 
 
+def data_batch(root, batch_size):
+    """one batch of parameters/_gan_data.yml's ``train`` block over the lists and images under ``root``"""
+    import random
+    import numpy as np
+    from gandtr_amd.components.data import dataset
+    params = {"dataset": {"name": "RandomDomainsPair", "dataset_X": os.path.join(root, "train_day.txt"), "dataset_Y": os.path.join(root, "train_night.txt"),
+                          "image_dir": os.path.join(root, "ims") + "/*", "size": batch_size},
+              "loader": {"batch_size": batch_size}, "transforms": "pil2np | scalecrop:256_256:0.8_1 | totensor | normalize",
+              "mean_std": [[0.5, 0.5, 0.5], [0.5, 0.5, 0.5]]}
+    loader = dataset.initialize_dataset_loader(None, "train", params, device=dev)
+    np.random.seed(0)
+    random.seed(0)
+    loader.dataset.prepare_epoch(None, None)
+    return next(iter(loader))
+
+
 def step_rows():
     shape = (16, 3, 256, 256)
-    X, Y = synth.synth_input(2, shape, 1.0, name="src").to(dev), synth.synth_input(2, shape, 1.0, name="tgt").to(dev)
+    if data_dir is not None:
+        X, Y = data_batch(data_dir, shape[0])
+    else:
+        X, Y = synth.synth_input(2, shape, 1.0, name="src").to(dev), synth.synth_input(2, shape, 1.0, name="tgt").to(dev)
     rows = {}
     adv = {"loss": "discriminator_loss", "criterion": {"loss": "mse"}}
     weights = {"adversarial": 1, "edge": 5, "hed": 1}
@@ -161,7 +188,7 @@ def step_rows():
 
 
 out = {"workload": "gdt_map_loss and the GAN scenarios' step_losses, synthetic weights, generator f16c, discriminator / HED f16",
-       "iters": iters, "kernel_burst": KERNEL_BURST, "step_burst": STEP_BURST, "float4_copy_rate_bytes_per_s": COPY_RATE}
+       "inputs": "synthetic" if data_dir is None else "RandomDomainsPair over " + data_dir, "iters": iters, "kernel_burst": KERNEL_BURST, "step_burst": STEP_BURST, "float4_copy_rate_bytes_per_s": COPY_RATE}
 with torch.no_grad():
     out["map_loss"] = kernel_rows()
     out["step_losses"] = step_rows()
