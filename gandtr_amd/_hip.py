@@ -93,6 +93,7 @@ SIGNATURES = {
     "gdt_net_instance_norm_leaky": (c_int, [c_void_p, c_int, c_float, c_float, _IP]),
     "gdt_net_conv_transposed4": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int,
                                          c_int, _IP]),
+    "gdt_net_conv_cat": (c_int, [c_void_p, c_int, c_int, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _IP]),
     "gdt_net_gem_l2n": (c_int, [c_void_p, c_int, c_float, c_float, c_float, _IP]),
     "gdt_net_pool_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, _IP]),
     "gdt_net_output_nchw": (c_int, [c_void_p, c_int, c_void_p, _IP]),

@@ -1,9 +1,9 @@
 """Model registry (plugin API) -- mirror of mdir/components/model/network/__init__.py:20-48 restricted to the
-architectures reachable from the hub entrypoints, the BASELINE configs, the published GAN scenarios' discriminators, CUT's ``featdown`` network and the pix2pix U-Net generator.  Unknown names raise KeyError like the
+architectures reachable from the hub entrypoints, the BASELINE configs, the published GAN scenarios' discriminators, CUT's ``featdown`` network, the pix2pix U-Net generator and the learnable photometric normalisation U-Nets (unet.py).  Unknown names raise KeyError like the
 reference (:48)."""
 import torch.nn as nn
 
-from . import cirnet, hed, p2p_networks, rcf
+from . import cirnet, hed, p2p_networks, rcf, unet
 
 
 class Identity(nn.Module):
@@ -24,6 +24,11 @@ MODEL_LABELS = {
     "cirnet": cirnet.init_cirnet,
     "hed_interpolation": hed.HedInterpolation,
     "rcf": rcf.RCF,
+    "p2p_unet": unet.P2pUNet,
+    "outconv_unet": unet.OutconvP2pUNet,
+    "shallow_p2p_unet": unet.ShallowP2pUNet,
+    "inconv_p2p_unet": unet.InconvP2pUNet,
+    "aligned_p2p_unet": unet.AlignedP2pUNet,
 }
 
 

@@ -66,7 +66,8 @@ __global__ __launch_bounds__(WGM * WGN * 64, 2) void conv4x4t_halo_kernel(const 
     const int nca = d.Cin >> 6, nchunks = (d.Cin + d.in2_cin) >> 6;
 
     // ---- halo loader: round r stages halo rows r * RPR .. + RPR - 1, eight lanes per row (one 16-byte channel group each); the swizzle
-    // chunk' = chunk ^ ((halo column >> 1) & 7) is applied to the SOURCE channel group (conv3x3_halo.hip)
+    // chunk' = chunk ^ ((halo column >> 1) & 7) is applied to the SOURCE channel group (conv3x3_halo.hip).  Local code: the same statements as
+    // gdt_stage_halo_cat (conv_device.h), which this kernel does not call -- through the helper it compiles to another schedule (238 VGPRs against 232)
     const int lrow = tid >> 3;
     auto issue_a = [&](int chunk, int stage, int r) {
         if (r * RPR + wave * 8 >= HROWS_PAD) return;               // wave-uniform: rows beyond the padded halo

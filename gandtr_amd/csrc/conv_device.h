@@ -84,6 +84,26 @@ __device__ __forceinline__ void gdt_halo_yx(int h, int& hy, int& hx) {
     static_assert((MAGIC * HW - 65536) * 2048 < 65536, "multiply-shift division by the halo width");
     hy = (h * MAGIC) >> 16; hx = h - hy * HW;
 }
+// One loader round of the (PH + 2) x HW halo of a PH x 16 patch, 64-channel chunk `chunk`, taken from `d.in` (chunks 0 .. nca - 1) or from `d.in2` (the rest): the
+// channel concatenation of the two tensors is never materialised (conv4x4t_halo.hip, conv3x3_cat_halo.hip).  Round r stages halo rows r * RPR .. + RPR - 1 of the
+// HROWS (padded to HROWS_PAD) into `stage_base`, eight lanes per row (one 16-byte channel group each); the zero ring, ragged edges and pad rows read `d.zeros`,
+// and the swizzle chunk' = chunk ^ ((halo column >> 1) & 7) is applied to the SOURCE channel group (conv3x3_halo.hip).  (y0 - 1, x0 - 1) = halo position (0, 0).
+template <int HW, int HROWS, int HROWS_PAD, int RPR>
+__device__ __forceinline__ void gdt_stage_halo_cat(const ConvLaunch& d, char* stage_base, int n, int y0, int x0, int nca, int chunk, int r, int wave, int lane, int lrow) {
+    if (r * RPR + wave * 8 >= HROWS_PAD) return;               // wave-uniform: rows beyond the padded halo
+    const int h = r * RPR + lrow;
+    int hy, hx;
+    gdt_halo_yx<HW>(h, hy, hx);
+    const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
+    const bool ok = (h < HROWS) & ((unsigned)iy < (unsigned)d.H) & ((unsigned)ix < (unsigned)d.W);      // zero ring, ragged edges, pad rows: zeros
+    const int q = (lane & 7) ^ ((hx >> 1) & 7);
+    const long pix = ((long)n * d.H + (ok ? iy : 0)) * d.W + (ok ? ix : 0);
+    const bool second = chunk >= nca;                          // (wave-uniform)
+    const f16* base = second ? d.in2 : d.in;
+    const int cs = second ? d.in2_cin : d.Cin, cc = second ? chunk - nca : chunk;
+    const f16* src = base + (pix * cs + (cc * 8 + q) * 8);
+    gdt_glds16(ok ? src : d.zeros, stage_base + (r * RPR + wave * 8) * 128);
+}
 // Input coordinate (iy, ix) of an H x W image under reflect padding -> (ry, rx): BOTH reflections first, then (GDT_REFLECT_CLAMP) both clamps.  In
 // bounds the reflection is the identity; the clamp makes the address valid for any coordinate (zero padding, rows past the halo), whose data the
 // caller then replaces by zeros.  Macros, not functions: as a function -- two coordinates through references, through an int2, or one coordinate

@@ -265,6 +265,10 @@ inline void gdt_t4_step(int step, int& sy, int& sx, int& py, int& px) {
                 for (px = 0; px < 2; ++px)
                     if (gdt_t4_meets(sy, py) && gdt_t4_meets(sx, px) && s++ == step) return;
 }
+// conv3x3_cat_halo.hip: Conv2d(k3, s1, p1) of the channel concatenation of `in` (Cin channels) and `in2` (in2_cin channels), variant 908064; the fragment-ordered
+// weights have k = (chunk * 9 + tap) * 64 + channel, chunks counted over both inputs
+bool gdt_conv3x3_cat_halo_eligible(const ConvLaunch& d);
+int gdt_launch_conv3x3_cat_halo(const ConvLaunch& d, hipStream_t stream, int* variant);
 bool gdt_conv_halo_rb_eligible(const ConvLaunch& d);       // conv3x3_halo_rb.hip (weights streamed into registers)
 bool gdt_conv3x3_expand_eligible(const ConvLaunch& d);     // conv3x3_expand_rb.hip (3x3 + expand 1x1 + residual of a Bottleneck, variant 939000 + x_cout / 8)
 int gdt_launch_conv3x3_expand(const ConvLaunch& d, hipStream_t stream);

@@ -608,6 +608,50 @@ static int add_conv_t4(gdt_net* net, int in_a, int in_b, int relu_a, const gdt_c
     return GDT_OK;
 }
 
+// conv3x3_cat_halo.hip: [cout_pad][9 cin] with k = (chunk * 9 + tap) * 64 + channel, in fragment order; cin counts the channels of both inputs
+static void pack_cc(ConvPack& cp) {
+    gdt_net* net = cp.net; Op& o = cp.o;
+    const gdt_conv_desc& cd = o.cd;
+    const int K = 9 * cd.cin;
+    std::vector<f16> pk((size_t)o.cout_pad * K, (f16)0.f);
+    for (int co = 0; co < cd.cout; ++co)
+        for (int c = 0; c < cd.cin; ++c)
+            for (int t = 0; t < 9; ++t)
+                pk[(size_t)co * K + ((size_t)(c >> 6) * 9 + t) * 64 + (c & 63)] = (f16)(cp.weight[((size_t)co * cd.cin + c) * 9 + t] * cp.scale[co]);
+    const std::vector<f16> pf = frag_order(pk, o.cout_pad, K);
+    o.cc_frag_off = net->blob_append(pf.data(), pf.size() * sizeof(f16));
+    o.has_cc = true;
+}
+
+// gdt_net_conv_cat: the generic route's input -- the concatenation as a tensor of its own -- and the conv of one tensor over it; where conv3x3_cat_halo.hip
+// can take the layer, its weights too
+static int add_conv_cat(gdt_net* net, int in_a, int in_b, const gdt_conv_desc& cd, const float* weight, const float* bias,
+                        const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor) {
+    const int ca = net->tensors[in_a].Creal, cb = net->tensors[in_b].Creal;
+    {
+        Op c; c.kind = OP_CONCAT; c.in = in_a; c.res = in_b; c.relu = 0;
+        c.out = net->new_tensor(next_pow2(cd.cin), cd.cin);
+        c.cat_for = (int)net->ops.size() + 1;
+        net->ops.push_back(c);
+    }
+    const int cat_op = (int)net->ops.size() - 1, cat_out = net->ops[cat_op].out;
+    const int rc = add_conv(net, cat_out, &cd, 1, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, -1, out_tensor);
+    if (rc != GDT_OK) {                       // (nothing of a refused layer stays in the graph)
+        net->ops.pop_back(); net->tensors.pop_back();
+        return rc;
+    }
+    Op& o = net->ops.back();
+    o.cat_op = cat_op; o.cc_a = in_a; o.cc_b = in_b;
+    o.feats.push_back(in_a); o.feats.push_back(in_b);      // (read by the patch kernel itself: alive until this op)
+    if (!net->precision && !cd.out_f32_nchw && cd.kh == 3 && cd.kw == 3 && cd.stride == 1 && cd.pad == 1 && !cd.pad_reflect && ca % 64 == 0 && cb % 64 == 0 &&
+        net->tensors[in_a].C == ca && net->tensors[in_b].C == cb && cd.cout % 64 == 0 && o.cout_pad % 64 == 0) {
+        ConvPack cp{net, o, weight, 1};
+        fold_bn(cd, bias, bn_gamma, bn_beta, bn_mean, bn_var, cp.scale, cp.shift, cp.has_shift);
+        pack_cc(cp);
+    }
+    return GDT_OK;
+}
+
 }  // namespace
 
 // fp16 mode: for every 1x1 conv c (stride 1, ReLU) whose residual is the output of a 1x1 projection conv ds (no ReLU, stride 1 or 2, no other consumer),
@@ -735,6 +779,19 @@ int gdt_net_conv_transposed4(gdt_net* net, int in_a, int in_b, int relu_a, int c
     cd.cin = ca + cb; cd.cout = cout; cd.kh = cd.kw = 4; cd.stride = 2; cd.pad = 1; cd.transposed = 1; cd.relu = relu ? 1 : 0;
     cd.out_f32_nchw = out_f32_nchw ? 1 : 0; cd.act = act; cd.bn_eps = bn_eps;
     return add_conv_t4(net, in_a, in_b, relu_a, cd, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, out_tensor);
+}
+
+int gdt_net_conv_cat(gdt_net* net, int in_a, int in_b, const gdt_conv_desc* desc, const float* weight, const float* bias, const float* bn_gamma,
+                     const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor) {
+    GDT_REQUIRE(net && !net->finalized && desc && weight && out_tensor, "net/desc/weight");
+    GDT_REQUIRE(net->precision == 0 || net->precision == 1, "a Conv2d of a concatenation exists in the f16 and f16x3 modes");
+    GDT_REQUIRE(in_a >= 0 && in_a < (int)net->tensors.size() && in_b >= 0 && in_b < (int)net->tensors.size(), "input tensor id");
+    GDT_REQUIRE(!desc->transposed, "a Conv2d of a concatenation is not transposed");
+    GDT_REQUIRE(!desc->pad_reflect, "a Conv2d of a concatenation pads with zeros");
+    const int ca = net->tensors[in_a].Creal, cb = net->tensors[in_b].Creal;
+    GDT_REQUIRE(ca % 8 == 0 && cb % 8 == 0, "a concatenated input needs channel counts % 8 == 0");
+    GDT_REQUIRE(desc->cin == ca + cb && ca + cb <= 4096, "the channels of the two inputs do not add up to the conv's cin");
+    return add_conv_cat(net, in_a, in_b, *desc, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, out_tensor);
 }
 
 static int add_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, float leaky, int residual_tensor, int* out_tensor) {

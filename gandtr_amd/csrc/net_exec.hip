@@ -216,6 +216,16 @@ int exec_conv(const ConvStep& s) {
             return rc;
         }
     }
+    if (conv_takes_cat_kernel(s.x, s.c.plan, stp.op)) {     // Conv2d(k3,s1,p1) from its own two inputs (conv3x3_cat_halo.hip) -- else the conv of one tensor below, over the concatenation
+        int variant = 0;
+        const int rc = gdt_launch_conv3x3_cat_halo(conv_desc_cc(s.x, stp.op, fold_of(net, s.c.plan, stp.op)), s.st, &variant);
+        s.variant(variant);
+        if (net->profiling && s.book) {                     // bytes: the concatenation is neither written nor read; its two sources are read once
+            const Op& oc = net->ops[s.o.cat_op];
+            net->last_bytes[stp.op] += s.tbytes(oc.in) + s.tbytes(oc.res) - s.tbytes(s.o.in);
+        }
+        return rc;
+    }
     const ConvFold f = fold_of(net, s.c.plan, stp.op);      // InstanceNorm(+ReLU) of the producer applied while staging the input, statistics, pool
     if (f.norm >= 0 && net->profiling)        // bytes the folded form must move on top of the conv's own: the residual tensor read, the normalised tensor written back
         net->last_bytes[stp.op] += s.tbytes(net->ops[f.norm].in) * ((f.res ? 1.0 : 0.0) + (f.wb ? 1.0 : 0.0));
@@ -265,6 +275,7 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
             case OP_CONCAT: {
                 const Op& oc = net->ops[o.cat_for];
                 if (oc.has_t4 && gdt_conv4x4t_halo_eligible(conv_desc_t4(DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}, o.cat_for))) break;   // the conv reads the sources itself
+                if (conv_takes_cat_kernel(DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}, plan, o.cat_for)) break;           // (likewise, conv3x3_cat_halo.hip)
                 const Tensor& ta = T[o.in]; const Tensor& to = T[o.out];
                 rc = gdt_k_concat(tptr(o.in), o.res >= 0 ? tptr(o.res) : nullptr, tptr(o.out), f32, (long)n * ta.H * ta.W, ta.C, ta.Creal,
                                   o.res >= 0 ? T[o.res].C : 0, o.res >= 0 ? T[o.res].Creal : 0, to.C, o.relu, st);

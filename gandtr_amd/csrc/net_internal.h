@@ -67,6 +67,10 @@ struct Op {
     // op `cat_op` (channel concatenation of t4_a and t4_b, ReLU on the t4_a part when t4_relu); has_t4: the fragment-ordered weights of conv4x4t_halo.hip, which
     // reads t4_a / t4_b itself (they are also in `feats`, so that they live until this op) -- then the concatenation is never written
     bool has_t4 = false; size_t t4_frag_off = 0; int t4_a = -1, t4_b = -1, t4_relu = 0, cat_op = -1;
+    // Conv2d of a concatenation (gdt_net_conv_cat): `in` is the output of the OP_CONCAT op `cat_op` (channel concatenation of cc_a and cc_b), which the conv of one
+    // tensor reads; has_cc: the fragment-ordered weights of conv3x3_cat_halo.hip, which reads cc_a / cc_b itself (they are also in `feats`) -- then the
+    // concatenation is never written
+    bool has_cc = false; size_t cc_frag_off = 0; int cc_a = -1, cc_b = -1;
     // concat (OP_CONCAT): in / res = the two tensors (res < 0: one), relu = ReLU on the first; cat_for = the conv op that reads the output
     int cat_for = -1;
     int dil = 1;          // conv: dilation (gdt_net_conv_dilated); the taps are (dy0 + (t / TW) * dil, ...): only the generic implicit-GEMM kernels take it
@@ -264,5 +268,9 @@ ConvLaunch conv_desc_xexp(const DescCtx& x, int i, int chain, float group_factor
 ConvLaunch conv_desc_kcat(const DescCtx& x, int i);                                      // expand conv + its projection shortcut, K-concatenated
 ConvLaunch conv_desc_stem_direct(const DescCtx& x, int i, int pool_into);                // ResNet stem from the caller's image (+ the 3 x 3 max-pool behind it)
 ConvLaunch conv_desc_t4(const DescCtx& x, int i);                                        // ConvTranspose2d(k4,s2,p1) from its one or two inputs (Op::has_t4, conv4x4t_halo.hip)
+
+ConvLaunch conv_desc_cc(const DescCtx& x, int i, const ConvFold& f);                     // Conv2d(k3,s1,p1) from its two inputs (Op::has_cc, conv3x3_cat_halo.hip)
+// conv op i of a planned geometry runs on conv3x3_cat_halo.hip: its own plain launch in the plan, and eligible (the knob is read here: a launch-time choice)
+bool conv_takes_cat_kernel(const DescCtx& x, const Plan& plan, int i);
 
 }  // namespace gdtn

@@ -226,6 +226,25 @@ ConvLaunch conv_desc_t4(const DescCtx& x, int i) {
     return d;
 }
 
+ConvLaunch conv_desc_cc(const DescCtx& x, int i, const ConvFold& f) {
+    const Op& o = x.net->ops[i];
+    const auto& T = *x.T;
+    ConvLaunch d = conv_desc_phase(x, i, o.phases[0], 0, f);        // geometry, epilogue and what the plan folded around the conv (all of which the kernel refuses)
+    d.in = x.p.act(T, o.cc_a); d.Cin = T[o.cc_a].C; d.lc8 = ilog2(d.Cin / 8);
+    d.in2 = x.p.act(T, o.cc_b); d.in2_cin = T[o.cc_b].C; d.in2_h = T[o.cc_b].H; d.in2_w = T[o.cc_b].W; d.in2_stride = 1;
+    d.Kpad = 9 * (d.Cin + d.in2_cin); d.nk = d.Kpad / 64;
+    d.w = nullptr; d.w_lo = nullptr;
+    d.w_frag = o.has_cc ? x.p.w<const f16*>(o.cc_frag_off) : nullptr;
+    return d;
+}
+
+bool conv_takes_cat_kernel(const DescCtx& x, const Plan& plan, int i) {
+    const Op& o = x.net->ops[i];
+    const Step& st = plan.steps[i];
+    if (o.kind != OP_CONV || !o.has_cc || st.skip || st.bneck || st.direct || st.xexp || st.kcat || st.ctf || st.s2 || st.ctp || st.aug) return false;
+    return gdt_conv3x3_cat_halo_eligible(conv_desc_cc(x, i, fold_of(x.net, plan, i)));
+}
+
 // ---- make_plan, pass by pass ------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -777,7 +796,8 @@ int gdt_net_workspace_bytes(gdt_net* net, int n, int rh, int rw, size_t* bytes) 
 // [8] transposed convs as one fused-phase launch, [9] stride-2 convs as the shift form, [10] dilated convs, [11] of those on a special form; with n_counts >= 14:
 // [12] launches of the pool-head ops (gdt_net_pool_head), [13] of those the ones that read the feature map; with n_counts >= 15: [14] conv launches that
 // conv4x4_halo.hip takes (what gdt_launch_conv decides for the conv as its own plain launch; GDT_CONV4X4_HALO=0: none); with n_counts >= 16: [15] transposed 4x4 convs
-// that conv4x4t_halo.hip takes (one launch each, the concatenation in front never written; GDT_CONV4X4T_HALO=0: none -- then four phase launches each)
+// that conv4x4t_halo.hip takes (one launch each, the concatenation in front never written; GDT_CONV4X4T_HALO=0: none -- then four phase launches each); with
+// n_counts >= 17: [16] convs of a concatenation (gdt_net_conv_cat) that conv3x3_cat_halo.hip takes (GDT_CONV3X3_CAT_HALO=0: none -- then a copy + the conv of one tensor)
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts) {
     GDT_REQUIRE(net && counts && n_counts >= 10 && n >= 1 && rh >= 1 && rw >= 1, "plan summary arguments");
     if (!net->finalized && !net->precision) build_kcat_weights(net);       // (what finalize would add: the K-concatenated shortcut weights the planner may choose)
@@ -802,6 +822,7 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
             counts[14] += gdt_conv4x4_halo_eligible(conv_desc_phase(DescCtx{net, &net->tensors, n, Ptrs{}}, (int)i, o.phases[0], 0, fold_of(net, plan, (int)i)));
         if (o.kind == OP_CONV && n_counts >= 16 && o.has_t4 && !st.skip)
             counts[15] += gdt_conv4x4t_halo_eligible(conv_desc_t4(DescCtx{net, &net->tensors, n, Ptrs{}}, (int)i));
+        if (n_counts >= 17) counts[16] += conv_takes_cat_kernel(DescCtx{net, &net->tensors, n, Ptrs{}}, plan, (int)i);
         if (o.kind == OP_CONV && o.dil != 1 && n_counts >= 12) {
             ++counts[10];
             // what gdt_launch_conv / gdt_launch_conv_x3 would be handed for the conv as its own plain launch

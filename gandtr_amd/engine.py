@@ -7,6 +7,7 @@
   build_embedder    ImageRetrievalNet          mdir/external/cirtorch/networks/imageretrievalnet.py:101-123, :185-190
   build_hed         HedInterpolation           mdir/components/model/network/hed.py:30-83
   build_rcf         RCF                        mdir/components/model/network/rcf.py:28-155
+  build_p2p_unet    P2pUNet and its four kin   mdir/components/model/network/unet.py:48-350
 
 PyTorch is used for device memory and streams only; no torch op runs on the data path.
 """
@@ -167,6 +168,18 @@ class HipNet:
         return self._add("conv_transposed4", a, b, int(relu_a), w.shape[1], _ptr(w), _ptr(bias), _ptr(g), _ptr(be), _ptr(m), _ptr(v), 1e-5, int(relu),
                          int(out_f32), act)
 
+    def conv_cat(self, a, b, weight, bias=None, bn=None, stride=1, pad=0, relu=False, out_f32=False, act=0):
+        """nn.Conv2d of ``torch.cat([a, b], 1)`` (gdt_net_conv_cat); ``weight`` [cout][cin_a + cin_b][kh][kw], ``a``'s channels first"""
+        w = _f32(weight)
+        if w.ndim != 4:
+            raise ValueError("conv_cat takes a [cout][cin][kh][kw] weight, got %s" % (tuple(w.shape),))
+        d = ConvDesc(w.shape[1], w.shape[0], w.shape[2], w.shape[3], stride, pad, 0, 0, int(relu), int(out_f32), act, 1e-5)
+        g = be = m = v = None
+        if bn is not None:
+            g, be, m, v = (_f32(t) for t in bn)
+        bias = _f32(bias)
+        return self._add("conv_cat", a, b, ctypes.byref(d), _ptr(w), _ptr(bias), _ptr(g), _ptr(be), _ptr(m), _ptr(v))
+
     def instance_norm(self, x, relu=False, residual=-1, eps=1e-5, leaky=0.0):
         """``leaky``: slope of an nn.LeakyReLU behind the norm in place of ``relu`` (gdt_net_instance_norm_leaky)"""
         if leaky:
@@ -277,6 +290,10 @@ class HipNet:
     def conv4x4t_launches(self, n, rh, rw):
         """transposed 4x4 convs of a geometry that run as one launch of conv4x4t_halo.hip (GDT_CONV4X4T_HALO=0: none) -- the planner's count"""
         return self._plan_counts(n, rh, rw, False, 16)[15]
+
+    def conv3x3_cat_launches(self, n, rh, rw):
+        """convs of a concatenation of a geometry that run as one launch of conv3x3_cat_halo.hip (GDT_CONV3X3_CAT_HALO=0: none) -- the planner's count"""
+        return self._plan_counts(n, rh, rw, False, 17)[16]
 
     def head_launches(self, n, rh, rw):
         """(launches of the net's pool-head ops, launches among them that read the feature map) for a geometry -- the planner's count"""
@@ -870,6 +887,88 @@ def build_unet_generator(sd, device, precision="f16", pre_tanh=False, finalize=T
         else:
             u = net.conv_transposed4(s[i], sd[key + ".weight"], u, relu_a=relu_a, bias=sd.get(key + ".bias"), bn=_bn(sd, nkey), relu=True)
     net.out_slot = net.conv_transposed4(s[0], sd[block(0) + "3.weight"], u, relu_a=True, bias=sd[block(0) + "3.bias"], out_f32=True, act=0 if pre_tanh else 1)
+    if finalize:
+        net.finalize()
+    return net
+
+
+def p2p_unet_check(label, cfg):
+    """what the device path of the normalisation U-Nets (components/model/network/unet.py) does not do, refused before anything is built"""
+    co = dict(cfg["conv_opts"])
+    co.pop("bias", None)
+    if co != {"kernel_size": 4, "stride": 2, "padding": 1}:
+        raise NotImplementedError("HIP %s runs the reference's down / up convs, kernel_size 4, stride 2, padding 1; conv_opts %r has no device form" % (label, cfg["conv_opts"]))
+    if cfg["in_channels"] > 8:
+        raise NotImplementedError("HIP %s takes at most 8 input channels (the input pack kernel), got %d" % (label, cfg["in_channels"]))
+
+
+def build_p2p_unet(label, sd, device, cfg, precision="f16", pre_act=False, finalize=True):
+    """One of the normalisation U-Nets (unet.py: ``p2p_unet``, ``outconv_unet``, ``inconv_p2p_unet``, ``aligned_p2p_unet``, ``shallow_p2p_unet``) as a HIP graph,
+    built by walking the family's own layer list (``unet.family_layers(label, cfg)``; ``cfg`` from ``unet.family_config``).
+
+    A conv takes the BatchNorm behind it (folded) and the activation behind that (epilogue) with it; Dropout is the identity.  No activation of the family is
+    in place, so the stored tensors are the post-activation ones and a skip block's value is the PAIR (what the block received, what its ``nested`` chain
+    returned): the layer that follows reads the concatenation from the two tensors -- a ConvTranspose2d(k4, s2, p1) through gdt_net_conv_transposed4, a Conv2d
+    (the aligned net's Conv2d(128, 64, 3, padding=1)) through gdt_net_conv_cat.  The last layer writes the external fp32 NCHW output, with the Tanh where the
+    net has one (``pre_act``: the map in front of it)."""
+    from .components.model.network import unet
+    if precision not in ("f16", "f16x3"):
+        raise NotImplementedError("%s runs in 'f16' or 'f16x3'; %r is a ResnetGenerator mode" % (label, precision))
+    p2p_unet_check(label, cfg)
+    layers = unet.family_layers(label, cfg)
+    net, x = _open(device, precision, cfg["in_channels"])
+
+    def walk(items, prefix, value, top):
+        i = 0
+        while i < len(items):
+            item, name = items[i], "%s%d" % (prefix, i)
+            if item[0] == "skip":
+                if isinstance(value, tuple):
+                    raise NotImplementedError("a skip block that receives a concatenation has no device form")
+                value = (value, walk(item[1], name + ".nested.", value, False))
+                i += 1
+                continue
+            if item[0] not in ("conv", "convt"):
+                raise NotImplementedError("layer %s of %s does not follow a conv" % (item[0], label))
+            # ---- the conv and what rides on it: [BatchNorm] [Dropout] [activation]
+            bn, relu, leaky, tanh = None, False, 0.0, False
+            j = i + 1
+            if j < len(items) and items[j][0] == "bn":
+                key = "%s%d" % (prefix, j)
+                if key + ".running_mean" not in sd:
+                    raise NotImplementedError("BatchNorm without running statistics (track_running_stats=False) has no inference form on the HIP path")
+                if items[j][2].get("eps", 1e-5) != 1e-5 or not items[j][2].get("affine", True):
+                    raise NotImplementedError("HIP %s folds nn.BatchNorm2d(eps=1e-5, affine=True) only, got %r" % (label, items[j][2]))
+                bn = _bn(sd, key)
+                j += 1
+            if j < len(items) and items[j][0] == "dropout":
+                j += 1
+            if j < len(items) and items[j][0] in ("relu", "leaky", "tanh"):
+                relu, leaky, tanh = items[j][0] == "relu", items[j][1] if items[j][0] == "leaky" else 0.0, items[j][0] == "tanh"
+                j += 1
+            last = top and j == len(items)
+            if tanh and not last:
+                raise NotImplementedError("a Tanh inside the net has no device form")
+            act = 1 if tanh and not pre_act else 0
+            w, b = sd[name + ".weight"], sd.get(name + ".bias")
+            opts = item[3]
+            k, stride, pad = opts.get("kernel_size", 1), opts.get("stride", 1), opts.get("padding", 0)
+            pair = isinstance(value, tuple)
+            if item[0] == "convt":
+                if leaky:
+                    raise NotImplementedError("a LeakyReLU behind a transposed conv has no device form")
+                a, second = value if pair else (value, -1)
+                value = net.conv_transposed4(a, w, second, bias=b, bn=bn, relu=relu, out_f32=last, act=act)
+            elif pair:
+                if leaky:
+                    raise NotImplementedError("a LeakyReLU behind a conv of a concatenation has no device form")
+                value = net.conv_cat(value[0], value[1], w, bias=b, bn=bn, stride=stride, pad=pad, relu=relu, out_f32=last, act=act)
+            else:
+                value = net.conv(value, w, b, bn=bn, stride=stride, pad=pad, relu=relu, leaky=leaky, out_f32=last, act=act)
+            i = j
+        return value
+
+    net.out_slot = walk(layers, "outerblock.", x, True)
     if finalize:
         net.finalize()
     return net

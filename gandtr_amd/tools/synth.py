@@ -139,6 +139,36 @@ def unet_state(seed=0, norm="instance", ngf=64, num_downs=8, in_nc=3, out_nc=3, 
     return sd
 
 
+def p2p_unet_state(label, seed=0, in_channels=3, out_channels=3, out_gain=1.0, **cfg):
+    """State dict of one of the normalisation U-Nets (components/model/network/unet.py: ``label`` and the constructor arguments in ``cfg``), filled along
+    the family's own layer list, so its keys are the module's: kaiming-scaled conv weights (a k4 / s2 transposed conv's fan-in counted as the 4 taps x cin that
+    meet one output pixel), N(0, 0.1) biases wherever the layer has one, non-trivial BatchNorm statistics and affine parameters.  The last layer is
+    N(0, out_gain * sqrt(2 / fan_in)) like the others: behind ReLU / LeakyReLU layers of unit scale that leaves the output map O(1)."""
+    from ..components.model.network import unet
+    full = unet.family_config(label, in_channels, out_channels, **cfg)
+    sd = {}
+
+    def fill(layers, prefix, last_conv):
+        for i, item in enumerate(layers):
+            name = "%s%d" % (prefix, i)
+            if item[0] in ("conv", "convt"):
+                _, cin, cout, opts = item
+                k = opts.get("kernel_size", 1)
+                tr = item[0] == "convt"
+                stride = opts.get("stride", 1)
+                fan = cin * k * k // (stride * stride) if tr else cin * k * k
+                gain = math.sqrt(2.0 / fan) * (out_gain if item is last_conv else 1.0)
+                _conv(sd, seed, name, cout, cin, k, opts.get("bias", True), gain, transposed=tr)
+            elif item[0] == "bn":
+                _bn(sd, seed, name, item[1])
+            elif item[0] == "skip":
+                fill(item[1], name + ".nested.", last_conv)
+
+    layers = unet.family_layers(label, full)
+    fill(layers, "outerblock.", [it for it in layers if it[0] in ("conv", "convt")][-1])
+    return sd
+
+
 def patchsample_state(seed=0, channels=(128, 256, 256, 256), nc=256, gain=1.0):
     """PatchSampleF state dict (p2p_networks.py:628-636): per feature map i of ``channels[i]`` channels ``mlp_<i>.0`` Linear(channels[i], nc) and
     ``mlp_<i>.2`` Linear(nc, nc), N(0, gain * sqrt(2 / fan_in)) weights and N(0, 0.1) biases: on O(1) features the hidden and the output rows are O(1)"""

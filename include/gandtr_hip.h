@@ -109,6 +109,16 @@ int gdt_net_conv_leaky(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, f
  * generic implicit-GEMM kernels (gdt_net_plan_summary count [15]). */
 int gdt_net_conv_transposed4(gdt_net* net, int in_a, int in_b, int relu_a, int cout, const float* weight, const float* bias, const float* bn_gamma,
                              const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps, int relu, int out_f32_nchw, int act, int* out_tensor);
+/* nn.Conv2d(cin_a + cin_b, cout, k, stride, padding) (+ folded BatchNorm2d(eval), as gdt_net_conv) (+ ReLU: desc->relu) of the channel concatenation
+ * torch.cat([a, b], 1): the nn.Conv2d(128, 64, 3, padding=1) that AlignedP2pUNet applies to the output [x, nested(x)] of its inner SkipConnBlock
+ * (unet.py, AlignedP2pUNet.__init__ / P2pUNet.SkipConnBlock.forward).  desc->cin = cin_a + cin_b (each % 8 == 0), desc->transposed and pad_reflect must be 0,
+ * no dilation, no residual; weight: host fp32 [cout][cin_a + cin_b][kh][kw], in_a's channels first; bias and the four BatchNorm vectors may be NULL;
+ * desc->out_f32_nchw as in gdt_net_conv.  Precision modes f16 and f16x3.  In f16, k3 / stride 1 / pad 1 layers with cin_a % 64 == 0, cin_b % 64 == 0,
+ * cout % 64 == 0 and an internal output run as ONE launch of conv3x3_cat_halo.hip, which reads both inputs itself, where that measured faster (cout <= 128,
+ * cin_a + cin_b no power of two, or few patches; GDT_CONV3X3_CAT_HALO=2: every such layer); everything else (and everything with
+ * GDT_CONV3X3_CAT_HALO=0) runs as a copy that writes the concatenation once and the conv of one tensor (gdt_net_plan_summary count [16]). */
+int gdt_net_conv_cat(gdt_net* net, int in_a, int in_b, const gdt_conv_desc* desc, const float* weight, const float* bias, const float* bn_gamma,
+                     const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor);
 
 /* nn.InstanceNorm2d(affine=False, eps) (+ fused ReLU) (+ fused residual add AFTER the norm): p2p_networks.py:29,:272,:505 */
 int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, int residual_tensor, int* out_tensor);
@@ -219,7 +229,8 @@ int gdt_net_flops(gdt_net* net, int n, int rh, int rw, double* flops);
  * [12] the launches of the pool-head ops (gdt_net_pool_head: fixed by the layers present, whatever the batch and the number of regions) and [13] those
  * among them that read the feature map (one per op); with n_counts >= 15 also [14] the conv launches that run on the 4x4 patch kernel (conv4x4_halo.hip;
  * none with GDT_CONV4X4_HALO=0); with n_counts >= 16 also [15] the transposed 4x4 convs (gdt_net_conv_transposed4) that run as one launch of
- * conv4x4t_halo.hip (none with GDT_CONV4X4T_HALO=0).  (Diagnostics / tests; no reference counterpart.) */
+ * conv4x4t_halo.hip (none with GDT_CONV4X4T_HALO=0); with n_counts >= 17 also [16] the convs of a concatenation (gdt_net_conv_cat) that run as one launch of
+ * conv3x3_cat_halo.hip (none with GDT_CONV3X3_CAT_HALO=0).  (Diagnostics / tests; no reference counterpart.) */
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts);
 
 /* Per-op timing for bench.py's roofline line: when enabled, gdt_net_forward records HIP events on the caller's stream

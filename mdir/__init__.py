@@ -2,6 +2,7 @@
 
     mdir.hub.model                         -> gandtr_amd.hub.model
     mdir.components.model.network          -> gandtr_amd.components.model.network   (MODEL_LABELS, initialize_model)
+    mdir.components.model.network.unet     -> gandtr_amd.components.model.network.unet (P2pUNet, OutconvP2pUNet, InconvP2pUNet, AlignedP2pUNet, ShallowP2pUNet)
     mdir.components.data.wrapper           -> gandtr_amd.components.data.wrapper    (WRAPPERS_LABELS, initialize_wrappers)
     mdir.components.data.transform         -> gandtr_amd.components.data.transform  (initialize_transforms)
     mdir.components.data.dataset           -> gandtr_amd.components.data.dataset    (DATASET_LABELS, initialize_dataset_loader: the GAN scenarios' data)
@@ -34,6 +35,7 @@ _ALIASES = {
     "mdir.components.model.network.cirnet": "gandtr_amd.components.model.network.cirnet",
     "mdir.components.model.network.hed": "gandtr_amd.components.model.network.hed",
     "mdir.components.model.network.rcf": "gandtr_amd.components.model.network.rcf",
+    "mdir.components.model.network.unet": "gandtr_amd.components.model.network.unet",
     "mdir.components.model.weight_initialization": "gandtr_amd.components.model.weight_initialization",
     "mdir.components.data": "gandtr_amd.components.data",
     "mdir.components.data.wrapper": "gandtr_amd.components.data.wrapper",
