@@ -96,6 +96,8 @@ SIGNATURES = {
     "gdt_net_conv_cat": (c_int, [c_void_p, c_int, c_int, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _IP]),
     "gdt_net_gem_l2n": (c_int, [c_void_p, c_int, c_float, c_float, c_float, _IP]),
     "gdt_net_pool_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, _IP]),
+    "gdt_net_pool_head_attention": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_int, _IP]),
+    "gdt_net_input_filter": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_float, c_float]),
     "gdt_net_output_nchw": (c_int, [c_void_p, c_int, c_void_p, _IP]),
     "gdt_net_hed_head": (c_int, [c_void_p, _IP, POINTER(c_void_p), _FP, _FP, c_float, c_int, _IP]),
     "gdt_net_rcf_head": (c_int, [c_void_p, _IP, _IP, POINTER(c_void_p), _FP, _FP, c_float, c_int, _IP]),
@@ -140,6 +142,10 @@ SIGNATURES = {
     "gdt_gem_l2n": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "gdt_rpool_regions": (c_int, [c_int, c_int, c_int, _IP, c_int, _IP]),
     "gdt_pool_regions": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_float, c_int, c_void_p, c_void_p]),
+    "gdt_pool_regions_weighted": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "gdt_pixel_attention_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "gdt_pixel_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gdt_pack_input_filter": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
     "gdt_mfma_only_tflops": (c_int, [c_int, POINTER(c_double), c_void_p]),
     "gdt_ingest_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "gdt_ingest_resize_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int, c_void_p, c_void_p,

@@ -1,9 +1,10 @@
 """Model registry (plugin API) -- mirror of mdir/components/model/network/__init__.py:20-48 restricted to the
-architectures reachable from the hub entrypoints, the BASELINE configs, the published GAN scenarios' discriminators, CUT's ``featdown`` network, the pix2pix U-Net generator and the learnable photometric normalisation U-Nets (unet.py).  Unknown names raise KeyError like the
+architectures reachable from the hub entrypoints, the BASELINE configs, the published GAN scenarios' discriminators, CUT's ``featdown`` network, the pix2pix U-Net generator, the learnable photometric normalisation U-Nets (unet.py), the retrieval embedder's attention (``cirnet_attention``) and edge-map
+(``cirnet_inchan``) variants and ``normalization_l2``.  Unknown names raise KeyError like the
 reference (:48)."""
 import torch.nn as nn
 
-from . import cirnet, hed, p2p_networks, rcf, unet
+from . import cirnet, hed, p2p_networks, rcf, single_layer, unet
 
 
 class Identity(nn.Module):
@@ -22,6 +23,9 @@ MODEL_LABELS = {
     "official_p2p_discriminator": p2p_networks.NLayerDiscriminator,
     "official_p2p_mlp": p2p_networks.PatchSampleF,
     "cirnet": cirnet.init_cirnet,
+    "cirnet_inchan": cirnet.init_cirnet_inchan,
+    "cirnet_attention": cirnet.init_cirnet_attention,
+    "normalization_l2": single_layer.NormalizationL2,
     "hed_interpolation": hed.HedInterpolation,
     "rcf": rcf.RCF,
     "p2p_unet": unet.P2pUNet,

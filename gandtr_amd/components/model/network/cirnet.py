@@ -2,10 +2,12 @@
   mdir/external/cirtorch/layers/functional.py:11-123 (mac, spoc, gem, rmac, roipool), :130-131 (l2n)
   mdir/external/cirtorch/layers/pooling.py:12-113 (MAC, SPoC, GeM, GeMmp, RMAC, Rpool), layers/normalization.py:10-20 (L2N)
   mdir/external/cirtorch/networks/imageretrievalnet.py:86-123 (ImageRetrievalNet), :146-309 (init_network)
-  mdir/components/model/network/cirnet.py:8-65 (CirRetrievalNet, init_cirnet)
+  mdir/components/model/network/cirnet.py:8-65 (CirRetrievalNet, init_cirnet), :68-104 (CirRetrievalNetPreprocessing, init_cirnet_inchan),
+  :107-137 (CirRetrievalNetAttention, init_cirnet_attention)
 The whole descriptor head runs on the HIP path: any of the five poolings, made regional or not, with the local, the regional
 and the final whitening layers (engine.build_embedder, csrc/pool_head.hip); the hub configuration (mdir/hub/embedding.yml:6-10:
-plain GeM, no whitening layers) keeps its own two-launch op.
+plain GeM, no whitening layers) keeps its own two-launch op.  The attention net's weights are computed and folded into the pooling pass there too
+(pixel_norm_kernel, the weighted pool_regions_kernel), and the EdgeFilter of the edge-map net is evaluated by the input pack (csrc/aux_kernels.hip).
 """
 import math
 
@@ -15,6 +17,7 @@ import torch.nn.functional as F
 from torch.nn.parameter import Parameter
 
 from . import backbones
+from ..layers import attention as attention_layers, preprocessing as preprocessing_layers
 from ._hipbacked import HipBacked, ScaledInput
 
 
@@ -198,7 +201,14 @@ class ImageRetrievalNet(HipBacked, nn.Module):
             return self._forward_hip(x, scale)
         if scale is not None:
             x = F.interpolate(x, scale_factor=scale, mode="bilinear", align_corners=False)
-        o = self.features(x)
+        return self._head(self.features(self._preprocess(x)))
+
+    def _preprocess(self, x):
+        """what the torch path applies to the (resized) input in front of the trunk"""
+        return x
+
+    def _head(self, o):
+        """the torch path behind the trunk's map"""
         if self.lwhiten is not None:
             s = o.size()
             o = self.lwhiten(o.permute(0, 2, 3, 1).contiguous().view(-1, s[1]))
@@ -227,14 +237,22 @@ class ImageRetrievalNet(HipBacked, nn.Module):
         L = pool.L if regional else (inner.L if kind == "rmac" else 0)
         return (kind, regional, int(L), float(getattr(inner, "eps", 1e-6)), self.lwhiten is not None, self.whiten is not None)
 
+    def _hip_variant(self):
+        """What engine.build_embedder needs beyond the head, as a hashable dict-like tuple of (keyword, value) pairs; part of the cache key as well
+        (the input channel count is in the state dict, whose stamp the cache holds)."""
+        return ()
+
     def _hip_embedder(self):
         from .... import engine
         if self.meta.get("architecture") not in self.HIP_TRUNKS:
             raise NotImplementedError("HIP embedder supports vgg16 / resnet50 / resnet101 / resnet152 trunks")
         head = self._hip_head()
+        variant = self._hip_variant()
         self._hip_check_inference()
         prec = self._hip_precision()
-        return self._hip_net(("embed", prec, head), lambda sd, dev: engine.build_embedder(sd, dev, precision=prec, head=head))
+        in_c = int(self.features[0].weight.shape[1])
+        return self._hip_net(("embed", prec, head) + ((in_c,) + variant if variant or in_c != 3 else ()),
+                             lambda sd, dev: engine.build_embedder(sd, dev, precision=prec, head=head, **dict(variant)))
 
     def _forward_hip(self, x, scale):
         net = self._hip_embedder()
@@ -346,3 +364,85 @@ def init_cirnet(**params):
     net.meta["in_channels"] = 3
     net.meta["out_channels"] = net.meta["outputdim"]
     return CirRetrievalNet(net.features, net.lwhiten, net.pool, net.whiten, net.meta)
+
+
+class CirRetrievalNetPreprocessing(CirRetrievalNet):
+    """CirRetrievalNet behind a preprocessing layer applied to the net's input (behind whatever the wrappers did: the resize of cirmultiscale,
+    meanstd_pre); the layer's parameters train at 10x lr.  On a HIP device the EdgeFilter is part of the input pack."""
+
+    def __init__(self, preprocessing, features, lwhiten, pool, whiten, meta):
+        super().__init__(features, lwhiten, pool, whiten, meta)
+        self.preprocessing = preprocessing
+
+    def _preprocess(self, x):
+        return self.preprocessing(x)
+
+    def _hip_variant(self):
+        f = self.preprocessing
+        if not isinstance(f, preprocessing_layers.EdgeFilter):
+            raise NotImplementedError("HIP embedder: preprocessing %r is not an EdgeFilter" % (f,))
+        # (p and tau are parameters: the builder reads them from the state dict, and the cache's stamp sees them change)
+        return (("preprocessing", ("edgefilter", f.w, None, f.beta, None, f.eps)),)
+
+    def parameter_groups(self, optimizer_opts):
+        return super().parameter_groups(optimizer_opts) + [{"params": self.preprocessing.parameters(), "lr": optimizer_opts["lr"] * 10}]
+
+
+def init_cirnet_inchan(inputs, **params):
+    """init_cirnet for ``inputs["channels"]`` 1 or 3 input channels (1: the first conv's weight summed over its input dimension) behind
+    ``inputs["preprocessing"]``: falsy, or {"type": "edgefilter", w, p, beta, tau, eps}"""
+    model = init_cirnet(**params)
+    if inputs["channels"] == 1:
+        first = model.features[0]
+        first.in_channels = 1
+        first.weight.data = first.weight.data.sum(dim=1, keepdim=True)
+        model.meta["in_channels"] = 1
+    elif inputs["channels"] != 3:
+        raise NotImplementedError("Unsupported number of channels %s" % inputs["channels"])
+    if inputs["preprocessing"]:
+        model.meta["preprocessing"] = inputs["preprocessing"].pop("type")
+        if model.meta["preprocessing"] != "edgefilter":
+            raise NotImplementedError("Unsupported preprocessing type '%s'" % model.meta["preprocessing"])
+        layer = preprocessing_layers.EdgeFilter(**inputs["preprocessing"])
+        model = CirRetrievalNetPreprocessing(layer, model.features, model.lwhiten, model.pool, model.whiten, model.meta)
+    return model
+
+
+class CirRetrievalNetAttention(CirRetrievalNet):
+    """CirRetrievalNet whose map is weighted per position by an attention in front of the pooling: norm(pool(features(x) * att)), D x N.
+
+    The reference's forward (its ``squeeze(0)`` and the broadcast ``feats * att``) only works for a batch of one, which is all ``cirfaketuplebatch``
+    feeds it.  What is reproduced here, on the torch and on the HIP path, is that batch-of-one behaviour applied to each image separately: the
+    attention, and with ``normalize_max`` its maximum, are the image's own, so that a batch equals its images run one by one.  The reference asserts
+    in ``forward`` that there is no local and no final whitening; here that is refused at construction.  The attention's parameters (none for
+    ``l2norm``, the group is appended all the same) train at 100x lr."""
+
+    def __init__(self, attention, features, lwhiten, pool, whiten, meta):
+        assert not lwhiten and not whiten, "the attention net takes no local and no final whitening layer"
+        super().__init__(features, lwhiten, pool, whiten, meta)
+        self.attention = attention
+
+    def _head(self, o):
+        att = torch.stack([self.attention(o[i:i + 1]).reshape(o.shape[2:]) for i in range(o.size(0))])       # N x H x W, each image's own
+        return self.norm(self.pool(o * att.unsqueeze(1))).squeeze(-1).squeeze(-1).permute(1, 0)
+
+    def _hip_head(self):
+        head = super()._hip_head()
+        if head is not None and (head[4] or head[5]):
+            raise NotImplementedError("HIP embedder: the attention net takes no local and no final whitening layer")
+        return head
+
+    def _hip_variant(self):
+        if not isinstance(self.attention, attention_layers.L2NormAttention):
+            raise NotImplementedError("HIP embedder: attention %r is not an L2NormAttention" % (self.attention,))
+        return (("attention", ("l2norm", bool(self.attention.normalize_max))),)
+
+    def parameter_groups(self, optimizer_opts):
+        return super().parameter_groups(optimizer_opts) + [{"params": self.attention.parameters(), "lr": optimizer_opts["lr"] * 100}]
+
+
+def init_cirnet_attention(attention, **params):
+    """init_cirnet with ``attention`` = {"type": "l2norm", "normalize_max": bool} in front of the pooling"""
+    model = init_cirnet(**params)
+    layer = attention_layers.ATTENTIONS[attention.pop("type")](**attention)
+    return CirRetrievalNetAttention(layer, model.features, model.lwhiten, model.pool, model.whiten, model.meta)

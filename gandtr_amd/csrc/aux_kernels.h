@@ -6,8 +6,12 @@
 
 #include "gdt_common.h"
 
+// A per-pixel function of the input pack, applied in fp32 behind resize, permutation and affine and in front of the rounding to fp16.  kind 1 = EdgeFilter
+// (mdir/components/model/layers/preprocessing.py:18-25): w * max(x, eps)^p / (exp(min(-beta * (x - tau), 50)) + 1); tau is clamped by whoever fills this.
+struct GdtInputFilter { int kind = 0; float w = 0.f, p = 0.f, beta = 0.f, tau = 0.f, eps = 0.f; };
+enum { GDT_FILTER_NONE = 0, GDT_FILTER_EDGE = 1 };
 int gdt_k_pack_input(const float* x, void* y, int f32, int N, int C, int H, int W, int OH, int OW, float rscale, int resize,
-                     const int* perm, const float* scale, const float* shift, hipStream_t st);
+                     const int* perm, const float* scale, const float* shift, hipStream_t st, const GdtInputFilter* filter = nullptr);
 int gdt_in_stats_chunks(int HW);
 int gdt_k_instance_norm(const void* x, const void* res, void* y, int f32, float* partial, float* mean_rstd, int N, int HW, int C,
                         float eps, int relu, hipStream_t st, float leaky = 0.f);      // leaky: LeakyReLU slope applied instead of ReLU (0: none)
@@ -53,11 +57,16 @@ struct GdtPoolHead {
     int kind = GDT_POOL_GEM; float p = 3.f; const float* p_channels = nullptr; float eps = 1e-6f, eps_l2 = 1e-6f;
     int aggregate = 0;                                      // 0: one vector per image, 1: R-MAC, 2: Rpool (gdt_k_pool_head)
     const float *rw = nullptr, *rb = nullptr, *fw = nullptr, *fb = nullptr;     // regional / final whitening (device, fp32 [D][D] and [D])
+    const float* weights = nullptr;                         // attention head: one fp32 weight per pixel [N][H * W], folded into the pooling pass
 };
 int gdt_pool_grid(int H, int W, int L, std::vector<GdtPoolBox>& boxes);          // the whole map, then the L levels of LF.roipool (host)
 int gdt_pool_regions_of(const std::vector<GdtPoolBox>& boxes, GdtPoolRegions& g);
 int gdt_k_pool_regions(const void* x, int f32, float* out, int N, int H, int W, int D, int kind, float p, const float* p_channels, float eps,
-                       const GdtPoolRegions& g, hipStream_t st);
+                       const GdtPoolRegions& g, hipStream_t st, const float* weights = nullptr);     // weights: pools x * weights[n][pixel]
+// L2NormAttention (mdir/components/model/layers/attention.py:10-15): out[n][pixel] = sqrt(sum_c x^2 + 1e-10), divided by the image's maximum when
+// normalize_max; `partial`: gdt_pixel_attention_partial_floats(N, HW) floats (the workgroups' maxima), unused without normalize_max
+size_t gdt_pixel_attention_partial_floats(int N, long HW);
+int gdt_k_pixel_attention(const void* x, int f32, int N, long HW, int D, int normalize_max, float* out, float* partial, hipStream_t st);
 int gdt_k_linear_rows(const float* a, const float* w, const float* bias, float* out, int rows, int K, int Dout, hipStream_t st);
 int gdt_k_region_sum(const float* v, float* y, int N, int R, int D, float eps, int l2n, hipStream_t st);
 size_t gdt_pool_head_scratch_floats(int N, int R, int D);

@@ -2,7 +2,8 @@
 //
 //   pack_input      fp32 NCHW image -> fp16 NHWC8, optional bilinear resize (F.interpolate(scale_factor=s,
 //                   mode='bilinear', align_corners=False), mdir/components/data/wrapper.py:225), channel permutation
-//                   (RgbToBgrPre wrapper.py:351-364) and per-channel affine (MeanStdPost._adapt wrapper.py:172-175)
+//                   (RgbToBgrPre wrapper.py:351-364) and per-channel affine (MeanStdPost._adapt wrapper.py:172-175), optional EdgeFilter
+//                   behind them, in fp32 in front of the rounding (mdir/components/model/layers/preprocessing.py:18-25)
 //   in_stats / in_finalize / in_apply
 //                   nn.InstanceNorm2d(affine=False), eps 1e-5, biased variance (p2p_networks.py:29) + fused ReLU
 //                   (:272) + fused residual add (ResnetBlock.forward :505)
@@ -54,7 +55,15 @@ struct PackArgs {
     int resize;
     int aug;               // fp16 output only: slots [C, 2C) of the pixel word carry (v - fp16(v)) * 2^8 (conv_stem.hip, f16c form)
     int perm[8]; float scale[8], shift[8];
+    GdtInputFilter filt;   // kind 0: none
 };
+
+// EdgeFilter.forward (mdir/components/model/layers/preprocessing.py:25) in fp32, the reference's own operation order
+__device__ __forceinline__ float edge_filter(float x, const GdtInputFilter& f) {
+    const float num = f.w * powf(fmaxf(x, f.eps), f.p);
+    const float den = expf(fminf(-f.beta * (x - f.tau), 50.0f)) + 1.0f;
+    return num / den;
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void pack_input_kernel(const PackArgs a) {
@@ -88,6 +97,11 @@ __global__ __launch_bounds__(256) void pack_input_kernel(const PackArgs a) {
                                     ly1 * (lx0 * p[(long)y1 * a.W + x0] + lx1 * p[(long)y1 * a.W + x1]);
                     o[c] = v * a.scale[c] + a.shift[c];
                 }
+        }
+        if (a.filt.kind == GDT_FILTER_EDGE) {          // on the fp32 value, in front of the rounding: the filter is a step of slope ~1e3 around tau
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                if (c < a.C) o[c] = edge_filter(o[c], a.filt);
         }
         if (a.aug) {
 #pragma unroll
@@ -578,8 +592,10 @@ inline int grid_for(long work_items, int cap = 256 * 16) {
 #define TP(T, p) ((T*)(p))
 
 int gdt_k_pack_input(const float* x, void* y, int f32, int N, int C, int H, int W, int OH, int OW, float rscale, int resize,
-                     const int* perm, const float* scale, const float* shift, hipStream_t st) {
+                     const int* perm, const float* scale, const float* shift, hipStream_t st, const GdtInputFilter* filter) {
     GDT_REQUIRE(C >= 1 && C <= 8, "pack_input supports 1..8 channels");
+    GDT_REQUIRE(!filter || filter->kind == GDT_FILTER_NONE || filter->kind == GDT_FILTER_EDGE, "pack_input: unknown input filter");
+    GDT_REQUIRE(!filter || filter->kind == GDT_FILTER_NONE || f32 != 2, "pack_input: the augmented pixel words take no input filter");
     PackArgs a;
     a.x = x; a.y = y; a.N = N; a.C = C; a.H = H; a.W = W; a.OH = OH; a.OW = OW; a.rscale = rscale; a.resize = resize;
     for (int c = 0; c < 8; ++c) {
@@ -588,6 +604,7 @@ int gdt_k_pack_input(const float* x, void* y, int f32, int N, int C, int H, int 
         a.shift[c] = (shift && c < C) ? shift[c] : 0.f;
     }
     a.aug = f32 == 2 ? 1 : 0;
+    a.filt = filter ? *filter : GdtInputFilter{};
     GDT_REQUIRE(!a.aug || 2 * C <= 8, "augmented pixel words need 2 * channels <= 8");
     LAUNCH_T(pack_input_kernel, f32 == 1, dim3(grid_for((long)N * OH * OW)), 0, st, a);
     return GDT_OK;

@@ -883,6 +883,26 @@ int gdt_net_pool_head(gdt_net* net, int in_tensor, int kind, const float* p, int
     return GDT_OK;
 }
 
+int gdt_net_pool_head_attention(gdt_net* net, int in_tensor, int kind, const float* p, int n_p, float eps, int aggregate, int levels, const float* rw,
+                                const float* rb, float eps_l2, int attention, int normalize_max, int* out_slot) {
+    GDT_REQUIRE(attention == 1, "pool head attention: attention 1 = L2-norm attention");
+    GDT_REQUIRE(normalize_max == 0 || normalize_max == 1, "pool head attention: normalize_max is 0 or 1");
+    const int rc = gdt_net_pool_head(net, in_tensor, kind, p, n_p, eps, aggregate, levels, rw, rb, nullptr, nullptr, eps_l2, out_slot);
+    if (rc != GDT_OK) return rc;
+    net->ops.back().att = attention; net->ops.back().att_max = normalize_max;
+    return GDT_OK;
+}
+
+int gdt_net_input_filter(gdt_net* net, int kind, float w, float p, float beta, float tau, float eps) {
+    GDT_REQUIRE(net && !net->finalized && net->input_op >= 0, "input filter: between gdt_net_input and gdt_net_finalize");
+    GDT_REQUIRE(kind == GDT_FILTER_EDGE, "input filter: kind 1 = EdgeFilter");
+    GDT_REQUIRE(net->ops[net->input_op].filter.kind == GDT_FILTER_NONE, "input filter: the input already has one");
+    GDT_REQUIRE(eps > 0.f && std::isfinite(w) && std::isfinite(p) && std::isfinite(beta) && std::isfinite(tau), "input filter: EdgeFilter takes finite constants and eps > 0");
+    GdtInputFilter& f = net->ops[net->input_op].filter;
+    f.kind = kind; f.w = w; f.p = p; f.beta = beta; f.tau = std::min(std::max(tau, 0.01f), 0.9f); f.eps = eps;
+    return GDT_OK;
+}
+
 int gdt_net_output_nchw(gdt_net* net, int in_tensor, const float* bias, int* out_slot) {
     GDT_REQUIRE(net && !net->finalized && out_slot, "net");
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "tensor id");

@@ -250,7 +250,8 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
             case OP_INPUT: {
                 const int resize = (rh != h || rw != w) ? 1 : 0;
                 if (stp.direct) break;                       // the stem conv reads x itself (planned only for calls that do not resize)
-                rc = gdt_k_pack_input(c.x, tptr(o.out), stp.aug ? 2 : f32, n, o.in_c, h, w, rh, rw, c.rscale, resize, o.perm, o.scale, o.shift, st);
+                rc = gdt_k_pack_input(c.x, tptr(o.out), stp.aug ? 2 : f32, n, o.in_c, h, w, rh, rw, c.rscale, resize, o.perm, o.scale, o.shift, st,
+                                      o.filter.kind ? &o.filter : nullptr);
                 break;
             }
             case OP_CONV:
@@ -305,6 +306,12 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                 if (o.pool_kind == GDT_POOL_GEMMP) hd.p_channels = (const float*)(net->dev_blob + o.pch_off);
                 if (o.has_rw) { hd.rw = (const float*)(net->dev_blob + o.rw_off); hd.rb = (const float*)(net->dev_blob + o.rb_off); }
                 if (o.has_fw) { hd.fw = (const float*)(net->dev_blob + o.fw_off); hd.fb = (const float*)(net->dev_blob + o.fb_off); }
+                if (o.att) {                // the attention weights [n][H * W] and the workgroups' maxima, behind the head's own scratch (net_plan.hip)
+                    float* wts = (float*)(ws + stp.aux_off[0]) + gdt_pool_head_scratch_floats(n, g.R, ti.C);
+                    rc = gdt_k_pixel_attention(tptr(o.in), f32, n, (long)ti.H * ti.W, ti.C, o.att_max, wts, wts + (size_t)n * ti.H * ti.W, st);
+                    if (rc != GDT_OK) break;
+                    hd.weights = wts;
+                }
                 rc = gdt_k_pool_head(tptr(o.in), f32, n, ti.H, ti.W, ti.C, hd, g, (float*)(ws + stp.aux_off[0]), (float*)outputs[o.slot], st);
                 break;
             }
@@ -554,6 +561,17 @@ int gdt_gem_l2n(const float* fmap, int n, int d, int h, int w, float p, float ep
 int gdt_l2n_rows(const float* x, float* y, int n, int d, float eps, void* stream) {
     GDT_REQUIRE(x && y && n >= 1 && d >= 1, "l2n arguments");
     return gdt_k_l2n_rows(x, y, n, d, eps, (hipStream_t)stream);
+}
+
+int gdt_pack_input_filter(const float* x, int n, int c, int h, int w, int out_f32, int kind, float fw, float fp, float fbeta, float ftau, float feps,
+                          void* out, void* stream) {
+    GDT_REQUIRE(x && out && n >= 1 && c >= 1 && c <= 8 && h >= 1 && w >= 1 && (out_f32 == 0 || out_f32 == 1), "pack_input_filter arguments");
+    GDT_REQUIRE(kind == GDT_FILTER_NONE || kind == GDT_FILTER_EDGE, "pack_input_filter: kind 0 none, 1 EdgeFilter");
+    GDT_REQUIRE(kind == GDT_FILTER_NONE || (feps > 0.f && std::isfinite(fw) && std::isfinite(fp) && std::isfinite(fbeta) && std::isfinite(ftau)),
+                "pack_input_filter: EdgeFilter takes finite constants and eps > 0");
+    GdtInputFilter f;
+    f.kind = kind; f.w = fw; f.p = fp; f.beta = fbeta; f.tau = std::min(std::max(ftau, 0.01f), 0.9f); f.eps = feps;
+    return gdt_k_pack_input(x, out, out_f32, n, c, h, w, h, w, 1.f, 0, nullptr, nullptr, nullptr, (hipStream_t)stream, &f);
 }
 
 }  // extern "C"

@@ -45,6 +45,7 @@ struct Op {
     size_t bias_frag_off = 0; bool has_bias_frag = false;    // 1x1 convs from 256 channels: the bias as an MFMA weight fragment (conv3x3_expand_rb.hip)
     // input
     int in_c = 0; int perm[8]; float scale[8], shift[8];
+    GdtInputFilter filter;      // gdt_net_input_filter: per-pixel function applied by the input pack (kind 0: none)
     // inorm
     float eps = 1e-5f; int relu = 0;
     int stats_from = -1;   // INORM: index of the conv op whose epilogue can deliver the statistics
@@ -82,6 +83,7 @@ struct Op {
     // 1 = R-MAC, 2 = Rpool over `levels` levels of regions; the per-channel exponents and the two whitening layers in the blob (fp32)
     int pool_kind = 0, pool_aggregate = 0, pool_levels = 0;
     size_t pch_off = 0, rw_off = 0, rb_off = 0, fw_off = 0, fb_off = 0; bool has_rw = false, has_fw = false;
+    int att = 0, att_max = 0;   // gdt_net_pool_head_attention: 1 = L2-norm attention weights in front of the pooling, divided by the image's maximum when att_max
     // out_nchw
     size_t tap_bias_off = 0; bool tap_has_bias = false;
     // head ops (OP_HED, OP_RCF): the feature tensors they read -- inputs like `in` / `res` (op_inputs), kept alive until the head runs

@@ -364,6 +364,7 @@ void Planner::split_mode_forms() {
         const Op& o = ops[i];
         if (o.kind != OP_CONV || o.cd.transposed || o.rowsplit || o.phases.empty() || !o.phases[0].has_aug) continue;
         if (o.in < 0 || ops[net->input_op].out != o.in || consumers[o.in] != 1) continue;
+        if (ops[net->input_op].filter.kind) continue;        // the augmented pixel words take no input filter (gdt_k_pack_input)
         if (gdt_conv_stem_c_eligible(conv_desc_phase(probe, i, o.phases[0], 0, fold(i), true))) { plan.steps[i].aug = true; plan.steps[net->input_op].aug = true; }
     }
     for (int i = 0; i < nops; ++i) {
@@ -569,7 +570,7 @@ void Planner::kcat_folds() {
 
 // ---- pass 2e (fp16 mode): the ResNet stem straight from the caller's image (no input pack) -- decided here, taken by the executor when the call does not resize
 void Planner::direct_stem() {
-    if (!direct_ok || net->precision || nops < 2 || ops[0].kind != OP_INPUT || ops[0].in_c > 3 || consumers[ops[0].out] != 1) return;
+    if (!direct_ok || net->precision || nops < 2 || ops[0].kind != OP_INPUT || ops[0].in_c != 3 || ops[0].filter.kind || consumers[ops[0].out] != 1) return;      // (three plain channels: the kernel applies permutation and affine, no filter)
     const int j = consumer_op[ops[0].out];
     const Op& o = ops[j];
     if (o.kind != OP_CONV || o.in != ops[0].out || o.res >= 0 || o.leaky != 0.f || o.phases.size() != 1 || !o.phases[0].has_pair || plan.steps[j].aug || o.stats_for >= 0 || taken(j)) return;
@@ -663,7 +664,9 @@ int Planner::layout() {
                 const int rc = gdt_pool_grid(ti.H, ti.W, o.pool_aggregate ? o.pool_levels : 0, boxes);
                 if (rc != GDT_OK) return rc;
                 GDT_REQUIRE((int)boxes.size() <= GDT_POOL_MAX_REGIONS, "pool head: more than 64 regions per image for this map size");
-                st.aux_off[0] = arena.scratch(gdt_pool_head_scratch_floats(N, (int)boxes.size(), ti.C) * sizeof(float));
+                size_t floats = gdt_pool_head_scratch_floats(N, (int)boxes.size(), ti.C);
+                if (o.att) floats += (size_t)N * ti.H * ti.W + gdt_pixel_attention_partial_floats(N, (long)ti.H * ti.W);      // the weights and the workgroups' maxima behind it
+                st.aux_off[0] = arena.scratch(floats * sizeof(float));
                 break;
             }
             case OP_OUT_NCHW: break;
@@ -797,7 +800,8 @@ int gdt_net_workspace_bytes(gdt_net* net, int n, int rh, int rw, size_t* bytes) 
 // [12] launches of the pool-head ops (gdt_net_pool_head), [13] of those the ones that read the feature map; with n_counts >= 15: [14] conv launches that
 // conv4x4_halo.hip takes (what gdt_launch_conv decides for the conv as its own plain launch; GDT_CONV4X4_HALO=0: none); with n_counts >= 16: [15] transposed 4x4 convs
 // that conv4x4t_halo.hip takes (one launch each, the concatenation in front never written; GDT_CONV4X4T_HALO=0: none -- then four phase launches each); with
-// n_counts >= 17: [16] convs of a concatenation (gdt_net_conv_cat) that conv3x3_cat_halo.hip takes (GDT_CONV3X3_CAT_HALO=0: none -- then a copy + the conv of one tensor)
+// n_counts >= 17: [16] convs of a concatenation (gdt_net_conv_cat) that conv3x3_cat_halo.hip takes (GDT_CONV3X3_CAT_HALO=0: none -- then a copy + the conv of one tensor);
+// with n_counts >= 19: [17] launches the attention of gdt_net_pool_head_attention adds in front of the pooling, [18] launches of such heads that read the feature map
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts) {
     GDT_REQUIRE(net && counts && n_counts >= 10 && n >= 1 && rh >= 1 && rw >= 1, "plan summary arguments");
     if (!net->finalized && !net->precision) build_kcat_weights(net);       // (what finalize would add: the K-concatenated shortcut weights the planner may choose)
@@ -815,6 +819,10 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
         if (o.kind == OP_POOL_HEAD && n_counts >= 14) {   // the launches of gdt_k_pool_head: fixed by the layers present, whatever the batch and the number of regions
             counts[12] += 1 + (o.pool_aggregate ? 2 + (o.has_rw ? 2 : 0) + (o.pool_aggregate == 2 ? 1 : 0) : 1) + (o.has_fw ? 2 : 0);
             counts[13] += 1;                              // ... of which read the feature map: the pooling pass
+        }
+        if (o.kind == OP_POOL_HEAD && o.att && n_counts >= 19) {      // the attention in front of the pooling: the norm pass (+ the division by the image's maximum)
+            counts[17] += 1 + (o.att_max ? 1 : 0);
+            counts[18] += 2;                              // the map is read by the norm pass and by the weighted pooling pass
         }
         if (o.kind == OP_INPUT) counts[7] += st.direct;
         if (o.kind == OP_CONV && n_counts >= 15 && !net->precision && o.phases.size() == 1 && !o.rowsplit &&

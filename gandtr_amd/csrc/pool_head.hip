@@ -5,6 +5,9 @@
 //   pool_regions_kernel   max / mean / GeM / per-channel GeM of EVERY region of an image in ONE pass over the map (layers/pooling.py:12-61 per region)
 //   linear_rows_kernel    rows through an nn.Linear, fp32 FMA (the regional and the final whitening, imageretrievalnet.py:236, :254)
 //   region_sum_kernel     sum over an image's regions (+ l2n): Rpool.forward (layers/pooling.py:105-108), the tail of LF.rmac (functional.py:73)
+//   pixel_norm_kernel, attention_scale_kernel
+//                         L2NormAttention (mdir/components/model/layers/attention.py:10-15): one weight per position, reduced across the channels; the weighted
+//                         form of pool_regions_kernel folds it into the pooling pass (CirRetrievalNetAttention.forward, mdir/components/model/network/cirnet.py:116-125)
 //
 // The reference pools region by region (one narrow + pool call each, 15 to 51 per forward, GeM's pow once per region a pixel lies in).  Here a region is
 // (row range) x (column band); a pixel's value -- for GeM: max(x, eps)^p, evaluated once -- is folded into the few column bands that contain x, and at
@@ -86,9 +89,12 @@ namespace {
 // the rows.  LDS: per wave R region accumulators and B band partials of 64 floats; a lane only ever touches its own column of them, so nothing is
 // shared inside a wave and the only barrier is the one before the waves' partials are combined (in wave order).
 // Which bands contain x / which regions contain y: lane b holds band b's range, lane r region r's -- one compare + ballot gives the set as a mask.
-template <typename T, int KIND>
+// WEIGHTED: the value folded into the bands is x * wts[n][y][x] (one fp32 multiply in front of GeM's clamp and power: the pooling of CirRetrievalNetAttention sees
+// feats * att); the weight of a pixel is the same for every lane of the wave, and the unweighted instantiation is the kernel it was.
+template <typename T, int KIND, bool WEIGHTED>
 __global__ __launch_bounds__(256) void pool_regions_kernel(const T* __restrict__ x, float* __restrict__ out, int H, int W, int D, float p,
-                                                            const float* __restrict__ p_channels, float eps, const GdtPoolRegions g) {
+                                                            const float* __restrict__ p_channels, float eps, const GdtPoolRegions g,
+                                                            const float* __restrict__ wts) {
     extern __shared__ float acc[];
     constexpr bool MAX = KIND == GDT_POOL_MAX;
     const float ident = MAX ? -INFINITY : 0.f;
@@ -106,10 +112,15 @@ __global__ __launch_bounds__(256) void pool_regions_kernel(const T* __restrict__
     const T* img = x + (size_t)n * H * W * D + d0 + lane;
     for (int y = wave; y < H; y += NW) {
         const T* row = img + (size_t)y * W * D;
+        const float* wrow = WEIGHTED ? wts + ((size_t)n * H + y) * W : nullptr;
         for (int x0 = 0; x0 < W; x0 += 8) {
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = x0 + j < W ? (float)row[(size_t)(x0 + j) * D] : 0.f;      // eight loads in flight per lane
+            if (WEIGHTED) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = x0 + j < W ? v[j] * wrow[x0 + j] : 0.f;
+            }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int xx = x0 + j;
@@ -211,21 +222,115 @@ __global__ __launch_bounds__(256) void region_sum_kernel(const float* __restrict
     for (int i = threadIdx.x; i < D; i += 256) yn[i] = yn[i] / nrm;          // (each thread rescales the entries it wrote itself)
 }
 
-template <typename T>
+template <typename T, bool WEIGHTED>
 void launch_pool(int kind, dim3 grid, dim3 block, size_t lds, hipStream_t st, const T* x, float* out, int H, int W, int D, float p, const float* pch,
-                 float eps, const GdtPoolRegions& g) {
+                 float eps, const GdtPoolRegions& g, const float* wts) {
     switch (kind) {
-        case GDT_POOL_MAX: hipLaunchKernelGGL((pool_regions_kernel<T, GDT_POOL_MAX>), grid, block, lds, st, x, out, H, W, D, p, pch, eps, g); break;
-        case GDT_POOL_MEAN: hipLaunchKernelGGL((pool_regions_kernel<T, GDT_POOL_MEAN>), grid, block, lds, st, x, out, H, W, D, p, pch, eps, g); break;
-        case GDT_POOL_GEM: hipLaunchKernelGGL((pool_regions_kernel<T, GDT_POOL_GEM>), grid, block, lds, st, x, out, H, W, D, p, pch, eps, g); break;
-        default: hipLaunchKernelGGL((pool_regions_kernel<T, GDT_POOL_GEMMP>), grid, block, lds, st, x, out, H, W, D, p, pch, eps, g); break;
+        case GDT_POOL_MAX: hipLaunchKernelGGL((pool_regions_kernel<T, GDT_POOL_MAX, WEIGHTED>), grid, block, lds, st, x, out, H, W, D, p, pch, eps, g, wts); break;
+        case GDT_POOL_MEAN: hipLaunchKernelGGL((pool_regions_kernel<T, GDT_POOL_MEAN, WEIGHTED>), grid, block, lds, st, x, out, H, W, D, p, pch, eps, g, wts); break;
+        case GDT_POOL_GEM: hipLaunchKernelGGL((pool_regions_kernel<T, GDT_POOL_GEM, WEIGHTED>), grid, block, lds, st, x, out, H, W, D, p, pch, eps, g, wts); break;
+        default: hipLaunchKernelGGL((pool_regions_kernel<T, GDT_POOL_GEMMP, WEIGHTED>), grid, block, lds, st, x, out, H, W, D, p, pch, eps, g, wts); break;
     }
+}
+
+// ------------------------------------------------------------------------------------------------ pixel attention (L2NormAttention)
+// out[n][pixel] = sqrt(sum_c x_c^2 + 1e-10).  A pixel's D channels are contiguous: a wave takes ATT_PX pixels at a time, a lane the 16-byte pieces lane, lane + 64, ..
+// of each (ascending), squares accumulated in fp32, then the xor butterfly across the lanes: the order of the sum is fixed by D alone, and every lane ends with the
+// same bits.  grid (G, N): workgroup g of an image takes the wave-chunks g, g + G, ..; with MAXP the workgroup's maximum goes to partial[n][g] (a maximum is exact in
+// any order; no atomics) and attention_scale_kernel finishes: maximum of the G partials, then a / M -- a division, as the reference's m / m.max().
+constexpr int ATT_PX = 4;             // pixels a wave has in flight
+constexpr int ATT_MAX_GROUPS = 256;   // workgroups per image at most
+
+template <typename T>
+__global__ __launch_bounds__(256) void pixel_norm_kernel(const T* __restrict__ x, float* __restrict__ out, float* __restrict__ partial, long HW, int D, int maxp) {
+    constexpr int E = 16 / sizeof(T);            // elements of a 16-byte piece
+    __shared__ float red[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = blockIdx.y, pieces = D / E;
+    const T* img = x + (size_t)n * HW * D;
+    float* o = out + (size_t)n * HW;
+    float wmax = 0.f;
+    for (long p0 = ((long)blockIdx.x * 4 + wave) * ATT_PX; p0 < HW; p0 += (long)gridDim.x * 4 * ATT_PX) {
+        float acc[ATT_PX];
+#pragma unroll
+        for (int j = 0; j < ATT_PX; ++j) acc[j] = 0.f;
+        for (int pc = lane; pc < pieces; pc += 64) {
+            float v[ATT_PX][E];
+#pragma unroll
+            for (int j = 0; j < ATT_PX; ++j) {
+                const long px = p0 + j < HW ? p0 + j : HW - 1;            // (a chunk past the end repeats the last pixel: loads stay inside the map)
+                const T* src = img + (size_t)px * D + (size_t)pc * E;
+                if constexpr (sizeof(T) == 2) {
+                    const f16x8 t = *(const f16x8*)src;
+#pragma unroll
+                    for (int e = 0; e < E; ++e) v[j][e] = (float)t[e];
+                } else {
+                    const float4 t = *(const float4*)src;
+                    v[j][0] = t.x; v[j][1] = t.y; v[j][2] = t.z; v[j][3] = t.w;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < ATT_PX; ++j)
+#pragma unroll
+                for (int e = 0; e < E; ++e) acc[j] = fmaf(v[j][e], v[j][e], acc[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < ATT_PX; ++j) {
+            float s = acc[j];
+#pragma unroll
+            for (int k = 32; k > 0; k >>= 1) s += __shfl_xor(s, k);
+            const float m = sqrtf(s + 1e-10f);
+            if (p0 + j < HW) {
+                wmax = fmaxf(wmax, m);
+                if (lane == j) o[p0 + j] = m;
+            }
+        }
+    }
+    if (!maxp) return;
+    if (lane == 0) red[wave] = wmax;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(size_t)n * gridDim.x + blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// a[n][pixel] /= max_g partial[n][g]; grid (blocks over the pixels, N), G <= ATT_MAX_GROUPS = one partial per thread at most
+__global__ __launch_bounds__(256) void attention_scale_kernel(float* __restrict__ a, const float* __restrict__ partial, long HW, int G) {
+    __shared__ float red[4];
+    const int n = blockIdx.y;
+    float m = threadIdx.x < G ? partial[(size_t)n * G + threadIdx.x] : 0.f;
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) m = fmaxf(m, __shfl_xor(m, k));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    const float M = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float* an = a + (size_t)n * HW;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long)gridDim.x * 256) an[i] = an[i] / M;
+}
+
+int attention_groups(long HW) {
+    const long chunks = (HW + 4 * ATT_PX - 1) / (4 * ATT_PX);
+    return (int)std::min<long>(std::max<long>(chunks, 1), ATT_MAX_GROUPS);
 }
 
 }  // namespace
 
+size_t gdt_pixel_attention_partial_floats(int N, long HW) { return (size_t)N * attention_groups(HW); }
+
+int gdt_k_pixel_attention(const void* x, int f32, int N, long HW, int D, int normalize_max, float* out, float* partial, hipStream_t st) {
+    GDT_REQUIRE(N >= 1 && N <= 65535 && HW >= 1 && D >= 64 && D % 64 == 0, "pixel attention needs D % 64 == 0 and at most 65535 images");
+    GDT_REQUIRE(!normalize_max || partial, "pixel attention: the maximum needs its workspace");
+    const int G = attention_groups(HW);
+    if (f32) hipLaunchKernelGGL(pixel_norm_kernel<float>, dim3(G, N), dim3(256), 0, st, (const float*)x, out, partial, HW, D, normalize_max);
+    else hipLaunchKernelGGL(pixel_norm_kernel<f16>, dim3(G, N), dim3(256), 0, st, (const f16*)x, out, partial, HW, D, normalize_max);
+    GDT_CHECK_HIP(hipGetLastError());
+    if (!normalize_max) return GDT_OK;
+    const int blocks = (int)std::min<long>((HW + 255) / 256, 64);
+    hipLaunchKernelGGL(attention_scale_kernel, dim3(blocks, N), dim3(256), 0, st, out, (const float*)partial, HW, G);
+    GDT_CHECK_HIP(hipGetLastError());
+    return GDT_OK;
+}
+
 int gdt_k_pool_regions(const void* x, int f32, float* out, int N, int H, int W, int D, int kind, float p, const float* p_channels, float eps,
-                       const GdtPoolRegions& g, hipStream_t st) {
+                       const GdtPoolRegions& g, hipStream_t st, const float* weights) {
     GDT_REQUIRE(D % 64 == 0, "region pooling needs D % 64 == 0");
     GDT_REQUIRE(kind >= GDT_POOL_MAX && kind <= GDT_POOL_GEMMP, "pooling kind 0..3 (max, mean, GeM, per-channel GeM)");
     GDT_REQUIRE(kind != GDT_POOL_GEMMP || p_channels, "per-channel GeM needs its exponents");
@@ -240,8 +345,13 @@ int gdt_k_pool_regions(const void* x, int f32, float* out, int N, int H, int W, 
     const size_t per_wave = (size_t)(g.R + g.B) * 64 * sizeof(float);
     const int nw = 4 * per_wave <= 49152 ? 4 : 2;
     const dim3 grid(D / 64, N), block(64 * nw);
-    if (f32) launch_pool<float>(kind, grid, block, per_wave * nw, st, (const float*)x, out, H, W, D, p, p_channels, eps, g);
-    else launch_pool<f16>(kind, grid, block, per_wave * nw, st, (const f16*)x, out, H, W, D, p, p_channels, eps, g);
+    if (weights) {
+        if (f32) launch_pool<float, true>(kind, grid, block, per_wave * nw, st, (const float*)x, out, H, W, D, p, p_channels, eps, g, weights);
+        else launch_pool<f16, true>(kind, grid, block, per_wave * nw, st, (const f16*)x, out, H, W, D, p, p_channels, eps, g, weights);
+    } else {
+        if (f32) launch_pool<float, false>(kind, grid, block, per_wave * nw, st, (const float*)x, out, H, W, D, p, p_channels, eps, g, nullptr);
+        else launch_pool<f16, false>(kind, grid, block, per_wave * nw, st, (const f16*)x, out, H, W, D, p, p_channels, eps, g, nullptr);
+    }
     GDT_CHECK_HIP(hipGetLastError());
     return GDT_OK;
 }
@@ -270,7 +380,7 @@ int gdt_k_pool_head(const void* x, int f32, int N, int H, int W, int D, const Gd
     GDT_REQUIRE(hd.aggregate >= 0 && hd.aggregate <= 2 && (hd.aggregate || R == 1), "pool head: regions need an aggregation");
     GDT_REQUIRE(!hd.rw || hd.aggregate == 2, "pool head: the regional whitening belongs to a regional pooling");
     float* P = scratch; float* Q = P + (size_t)N * R * D; float* U = Q + (size_t)N * R * D; float* V = U + (size_t)N * D;
-    int rc = gdt_k_pool_regions(x, f32, P, N, H, W, D, hd.kind, hd.p, hd.p_channels, hd.eps, g, st);
+    int rc = gdt_k_pool_regions(x, f32, P, N, H, W, D, hd.kind, hd.p, hd.p_channels, hd.eps, g, st, hd.weights);
     if (rc != GDT_OK) return rc;
     float* cur;                             // the [N][D] vector after the net's first l2n
     if (!hd.aggregate) {
@@ -324,6 +434,34 @@ int gdt_pool_regions(const void* fmap, int f32, int n, int h, int w, int d, int 
     rc = gdt_pool_regions_of(bx, g);
     if (rc != GDT_OK) return rc;
     return gdt_k_pool_regions(fmap, f32, out, n, h, w, d, kind, p, p_channels, eps, g, (hipStream_t)stream);
+}
+
+int gdt_pool_regions_weighted(const void* fmap, int f32, int n, int h, int w, int d, int kind, float p, const float* p_channels, float eps, int levels,
+                              const float* weights, float* out, void* stream) {
+    GDT_REQUIRE(fmap && out && weights && n >= 1 && d >= 1 && (f32 == 0 || f32 == 1), "pool_regions_weighted arguments");
+    std::vector<GdtPoolBox> bx;
+    int rc = gdt_pool_grid(h, w, levels, bx);
+    if (rc != GDT_OK) return rc;
+    GdtPoolRegions g{};
+    rc = gdt_pool_regions_of(bx, g);
+    if (rc != GDT_OK) return rc;
+    return gdt_k_pool_regions(fmap, f32, out, n, h, w, d, kind, p, p_channels, eps, g, (hipStream_t)stream, weights);
+}
+
+int gdt_pixel_attention_workspace_bytes(int n, int h, int w, size_t* bytes) {
+    GDT_REQUIRE(bytes && n >= 1 && h >= 1 && w >= 1 && h <= 32767 && w <= 32767, "pixel attention geometry");
+    *bytes = gdt_pixel_attention_partial_floats(n, (long)h * w) * sizeof(float);
+    return GDT_OK;
+}
+
+int gdt_pixel_attention(const void* fmap, int f32, int n, int h, int w, int d, int normalize_max, float* out, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    GDT_REQUIRE(fmap && out && n >= 1 && h >= 1 && w >= 1 && h <= 32767 && w <= 32767 && d >= 1 && (f32 == 0 || f32 == 1), "pixel_attention arguments");
+    GDT_REQUIRE(normalize_max == 0 || normalize_max == 1, "pixel_attention: normalize_max is 0 or 1");
+    GDT_REQUIRE(d % 64 == 0 && n <= 65535, "pixel attention needs D % 64 == 0 and at most 65535 images");
+    if (normalize_max)
+        GDT_REQUIRE(workspace && workspace_bytes >= gdt_pixel_attention_partial_floats(n, (long)h * w) * sizeof(float), "pixel_attention: workspace too small");
+    return gdt_k_pixel_attention(fmap, f32, n, (long)h * w, d, normalize_max, out, (float*)workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -134,6 +134,13 @@ class HipNet:
         self.in_channels = channels
         return out
 
+    def input_filter(self, kind, w, p, beta, tau, eps):
+        """gdt_net_input_filter: ``kind`` "edgefilter" = EdgeFilter(w, p, beta, tau, eps) applied by the input pack in fp32 (``tau`` is clamped into
+        [0.01, 0.9] by the library, as EdgeFilter.forward clamps its parameter)"""
+        if kind != "edgefilter":
+            raise NotImplementedError("input filter %r: only 'edgefilter' is on the HIP path" % (kind,))
+        _hip.check(self.lib.gdt_net_input_filter(self.handle, 1, float(w), float(p), float(beta), float(tau), float(eps)))
+
     def conv(self, x, weight, bias=None, bn=None, stride=1, pad=0, reflect=False, transposed=False, relu=False,
              residual=-1, out_f32=False, act=0, dilation=1, leaky=0.0):
         """``leaky``: slope of an nn.LeakyReLU applied after bias and BatchNorm in place of ``relu`` (gdt_net_conv_leaky)"""
@@ -208,6 +215,14 @@ class HipNet:
         fw, fb = (_f32(whiten[0]), _f32(whiten[1])) if whiten is not None else (None, None)
         return self._add("pool_head", x, self.POOL_KINDS[kind], _ptr(pa), 0 if pa is None else pa.size, float(eps), int(aggregate),
                          int(levels), _ptr(rw), _ptr(rb), _ptr(fw), _ptr(fb), float(eps_l2))
+
+    def pool_head_attention(self, x, kind, normalize_max, p=None, eps=1e-6, aggregate=0, levels=3, rwhiten=None, eps_l2=1e-6):
+        """gdt_net_pool_head_attention: ``pool_head`` (no final whitening) of the map weighted per position by its L2-norm attention, divided by the
+        image's maximum when ``normalize_max``"""
+        pa = _f32(p).reshape(-1) if p is not None else None
+        rw, rb = (_f32(rwhiten[0]), _f32(rwhiten[1])) if rwhiten is not None else (None, None)
+        return self._add("pool_head_attention", x, self.POOL_KINDS[kind], _ptr(pa), 0 if pa is None else pa.size, float(eps), int(aggregate),
+                         int(levels), _ptr(rw), _ptr(rb), float(eps_l2), 1, int(bool(normalize_max)))
 
     def output_nchw(self, x, bias=None):
         b = _f32(bias)
@@ -298,6 +313,11 @@ class HipNet:
     def head_launches(self, n, rh, rw):
         """(launches of the net's pool-head ops, launches among them that read the feature map) for a geometry -- the planner's count"""
         return tuple(self._plan_counts(n, rh, rw, False, 14)[12:])
+
+    def attention_launches(self, n, rh, rw):
+        """(launches the attention of the net's pool-head ops adds in front of the pooling, launches of such heads that read the feature map: the norm
+        pass and the weighted pooling pass) for a geometry -- the planner's count"""
+        return tuple(self._plan_counts(n, rh, rw, False, 19)[17:])
 
     def flops(self, n, rh, rw):
         f = ctypes.c_double()
@@ -684,17 +704,42 @@ def embedder_arch(sd):
     return "resnet" if "features.4.0.conv1.weight" in sd else "vgg16"
 
 
-def build_embedder(sd, device, in_affine=None, feature_tap=False, precision="f16", finalize=True, head=None):
+def build_embedder(sd, device, in_affine=None, feature_tap=False, precision="f16", finalize=True, head=None, attention=None, preprocessing=None):
     """ImageRetrievalNet.forward as a HIP graph.  External output 0: descriptors as a row-major [N][D] fp32 matrix (the reference returns its
     transpose view, D x N).
 
     ``head`` None: the hub configuration -- GeM, no whitening layers (lwhiten=None, whiten=None) -- on its own op (gem_l2n).  Otherwise the tuple
     ``ImageRetrievalNet._hip_head`` gives: (pooling "mac" | "spoc" | "gem" | "gemmp" | "rmac", regional, L, eps of the pooling, local whitening, final
     whitening); the layers' weights are the reference's state-dict entries (``lwhiten.*``, ``pool.p`` / ``pool.rpool.p``, ``pool.whiten.*``,
-    ``whiten.*``).  The local whitening is a 1x1 conv with bias and no ReLU in front of the pool; everything behind the map is one pool_head op."""
-    net, x = _open(device, precision, in_affine=in_affine)
+    ``whiten.*``).  The local whitening is a 1x1 conv with bias and no ReLU in front of the pool; everything behind the map is one pool_head op.
+
+    ``attention`` ("l2norm", normalize_max): CirRetrievalNetAttention -- the map is weighted per position by its L2 norm (divided by the image's maximum
+    when normalize_max) inside the pooling pass (pool_head_attention); no local and no final whitening, as the reference asserts.  With ``head`` None
+    the pooling is the hub's GeM.  ``preprocessing`` ("edgefilter", w, p, beta, tau, eps): CirRetrievalNetPreprocessing -- the EdgeFilter is evaluated by
+    the input pack, behind resize and ``in_affine``; p / tau None: the state dict's ``preprocessing.p`` / ``preprocessing.tau``.  The number of input
+    channels is that of ``features.0.weight`` (init_cirnet_inchan: 1 or 3)."""
+    channels = int(sd["features.0.weight"].shape[1])
+    net, x = _open(device, precision, channels=channels, in_affine=in_affine)
+    if preprocessing is not None:
+        kind, fw, fp, fbeta, ftau, feps = preprocessing
+        fp = float(sd["preprocessing.p"].reshape(-1)[0]) if fp is None else fp
+        ftau = float(sd["preprocessing.tau"].reshape(-1)[0]) if ftau is None else ftau
+        net.input_filter(kind, fw, fp, fbeta, ftau, feps)
     f = _resnet_trunk(net, x, sd) if embedder_arch(sd) == "resnet" else _vgg16_trunk(net, x, sd)
-    if head is None:
+    if attention is not None:
+        akind, normalize_max = attention
+        if akind != "l2norm":
+            raise NotImplementedError("attention %r: only 'l2norm' is on the HIP path" % (akind,))
+        kind, regional, levels, eps, local_whitening, whitening = head if head is not None else ("gem", False, 0, 1e-6, False, False)
+        if local_whitening or whitening:
+            raise NotImplementedError("the attention net takes no local and no final whitening (cirnet.py:117)")
+        if regional and kind == "rmac":
+            raise NotImplementedError("regions of R-MAC regions are not on the HIP path")
+        p = sd.get("pool.rpool.p" if regional else "pool.p") if kind in ("gem", "gemmp") else None
+        rwhiten = (sd["pool.whiten.weight"], sd["pool.whiten.bias"]) if regional and "pool.whiten.weight" in sd else None
+        net.out_slot = net.pool_head_attention(f, "mac" if kind == "rmac" else kind, normalize_max, p=p, eps=eps,
+                                               aggregate=2 if regional else (1 if kind == "rmac" else 0), levels=levels or 3, rwhiten=rwhiten)
+    elif head is None:
         net.out_slot = net.gem_l2n(f, float(sd["pool.p"].reshape(-1)[0]))
     else:
         kind, regional, levels, eps, local_whitening, whitening = head
@@ -1018,6 +1063,64 @@ def gem_l2n(fmap, p=3.0, eps_gem=1e-6, eps_l2=1e-6):
     with torch.cuda.device(fmap.device):
         _hip.check(lib.gdt_gem_l2n(fmap.data_ptr(), n, d, h, w, float(p), eps_gem, eps_l2, pooled.data_ptr(), out.data_ptr(), _stream(fmap)))
     return pooled.view(n, d, 1, 1), out.view(n, d, 1, 1)
+
+
+def _nhwc_map(fmap, what):
+    if not fmap.is_cuda or fmap.dim() != 4 or fmap.dtype not in (torch.float16, torch.float32):
+        raise ValueError("%s needs an N x H x W x D fp16 or fp32 tensor on a HIP device" % what)
+    return fmap.contiguous()
+
+
+def pixel_attention(fmap, normalize_max=False):
+    """gdt_pixel_attention: L2NormAttention of an NHWC map (N x H x W x D, fp16 or fp32, D % 64 == 0) per image -> fp32 N x H x W"""
+    lib = _hip.load()
+    fmap = _nhwc_map(fmap, "pixel_attention")
+    n, h, w, d = fmap.shape
+    with torch.cuda.device(fmap.device):
+        need = ctypes.c_size_t()
+        _hip.check(lib.gdt_pixel_attention_workspace_bytes(n, h, w, ctypes.byref(need)))
+        ws = torch.empty(max(1, need.value), dtype=torch.uint8, device=fmap.device)
+        out = torch.empty((n, h, w), dtype=torch.float32, device=fmap.device)
+        _hip.check(lib.gdt_pixel_attention(fmap.data_ptr(), int(fmap.dtype == torch.float32), n, h, w, d, int(bool(normalize_max)), out.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), _stream(fmap)))
+    return out
+
+
+def pool_regions_weighted(fmap, weights, kind, p=3.0, p_channels=None, eps=1e-6, levels=0):
+    """gdt_pool_regions_weighted: the one-pass region pooling of ``fmap * weights[..., None]`` (NHWC map, fp32 N x H x W weights) -> fp32 N x R x D, R the
+    boxes of gdt_rpool_regions(h, w, levels); ``kind`` as HipNet.POOL_KINDS"""
+    lib = _hip.load()
+    fmap = _nhwc_map(fmap, "pool_regions_weighted")
+    n, h, w, d = fmap.shape
+    if not weights.is_cuda or weights.dtype != torch.float32 or tuple(weights.shape) != (n, h, w):
+        raise ValueError("pool_regions_weighted needs fp32 N x H x W weights on the map's device")
+    weights = weights.contiguous()
+    cnt = ctypes.c_int()
+    _hip.check(lib.gdt_rpool_regions(h, w, levels, None, 0, ctypes.byref(cnt)))
+    pc = p_channels.to(fmap.device, torch.float32).contiguous() if p_channels is not None else None
+    with torch.cuda.device(fmap.device):
+        out = torch.empty((n, cnt.value, d), dtype=torch.float32, device=fmap.device)
+        _hip.check(lib.gdt_pool_regions_weighted(fmap.data_ptr(), int(fmap.dtype == torch.float32), n, h, w, d, HipNet.POOL_KINDS[kind], float(p),
+                                                 pc.data_ptr() if pc is not None else None, float(eps), int(levels), weights.data_ptr(), out.data_ptr(),
+                                                 _stream(fmap)))
+    return out
+
+
+def pack_input_filter(x, filt, out_f32=True):
+    """gdt_pack_input_filter: the input pack (fp32 NCHW -> NHWC8) with ``filt`` = ("edgefilter", w, p, beta, tau, eps) applied in fp32 in front of the rounding"""
+    lib = _hip.load()
+    if not x.is_cuda or x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("pack_input_filter needs an fp32 N x C x H x W tensor on a HIP device")
+    kind, fw, fp, fbeta, ftau, feps = filt
+    if kind != "edgefilter":
+        raise NotImplementedError("input filter %r" % (kind,))
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    with torch.cuda.device(x.device):
+        out = torch.empty((n, h, w, 8), dtype=torch.float32 if out_f32 else torch.float16, device=x.device)
+        _hip.check(lib.gdt_pack_input_filter(x.data_ptr(), n, c, h, w, int(bool(out_f32)), 1, float(fw), float(fp), float(fbeta), float(ftau), float(feps),
+                                             out.data_ptr(), _stream(x)))
+    return out
 
 
 def l2n_rows(x, eps=1e-6):

@@ -65,6 +65,13 @@ int gdt_net_set_precision(gdt_net* net, int mode);
  * (MeanStdPost/Pre._adapt, wrapper.py:172-175); pass NULL for identity.  A bilinear resize
  * (F.interpolate(scale_factor=s, mode='bilinear', align_corners=False), wrapper.py:225) is selected per forward call. */
 int gdt_net_input(gdt_net* net, int channels, const int* perm, const float* scale, const float* shift, int* out_tensor);
+/* A per-pixel function of the net's input, evaluated by the input pack in fp32 behind resize, permutation and affine and in front of the rounding to the
+ * activation type.  kind 1: EdgeFilter (mdir/components/model/layers/preprocessing.py:9-25) on every input channel,
+ *   y = w * max(x, eps)^p / (exp(min(-beta * (x - tau), 50)) + 1)
+ * with tau clamped into [0.01, 0.9] here, as EdgeFilter.forward clamps its parameter.  (With beta = 500 the filter is a step of slope ~1e3 around tau: it cannot
+ * be evaluated on an fp16-rounded input, nor folded into the affine.)  Valid between gdt_net_input and gdt_net_finalize, once.  A filtered input is always
+ * packed: the stem forms that read the caller's image themselves, and the augmented pixel words of the split modes, are not planned. */
+int gdt_net_input_filter(gdt_net* net, int kind, float w, float p, float beta, float tau, float eps);
 
 typedef struct gdt_conv_desc {
     int cin, cout;        /* logical channel counts (cin is padded to a power of two >= 8 internally)            */
@@ -150,6 +157,14 @@ int gdt_net_gem_l2n(gdt_net* net, int in_tensor, float p, float eps_gem, float e
  * precision mode.  External output: fp32 [N][D] row-major, as gdt_net_gem_l2n. */
 int gdt_net_pool_head(gdt_net* net, int in_tensor, int kind, const float* p, int n_p, float eps, int aggregate, int levels, const float* rw,
                       const float* rb, const float* fw, const float* fb, float eps_l2, int* out_slot);
+/* The head of CirRetrievalNetAttention.forward (mdir/components/model/network/cirnet.py:116-125): pool(x * att) -> l2n, where att is one weight per
+ * position of the map.  attention 1: L2NormAttention (mdir/components/model/layers/attention.py:4-15), att = sqrt(sum_c x_c^2 + 1e-10), divided by its
+ * maximum over the IMAGE when normalize_max (the reference's forward only works on a batch of one; a batch here is that forward per image).  The other
+ * arguments as in gdt_net_pool_head; there is no final whitening (the reference asserts its absence), a regional pooling keeps its own.  The weights
+ * are computed in one pass over the map (+ one pass over the weights when normalize_max) and folded into the one pooling pass as an fp32 multiply in
+ * front of GeM's clamp and power: the head reads the map twice, whatever the batch and the number of regions (gdt_net_plan_summary counts [17], [18]). */
+int gdt_net_pool_head_attention(gdt_net* net, int in_tensor, int kind, const float* p, int n_p, float eps, int aggregate, int levels, const float* rw,
+                                const float* rb, float eps_l2, int attention, int normalize_max, int* out_slot);
 
 /* Feature tap: internal fp16 NHWC tensor -> external fp32 NCHW (+ optional per-channel bias), p2p_networks.py:316-334 */
 int gdt_net_output_nchw(gdt_net* net, int in_tensor, const float* bias, int* out_slot);
@@ -230,7 +245,10 @@ int gdt_net_flops(gdt_net* net, int n, int rh, int rw, double* flops);
  * among them that read the feature map (one per op); with n_counts >= 15 also [14] the conv launches that run on the 4x4 patch kernel (conv4x4_halo.hip;
  * none with GDT_CONV4X4_HALO=0); with n_counts >= 16 also [15] the transposed 4x4 convs (gdt_net_conv_transposed4) that run as one launch of
  * conv4x4t_halo.hip (none with GDT_CONV4X4T_HALO=0); with n_counts >= 17 also [16] the convs of a concatenation (gdt_net_conv_cat) that run as one launch of
- * conv3x3_cat_halo.hip (none with GDT_CONV3X3_CAT_HALO=0).  (Diagnostics / tests; no reference counterpart.) */
+ * conv3x3_cat_halo.hip (none with GDT_CONV3X3_CAT_HALO=0); with n_counts >= 19 also [17] the launches the attention of gdt_net_pool_head_attention adds in
+ * front of the pooling (the norm pass, and the division by the maximum when normalize_max) and [18] the launches of such heads that read the feature map (two per
+ * op: the norm pass and the weighted pooling pass) -- [12] and [13] count an attention head's launches behind the weights as for any head.
+ * (Diagnostics / tests; no reference counterpart.) */
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts);
 
 /* Per-op timing for bench.py's roofline line: when enabled, gdt_net_forward records HIP events on the caller's stream
@@ -283,6 +301,23 @@ int gdt_rpool_regions(int h, int w, int levels, int* boxes, int capacity, int* c
  * gdt_net_pool_head; p_channels: d exponents on the device (kind 3).  One pass over the map; max is exact, the sums have a fixed order. */
 int gdt_pool_regions(const void* fmap, int f32, int n, int h, int w, int d, int kind, float p, const float* p_channels, float eps, int levels,
                      float* out, void* stream);
+/* ... with one fp32 weight per position (weights [n][h * w] on the device): pools x * weight -- a single fp32 multiply, in front of GeM's clamp and power.
+ * Weights of 1 give gdt_pool_regions bit for bit. */
+int gdt_pool_regions_weighted(const void* fmap, int f32, int n, int h, int w, int d, int kind, float p, const float* p_channels, float eps, int levels,
+                              const float* weights, float* out, void* stream);
+
+/* L2NormAttention on its own (mdir/components/model/layers/attention.py:10-15): fmap an NHWC map [n][h][w][d] on the device (f32 = 0: fp16, 1: fp32;
+ * d % 64 == 0), out fp32 [n][h * w]: sqrt(sum_c x_c^2 + 1e-10), summed in fp32 in an order fixed by d, divided (not multiplied by a reciprocal) by the
+ * maximum of the image when normalize_max.  workspace: gdt_pixel_attention_workspace_bytes(n, h, w) bytes on the device (the workgroups' maxima; no
+ * atomics: two runs give the same bits).  One launch, two with normalize_max, whatever n. */
+int gdt_pixel_attention_workspace_bytes(int n, int h, int w, size_t* bytes);
+int gdt_pixel_attention(const void* fmap, int f32, int n, int h, int w, int d, int normalize_max, float* out, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
+/* The input pack of gdt_net_input with the filter of gdt_net_input_filter on its own (no resize, permutation or affine): x fp32 [n][c][h][w] on the
+ * device, c <= 8, out NHWC8 [n][h][w][8] (out_f32 = 0: fp16, 1: fp32), channels past c zero. */
+int gdt_pack_input_filter(const float* x, int n, int c, int h, int w, int out_f32, int kind, float fw, float fp, float fbeta, float ftau, float feps,
+                          void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Retrieval scoring ("next" row of SURVEY.md section 8f: the consumer of the gathered descriptors)
