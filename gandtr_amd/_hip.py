@@ -14,10 +14,26 @@ GDT_OK, GDT_ERR_INVALID, GDT_ERR_HIP, GDT_ERR_WORKSPACE, GDT_ERR_NOT_CONVERGED =
 
 
 class ConvDesc(ctypes.Structure):
-    """struct gdt_conv_desc (include/gandtr_hip.h)."""
+    """struct gdt_conv_desc (include/gandtr_hip.h); ``dilation`` is 1 (none) unless given."""
     _fields_ = [("cin", c_int), ("cout", c_int), ("kh", c_int), ("kw", c_int), ("stride", c_int), ("pad", c_int),
                 ("pad_reflect", c_int), ("transposed", c_int), ("relu", c_int), ("out_f32_nchw", c_int),
-                ("act", c_int), ("bn_eps", c_float)]
+                ("act", c_int), ("bn_eps", c_float), ("dilation", c_int), ("leaky", c_float), ("in_relu", c_int)]
+
+    def __init__(self, *args, **kw):
+        if len(args) < 13:
+            kw.setdefault("dilation", 1)
+        super().__init__(*args, **kw)
+
+
+class ConvWeights(ctypes.Structure):
+    """struct gdt_conv_weights (include/gandtr_hip.h): host fp32 arrays, all but ``weight`` may be NULL."""
+    _fields_ = [("weight", c_void_p), ("bias", c_void_p), ("bn_gamma", c_void_p), ("bn_beta", c_void_p), ("bn_mean", c_void_p), ("bn_var", c_void_p)]
+
+
+class PoolHeadDesc(ctypes.Structure):
+    """struct gdt_pool_head_desc (include/gandtr_hip.h)."""
+    _fields_ = [("kind", c_int), ("p", c_void_p), ("n_p", c_int), ("eps", c_float), ("aggregate", c_int), ("levels", c_int),
+                ("rw", c_void_p), ("rb", c_void_p), ("fw", c_void_p), ("fb", c_void_p), ("eps_l2", c_float), ("attention", c_int), ("normalize_max", c_int)]
 
 
 class IngestItem(ctypes.Structure):
@@ -83,20 +99,11 @@ SIGNATURES = {
     "gdt_net_destroy": (None, [c_void_p]),
     "gdt_net_set_precision": (c_int, [c_void_p, c_int]),
     "gdt_net_input": (c_int, [c_void_p, c_int, _IP, _FP, _FP, _IP]),
-    "gdt_net_conv": (c_int, [c_void_p, c_int, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_void_p, c_int, _IP]),
-    "gdt_net_instance_norm": (c_int, [c_void_p, c_int, c_float, c_int, c_int, _IP]),
-    "gdt_net_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _IP]),
-    "gdt_net_maxpool_ceil": (c_int, [c_void_p, c_int, c_int, c_int, _IP]),
-    "gdt_net_conv_dilated": (c_int, [c_void_p, c_int, POINTER(ConvDesc), c_int, c_void_p, c_void_p, _IP]),
-    "gdt_net_conv_leaky": (c_int, [c_void_p, c_int, POINTER(ConvDesc), c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _IP]),
-    "gdt_net_instance_norm_leaky": (c_int, [c_void_p, c_int, c_float, c_float, _IP]),
-    "gdt_net_conv_transposed4": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int,
-                                         c_int, _IP]),
-    "gdt_net_conv_cat": (c_int, [c_void_p, c_int, c_int, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _IP]),
+    "gdt_net_conv": (c_int, [c_void_p, c_int, c_int, POINTER(ConvDesc), POINTER(ConvWeights), c_int, _IP]),
+    "gdt_net_instance_norm": (c_int, [c_void_p, c_int, c_float, c_int, c_float, c_int, _IP]),
+    "gdt_net_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, _IP]),
     "gdt_net_gem_l2n": (c_int, [c_void_p, c_int, c_float, c_float, c_float, _IP]),
-    "gdt_net_pool_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, _IP]),
-    "gdt_net_pool_head_attention": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_int, _IP]),
+    "gdt_net_pool_head": (c_int, [c_void_p, c_int, POINTER(PoolHeadDesc), _IP]),
     "gdt_net_input_filter": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_float, c_float]),
     "gdt_net_output_nchw": (c_int, [c_void_p, c_int, c_void_p, _IP]),
     "gdt_net_hed_head": (c_int, [c_void_p, _IP, POINTER(c_void_p), _FP, _FP, c_float, c_int, _IP]),
@@ -111,6 +118,7 @@ SIGNATURES = {
     "gdt_net_levels_joined": (c_int, [c_void_p, _IP]),
     "gdt_net_set_group_factor": (c_int, [c_void_p, c_float]),
     "gdt_plan_knob_name": (c_char_p, [c_int]),
+    "gdt_plan_count_name": (c_char_p, [c_int]),
     "gdt_net_flops": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_double)]),
     "gdt_net_set_profiling": (c_int, [c_void_p, c_int]),
     "gdt_net_profile_read": (c_int, [c_void_p, c_int, _IP, _IP, _IP, POINTER(c_double), POINTER(c_double)]),
@@ -210,14 +218,24 @@ def load():
     return lib
 
 
-def plan_knobs():
-    """Names of the environment knobs the library reads every time it plans a geometry (gdt_plan_knob_name), in its order."""
-    lib, names = load(), []
+def _names(fn):
+    """the names ``fn(0)``, ``fn(1)``, .. up to the first NULL"""
+    names = []
     while True:
-        name = lib.gdt_plan_knob_name(len(names))
+        name = fn(len(names))
         if name is None:
             return tuple(names)
         names.append(name.decode())
+
+
+def plan_knobs():
+    """Names of the environment knobs the library reads every time it plans a geometry (gdt_plan_knob_name), in its order."""
+    return _names(load().gdt_plan_knob_name)
+
+
+def plan_count_names():
+    """Names of the counters gdt_net_plan_summary fills (gdt_plan_count_name), in index order."""
+    return _names(load().gdt_plan_count_name)
 
 
 def check(rc):

@@ -25,7 +25,7 @@ __device__ __forceinline__ void conv_epilogue_f16(const ConvLaunch& d, const f32
     f16* Ct = (f16*)smem;
     float* sl = (float*)(smem + STATS_OFF);
     const bool relu_now = d.relu && !d.res;
-    const bool leaky_now = d.leaky != 0.f;                          // LeakyReLU (never together with ReLU or a residual: gdt_net_conv_leaky)
+    const bool leaky_now = d.leaky != 0.f;                          // LeakyReLU (never together with ReLU or a residual: gdt_conv_desc::leaky)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int col = wn * WTN + j * 32 + fr;

@@ -29,6 +29,24 @@ int quant_e2m3(float x) {
     return sign | ((e + 1) << 3) | m;
 }
 
+// 32 values as e2m3 codes of  value * 2^-e  under one E8M0 exponent byte 127 + e (the return value), the largest magnitude mapped into (3.75, 7.5]; code i
+// sits at bit 6i of the 24 bytes
+unsigned quant_block32(const float (&v)[32], unsigned char (&bytes)[24]) {
+    float mx = 0.f;
+    for (int i = 0; i < 32; ++i) mx = std::max(mx, std::fabs(v[i]));
+    int e = 0;
+    if (mx > 0.f) { e = (int)std::ceil(std::log2(mx / 7.5f)); if (std::ldexp(mx, -e) > 7.5f) ++e; }
+    e = std::min(std::max(e, -126), 127);
+    std::fill(bytes, bytes + 24, (unsigned char)0);
+    for (int i = 0; i < 32; ++i) {
+        const unsigned code = (unsigned)quant_e2m3(std::ldexp(v[i], -e));
+        const int bit = 6 * i;
+        bytes[bit >> 3] |= (unsigned char)(code << (bit & 7));
+        if ((bit & 7) > 2) bytes[(bit >> 3) + 1] |= (unsigned char)(code >> (8 - (bit & 7)));
+    }
+    return (unsigned)(127 + e);
+}
+
 // Block-scaled correction operands of a packed weight matrix wf [cout_pad][Kpad] (fp32, BatchNorm folded) in MFMA fragment order:
 // per (32-channel block cb, 32-k block ms, lane): lanes 0-31 hold fp16(w), lanes 32-63 hold w - fp16(w) of output channel cb*32 + (lane & 31),
 // each as 32 e2m3 values of  value * 2^-e  with the block's own E8M0 exponent byte 127 + e (largest magnitude of the block mapped into
@@ -53,25 +71,15 @@ void pack_mx(const std::vector<float>& wf, int cout_pad, int Kpad, std::vector<u
         for (int ms = 0; ms < nms; ++ms)
             for (int ln = 0; ln < 64; ++ln) {
                 const float* src = wf.data() + (size_t)(cb * 32 + (ln & 31)) * Kpad + ms * 32;
-                float v[32], mx = 0.f;
+                float v[32];
                 for (int i = 0; i < 32; ++i) {
                     const float hi = (float)(f16)src[i];
                     v[i] = (ln >> 5) ? src[i] - hi : hi;
-                    mx = std::max(mx, std::fabs(v[i]));
                 }
-                int e = 0;
-                if (mx > 0.f) { e = (int)std::ceil(std::log2(mx / 7.5f)); if (std::ldexp(mx, -e) > 7.5f) ++e; }
-                e = std::min(std::max(e, -126), 127);
-                unsigned char bytes[24] = {0};
-                for (int i = 0; i < 32; ++i) {
-                    const unsigned code = (unsigned)quant_e2m3(std::ldexp(v[i], -e));
-                    const int bit = 6 * i;
-                    bytes[bit >> 3] |= (unsigned char)(code << (bit & 7));
-                    if ((bit & 7) > 2) bytes[(bit >> 3) + 1] |= (unsigned char)(code >> (8 - (bit & 7)));
-                }
+                unsigned char bytes[24];
                 const size_t fi = (((size_t)(cb >> 2) * nms + ms) * 4 + (cb & 3)) * 64 + ln;
-                const unsigned scale = (unsigned)(127 + e);           // E8M0 block scale
-                memcpy(a.data() + fi * 16, bytes, 16); memcpy(b.data() + fi * 8, bytes + 16, 8); sc[fi] = scale;
+                sc[fi] = quant_block32(v, bytes);                     // E8M0 block scale
+                memcpy(a.data() + fi * 16, bytes, 16); memcpy(b.data() + fi * 8, bytes + 16, 8);
             }
 }
 
@@ -99,25 +107,15 @@ void pack_mx16(const std::vector<float>& wf, int cout_pad, int Kpad, std::vector
                 for (int ln = 0; ln < 64; ++ln) {
                     const int blk = ln >> 4;
                     const float* src = wf.data() + (size_t)(g * 64 + cb * 16 + (ln & 15)) * Kpad + ms * 64 + (blk >> 1) * 32;
-                    float v[32], mx = 0.f;
+                    float v[32];
                     for (int i = 0; i < 32; ++i) {
                         const float hi = (float)(f16)src[i];
                         v[i] = (blk & 1) ? src[i] - hi : hi;
-                        mx = std::max(mx, std::fabs(v[i]));
                     }
-                    int e = 0;
-                    if (mx > 0.f) { e = (int)std::ceil(std::log2(mx / 7.5f)); if (std::ldexp(mx, -e) > 7.5f) ++e; }
-                    e = std::min(std::max(e, -126), 127);
-                    unsigned char bytes[24] = {0};
-                    for (int i = 0; i < 32; ++i) {
-                        const unsigned code = (unsigned)quant_e2m3(std::ldexp(v[i], -e));
-                        const int bit = 6 * i;
-                        bytes[bit >> 3] |= (unsigned char)(code << (bit & 7));
-                        if ((bit & 7) > 2) bytes[(bit >> 3) + 1] |= (unsigned char)(code >> (8 - (bit & 7)));
-                    }
+                    unsigned char bytes[24];
+                    sc[(((size_t)g * nms + ms) * 64 + ln) * 4 + cb] = quant_block32(v, bytes);  // (a lane's four block scales side by side: one dwordx4)
                     const size_t fi = (((size_t)g * nms + ms) * 4 + cb) * 64 + ln;
                     memcpy(a.data() + fi * 16, bytes, 16); memcpy(b.data() + fi * 8, bytes + 16, 8);
-                    sc[(((size_t)g * nms + ms) * 64 + ln) * 4 + cb] = (unsigned)(127 + e);      // (a lane's four block scales side by side: one dwordx4)
                 }
 }
 
@@ -465,35 +463,110 @@ static void pack_bias(ConvPack& cp) {
     }
 }
 
-// gdt_net_conv (dil == 1), gdt_net_conv_dilated and gdt_net_conv_leaky (leaky != 0)
-static int add_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, int dil, const float* weight, const float* bias,
-                    const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
-                    int residual_tensor, int* out_tensor, float leaky = 0.f) {
-    GDT_REQUIRE(net && !net->finalized && desc && weight && out_tensor, "net/desc/weight");
-    GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "input tensor id");
-    GDT_REQUIRE(residual_tensor < (int)net->tensors.size(), "residual tensor id");
+// The weights of the patch kernels that read both inputs themselves -- conv4x4t_halo.hip (16 steps: gdt_t4_step) and conv3x3_cat_halo.hip (9 taps):
+// [cout_pad][steps * cin] with k = (chunk * steps + step) * 64 + channel, in fragment order; cin counts the channels of both inputs; wget(cout, c, step) -> float
+template <typename WGet>
+static void pack_cat_frag(ConvPack& cp, int steps, WGet&& wget) {
+    gdt_net* net = cp.net; Op& o = cp.o;
+    const gdt_conv_desc& cd = o.cd;
+    const int K = steps * cd.cin;
+    std::vector<f16> pk((size_t)o.cout_pad * K, (f16)0.f);
+    for (int co = 0; co < cd.cout; ++co)
+        for (int c = 0; c < cd.cin; ++c)
+            for (int s = 0; s < steps; ++s)
+                pk[(size_t)co * K + ((size_t)(c >> 6) * steps + s) * 64 + (c & 63)] = (f16)(wget(co, c, s) * cp.scale[co]);
+    const std::vector<f16> pf = frag_order(pk, o.cout_pad, K);
+    o.cat_frag_off = net->blob_append(pf.data(), pf.size() * sizeof(f16));
+    o.has_cat_frag = true;
+}
+
+// An op's result registered -- a new external output slot, or a new internal tensor of C (Creal real) channels -- and the op pushed; returns the slot / tensor id
+static int push_op(gdt_net* net, Op&& o, bool external, int C = 0, int Creal = 0) {
+    if (external) { o.slot = (int)net->out_ops.size(); net->out_ops.push_back((int)net->ops.size()); }
+    else o.out = net->new_tensor(C, Creal);
+    const int id = external ? o.slot : o.out;
+    net->ops.push_back(std::move(o));
+    return id;
+}
+
+// the channel concatenation of a and b (b < 0: a alone), ReLU on the a part when relu, as a tensor of its own in front of the conv that is added next; returns the op's index
+static int add_concat(gdt_net* net, int a, int b, int relu, int cin) {
+    Op c; c.kind = OP_CONCAT; c.in = a; c.res = b; c.relu = relu ? 1 : 0;
+    c.cat_for = (int)net->ops.size() + 1;
+    push_op(net, std::move(c), false, next_pow2(cin), cin);
+    return (int)net->ops.size() - 1;
+}
+
+// a LeakyReLU slope as the conv and the InstanceNorm take it
+#define GDT_REQUIRE_SLOPE(slope) GDT_REQUIRE((slope) > 0.f && (slope) < 1.f, "LeakyReLU slope must lie in (0, 1)")
+
+// gdt_net_conv: every check of the three routes first (a refused layer leaves nothing in the graph), then the concatenation op of the two-input routes, the conv op
+// and its packed weights
+static int add_conv(gdt_net* net, int in_a, int in_b, const gdt_conv_desc* desc, const gdt_conv_weights* wts, int residual_tensor, int* out_tensor) {
+    GDT_REQUIRE(net && !net->finalized && desc && wts && wts->weight && out_tensor, "net/desc/weight");
     const gdt_conv_desc& cd = *desc;
+    const float* weight = wts->weight;
+    const int dil = cd.dilation, ntensors = (int)net->tensors.size();
+    const bool t4 = cd.transposed && cd.kh == 4 && cd.kw == 4 && cd.stride == 2 && cd.pad == 1;       // the transposed-4 route
+    const bool cat = in_b >= 0 && !t4;                                                                   // the conv-of-a-concatenation route
+    GDT_REQUIRE(dil >= 1 && dil <= 16, "dilation must be 1..16");
+    GDT_REQUIRE(dil == 1 || (!cd.transposed && !cd.pad_reflect && !cd.out_f32_nchw), "a dilated conv is a plain Conv2d with zero padding and an internal output");
+    GDT_REQUIRE(dil == 1 || (in_b < 0 && cd.leaky == 0.f && !wts->bn_gamma && residual_tensor < 0),
+                "a dilated conv takes one input, no LeakyReLU, no BatchNorm and no residual");
+    if (cd.leaky != 0.f) {
+        GDT_REQUIRE_SLOPE(cd.leaky);
+        GDT_REQUIRE(net->precision != 2, "a LeakyReLU conv exists in the f16 and f16x3 modes");
+        GDT_REQUIRE(!cd.relu && !cd.transposed && !cd.out_f32_nchw, "a LeakyReLU conv is a plain Conv2d with an internal output and no ReLU");
+        GDT_REQUIRE(in_b < 0 && residual_tensor < 0, "a LeakyReLU conv takes one input and no residual");
+    }
+    GDT_REQUIRE(t4 || !cd.in_relu, "ReLU on read exists for ConvTranspose2d(k4,s2,p1) only");
+    GDT_REQUIRE(!(t4 || cat) || residual_tensor < 0, "a ConvTranspose2d(k4,s2,p1) and a conv of a concatenation take no residual");
+    if (t4) GDT_REQUIRE(net->precision == 0 || net->precision == 1, "ConvTranspose2d(k4,s2,p1) exists in the f16 and f16x3 modes");
+    if (cat) GDT_REQUIRE(net->precision == 0 || net->precision == 1, "a Conv2d of a concatenation exists in the f16 and f16x3 modes");
+    GDT_REQUIRE(in_a >= 0 && in_a < ntensors && in_b >= -1 && in_b < ntensors, "input tensor id");
+    GDT_REQUIRE(residual_tensor < ntensors, "residual tensor id");
+    if (cat) {
+        GDT_REQUIRE(!cd.transposed, "a Conv2d of a concatenation is not transposed");
+        GDT_REQUIRE(!cd.pad_reflect, "a Conv2d of a concatenation pads with zeros");
+    }
     GDT_REQUIRE(cd.cin >= 1 && cd.cout >= 1 && cd.kh >= 1 && cd.kw >= 1 && cd.kh * cd.kw <= 64, "conv geometry");
     GDT_REQUIRE(cd.stride == 1 || cd.stride == 2, "stride must be 1 or 2");
-    GDT_REQUIRE((bn_gamma && bn_beta && bn_mean && bn_var) || (!bn_gamma && !bn_beta && !bn_mean && !bn_var), "BN vectors");
+    GDT_REQUIRE((wts->bn_gamma && wts->bn_beta && wts->bn_mean && wts->bn_var) || (!wts->bn_gamma && !wts->bn_beta && !wts->bn_mean && !wts->bn_var), "BN vectors");
     const int cin_pad = next_pow2(cd.cin);
-    GDT_REQUIRE(net->tensors[in_tensor].C == cin_pad && net->tensors[in_tensor].Creal == cd.cin,
-                "input tensor channel count does not match conv cin");
-    if (cd.transposed) GDT_REQUIRE(cd.kh == 3 && cd.kw == 3 && cd.stride == 2 && cd.pad == 1 && !cd.pad_reflect,
-                                   "only ConvTranspose2d(k3,s2,p1,op1) is supported");
+    const int ca = net->tensors[in_a].Creal, cb = in_b >= 0 ? net->tensors[in_b].Creal : 0;
+    const bool concat = in_b >= 0 || cd.in_relu;        // the generic launches read the concatenation (+ ReLU on the first part) as a tensor of its own
+    if (t4) {
+        GDT_REQUIRE(!cd.pad_reflect, "ConvTranspose2d(k4,s2,p1) pads with zeros");
+        GDT_REQUIRE(ca + cb <= 4096, "conv geometry");
+        if (concat) GDT_REQUIRE(ca % 8 == 0 && cb % 8 == 0, "a concatenated or ReLU-on-read input needs channel counts % 8 == 0");
+        else GDT_REQUIRE(net->tensors[in_a].C == next_pow2(ca), "a single input read as stored needs a power-of-two channel count");
+        GDT_REQUIRE(cd.cin == ca + cb, "the channels of the inputs do not add up to the conv's cin");
+        if (!cd.out_f32_nchw) GDT_REQUIRE(cd.cout % 8 == 0 && cd.act == 0, "internal conv outputs need cout % 8 == 0 and take no activation but ReLU");
+        GDT_REQUIRE(cd.act >= 0 && cd.act <= 2 && !(cd.out_f32_nchw && cd.relu), "output activation");
+    } else if (cat) {
+        GDT_REQUIRE(ca % 8 == 0 && cb % 8 == 0, "a concatenated input needs channel counts % 8 == 0");
+        GDT_REQUIRE(cd.cin == ca + cb && ca + cb <= 4096, "the channels of the two inputs do not add up to the conv's cin");
+    } else {
+        GDT_REQUIRE(net->tensors[in_a].C == cin_pad && ca == cd.cin, "input tensor channel count does not match conv cin");
+        if (cd.transposed) GDT_REQUIRE(cd.kh == 3 && cd.kw == 3 && cd.stride == 2 && cd.pad == 1 && !cd.pad_reflect,
+                                       "only ConvTranspose2d(k3,s2,p1,op1) is supported");
+    }
     if (!cd.out_f32_nchw) GDT_REQUIRE(cd.cout % 8 == 0, "internal conv outputs need cout % 8 == 0");
     if (residual_tensor >= 0) GDT_REQUIRE(net->tensors[residual_tensor].C == cd.cout && !cd.out_f32_nchw, "residual channels");
 
-    Op o; o.kind = OP_CONV; o.in = in_tensor; o.res = residual_tensor; o.cd = cd; o.cin_pad = cin_pad; o.dil = dil; o.leaky = leaky;
+    const int cat_op = concat ? add_concat(net, in_a, in_b, cd.in_relu, cd.cin) : -1;
+    Op o; o.kind = OP_CONV; o.in = concat ? net->ops[cat_op].out : in_a; o.res = residual_tensor; o.cd = cd; o.cin_pad = cin_pad; o.dil = dil; o.leaky = cd.leaky;
+    o.cat_op = cat_op;
+    if (t4 || cat) { o.src_a = in_a; o.src_b = in_b; o.src_relu = cd.in_relu ? 1 : 0; }
     o.rowsplit = dil == 1 && cd.out_f32_nchw && !cd.transposed && cd.stride == 1 && cd.kw >= 3 && cd.cout <= 4 && cd.cout * cd.kw <= 32 &&
-                 cd.kw == 2 * cd.pad + 1 && !cd.relu && !bn_gamma;
+                 cd.kw == 2 * cd.pad + 1 && !cd.relu && !wts->bn_gamma;
     const int gemm_cout = o.rowsplit ? cd.cout * cd.kw : cd.cout;
     if (o.rowsplit) o.rs_cout8 = (gemm_cout + 7) / 8 * 8;
     const int bn_tile = gdt_conv_bn(gemm_cout);
     o.cout_pad = (gemm_cout + bn_tile - 1) / bn_tile * bn_tile;
 
     ConvPack cp{net, o, weight, dil};
-    fold_bn(cd, bias, bn_gamma, bn_beta, bn_mean, bn_var, cp.scale, cp.shift, cp.has_shift);
+    fold_bn(cd, wts->bias, wts->bn_gamma, wts->bn_beta, wts->bn_mean, wts->bn_var, cp.scale, cp.shift, cp.has_shift);
     pack_bias(cp);
 
     if (o.rowsplit) {
@@ -508,147 +581,38 @@ static int add_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, int 
             residual_tensor < 0 && (cin_pad == 64 || cin_pad == 128) && cd.cin == cin_pad)
             pack_s2(cp);
     } else {
-        // o = 2i - 1 + k.  Even outputs (parity 0): k = 1, i = y.  Odd outputs: k = 0 (i = y + 1) and k = 2 (i = y).
+        // four sub-pixel phases.  k3: o = 2i - 1 + k.  Even outputs (parity 0): k = 1, i = y.  Odd outputs: k = 0 (i = y + 1) and k = 2 (i = y).
+        // k4: 2 x 2 taps each: output parity 0 meets kernel rows 1 (input row y) and 3 (y - 1), parity 1 rows 0 (y + 1) and 2 (y); columns alike
+        const int k = cd.kh;
         for (int py = 0; py < 2; ++py)
             for (int px = 0; px < 2; ++px) {
                 PackedPhase ph;
-                const int th = py ? 2 : 1, tw = px ? 2 : 1;
+                const int th = t4 || py ? 2 : 1, tw = t4 || px ? 2 : 1;
                 ph.ntaps = th * tw; ph.TW = tw;
-                ph.dy0 = py ? 1 : 0; ph.dys = -1; ph.dx0 = px ? 1 : 0; ph.dxs = -1;
+                ph.dy0 = py; ph.dys = -1; ph.dx0 = px; ph.dxs = -1;
                 ph.ooy = py; ph.oox = px;
-                pack_phase(cp, ph, [&](int co, int c, int t) {
-                    const int ty = t / tw, tx = t % tw;
-                    const int ky = py ? (ty == 0 ? 0 : 2) : 1, kx = px ? (tx == 0 ? 0 : 2) : 1;
-                    return weight[(((size_t)c * cd.cout + co) * 3 + ky) * 3 + kx];
-                });
+                auto tap = [&](int par, int t) { return par ? (t == 0 ? 0 : 2) : (t4 ? (t == 0 ? 1 : 3) : 1); };      // kernel row / column of tap t at output parity par
+                pack_phase(cp, ph, [&](int co, int c, int t) { return weight[(((size_t)c * cd.cout + co) * k + tap(py, t / tw)) * k + tap(px, t % tw)]; });
                 o.phases.push_back(ph);
             }
-        if (net->precision == 1 && cd.cout == 64 && cin_pad % 32 == 0 && cd.cin == cin_pad && residual_tensor < 0) pack_pairs(cp);
-        if (net->precision != 1 && cin_pad % 64 == 0 && (4 * cd.cout) % 256 == 0 && 256 % cd.cout == 0 && cd.cout >= 64 && residual_tensor < 0) pack_ctf(cp);
+        if (!t4 && net->precision == 1 && cd.cout == 64 && cin_pad % 32 == 0 && cd.cin == cin_pad && residual_tensor < 0) pack_pairs(cp);
+        if (!t4 && net->precision != 1 && cin_pad % 64 == 0 && (4 * cd.cout) % 256 == 0 && 256 % cd.cout == 0 && cd.cout >= 64 && residual_tensor < 0) pack_ctf(cp);
     }
-    if (cd.out_f32_nchw) {
-        o.slot = (int)net->out_ops.size();
-        net->out_ops.push_back((int)net->ops.size());
-        *out_tensor = o.slot;
-    } else {
-        o.out = net->new_tensor(cd.cout, cd.cout);
-        *out_tensor = o.out;
-    }
-    net->ops.push_back(std::move(o));
-    return GDT_OK;
-}
-
-// conv4x4t_halo.hip: [cout_pad][16 cin] with k = (chunk * 16 + step) * 64 + channel (gdt_t4_step), in fragment order; cin counts the channels of both inputs
-static void pack_t4(ConvPack& cp) {
-    gdt_net* net = cp.net; Op& o = cp.o;
-    const gdt_conv_desc& cd = o.cd;
-    const int K = 16 * cd.cin;
-    std::vector<f16> pk((size_t)o.cout_pad * K, (f16)0.f);
-    for (int s = 0; s < 16; ++s) {
-        int sy, sx, py, px;
-        gdt_t4_step(s, sy, sx, py, px);
-        const int ky = gdt_t4_tap(sy, py), kx = gdt_t4_tap(sx, px);
-        for (int co = 0; co < cd.cout; ++co)
-            for (int c = 0; c < cd.cin; ++c)
-                pk[(size_t)co * K + ((size_t)(c >> 6) * 16 + s) * 64 + (c & 63)] = (f16)(cp.weight[(((size_t)c * cd.cout + co) * 4 + ky) * 4 + kx] * cp.scale[co]);
-    }
-    const std::vector<f16> pf = frag_order(pk, o.cout_pad, K);
-    o.t4_frag_off = net->blob_append(pf.data(), pf.size() * sizeof(f16));
-    o.has_t4 = true;
-}
-
-// gdt_net_conv_transposed4
-static int add_conv_t4(gdt_net* net, int in_a, int in_b, int relu_a, const gdt_conv_desc& cd, const float* weight, const float* bias,
-                       const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor) {
-    const int ca = net->tensors[in_a].Creal, cb = in_b >= 0 ? net->tensors[in_b].Creal : 0;
-    int in = in_a, cat_op = -1;
-    if (in_b >= 0 || relu_a) {          // the generic route's input: the concatenation (+ ReLU on the first part) as a tensor of its own
-        Op c; c.kind = OP_CONCAT; c.in = in_a; c.res = in_b; c.relu = relu_a ? 1 : 0;
-        c.out = net->new_tensor(next_pow2(cd.cin), cd.cin);
-        c.cat_for = (int)net->ops.size() + 1;
-        cat_op = (int)net->ops.size();
-        in = c.out;
-        net->ops.push_back(c);
-    }
-    Op o; o.kind = OP_CONV; o.in = in; o.cd = cd; o.cin_pad = next_pow2(cd.cin); o.cat_op = cat_op;
-    o.t4_a = in_a; o.t4_b = in_b; o.t4_relu = relu_a ? 1 : 0;
-    const int bn_tile = gdt_conv_bn(cd.cout);
-    o.cout_pad = (cd.cout + bn_tile - 1) / bn_tile * bn_tile;
-    ConvPack cp{net, o, weight, 1};
-    fold_bn(cd, bias, bn_gamma, bn_beta, bn_mean, bn_var, cp.scale, cp.shift, cp.has_shift);
-    pack_bias(cp);
-    // four sub-pixel phases of 2 x 2 taps: output parity 0 meets kernel rows 1 (input row y) and 3 (y - 1), parity 1 rows 0 (y + 1) and 2 (y); columns alike
-    for (int py = 0; py < 2; ++py)
-        for (int px = 0; px < 2; ++px) {
-            PackedPhase ph;
-            ph.ntaps = 4; ph.TW = 2;
-            ph.dy0 = py; ph.dys = -1; ph.dx0 = px; ph.dxs = -1;
-            ph.ooy = py; ph.oox = px;
-            pack_phase(cp, ph, [&](int co, int c, int t) {
-                const int ty = t >> 1, tx = t & 1;
-                const int ky = py ? (ty == 0 ? 0 : 2) : (ty == 0 ? 1 : 3), kx = px ? (tx == 0 ? 0 : 2) : (tx == 0 ? 1 : 3);
-                return weight[(((size_t)c * cd.cout + co) * 4 + ky) * 4 + kx];
-            });
-            o.phases.push_back(ph);
-        }
-    if (!net->precision && !cd.out_f32_nchw && ca % 64 == 0 && cb % 64 == 0 && cd.cout % 64 == 0) {
-        pack_t4(cp);
-        o.feats.push_back(in_a);                  // (read by the patch kernel itself: alive until this op)
+    // the patch kernels that read the sources themselves (which then live until this op: feats)
+    if (t4 && !net->precision && !cd.out_f32_nchw && ca % 64 == 0 && cb % 64 == 0 && cd.cout % 64 == 0) {
+        int ky[16], kx[16];
+        for (int s = 0; s < 16; ++s) { int sy, sx, py, px; gdt_t4_step(s, sy, sx, py, px); ky[s] = gdt_t4_tap(sy, py); kx[s] = gdt_t4_tap(sx, px); }
+        pack_cat_frag(cp, 16, [&](int co, int c, int s) { return weight[(((size_t)c * cd.cout + co) * 4 + ky[s]) * 4 + kx[s]]; });
+        o.feats.push_back(in_a);
         if (in_b >= 0) o.feats.push_back(in_b);
     }
-    if (cd.out_f32_nchw) {
-        o.slot = (int)net->out_ops.size();
-        net->out_ops.push_back((int)net->ops.size());
-        *out_tensor = o.slot;
-    } else {
-        o.out = net->new_tensor(cd.cout, cd.cout);
-        *out_tensor = o.out;
+    if (cat) {
+        o.feats.push_back(in_a); o.feats.push_back(in_b);
+        if (!net->precision && !cd.out_f32_nchw && cd.kh == 3 && cd.kw == 3 && cd.stride == 1 && cd.pad == 1 && !cd.pad_reflect && ca % 64 == 0 && cb % 64 == 0 &&
+            net->tensors[in_a].C == ca && net->tensors[in_b].C == cb && cd.cout % 64 == 0 && o.cout_pad % 64 == 0)
+            pack_cat_frag(cp, 9, [&](int co, int c, int t) { return weight[((size_t)co * cd.cin + c) * 9 + t]; });
     }
-    net->ops.push_back(std::move(o));
-    return GDT_OK;
-}
-
-// conv3x3_cat_halo.hip: [cout_pad][9 cin] with k = (chunk * 9 + tap) * 64 + channel, in fragment order; cin counts the channels of both inputs
-static void pack_cc(ConvPack& cp) {
-    gdt_net* net = cp.net; Op& o = cp.o;
-    const gdt_conv_desc& cd = o.cd;
-    const int K = 9 * cd.cin;
-    std::vector<f16> pk((size_t)o.cout_pad * K, (f16)0.f);
-    for (int co = 0; co < cd.cout; ++co)
-        for (int c = 0; c < cd.cin; ++c)
-            for (int t = 0; t < 9; ++t)
-                pk[(size_t)co * K + ((size_t)(c >> 6) * 9 + t) * 64 + (c & 63)] = (f16)(cp.weight[((size_t)co * cd.cin + c) * 9 + t] * cp.scale[co]);
-    const std::vector<f16> pf = frag_order(pk, o.cout_pad, K);
-    o.cc_frag_off = net->blob_append(pf.data(), pf.size() * sizeof(f16));
-    o.has_cc = true;
-}
-
-// gdt_net_conv_cat: the generic route's input -- the concatenation as a tensor of its own -- and the conv of one tensor over it; where conv3x3_cat_halo.hip
-// can take the layer, its weights too
-static int add_conv_cat(gdt_net* net, int in_a, int in_b, const gdt_conv_desc& cd, const float* weight, const float* bias,
-                        const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor) {
-    const int ca = net->tensors[in_a].Creal, cb = net->tensors[in_b].Creal;
-    {
-        Op c; c.kind = OP_CONCAT; c.in = in_a; c.res = in_b; c.relu = 0;
-        c.out = net->new_tensor(next_pow2(cd.cin), cd.cin);
-        c.cat_for = (int)net->ops.size() + 1;
-        net->ops.push_back(c);
-    }
-    const int cat_op = (int)net->ops.size() - 1, cat_out = net->ops[cat_op].out;
-    const int rc = add_conv(net, cat_out, &cd, 1, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, -1, out_tensor);
-    if (rc != GDT_OK) {                       // (nothing of a refused layer stays in the graph)
-        net->ops.pop_back(); net->tensors.pop_back();
-        return rc;
-    }
-    Op& o = net->ops.back();
-    o.cat_op = cat_op; o.cc_a = in_a; o.cc_b = in_b;
-    o.feats.push_back(in_a); o.feats.push_back(in_b);      // (read by the patch kernel itself: alive until this op)
-    if (!net->precision && !cd.out_f32_nchw && cd.kh == 3 && cd.kw == 3 && cd.stride == 1 && cd.pad == 1 && !cd.pad_reflect && ca % 64 == 0 && cb % 64 == 0 &&
-        net->tensors[in_a].C == ca && net->tensors[in_b].C == cb && cd.cout % 64 == 0 && o.cout_pad % 64 == 0) {
-        ConvPack cp{net, o, weight, 1};
-        fold_bn(cd, bias, bn_gamma, bn_beta, bn_mean, bn_var, cp.scale, cp.shift, cp.has_shift);
-        pack_cc(cp);
-    }
+    *out_tensor = push_op(net, std::move(o), cd.out_f32_nchw != 0, cd.cout, cd.cout);
     return GDT_OK;
 }
 
@@ -737,108 +701,39 @@ int gdt_net_input(gdt_net* net, int channels, const int* perm, const float* scal
     return GDT_OK;
 }
 
-int gdt_net_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, const float* weight, const float* bias,
-                 const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
-                 int residual_tensor, int* out_tensor) {
-    return add_conv(net, in_tensor, desc, 1, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, residual_tensor, out_tensor);
+int gdt_net_conv(gdt_net* net, int in_a, int in_b, const gdt_conv_desc* desc, const gdt_conv_weights* weights, int residual_tensor, int* out_tensor) {
+    return add_conv(net, in_a, in_b, desc, weights, residual_tensor, out_tensor);
 }
 
-int gdt_net_conv_dilated(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, int dilation, const float* weight, const float* bias, int* out_tensor) {
-    GDT_REQUIRE(net && !net->finalized && desc && weight && out_tensor, "net/desc/weight");
-    GDT_REQUIRE(dilation >= 1 && dilation <= 16, "dilation must be 1..16");
-    GDT_REQUIRE(dilation == 1 || (!desc->transposed && !desc->pad_reflect && !desc->out_f32_nchw),
-                "a dilated conv is a plain Conv2d with zero padding and an internal output");
-    return add_conv(net, in_tensor, desc, dilation, weight, bias, nullptr, nullptr, nullptr, nullptr, -1, out_tensor);
-}
-
-// a LeakyReLU slope as the two leaky entries take it
-#define GDT_REQUIRE_SLOPE(slope) GDT_REQUIRE((slope) > 0.f && (slope) < 1.f, "LeakyReLU slope must lie in (0, 1)")
-
-int gdt_net_conv_leaky(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, float slope, const float* weight, const float* bias,
-                       const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor) {
-    GDT_REQUIRE(net && !net->finalized && desc && weight && out_tensor, "net/desc/weight");
-    GDT_REQUIRE_SLOPE(slope);
-    GDT_REQUIRE(net->precision != 2, "a LeakyReLU conv exists in the f16 and f16x3 modes");
-    GDT_REQUIRE(!desc->relu && !desc->transposed && !desc->out_f32_nchw, "a LeakyReLU conv is a plain Conv2d with an internal output and no ReLU");
-    return add_conv(net, in_tensor, desc, 1, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, -1, out_tensor, slope);
-}
-
-int gdt_net_conv_transposed4(gdt_net* net, int in_a, int in_b, int relu_a, int cout, const float* weight, const float* bias, const float* bn_gamma,
-                             const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps, int relu, int out_f32_nchw, int act, int* out_tensor) {
-    GDT_REQUIRE(net && !net->finalized && weight && out_tensor, "net/weight");
-    GDT_REQUIRE(net->precision == 0 || net->precision == 1, "ConvTranspose2d(k4,s2,p1) exists in the f16 and f16x3 modes");
-    GDT_REQUIRE(in_a >= 0 && in_a < (int)net->tensors.size() && in_b >= -1 && in_b < (int)net->tensors.size(), "input tensor id");
-    GDT_REQUIRE((bn_gamma && bn_beta && bn_mean && bn_var) || (!bn_gamma && !bn_beta && !bn_mean && !bn_var), "BN vectors");
-    const int ca = net->tensors[in_a].Creal, cb = in_b >= 0 ? net->tensors[in_b].Creal : 0;
-    GDT_REQUIRE(cout >= 1 && ca + cb <= 4096, "conv geometry");
-    if (in_b >= 0 || relu_a) GDT_REQUIRE(ca % 8 == 0 && cb % 8 == 0, "a concatenated or ReLU-on-read input needs channel counts % 8 == 0");
-    else GDT_REQUIRE(net->tensors[in_a].C == next_pow2(ca), "a single input read as stored needs a power-of-two channel count");
-    if (!out_f32_nchw) GDT_REQUIRE(cout % 8 == 0 && act == 0, "internal conv outputs need cout % 8 == 0 and take no activation but ReLU");
-    GDT_REQUIRE(act >= 0 && act <= 2 && !(out_f32_nchw && relu), "output activation");
-    gdt_conv_desc cd{};
-    cd.cin = ca + cb; cd.cout = cout; cd.kh = cd.kw = 4; cd.stride = 2; cd.pad = 1; cd.transposed = 1; cd.relu = relu ? 1 : 0;
-    cd.out_f32_nchw = out_f32_nchw ? 1 : 0; cd.act = act; cd.bn_eps = bn_eps;
-    return add_conv_t4(net, in_a, in_b, relu_a, cd, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, out_tensor);
-}
-
-int gdt_net_conv_cat(gdt_net* net, int in_a, int in_b, const gdt_conv_desc* desc, const float* weight, const float* bias, const float* bn_gamma,
-                     const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor) {
-    GDT_REQUIRE(net && !net->finalized && desc && weight && out_tensor, "net/desc/weight");
-    GDT_REQUIRE(net->precision == 0 || net->precision == 1, "a Conv2d of a concatenation exists in the f16 and f16x3 modes");
-    GDT_REQUIRE(in_a >= 0 && in_a < (int)net->tensors.size() && in_b >= 0 && in_b < (int)net->tensors.size(), "input tensor id");
-    GDT_REQUIRE(!desc->transposed, "a Conv2d of a concatenation is not transposed");
-    GDT_REQUIRE(!desc->pad_reflect, "a Conv2d of a concatenation pads with zeros");
-    const int ca = net->tensors[in_a].Creal, cb = net->tensors[in_b].Creal;
-    GDT_REQUIRE(ca % 8 == 0 && cb % 8 == 0, "a concatenated input needs channel counts % 8 == 0");
-    GDT_REQUIRE(desc->cin == ca + cb && ca + cb <= 4096, "the channels of the two inputs do not add up to the conv's cin");
-    return add_conv_cat(net, in_a, in_b, *desc, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, out_tensor);
-}
-
-static int add_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, float leaky, int residual_tensor, int* out_tensor) {
+int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, float leaky, int residual_tensor, int* out_tensor) {
     GDT_REQUIRE(net && !net->finalized && out_tensor, "net");
+    if (leaky != 0.f) {
+        GDT_REQUIRE_SLOPE(leaky);
+        GDT_REQUIRE(!relu && residual_tensor < 0, "a LeakyReLU InstanceNorm takes no ReLU and no residual");
+    }
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size() && residual_tensor < (int)net->tensors.size(), "tensor id");
     const int C = net->tensors[in_tensor].C;
     GDT_REQUIRE((C & (C - 1)) == 0 && C >= 8 && C <= 2048, "InstanceNorm needs a power-of-two channel count in [8, 2048]");
     if (residual_tensor >= 0) GDT_REQUIRE(net->tensors[residual_tensor].C == C, "residual channels");
     Op o; o.kind = OP_INORM; o.in = in_tensor; o.res = residual_tensor; o.eps = eps; o.relu = relu; o.leaky = leaky;
-    o.out = net->new_tensor(C, net->tensors[in_tensor].Creal);
     // (a LeakyReLU norm stays a separate op with its own statistics pass: its producer delivers none, and no consumer's staging applies it)
     for (size_t k = 0; k < net->ops.size() && leaky == 0.f; ++k)
         if (net->ops[k].kind == OP_CONV && net->ops[k].out == in_tensor && net->ops[k].stats_for < 0) {
             net->ops[k].stats_for = (int)net->ops.size();
             o.stats_from = (int)k;
         }
-    net->ops.push_back(o);
-    *out_tensor = o.out;
+    *out_tensor = push_op(net, std::move(o), false, C, net->tensors[in_tensor].Creal);
     return GDT_OK;
 }
 
-int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, int residual_tensor, int* out_tensor) {
-    return add_instance_norm(net, in_tensor, eps, relu, 0.f, residual_tensor, out_tensor);
-}
-
-int gdt_net_instance_norm_leaky(gdt_net* net, int in_tensor, float eps, float slope, int* out_tensor) {
-    GDT_REQUIRE_SLOPE(slope);
-    return add_instance_norm(net, in_tensor, eps, 0, slope, -1, out_tensor);
-}
-
-static int add_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int ceil, int* out_tensor) {
+int gdt_net_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int ceil_mode, int* out_tensor) {
     GDT_REQUIRE(net && !net->finalized && out_tensor, "net");
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "tensor id");
     GDT_REQUIRE(kernel >= 1 && stride >= 1 && pad >= 0 && pad * 2 <= kernel, "maxpool geometry");
-    Op o; o.kind = OP_MAXPOOL; o.in = in_tensor; o.k = kernel; o.s = stride; o.p = pad; o.ceil = ceil;
-    o.out = net->new_tensor(net->tensors[in_tensor].C, net->tensors[in_tensor].Creal);
-    net->ops.push_back(o);
-    *out_tensor = o.out;
+    GDT_REQUIRE(!ceil_mode || pad == 0, "ceil-mode max-pooling takes no padding");
+    Op o; o.kind = OP_MAXPOOL; o.in = in_tensor; o.k = kernel; o.s = stride; o.p = pad; o.ceil = ceil_mode ? 1 : 0;
+    *out_tensor = push_op(net, std::move(o), false, net->tensors[in_tensor].C, net->tensors[in_tensor].Creal);
     return GDT_OK;
-}
-
-int gdt_net_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int* out_tensor) {
-    return add_maxpool(net, in_tensor, kernel, stride, pad, 0, out_tensor);
-}
-
-int gdt_net_maxpool_ceil(gdt_net* net, int in_tensor, int kernel, int stride, int* out_tensor) {
-    return add_maxpool(net, in_tensor, kernel, stride, 0, 1, out_tensor);
 }
 
 int gdt_net_gem_l2n(gdt_net* net, int in_tensor, float p, float eps_gem, float eps_l2, int* out_slot) {
@@ -847,49 +742,40 @@ int gdt_net_gem_l2n(gdt_net* net, int in_tensor, float p, float eps_gem, float e
     GDT_REQUIRE(net->tensors[in_tensor].C % 64 == 0, "GeM needs channels % 64 == 0");
     GDT_REQUIRE(p > 0.f, "GeM exponent must be positive");
     Op o; o.kind = OP_GEM; o.in = in_tensor; o.gem_p = p; o.eps_gem = eps_gem; o.eps_l2 = eps_l2;
-    o.slot = (int)net->out_ops.size();
-    net->out_ops.push_back((int)net->ops.size());
-    net->ops.push_back(o);
-    *out_slot = o.slot;
+    *out_slot = push_op(net, std::move(o), true);
     return GDT_OK;
 }
 
-int gdt_net_pool_head(gdt_net* net, int in_tensor, int kind, const float* p, int n_p, float eps, int aggregate, int levels, const float* rw,
-                      const float* rb, const float* fw, const float* fb, float eps_l2, int* out_slot) {
-    GDT_REQUIRE(net && !net->finalized && out_slot, "net");
+int gdt_net_pool_head(gdt_net* net, int in_tensor, const gdt_pool_head_desc* desc, int* out_slot) {
+    GDT_REQUIRE(net && !net->finalized && desc && out_slot, "net");
+    const gdt_pool_head_desc& h = *desc;
+    if (h.attention) {
+        GDT_REQUIRE(h.attention == 1, "pool head attention: attention 1 = L2-norm attention");
+        GDT_REQUIRE(h.normalize_max == 0 || h.normalize_max == 1, "pool head attention: normalize_max is 0 or 1");
+        GDT_REQUIRE(!h.fw && !h.fb, "pool head attention: there is no final whitening");
+    }
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "tensor id");
     const int D = net->tensors[in_tensor].C;
+    const float* p = h.p;
     GDT_REQUIRE(D % 64 == 0 && D == net->tensors[in_tensor].Creal, "pool head needs channels % 64 == 0");
-    GDT_REQUIRE(kind >= GDT_POOL_MAX && kind <= GDT_POOL_GEMMP, "pool head: kind 0 max, 1 mean, 2 GeM, 3 per-channel GeM");
-    GDT_REQUIRE(aggregate >= 0 && aggregate <= 2, "pool head: aggregate 0 none, 1 R-MAC, 2 regional pooling");
-    GDT_REQUIRE(aggregate != 1 || kind == GDT_POOL_MAX, "pool head: R-MAC aggregates maxima");
-    GDT_REQUIRE(!aggregate || (levels >= 1 && levels <= 3), "pool head: 1..3 levels of regions (at most 51 regions per image)");
-    GDT_REQUIRE((rw == nullptr) == (rb == nullptr) && (fw == nullptr) == (fb == nullptr), "pool head: a whitening layer is a weight and a bias");
-    GDT_REQUIRE(!rw || aggregate == 2, "pool head: the regional whitening belongs to a regional pooling");
-    if (kind == GDT_POOL_GEM) GDT_REQUIRE(p && n_p == 1 && p[0] > 0.f, "pool head: GeM takes one positive exponent");
-    if (kind == GDT_POOL_GEMMP) {
-        GDT_REQUIRE(p && n_p == D, "pool head: per-channel GeM takes one exponent per channel");
+    GDT_REQUIRE(h.kind >= GDT_POOL_MAX && h.kind <= GDT_POOL_GEMMP, "pool head: kind 0 max, 1 mean, 2 GeM, 3 per-channel GeM");
+    GDT_REQUIRE(h.aggregate >= 0 && h.aggregate <= 2, "pool head: aggregate 0 none, 1 R-MAC, 2 regional pooling");
+    GDT_REQUIRE(h.aggregate != 1 || h.kind == GDT_POOL_MAX, "pool head: R-MAC aggregates maxima");
+    GDT_REQUIRE(!h.aggregate || (h.levels >= 1 && h.levels <= 3), "pool head: 1..3 levels of regions (at most 51 regions per image)");
+    GDT_REQUIRE((h.rw == nullptr) == (h.rb == nullptr) && (h.fw == nullptr) == (h.fb == nullptr), "pool head: a whitening layer is a weight and a bias");
+    GDT_REQUIRE(!h.rw || h.aggregate == 2, "pool head: the regional whitening belongs to a regional pooling");
+    if (h.kind == GDT_POOL_GEM) GDT_REQUIRE(p && h.n_p == 1 && p[0] > 0.f, "pool head: GeM takes one positive exponent");
+    if (h.kind == GDT_POOL_GEMMP) {
+        GDT_REQUIRE(p && h.n_p == D, "pool head: per-channel GeM takes one exponent per channel");
         for (int i = 0; i < D; ++i) GDT_REQUIRE(p[i] > 0.f, "pool head: GeM exponents must be positive");
     }
-    Op o; o.kind = OP_POOL_HEAD; o.in = in_tensor; o.pool_kind = kind; o.pool_aggregate = aggregate; o.pool_levels = aggregate ? levels : 0;
-    o.gem_p = kind == GDT_POOL_GEM ? p[0] : 1.f; o.eps_gem = eps; o.eps_l2 = eps_l2;
-    if (kind == GDT_POOL_GEMMP) o.pch_off = net->blob_append(p, (size_t)D * sizeof(float));
-    if (rw) { o.rw_off = net->blob_append(rw, (size_t)D * D * sizeof(float)); o.rb_off = net->blob_append(rb, (size_t)D * sizeof(float)); o.has_rw = true; }
-    if (fw) { o.fw_off = net->blob_append(fw, (size_t)D * D * sizeof(float)); o.fb_off = net->blob_append(fb, (size_t)D * sizeof(float)); o.has_fw = true; }
-    o.slot = (int)net->out_ops.size();
-    net->out_ops.push_back((int)net->ops.size());
-    net->ops.push_back(o);
-    *out_slot = o.slot;
-    return GDT_OK;
-}
-
-int gdt_net_pool_head_attention(gdt_net* net, int in_tensor, int kind, const float* p, int n_p, float eps, int aggregate, int levels, const float* rw,
-                                const float* rb, float eps_l2, int attention, int normalize_max, int* out_slot) {
-    GDT_REQUIRE(attention == 1, "pool head attention: attention 1 = L2-norm attention");
-    GDT_REQUIRE(normalize_max == 0 || normalize_max == 1, "pool head attention: normalize_max is 0 or 1");
-    const int rc = gdt_net_pool_head(net, in_tensor, kind, p, n_p, eps, aggregate, levels, rw, rb, nullptr, nullptr, eps_l2, out_slot);
-    if (rc != GDT_OK) return rc;
-    net->ops.back().att = attention; net->ops.back().att_max = normalize_max;
+    Op o; o.kind = OP_POOL_HEAD; o.in = in_tensor; o.pool_kind = h.kind; o.pool_aggregate = h.aggregate; o.pool_levels = h.aggregate ? h.levels : 0;
+    o.gem_p = h.kind == GDT_POOL_GEM ? p[0] : 1.f; o.eps_gem = h.eps; o.eps_l2 = h.eps_l2;
+    o.att = h.attention; o.att_max = h.attention ? h.normalize_max : 0;
+    if (h.kind == GDT_POOL_GEMMP) o.pch_off = net->blob_append(p, (size_t)D * sizeof(float));
+    if (h.rw) { o.rw_off = net->blob_append(h.rw, (size_t)D * D * sizeof(float)); o.rb_off = net->blob_append(h.rb, (size_t)D * sizeof(float)); o.has_rw = true; }
+    if (h.fw) { o.fw_off = net->blob_append(h.fw, (size_t)D * D * sizeof(float)); o.fb_off = net->blob_append(h.fb, (size_t)D * sizeof(float)); o.has_fw = true; }
+    *out_slot = push_op(net, std::move(o), true);
     return GDT_OK;
 }
 
@@ -908,10 +794,7 @@ int gdt_net_output_nchw(gdt_net* net, int in_tensor, const float* bias, int* out
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "tensor id");
     Op o; o.kind = OP_OUT_NCHW; o.in = in_tensor;
     if (bias) { o.tap_bias_off = net->blob_append(bias, net->tensors[in_tensor].C * sizeof(float)); o.tap_has_bias = true; }
-    o.slot = (int)net->out_ops.size();
-    net->out_ops.push_back((int)net->ops.size());
-    net->ops.push_back(o);
-    *out_slot = o.slot;
+    *out_slot = push_op(net, std::move(o), true);
     return GDT_OK;
 }
 
@@ -926,10 +809,7 @@ int gdt_net_hed_head(gdt_net* net, const int* feature_tensors, const float* cons
         o.score_w_off[k] = net->blob_append(score_w[k], net->tensors[o.feats[k]].C * sizeof(float));
         o.score_b[k] = score_b[k]; o.fusion_w[k] = fusion_w[k];
     }
-    o.slot = (int)net->out_ops.size();
-    net->out_ops.push_back((int)net->ops.size());
-    net->ops.push_back(o);
-    *out_slot = o.slot;
+    *out_slot = push_op(net, std::move(o), true);
     return GDT_OK;
 }
 
@@ -966,10 +846,7 @@ int gdt_net_rcf_head(gdt_net* net, const int* feature_tensors, const int* stage_
                 f[(size_t)a * K + b] = (float)((1.0 - std::fabs(a - center) / factor) * (1.0 - std::fabs(b - center) / factor));
         o.bilin_off[s] = net->blob_append(f.data(), f.size() * sizeof(float));
     }
-    o.slot = (int)net->out_ops.size();
-    net->out_ops.push_back((int)net->ops.size());
-    net->ops.push_back(o);
-    *out_slot = o.slot;
+    *out_slot = push_op(net, std::move(o), true);
     return GDT_OK;
 }
 

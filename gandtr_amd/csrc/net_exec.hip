@@ -202,7 +202,7 @@ int exec_conv(const ConvStep& s) {
     if (stp.direct) return exec_stem_direct(s);
     if (stp.xexp) return exec_xexp(s);
     if (stp.kcat) return exec_kcat(s);
-    if (s.o.has_t4) {                      // ConvTranspose2d(k4,s2,p1) from its own inputs (conv4x4t_halo.hip) -- else the phase launches below, over the concatenation
+    if (s.o.has_cat_frag && s.o.cd.transposed) {   // ConvTranspose2d(k4,s2,p1) from its own inputs (conv4x4t_halo.hip) -- else the phase launches below, over the concatenation
         const ConvLaunch d = conv_desc_t4(s.x, stp.op);
         if (gdt_conv4x4t_halo_eligible(d)) {
             int variant = 0;
@@ -275,7 +275,7 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
             }
             case OP_CONCAT: {
                 const Op& oc = net->ops[o.cat_for];
-                if (oc.has_t4 && gdt_conv4x4t_halo_eligible(conv_desc_t4(DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}, o.cat_for))) break;   // the conv reads the sources itself
+                if (oc.has_cat_frag && oc.cd.transposed && gdt_conv4x4t_halo_eligible(conv_desc_t4(DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}, o.cat_for))) break;   // the conv reads the sources itself
                 if (conv_takes_cat_kernel(DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}, plan, o.cat_for)) break;           // (likewise, conv3x3_cat_halo.hip)
                 const Tensor& ta = T[o.in]; const Tensor& to = T[o.out];
                 rc = gdt_k_concat(tptr(o.in), o.res >= 0 ? tptr(o.res) : nullptr, tptr(o.out), f32, (long)n * ta.H * ta.W, ta.C, ta.Creal,

@@ -63,18 +63,16 @@ struct Op {
     // fp16 mode: a 1x1 expand conv whose residual is the output of a 1x1 projection conv (ResNet Bottleneck shortcut, stride 1 or 2) carries the two
     // weight matrices K-concatenated (conv1x1_rb.hip, CAT form): kcat_ds = index of the projection op
     int kcat_ds = -1; size_t kcat_frag_off = 0, kcat_bias_off = 0;
-    float leaky = 0.f;    // conv / inorm: LeakyReLU slope applied instead of ReLU, 0 = none (gdt_net_conv_leaky, gdt_net_instance_norm_leaky)
-    // ConvTranspose2d(k4,s2,p1) (gdt_net_conv_transposed4): `in` is what the four generic phase launches read -- the first input itself, or the output of the OP_CONCAT
-    // op `cat_op` (channel concatenation of t4_a and t4_b, ReLU on the t4_a part when t4_relu); has_t4: the fragment-ordered weights of conv4x4t_halo.hip, which
-    // reads t4_a / t4_b itself (they are also in `feats`, so that they live until this op) -- then the concatenation is never written
-    bool has_t4 = false; size_t t4_frag_off = 0; int t4_a = -1, t4_b = -1, t4_relu = 0, cat_op = -1;
-    // Conv2d of a concatenation (gdt_net_conv_cat): `in` is the output of the OP_CONCAT op `cat_op` (channel concatenation of cc_a and cc_b), which the conv of one
-    // tensor reads; has_cc: the fragment-ordered weights of conv3x3_cat_halo.hip, which reads cc_a / cc_b itself (they are also in `feats`) -- then the
+    float leaky = 0.f;    // conv / inorm: LeakyReLU slope applied instead of ReLU, 0 = none (gdt_conv_desc::leaky, gdt_net_instance_norm)
+    // The two-input routes of gdt_net_conv -- ConvTranspose2d(k4,s2,p1) (cd.transposed) and Conv2d of a concatenation: `in` is what the generic launches (four
+    // phases / the conv of one tensor) read -- the first input itself, or the output of the OP_CONCAT op `cat_op` (channel concatenation of src_a and src_b,
+    // ReLU on the src_a part when src_relu).  has_cat_frag: the fragment-ordered weights (cat_frag_off) of the patch kernel that reads src_a / src_b itself
+    // -- conv4x4t_halo.hip when cd.transposed, else conv3x3_cat_halo.hip; the sources are then also in `feats`, so that they live until this op, and the
     // concatenation is never written
-    bool has_cc = false; size_t cc_frag_off = 0; int cc_a = -1, cc_b = -1;
+    bool has_cat_frag = false; size_t cat_frag_off = 0; int src_a = -1, src_b = -1, src_relu = 0, cat_op = -1;
     // concat (OP_CONCAT): in / res = the two tensors (res < 0: one), relu = ReLU on the first; cat_for = the conv op that reads the output
     int cat_for = -1;
-    int dil = 1;          // conv: dilation (gdt_net_conv_dilated); the taps are (dy0 + (t / TW) * dil, ...): only the generic implicit-GEMM kernels take it
+    int dil = 1;          // conv: dilation (gdt_conv_desc::dilation); the taps are (dy0 + (t / TW) * dil, ...): only the generic implicit-GEMM kernels take it
     // maxpool
     int k = 0, s = 0, p = 0; int ceil = 0;
     // gem
@@ -83,7 +81,7 @@ struct Op {
     // 1 = R-MAC, 2 = Rpool over `levels` levels of regions; the per-channel exponents and the two whitening layers in the blob (fp32)
     int pool_kind = 0, pool_aggregate = 0, pool_levels = 0;
     size_t pch_off = 0, rw_off = 0, rb_off = 0, fw_off = 0, fb_off = 0; bool has_rw = false, has_fw = false;
-    int att = 0, att_max = 0;   // gdt_net_pool_head_attention: 1 = L2-norm attention weights in front of the pooling, divided by the image's maximum when att_max
+    int att = 0, att_max = 0;   // gdt_pool_head_desc::attention: 1 = L2-norm attention weights in front of the pooling, divided by the image's maximum when att_max
     // out_nchw
     size_t tap_bias_off = 0; bool tap_has_bias = false;
     // head ops (OP_HED, OP_RCF): the feature tensors they read -- inputs like `in` / `res` (op_inputs), kept alive until the head runs
@@ -269,9 +267,9 @@ ConvLaunch conv_desc_pair(const DescCtx& x, int i, int pair_idx, const ConvFold&
 ConvLaunch conv_desc_xexp(const DescCtx& x, int i, int chain, float group_factor);       // 3x3 + expand (op i + 1) (+ the next reduce conv, op `chain`)
 ConvLaunch conv_desc_kcat(const DescCtx& x, int i);                                      // expand conv + its projection shortcut, K-concatenated
 ConvLaunch conv_desc_stem_direct(const DescCtx& x, int i, int pool_into);                // ResNet stem from the caller's image (+ the 3 x 3 max-pool behind it)
-ConvLaunch conv_desc_t4(const DescCtx& x, int i);                                        // ConvTranspose2d(k4,s2,p1) from its one or two inputs (Op::has_t4, conv4x4t_halo.hip)
+ConvLaunch conv_desc_t4(const DescCtx& x, int i);                                        // ConvTranspose2d(k4,s2,p1) from its one or two inputs (Op::has_cat_frag, conv4x4t_halo.hip)
 
-ConvLaunch conv_desc_cc(const DescCtx& x, int i, const ConvFold& f);                     // Conv2d(k3,s1,p1) from its two inputs (Op::has_cc, conv3x3_cat_halo.hip)
+ConvLaunch conv_desc_cc(const DescCtx& x, int i, const ConvFold& f);                     // Conv2d(k3,s1,p1) from its two inputs (Op::has_cat_frag, conv3x3_cat_halo.hip)
 // conv op i of a planned geometry runs on conv3x3_cat_halo.hip: its own plain launch in the plan, and eligible (the knob is read here: a launch-time choice)
 bool conv_takes_cat_kernel(const DescCtx& x, const Plan& plan, int i);
 

@@ -212,14 +212,14 @@ ConvLaunch conv_desc_stem_direct(const DescCtx& x, int i, int pool_into) {
 ConvLaunch conv_desc_t4(const DescCtx& x, int i) {
     const Op& o = x.net->ops[i];
     const auto& T = *x.T;
-    const Tensor& ta = T[o.t4_a];
+    const Tensor& ta = T[o.src_a];
     ConvLaunch d{};
-    d.in = x.p.act(T, o.t4_a); d.Cin = ta.C; d.in_relu = o.t4_relu;
-    if (o.t4_b >= 0) { d.in2 = x.p.act(T, o.t4_b); d.in2_cin = T[o.t4_b].C; d.in2_h = ta.H; d.in2_w = ta.W; d.in2_stride = 1; }
+    d.in = x.p.act(T, o.src_a); d.Cin = ta.C; d.in_relu = o.src_relu;
+    if (o.src_b >= 0) { d.in2 = x.p.act(T, o.src_b); d.in2_cin = T[o.src_b].C; d.in2_h = ta.H; d.in2_w = ta.W; d.in2_stride = 1; }
     d.N = x.n; d.H = ta.H; d.W = ta.W; d.OH = d.H * 2; d.OW = d.W * 2; d.OHg = d.H; d.OWg = d.W; d.M = x.n * d.H * d.W;
     d.Cout = o.cd.cout; d.CoutPad = o.cout_pad; d.Kpad = 16 * o.cd.cin; d.nk = d.Kpad / 64;
     d.ntaps = 16; d.TW = 4; d.invTW = 65536 / 4; d.sy = d.sx = 1; d.osy = d.osx = 2; d.relu = o.cd.relu;
-    d.w_frag = o.has_t4 ? x.p.w<const f16*>(o.t4_frag_off) : nullptr;
+    d.w_frag = o.has_cat_frag ? x.p.w<const f16*>(o.cat_frag_off) : nullptr;
     d.bias = o.has_bias ? x.p.w<const float*>(o.bias_off) : nullptr;
     d.out = x.p.act(T, o.out);
     d.zeros = x.p.w<const f16*>(x.net->zeros_off);
@@ -230,18 +230,18 @@ ConvLaunch conv_desc_cc(const DescCtx& x, int i, const ConvFold& f) {
     const Op& o = x.net->ops[i];
     const auto& T = *x.T;
     ConvLaunch d = conv_desc_phase(x, i, o.phases[0], 0, f);        // geometry, epilogue and what the plan folded around the conv (all of which the kernel refuses)
-    d.in = x.p.act(T, o.cc_a); d.Cin = T[o.cc_a].C; d.lc8 = ilog2(d.Cin / 8);
-    d.in2 = x.p.act(T, o.cc_b); d.in2_cin = T[o.cc_b].C; d.in2_h = T[o.cc_b].H; d.in2_w = T[o.cc_b].W; d.in2_stride = 1;
+    d.in = x.p.act(T, o.src_a); d.Cin = T[o.src_a].C; d.lc8 = ilog2(d.Cin / 8);
+    d.in2 = x.p.act(T, o.src_b); d.in2_cin = T[o.src_b].C; d.in2_h = T[o.src_b].H; d.in2_w = T[o.src_b].W; d.in2_stride = 1;
     d.Kpad = 9 * (d.Cin + d.in2_cin); d.nk = d.Kpad / 64;
     d.w = nullptr; d.w_lo = nullptr;
-    d.w_frag = o.has_cc ? x.p.w<const f16*>(o.cc_frag_off) : nullptr;
+    d.w_frag = o.has_cat_frag ? x.p.w<const f16*>(o.cat_frag_off) : nullptr;
     return d;
 }
 
 bool conv_takes_cat_kernel(const DescCtx& x, const Plan& plan, int i) {
     const Op& o = x.net->ops[i];
     const Step& st = plan.steps[i];
-    if (o.kind != OP_CONV || !o.has_cc || st.skip || st.bneck || st.direct || st.xexp || st.kcat || st.ctf || st.s2 || st.ctp || st.aug) return false;
+    if (o.kind != OP_CONV || !o.has_cat_frag || o.cd.transposed || st.skip || st.bneck || st.direct || st.xexp || st.kcat || st.ctf || st.s2 || st.ctp || st.aug) return false;
     return gdt_conv3x3_cat_halo_eligible(conv_desc_cc(x, i, fold_of(x.net, plan, i)));
 }
 
@@ -792,50 +792,49 @@ int gdt_net_workspace_bytes(gdt_net* net, int n, int rh, int rw, size_t* bytes) 
     return GDT_OK;
 }
 
-// What the planner decides for a geometry, as counts (host logic only: no device call) -- so that the fusion decisions are testable without a GPU.
-// counts[0] launches of conv ops (a fused launch counts once), [1] whole Bottlenecks in one launch (conv_bneck.hip), [2] 3x3 + expand launches (conv3x3_expand_rb.hip),
-// [3] of those with the next block's reduce conv chained in, [4] projection shortcuts folded into their expand conv (K-concatenated 1x1), [5] InstanceNorms applied by
-// their consumer's staging, [6] max-pools written by their producer, [7] 1 if the stem reads the caller's image itself (calls that do not resize),
-// [8] transposed convs as one fused-phase launch, [9] stride-2 convs as the shift form, [10] dilated convs, [11] of those on a special form; with n_counts >= 14:
-// [12] launches of the pool-head ops (gdt_net_pool_head), [13] of those the ones that read the feature map; with n_counts >= 15: [14] conv launches that
-// conv4x4_halo.hip takes (what gdt_launch_conv decides for the conv as its own plain launch; GDT_CONV4X4_HALO=0: none); with n_counts >= 16: [15] transposed 4x4 convs
-// that conv4x4t_halo.hip takes (one launch each, the concatenation in front never written; GDT_CONV4X4T_HALO=0: none -- then four phase launches each); with
-// n_counts >= 17: [16] convs of a concatenation (gdt_net_conv_cat) that conv3x3_cat_halo.hip takes (GDT_CONV3X3_CAT_HALO=0: none -- then a copy + the conv of one tensor);
-// with n_counts >= 19: [17] launches the attention of gdt_net_pool_head_attention adds in front of the pooling, [18] launches of such heads that read the feature map
+// What the planner decides for a geometry, as counts (host logic only: no device call) -- so that the fusion decisions are testable without a GPU.  The counters
+// are documented next to their GDT_PLAN_* names in include/gandtr_hip.h; the names, in the enum's order:
+static const char* const PLAN_COUNT_NAMES[GDT_PLAN_COUNT] = {
+    "conv_launches", "bottlenecks_fused", "conv3x3_expand", "chained_reduce", "shortcuts_folded", "norms_folded", "pools_fused", "direct_stem", "transposed_fused",
+    "stride2_shift", "dilated_convs", "dilated_special_forms", "head_launches", "head_map_reads", "conv4x4_launches", "conv4x4t_launches", "conv3x3_cat_launches",
+    "attention_launches", "attention_map_reads"};
+const char* gdt_plan_count_name(int index) { return index >= 0 && index < GDT_PLAN_COUNT ? PLAN_COUNT_NAMES[index] : nullptr; }
+
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts) {
-    GDT_REQUIRE(net && counts && n_counts >= 10 && n >= 1 && rh >= 1 && rw >= 1, "plan summary arguments");
+    GDT_REQUIRE(net && counts && n_counts >= GDT_PLAN_COUNT && n >= 1 && rh >= 1 && rw >= 1, "plan summary arguments");
     if (!net->finalized && !net->precision) build_kcat_weights(net);       // (what finalize would add: the K-concatenated shortcut weights the planner may choose)
     Plan plan;
     int rc = make_plan(net, n, rh, rw, plan, resize == 0);
     if (rc != GDT_OK) return rc;
     for (int k = 0; k < n_counts; ++k) counts[k] = 0;
+    const DescCtx probe{net, &net->tensors, n, Ptrs{}};
     for (size_t i = 0; i < plan.steps.size(); ++i) {
         const Step& st = plan.steps[i];
         const Op& o = net->ops[i];
-        if (o.kind == OP_CONV && !st.skip) ++counts[0];
-        if (o.kind == OP_CONV) { counts[1] += st.bneck; counts[2] += st.xexp; counts[3] += st.xchain >= 0; counts[4] += st.kcat; counts[8] += st.ctf; counts[9] += st.s2; }
-        if (o.kind == OP_INORM) counts[5] += st.norm_into >= 0;
-        if (o.kind == OP_MAXPOOL) counts[6] += st.skip;
-        if (o.kind == OP_POOL_HEAD && n_counts >= 14) {   // the launches of gdt_k_pool_head: fixed by the layers present, whatever the batch and the number of regions
-            counts[12] += 1 + (o.pool_aggregate ? 2 + (o.has_rw ? 2 : 0) + (o.pool_aggregate == 2 ? 1 : 0) : 1) + (o.has_fw ? 2 : 0);
-            counts[13] += 1;                              // ... of which read the feature map: the pooling pass
+        if (o.kind == OP_INORM) counts[GDT_PLAN_NORMS_FOLDED] += st.norm_into >= 0;
+        if (o.kind == OP_MAXPOOL) counts[GDT_PLAN_POOLS_FUSED] += st.skip;
+        if (o.kind == OP_INPUT) counts[GDT_PLAN_DIRECT_STEM] += st.direct;
+        if (o.kind == OP_POOL_HEAD) {   // the launches of gdt_k_pool_head: fixed by the layers present, whatever the batch and the number of regions
+            counts[GDT_PLAN_HEAD_LAUNCHES] += 1 + (o.pool_aggregate ? 2 + (o.has_rw ? 2 : 0) + (o.pool_aggregate == 2 ? 1 : 0) : 1) + (o.has_fw ? 2 : 0);
+            counts[GDT_PLAN_HEAD_MAP_READS] += 1;                     // ... of which read the feature map: the pooling pass
+            if (o.att) {                                              // the attention in front of the pooling: the norm pass (+ the division by the image's maximum)
+                counts[GDT_PLAN_ATTENTION_LAUNCHES] += 1 + (o.att_max ? 1 : 0);
+                counts[GDT_PLAN_ATTENTION_MAP_READS] += 2;            // the map is read by the norm pass and by the weighted pooling pass
+            }
         }
-        if (o.kind == OP_POOL_HEAD && o.att && n_counts >= 19) {      // the attention in front of the pooling: the norm pass (+ the division by the image's maximum)
-            counts[17] += 1 + (o.att_max ? 1 : 0);
-            counts[18] += 2;                              // the map is read by the norm pass and by the weighted pooling pass
-        }
-        if (o.kind == OP_INPUT) counts[7] += st.direct;
-        if (o.kind == OP_CONV && n_counts >= 15 && !net->precision && o.phases.size() == 1 && !o.rowsplit &&
-            !(st.skip || st.bneck || st.xexp || st.kcat || st.direct || st.ctf || st.s2 || st.ctp || st.aug))
-            counts[14] += gdt_conv4x4_halo_eligible(conv_desc_phase(DescCtx{net, &net->tensors, n, Ptrs{}}, (int)i, o.phases[0], 0, fold_of(net, plan, (int)i)));
-        if (o.kind == OP_CONV && n_counts >= 16 && o.has_t4 && !st.skip)
-            counts[15] += gdt_conv4x4t_halo_eligible(conv_desc_t4(DescCtx{net, &net->tensors, n, Ptrs{}}, (int)i));
-        if (n_counts >= 17) counts[16] += conv_takes_cat_kernel(DescCtx{net, &net->tensors, n, Ptrs{}}, plan, (int)i);
-        if (o.kind == OP_CONV && o.dil != 1 && n_counts >= 12) {
-            ++counts[10];
+        if (o.kind != OP_CONV) continue;
+        counts[GDT_PLAN_CONV_LAUNCHES] += !st.skip;
+        counts[GDT_PLAN_BOTTLENECKS_FUSED] += st.bneck; counts[GDT_PLAN_CONV3X3_EXPAND] += st.xexp; counts[GDT_PLAN_CHAINED_REDUCE] += st.xchain >= 0;
+        counts[GDT_PLAN_SHORTCUTS_FOLDED] += st.kcat; counts[GDT_PLAN_TRANSPOSED_FUSED] += st.ctf; counts[GDT_PLAN_STRIDE2_SHIFT] += st.s2;
+        if (!net->precision && o.phases.size() == 1 && !o.rowsplit && !(st.skip || st.bneck || st.xexp || st.kcat || st.direct || st.ctf || st.s2 || st.ctp || st.aug))
+            counts[GDT_PLAN_CONV4X4_LAUNCHES] += gdt_conv4x4_halo_eligible(conv_desc_phase(probe, (int)i, o.phases[0], 0, fold_of(net, plan, (int)i)));
+        if (o.has_cat_frag && o.cd.transposed && !st.skip) counts[GDT_PLAN_CONV4X4T_LAUNCHES] += gdt_conv4x4t_halo_eligible(conv_desc_t4(probe, (int)i));
+        counts[GDT_PLAN_CONV3X3_CAT_LAUNCHES] += conv_takes_cat_kernel(probe, plan, (int)i);
+        if (o.dil != 1) {
+            ++counts[GDT_PLAN_DILATED_CONVS];
             // what gdt_launch_conv / gdt_launch_conv_x3 would be handed for the conv as its own plain launch
-            const ConvLaunch d = conv_desc_phase(DescCtx{net, &net->tensors, n, Ptrs{}}, (int)i, o.phases[0], 0, ConvFold{});
-            counts[11] += st.skip || st.bneck || st.xexp || st.pool_into >= 0 || st.s2 || st.aug || st.direct || gdt_conv_halo_eligible(d) ||
+            const ConvLaunch d = conv_desc_phase(probe, (int)i, o.phases[0], 0, ConvFold{});
+            counts[GDT_PLAN_DILATED_SPECIAL_FORMS] += st.skip || st.bneck || st.xexp || st.pool_into >= 0 || st.s2 || st.aug || st.direct || gdt_conv_halo_eligible(d) ||
                           gdt_conv_halo_rb_eligible(d) || gdt_conv_halo_x3_eligible(d) || gdt_conv_halo_x3_taps_eligible(d) || gdt_conv_halo_c_eligible(d) ||
                           gdt_conv_stem_eligible(d) || gdt_conv_stem_c_eligible(d) || gdt_conv_1x1_rb_eligible(d);
         }

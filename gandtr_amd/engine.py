@@ -1,6 +1,6 @@
 """Host-side driver of the HIP graph executor (C ABI: include/gandtr_hip.h, binding: gandtr_amd/_hip.py).
 
-``HipNet`` mirrors the builder calls one-to-one; the ``build_*`` functions translate the reference's state dicts
+``HipNet`` mirrors the builder calls; the ``build_*`` functions translate the reference's state dicts
 (names as produced by the reference modules, see gandtr_amd/tools/synth.py) into layer graphs:
 
   build_generator   ResnetGenerator            mdir/components/model/network/p2p_networks.py:269-313, :454-506
@@ -141,88 +141,71 @@ class HipNet:
             raise NotImplementedError("input filter %r: only 'edgefilter' is on the HIP path" % (kind,))
         _hip.check(self.lib.gdt_net_input_filter(self.handle, 1, float(w), float(p), float(beta), float(tau), float(eps)))
 
+    def _conv(self, a, b, w, bias, bn, residual=-1, **desc):
+        """gdt_net_conv of ``a`` (and ``b``, -1: none) with the fp32 weight array ``w``: the descriptor from the weight's shape and ``desc``, one gdt_conv_weights"""
+        transposed = desc.get("transposed", 0)
+        cin, cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
+        d = ConvDesc(cin=cin, cout=cout, kh=w.shape[2], kw=w.shape[3], bn_eps=1e-5, **desc)
+        arrays = [w, _f32(bias)] + ([_f32(t) for t in bn] if bn is not None else [None] * 4)      # (alive until the call has returned)
+        return self._add("conv", a, b, ctypes.byref(d), ctypes.byref(_hip.ConvWeights(*[_ptr(t) for t in arrays])), residual)
+
     def conv(self, x, weight, bias=None, bn=None, stride=1, pad=0, reflect=False, transposed=False, relu=False,
              residual=-1, out_f32=False, act=0, dilation=1, leaky=0.0):
-        """``leaky``: slope of an nn.LeakyReLU applied after bias and BatchNorm in place of ``relu`` (gdt_net_conv_leaky)"""
-        w = _f32(weight)
-        cin, cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
-        d = ConvDesc(cin, cout, w.shape[2], w.shape[3], stride, pad, int(reflect), int(transposed), int(relu),
-                     int(out_f32), act, 1e-5)
-        b = _f32(bias)
-        if dilation != 1:                 # gdt_net_conv_dilated: plain Conv2d + bias, no BN / residual
-            if bn is not None or residual != -1:
-                raise ValueError("a dilated conv takes no BatchNorm and no residual")
-            return self._add("conv_dilated", x, ctypes.byref(d), int(dilation), _ptr(w), _ptr(b))
-        g = be = m = v = None
-        if bn is not None:
-            g, be, m, v = (_f32(t) for t in bn)
-        if leaky:
-            if dilation != 1 or residual != -1 or relu:
-                raise ValueError("a LeakyReLU conv takes no dilation, no residual and no ReLU")
-            return self._add("conv_leaky", x, ctypes.byref(d), float(leaky), _ptr(w), _ptr(b), _ptr(g), _ptr(be), _ptr(m), _ptr(v))
-        return self._add("conv", x, ctypes.byref(d), _ptr(w), _ptr(b), _ptr(g), _ptr(be), _ptr(m), _ptr(v), residual)
+        """``leaky``: slope of an nn.LeakyReLU applied after bias and BatchNorm in place of ``relu``; ``dilation`` != 1: plain Conv2d + bias"""
+        if dilation != 1 and (bn is not None or residual != -1):
+            raise ValueError("a dilated conv takes no BatchNorm and no residual")
+        if leaky and (dilation != 1 or residual != -1 or relu):
+            raise ValueError("a LeakyReLU conv takes no dilation, no residual and no ReLU")
+        return self._conv(x, -1, _f32(weight), bias, bn, residual, stride=stride, pad=pad, pad_reflect=reflect, transposed=transposed, relu=relu,
+                          out_f32_nchw=out_f32, act=act, dilation=dilation, leaky=leaky)
 
     def conv_transposed4(self, a, weight, b=-1, relu_a=False, bias=None, bn=None, relu=False, out_f32=False, act=0):
         """nn.ConvTranspose2d(k4, s2, p1) of ``torch.cat([a, b], 1)`` (``b`` = -1: of ``a`` alone) with ReLU applied to ``a`` as it is read when ``relu_a``
-        (gdt_net_conv_transposed4); ``weight`` [cin_a + cin_b][cout][4][4]"""
+        (gdt_net_conv, transposed-4 route); ``weight`` [cin_a + cin_b][cout][4][4]"""
         w = _f32(weight)
         if w.ndim != 4 or w.shape[2:] != (4, 4):
             raise ValueError("conv_transposed4 takes a [cin][cout][4][4] weight, got %s" % (tuple(w.shape),))
-        g = be = m = v = None
-        if bn is not None:
-            g, be, m, v = (_f32(t) for t in bn)
-        bias = _f32(bias)
-        return self._add("conv_transposed4", a, b, int(relu_a), w.shape[1], _ptr(w), _ptr(bias), _ptr(g), _ptr(be), _ptr(m), _ptr(v), 1e-5, int(relu),
-                         int(out_f32), act)
+        return self._conv(a, b, w, bias, bn, stride=2, pad=1, transposed=1, relu=relu, out_f32_nchw=out_f32, act=act, in_relu=relu_a)
 
     def conv_cat(self, a, b, weight, bias=None, bn=None, stride=1, pad=0, relu=False, out_f32=False, act=0):
-        """nn.Conv2d of ``torch.cat([a, b], 1)`` (gdt_net_conv_cat); ``weight`` [cout][cin_a + cin_b][kh][kw], ``a``'s channels first"""
+        """nn.Conv2d of ``torch.cat([a, b], 1)`` (gdt_net_conv with two inputs); ``weight`` [cout][cin_a + cin_b][kh][kw], ``a``'s channels first"""
         w = _f32(weight)
         if w.ndim != 4:
             raise ValueError("conv_cat takes a [cout][cin][kh][kw] weight, got %s" % (tuple(w.shape),))
-        d = ConvDesc(w.shape[1], w.shape[0], w.shape[2], w.shape[3], stride, pad, 0, 0, int(relu), int(out_f32), act, 1e-5)
-        g = be = m = v = None
-        if bn is not None:
-            g, be, m, v = (_f32(t) for t in bn)
-        bias = _f32(bias)
-        return self._add("conv_cat", a, b, ctypes.byref(d), _ptr(w), _ptr(bias), _ptr(g), _ptr(be), _ptr(m), _ptr(v))
+        return self._conv(a, b, w, bias, bn, stride=stride, pad=pad, relu=relu, out_f32_nchw=out_f32, act=act)
 
     def instance_norm(self, x, relu=False, residual=-1, eps=1e-5, leaky=0.0):
-        """``leaky``: slope of an nn.LeakyReLU behind the norm in place of ``relu`` (gdt_net_instance_norm_leaky)"""
-        if leaky:
-            if relu or residual != -1:
-                raise ValueError("a LeakyReLU InstanceNorm takes no ReLU and no residual")
-            return self._add("instance_norm_leaky", x, eps, float(leaky))
-        return self._add("instance_norm", x, eps, int(relu), residual)
+        """``leaky``: slope of an nn.LeakyReLU behind the norm in place of ``relu``"""
+        if leaky and (relu or residual != -1):
+            raise ValueError("a LeakyReLU InstanceNorm takes no ReLU and no residual")
+        return self._add("instance_norm", x, eps, int(relu), float(leaky), residual)
 
     def maxpool(self, x, kernel, stride, pad=0, ceil=False):
-        if not ceil:
-            return self._add("maxpool", x, kernel, stride, pad)
-        if pad:
+        if ceil and pad:
             raise ValueError("ceil-mode max-pooling takes no padding here")
-        return self._add("maxpool_ceil", x, kernel, stride)
+        return self._add("maxpool", x, kernel, stride, pad, int(ceil))
 
     def gem_l2n(self, x, p, eps_gem=1e-6, eps_l2=1e-6):
         return self._add("gem_l2n", x, float(p), eps_gem, eps_l2)
 
     POOL_KINDS = {"mac": 0, "spoc": 1, "gem": 2, "gemmp": 3}         # include/gandtr_hip.h, gdt_net_pool_head
 
+    def _pool_head(self, x, kind, p, eps, aggregate, levels, rwhiten, whiten, eps_l2, attention=0, normalize_max=False):
+        arrays = [_f32(p).reshape(-1) if p is not None else None] + [_f32(t) for t in tuple(rwhiten or (None, None)) + tuple(whiten or (None, None))]
+        pa, rw, rb, fw, fb = (_ptr(t) for t in arrays)                 # (the arrays stay alive until the call has returned)
+        d = _hip.PoolHeadDesc(self.POOL_KINDS[kind], pa, 0 if arrays[0] is None else arrays[0].size, float(eps), int(aggregate), int(levels), rw, rb, fw, fb,
+                              float(eps_l2), attention, int(bool(normalize_max)))
+        return self._add("pool_head", x, ctypes.byref(d))
+
     def pool_head(self, x, kind, p=None, eps=1e-6, aggregate=0, levels=3, rwhiten=None, whiten=None, eps_l2=1e-6):
         """gdt_net_pool_head: pooling ``kind`` (global, ``aggregate`` 1 = R-MAC, 2 = regional over ``levels`` levels) -> l2n -> optional final
         whitening + l2n; ``rwhiten`` / ``whiten`` = (weight [D][D], bias [D]) of the nn.Linear layers or None"""
-        pa = _f32(p).reshape(-1) if p is not None else None
-        rw, rb = (_f32(rwhiten[0]), _f32(rwhiten[1])) if rwhiten is not None else (None, None)
-        fw, fb = (_f32(whiten[0]), _f32(whiten[1])) if whiten is not None else (None, None)
-        return self._add("pool_head", x, self.POOL_KINDS[kind], _ptr(pa), 0 if pa is None else pa.size, float(eps), int(aggregate),
-                         int(levels), _ptr(rw), _ptr(rb), _ptr(fw), _ptr(fb), float(eps_l2))
+        return self._pool_head(x, kind, p, eps, aggregate, levels, rwhiten, whiten, eps_l2)
 
     def pool_head_attention(self, x, kind, normalize_max, p=None, eps=1e-6, aggregate=0, levels=3, rwhiten=None, eps_l2=1e-6):
-        """gdt_net_pool_head_attention: ``pool_head`` (no final whitening) of the map weighted per position by its L2-norm attention, divided by the
+        """gdt_net_pool_head with attention 1: ``pool_head`` (no final whitening) of the map weighted per position by its L2-norm attention, divided by the
         image's maximum when ``normalize_max``"""
-        pa = _f32(p).reshape(-1) if p is not None else None
-        rw, rb = (_f32(rwhiten[0]), _f32(rwhiten[1])) if rwhiten is not None else (None, None)
-        return self._add("pool_head_attention", x, self.POOL_KINDS[kind], _ptr(pa), 0 if pa is None else pa.size, float(eps), int(aggregate),
-                         int(levels), _ptr(rw), _ptr(rb), float(eps_l2), 1, int(bool(normalize_max)))
+        return self._pool_head(x, kind, p, eps, aggregate, levels, rwhiten, None, eps_l2, attention=1, normalize_max=normalize_max)
 
     def output_nchw(self, x, bias=None):
         b = _f32(bias)
@@ -285,39 +268,36 @@ class HipNet:
     def output_shapes(self, n, rh, rw):
         return list(self._geometry(n, rh, rw)[1])
 
-    PLAN_KEYS = ("conv_launches", "bottlenecks_fused", "conv3x3_expand", "chained_reduce", "shortcuts_folded", "norms_folded", "pools_fused", "direct_stem",
-                 "transposed_fused", "stride2_shift", "dilated_convs", "dilated_special_forms")
-
-    def _plan_counts(self, n, rh, rw, resize, count):
-        """the first ``count`` counters of gdt_net_plan_summary for a geometry: host logic, no device call"""
-        c = (ctypes.c_int * count)()
-        _hip.check(self.lib.gdt_net_plan_summary(self.handle, n, rh, rw, int(bool(resize)), c, count))
-        return list(c)
+    PLAN_KEYS = property(lambda self: _hip.plan_count_names())       # gdt_plan_count_name: one name per counter of gdt_net_plan_summary
 
     def plan_summary(self, n, rh, rw, resize=False):
-        """the planner's fusion decisions for a geometry as a dict of counts"""
-        return dict(zip(self.PLAN_KEYS, self._plan_counts(n, rh, rw, resize, 12)))
+        """the planner's decisions for a geometry as a dict of named counts (GDT_PLAN_* in include/gandtr_hip.h): host logic, no device call"""
+        c = (ctypes.c_int * len(self.PLAN_KEYS))()
+        _hip.check(self.lib.gdt_net_plan_summary(self.handle, n, rh, rw, int(bool(resize)), c, len(c)))
+        return dict(zip(self.PLAN_KEYS, c))
 
     def conv4x4_launches(self, n, rh, rw):
         """conv launches of a geometry that run on the 4x4 patch kernel (conv4x4_halo.hip; GDT_CONV4X4_HALO=0: none) -- the planner's count"""
-        return self._plan_counts(n, rh, rw, False, 15)[14]
+        return self.plan_summary(n, rh, rw)["conv4x4_launches"]
 
     def conv4x4t_launches(self, n, rh, rw):
         """transposed 4x4 convs of a geometry that run as one launch of conv4x4t_halo.hip (GDT_CONV4X4T_HALO=0: none) -- the planner's count"""
-        return self._plan_counts(n, rh, rw, False, 16)[15]
+        return self.plan_summary(n, rh, rw)["conv4x4t_launches"]
 
     def conv3x3_cat_launches(self, n, rh, rw):
         """convs of a concatenation of a geometry that run as one launch of conv3x3_cat_halo.hip (GDT_CONV3X3_CAT_HALO=0: none) -- the planner's count"""
-        return self._plan_counts(n, rh, rw, False, 17)[16]
+        return self.plan_summary(n, rh, rw)["conv3x3_cat_launches"]
 
     def head_launches(self, n, rh, rw):
         """(launches of the net's pool-head ops, launches among them that read the feature map) for a geometry -- the planner's count"""
-        return tuple(self._plan_counts(n, rh, rw, False, 14)[12:])
+        s = self.plan_summary(n, rh, rw)
+        return s["head_launches"], s["head_map_reads"]
 
     def attention_launches(self, n, rh, rw):
         """(launches the attention of the net's pool-head ops adds in front of the pooling, launches of such heads that read the feature map: the norm
         pass and the weighted pooling pass) for a geometry -- the planner's count"""
-        return tuple(self._plan_counts(n, rh, rw, False, 19)[17:])
+        s = self.plan_summary(n, rh, rw)
+        return s["attention_launches"], s["attention_map_reads"]
 
     def flops(self, n, rh, rw):
         f = ctypes.c_double()
@@ -564,6 +544,22 @@ def _bn(sd, p):
     return (sd[p + ".weight"], sd[p + ".bias"], sd[p + ".running_mean"], sd[p + ".running_var"])
 
 
+def _norm_type(norm, key_norm):
+    """the norm type a builder runs: the module's configured one when the caller knows it (get_norm_layer, p2p_networks.py:23-35), else the one the
+    state-dict keys show"""
+    norm = norm or key_norm
+    if norm not in ("instance", "batch"):
+        raise NotImplementedError('normalization layer [%s] is not found' % norm)          # p2p_networks.py:34
+    if norm == "batch" and key_norm != "batch":
+        raise NotImplementedError("BatchNorm without running statistics (track_running_stats=False) has no inference form on the HIP path")
+    return norm
+
+
+def _check_inorm_width(width, what):
+    if width & (width - 1) or width > 2048:
+        raise NotImplementedError("InstanceNorm on the HIP path needs a power-of-two channel count <= 2048: %s gives a layer of %d channels" % (what, width))
+
+
 def _open(device, precision, channels=3, perm=None, in_affine=None):
     """(a new HipNet, its input tensor): ``perm`` / ``in_affine`` = (scale, shift) per channel are applied by the input pack kernel"""
     net = HipNet(device, precision)
@@ -591,12 +587,7 @@ def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precisi
     materialises the last requested tap; there is no generator output (``out_slot`` is None).  A tapped tensor is written by its own op before any later
     layer reads it, so the ops up to there are planned as in the full graph and the taps are the full graph's, bit for bit."""
     key_norm, ngf, n_blocks, in_nc, out_nc = generator_layout(sd)
-    norm = norm or key_norm          # the module's configured norm type when the caller knows it (get_norm_layer, p2p_networks.py:23-35)
-    if norm not in ("instance", "batch"):
-        raise NotImplementedError('normalization layer [%s] is not found' % norm)          # p2p_networks.py:34
-    if norm == "batch" and key_norm != "batch":
-        raise NotImplementedError("BatchNorm without running statistics (track_running_stats=False) has no inference form on the HIP path")
-    inorm = norm == "instance"
+    inorm = _norm_type(norm, key_norm) == "instance"
     net, x = _open(device, precision, in_nc, in_affine=in_affine)
     tap_slots = {}
 
@@ -726,33 +717,27 @@ def build_embedder(sd, device, in_affine=None, feature_tap=False, precision="f16
         ftau = float(sd["preprocessing.tau"].reshape(-1)[0]) if ftau is None else ftau
         net.input_filter(kind, fw, fp, fbeta, ftau, feps)
     f = _resnet_trunk(net, x, sd) if embedder_arch(sd) == "resnet" else _vgg16_trunk(net, x, sd)
-    if attention is not None:
-        akind, normalize_max = attention
-        if akind != "l2norm":
-            raise NotImplementedError("attention %r: only 'l2norm' is on the HIP path" % (akind,))
-        kind, regional, levels, eps, local_whitening, whitening = head if head is not None else ("gem", False, 0, 1e-6, False, False)
-        if local_whitening or whitening:
-            raise NotImplementedError("the attention net takes no local and no final whitening (cirnet.py:117)")
-        if regional and kind == "rmac":
-            raise NotImplementedError("regions of R-MAC regions are not on the HIP path")
-        p = sd.get("pool.rpool.p" if regional else "pool.p") if kind in ("gem", "gemmp") else None
-        rwhiten = (sd["pool.whiten.weight"], sd["pool.whiten.bias"]) if regional and "pool.whiten.weight" in sd else None
-        net.out_slot = net.pool_head_attention(f, "mac" if kind == "rmac" else kind, normalize_max, p=p, eps=eps,
-                                               aggregate=2 if regional else (1 if kind == "rmac" else 0), levels=levels or 3, rwhiten=rwhiten)
-    elif head is None:
+    if attention is not None and attention[0] != "l2norm":
+        raise NotImplementedError("attention %r: only 'l2norm' is on the HIP path" % (attention[0],))
+    if head is None and attention is None:
         net.out_slot = net.gem_l2n(f, float(sd["pool.p"].reshape(-1)[0]))
     else:
-        kind, regional, levels, eps, local_whitening, whitening = head
+        kind, regional, levels, eps, local_whitening, whitening = head if head is not None else ("gem", False, 0, 1e-6, False, False)
+        if attention is not None and (local_whitening or whitening):
+            raise NotImplementedError("the attention net takes no local and no final whitening (cirnet.py:117)")
         if regional and kind == "rmac":
             raise NotImplementedError("regions of R-MAC regions are not on the HIP path")
         if local_whitening:
             w = sd["lwhiten.weight"]
             f = net.conv(f, w.reshape(w.shape[0], w.shape[1], 1, 1), sd["lwhiten.bias"], relu=False)
-        p = sd.get("pool.rpool.p" if regional else "pool.p") if kind in ("gem", "gemmp") else None
-        rwhiten = (sd["pool.whiten.weight"], sd["pool.whiten.bias"]) if regional and "pool.whiten.weight" in sd else None
-        whiten = (sd["whiten.weight"], sd["whiten.bias"]) if whitening else None
-        net.out_slot = net.pool_head(f, "mac" if kind == "rmac" else kind, p=p, eps=eps, aggregate=2 if regional else (1 if kind == "rmac" else 0),
-                                     levels=levels or 3, rwhiten=rwhiten, whiten=whiten)
+        pool = dict(p=sd.get("pool.rpool.p" if regional else "pool.p") if kind in ("gem", "gemmp") else None, eps=eps,
+                    aggregate=2 if regional else (1 if kind == "rmac" else 0), levels=levels or 3,
+                    rwhiten=(sd["pool.whiten.weight"], sd["pool.whiten.bias"]) if regional and "pool.whiten.weight" in sd else None)
+        kind = "mac" if kind == "rmac" else kind
+        if attention is not None:
+            net.out_slot = net.pool_head_attention(f, kind, attention[1], **pool)
+        else:
+            net.out_slot = net.pool_head(f, kind, whiten=(sd["whiten.weight"], sd["whiten.bias"]) if whitening else None, **pool)
     net.feature_slot = net.output_nchw(f) if feature_tap else None
     if finalize:
         net.finalize()
@@ -843,11 +828,7 @@ def build_discriminator(sd, device, precision="f16", finalize=True, norm=None, s
     if precision not in ("f16", "f16x3"):
         raise NotImplementedError("the discriminator runs in 'f16' or 'f16x3'; %r is a generator mode" % (precision,))
     key_norm, ndf, n_layers, in_nc = discriminator_layout(sd)
-    norm = norm or key_norm
-    if norm not in ("instance", "batch"):
-        raise NotImplementedError('normalization layer [%s] is not found' % norm)
-    if norm == "batch" and key_norm != "batch":
-        raise NotImplementedError("BatchNorm without running statistics (track_running_stats=False) has no inference form on the HIP path")
+    norm = _norm_type(norm, key_norm)
     net, x = _open(device, precision, in_nc)
     h = net.conv(x, sd["model.0.weight"], sd["model.0.bias"], stride=2, pad=1, leaky=slope)
     i = 2
@@ -855,9 +836,7 @@ def build_discriminator(sd, device, precision="f16", finalize=True, norm=None, s
         key, nkey = "model.%d" % i, "model.%d" % (i + 1)
         stride = 2 if layer < n_layers else 1
         if norm == "instance":
-            width = sd[key + ".weight"].shape[0]
-            if width & (width - 1) or width > 2048:
-                raise NotImplementedError("InstanceNorm on the HIP path needs a power-of-two channel count <= 2048: ndf = %d gives a layer of %d channels" % (ndf, width))
+            _check_inorm_width(sd[key + ".weight"].shape[0], "ndf = %d" % ndf)
             h = net.instance_norm(net.conv(h, sd[key + ".weight"], None, stride=stride, pad=1), leaky=slope)
         else:
             h = net.conv(h, sd[key + ".weight"], sd.get(key + ".bias"), bn=_bn(sd, nkey), stride=stride, pad=1, leaky=slope)
@@ -893,22 +872,16 @@ def build_unet_generator(sd, device, precision="f16", pre_tanh=False, finalize=T
     relu(leaky(x)) = relu(x).  Per level i the graph therefore stores ONE down tensor s_i = leaky(d_i) (d_i the normalised down output; the next down
     conv reads it as it is, the up conv of level i reads it through ReLU-on-read) and ONE up tensor relu(u_i), which is only ever read through that ReLU.
     Down convs: BatchNorm folded + LeakyReLU in the conv epilogue, or conv + instance_norm(leaky) (the conv's bias cancels in the norm); the innermost
-    has no norm and a fused ReLU (its only reader is the ReLU in front of the up conv).  Up convs: gdt_net_conv_transposed4 of [relu(s_i), relu(u_(i+1))]
+    has no norm and a fused ReLU (its only reader is the ReLU in front of the up conv).  Up convs: conv_transposed4 of [relu(s_i), relu(u_(i+1))]
     -- BatchNorm folded + fused ReLU, or followed by instance_norm(relu).  The outermost up conv has a bias and writes the external fp32 NCHW output.
     Dropout (eval) is the identity."""
     if precision not in ("f16", "f16x3"):
         raise NotImplementedError("the U-Net generator runs in 'f16' or 'f16x3'; %r is a ResnetGenerator mode" % (precision,))
     key_norm, ngf, num_downs, in_nc, out_nc = unet_layout(sd)
-    norm = norm or key_norm
-    if norm not in ("instance", "batch"):
-        raise NotImplementedError('normalization layer [%s] is not found' % norm)
-    if norm == "batch" and key_norm != "batch":
-        raise NotImplementedError("BatchNorm without running statistics (track_running_stats=False) has no inference form on the HIP path")
-    inorm = norm == "instance"
+    inorm = _norm_type(norm, key_norm) == "instance"
     if inorm:
         for width in (ngf, 2 * ngf, 4 * ngf, 8 * ngf):
-            if width & (width - 1) or width > 2048:
-                raise NotImplementedError("InstanceNorm on the HIP path needs a power-of-two channel count <= 2048: ngf = %d gives a layer of %d channels" % (ngf, width))
+            _check_inorm_width(width, "ngf = %d" % ngf)
     net, x = _open(device, precision, in_nc)
     block = unet_block_prefix
     last = num_downs - 1
@@ -953,8 +926,8 @@ def build_p2p_unet(label, sd, device, cfg, precision="f16", pre_act=False, final
 
     A conv takes the BatchNorm behind it (folded) and the activation behind that (epilogue) with it; Dropout is the identity.  No activation of the family is
     in place, so the stored tensors are the post-activation ones and a skip block's value is the PAIR (what the block received, what its ``nested`` chain
-    returned): the layer that follows reads the concatenation from the two tensors -- a ConvTranspose2d(k4, s2, p1) through gdt_net_conv_transposed4, a Conv2d
-    (the aligned net's Conv2d(128, 64, 3, padding=1)) through gdt_net_conv_cat.  The last layer writes the external fp32 NCHW output, with the Tanh where the
+    returned): the layer that follows reads the concatenation from the two tensors -- a ConvTranspose2d(k4, s2, p1) through conv_transposed4, a Conv2d
+    (the aligned net's Conv2d(128, 64, 3, padding=1)) through conv_cat.  The last layer writes the external fp32 NCHW output, with the Tanh where the
     net has one (``pre_act``: the map in front of it)."""
     from .components.model.network import unet
     if precision not in ("f16", "f16x3"):

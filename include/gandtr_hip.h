@@ -79,66 +79,67 @@ typedef struct gdt_conv_desc {
     int stride;           /* 1 or 2                                                                                */
     int pad;              /* padding on every side                                                                 */
     int pad_reflect;      /* 0: zeros (Conv2d padding=p), 1: nn.ReflectionPad2d(p) in front of the conv            */
-    int transposed;       /* 1: nn.ConvTranspose2d(k3, s2, p1, output_padding 1)  (p2p_networks.py:295-298)        */
+    int transposed;       /* 1: nn.ConvTranspose2d(k3, s2, p1, output_padding 1)  (p2p_networks.py:295-298), or
+                             nn.ConvTranspose2d(k4, s2, p1): the transposed-4 route below                         */
     int relu;             /* fuse nn.ReLU after bias (+BN) (+residual)                                             */
     int out_f32_nchw;     /* 1: result is an EXTERNAL fp32 NCHW output (generator head), 0: internal fp16 tensor   */
     int act;              /* external output only: 0 none, 1 tanh (p2p_networks.py:311), 2 sigmoid                 */
     float bn_eps;         /* eps of the folded BatchNorm2d (1e-5)                                                  */
+    int dilation;         /* 1: none; 1..16 (below 1 or above 16 is refused)                                       */
+    float leaky;          /* slope of an nn.LeakyReLU applied in place of `relu`, 0: none, otherwise in (0, 1)     */
+    int in_relu;          /* transposed-4 route: ReLU applied to the first input as it is read                     */
 } gdt_conv_desc;
 
-/* Conv2d / ConvTranspose2d with host fp32 weights in torch layout ([cout][cin][kh][kw], transposed: [cin][cout][kh][kw]).
- * bias and the four BatchNorm2d(eval) vectors may be NULL; BN is folded into the packed weights (get_norm_layer "batch",
- * p2p_networks.py:27; torchvision ResNet BN).  residual_tensor >= 0 adds that tensor before the ReLU
- * (ResnetBlock.forward p2p_networks.py:505; torchvision Bottleneck).  out_tensor receives the new tensor id, or the
- * external output slot index when out_f32_nchw = 1. */
-int gdt_net_conv(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, const float* weight, const float* bias,
-                 const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
-                 int residual_tensor, int* out_tensor);
-/* Conv2d(cin, cout, k, stride, padding = desc->pad, dilation) + bias (may be NULL) (+ ReLU: desc->relu), internal output: RCF conv5_1-5_3
- * (nn.Conv2d(512, 512, 3, padding=2, dilation=2), rcf.py:40-42).  desc->transposed, pad_reflect and out_f32_nchw must be 0 when dilation > 1;
- * dilation 1 is gdt_net_conv.  Tap t reads input offset (t / kw * dilation - pad, t % kw * dilation - pad): the generic implicit-GEMM kernels run
- * it (conv_igemm / conv_igemm_rb, conv_igemm_x3 in the split modes); the 3x3 patch kernels, which stage a one-pixel halo, and every fused form
- * of the planner are not taken (gdt_net_plan_summary counts [10], [11]). */
-int gdt_net_conv_dilated(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, int dilation, const float* weight, const float* bias, int* out_tensor);
-/* Conv2d + bias (+ folded BatchNorm2d(eval), as gdt_net_conv) + nn.LeakyReLU(slope): the convs of NLayerDiscriminator
- * (nn.Conv2d(.., kernel_size=4, stride=2 | 1, padding=1) .. nn.LeakyReLU(0.2, True), p2p_networks.py:533, :543-547, :557-561).  0 < slope < 1; the
- * activation is applied in the epilogue after bias and BN.  desc->relu, transposed and out_f32_nchw must be 0; no residual; precision modes f16 and f16x3.
- * k4 / pad 1 layers with cin % 64 == 0 run on conv4x4_halo.hip (f16), everything else on the generic implicit-GEMM kernels. */
-int gdt_net_conv_leaky(gdt_net* net, int in_tensor, const gdt_conv_desc* desc, float slope, const float* weight, const float* bias,
-                       const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor);
-/* [nn.ReLU] nn.ConvTranspose2d(cin_a + cin_b, cout, kernel_size=4, stride=2, padding=1) (+ folded BatchNorm2d(eval), as gdt_net_conv) (+ ReLU: relu) of the
- * channel concatenation torch.cat([a, b], 1): the up-convolutions of UnetSkipConnectionBlock (p2p_networks.py:205-221, :236).  in_b = -1: one input (the
- * innermost block).  relu_a: ReLU applied to in_a as it is read (in_b is read as stored).  weight: host fp32 [cin_a + cin_b][cout][4][4], in_a's channels
- * first; bias and the four BatchNorm vectors may be NULL.  out_f32_nchw = 0: internal output tensor of 2H x 2W (cout % 8 == 0, act 0); 1: external fp32 NCHW
- * output with `act` (0 none, 1 tanh, 2 sigmoid), out_tensor receives the slot.  Precision modes f16 and f16x3.  In f16, layers with cin_a % 64 == 0,
- * cin_b % 64 == 0, cout % 64 == 0 and an internal output run as ONE launch of conv4x4t_halo.hip, which reads both inputs itself; everything else (and
- * everything with GDT_CONV4X4T_HALO=0) runs as a copy that writes the concatenation (+ ReLU) once and the four sub-pixel phases of 2 x 2 taps on the
- * generic implicit-GEMM kernels (gdt_net_plan_summary count [15]). */
-int gdt_net_conv_transposed4(gdt_net* net, int in_a, int in_b, int relu_a, int cout, const float* weight, const float* bias, const float* bn_gamma,
-                             const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps, int relu, int out_f32_nchw, int act, int* out_tensor);
-/* nn.Conv2d(cin_a + cin_b, cout, k, stride, padding) (+ folded BatchNorm2d(eval), as gdt_net_conv) (+ ReLU: desc->relu) of the channel concatenation
- * torch.cat([a, b], 1): the nn.Conv2d(128, 64, 3, padding=1) that AlignedP2pUNet applies to the output [x, nested(x)] of its inner SkipConnBlock
- * (unet.py, AlignedP2pUNet.__init__ / P2pUNet.SkipConnBlock.forward).  desc->cin = cin_a + cin_b (each % 8 == 0), desc->transposed and pad_reflect must be 0,
- * no dilation, no residual; weight: host fp32 [cout][cin_a + cin_b][kh][kw], in_a's channels first; bias and the four BatchNorm vectors may be NULL;
- * desc->out_f32_nchw as in gdt_net_conv.  Precision modes f16 and f16x3.  In f16, k3 / stride 1 / pad 1 layers with cin_a % 64 == 0, cin_b % 64 == 0,
- * cout % 64 == 0 and an internal output run as ONE launch of conv3x3_cat_halo.hip, which reads both inputs itself, where that measured faster (cout <= 128,
- * cin_a + cin_b no power of two, or few patches; GDT_CONV3X3_CAT_HALO=2: every such layer); everything else (and everything with
- * GDT_CONV3X3_CAT_HALO=0) runs as a copy that writes the concatenation once and the conv of one tensor (gdt_net_plan_summary count [16]). */
-int gdt_net_conv_cat(gdt_net* net, int in_a, int in_b, const gdt_conv_desc* desc, const float* weight, const float* bias, const float* bn_gamma,
-                     const float* bn_beta, const float* bn_mean, const float* bn_var, int* out_tensor);
+/* host fp32 weights of a conv in torch layout ([cout][cin][kh][kw], transposed: [cin][cout][kh][kw]; of a concatenation: in_a's channels first).  bias and
+ * the four BatchNorm2d(eval) vectors may be NULL (the four together); BN is folded into the packed weights (get_norm_layer "batch", p2p_networks.py:27;
+ * torchvision ResNet BN). */
+typedef struct gdt_conv_weights {
+    const float* weight; const float* bias;
+    const float* bn_gamma; const float* bn_beta; const float* bn_mean; const float* bn_var;
+} gdt_conv_weights;
 
-/* nn.InstanceNorm2d(affine=False, eps) (+ fused ReLU) (+ fused residual add AFTER the norm): p2p_networks.py:29,:272,:505 */
-int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, int residual_tensor, int* out_tensor);
-/* nn.InstanceNorm2d(affine=False, eps) + nn.LeakyReLU(slope): norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True) of NLayerDiscriminator
- * (p2p_networks.py:545-546, :559-560).  Always its own statistics and apply passes: neither its producer nor its consumer takes part of it. */
-int gdt_net_instance_norm_leaky(gdt_net* net, int in_tensor, float eps, float slope, int* out_tensor);
+/* Conv2d / ConvTranspose2d of in_a, or of the channel concatenation torch.cat([in_a, in_b], 1) (in_b = -1: one input).  residual_tensor >= 0 adds that tensor
+ * before the ReLU (ResnetBlock.forward p2p_networks.py:505; torchvision Bottleneck).  out_tensor receives the new tensor id, or the external output slot
+ * index when out_f32_nchw = 1.  A refused layer leaves nothing in the graph.  The descriptor selects one of three routes:
+ *
+ * Transposed-4 (desc->transposed, 4x4 kernel, stride 2, pad 1): [nn.ReLU] nn.ConvTranspose2d(cin_a + cin_b, cout, kernel_size=4, stride=2, padding=1)
+ *   (+ folded BatchNorm2d) (+ ReLU: desc->relu): the up-convolutions of UnetSkipConnectionBlock (p2p_networks.py:205-221, :236).  in_b = -1: one input (the
+ *   innermost block).  desc->in_relu: ReLU applied to in_a as it is read (in_b is read as stored).  desc->cin = cin_a + cin_b; weight [cin_a + cin_b][cout][4][4].
+ *   out_f32_nchw = 0: internal output tensor of 2H x 2W (cout % 8 == 0, act 0); 1: external fp32 NCHW output with `act`.  Precision modes f16 and f16x3; no
+ *   residual, no LeakyReLU, no dilation.  In f16, layers with cin_a % 64 == 0, cin_b % 64 == 0, cout % 64 == 0 and an internal output run as ONE launch of
+ *   conv4x4t_halo.hip, which reads both inputs itself; everything else (and everything with GDT_CONV4X4T_HALO=0) runs as a copy that writes the
+ *   concatenation (+ ReLU) once and the four sub-pixel phases of 2 x 2 taps on the generic implicit-GEMM kernels (GDT_PLAN_CONV4X4T_LAUNCHES).
+ *
+ * Conv of a concatenation (in_b >= 0 otherwise): nn.Conv2d(cin_a + cin_b, cout, k, stride, padding) (+ folded BatchNorm2d) (+ ReLU): the
+ *   nn.Conv2d(128, 64, 3, padding=1) that AlignedP2pUNet applies to the output [x, nested(x)] of its inner SkipConnBlock (unet.py, AlignedP2pUNet.__init__ /
+ *   P2pUNet.SkipConnBlock.forward).  desc->cin = cin_a + cin_b (each % 8 == 0), desc->transposed and pad_reflect must be 0, no dilation, no residual, no
+ *   LeakyReLU; weight [cout][cin_a + cin_b][kh][kw]; desc->out_f32_nchw as on the one-input route.  Precision modes f16 and f16x3.  In f16, k3 / stride 1 /
+ *   pad 1 layers with cin_a % 64 == 0, cin_b % 64 == 0, cout % 64 == 0 and an internal output run as ONE launch of conv3x3_cat_halo.hip, which reads both
+ *   inputs itself, where that measured faster (cout <= 128, cin_a + cin_b no power of two, or few patches; GDT_CONV3X3_CAT_HALO=2: every such layer);
+ *   everything else (and everything with GDT_CONV3X3_CAT_HALO=0) runs as a copy that writes the concatenation once and the conv of one tensor
+ *   (GDT_PLAN_CONV3X3_CAT_LAUNCHES).
+ *
+ * One input (everything else): Conv2d, or ConvTranspose2d(k3, s2, p1, output_padding 1).  desc->in_relu must be 0.
+ *   desc->dilation > 1: Conv2d(cin, cout, k, stride, padding = desc->pad, dilation) + bias (+ ReLU), internal output: RCF conv5_1-5_3
+ *     (nn.Conv2d(512, 512, 3, padding=2, dilation=2), rcf.py:40-42).  transposed, pad_reflect and out_f32_nchw must be 0; no BatchNorm, no residual, no
+ *     LeakyReLU.  Tap t reads input offset (t / kw * dilation - pad, t % kw * dilation - pad): the generic implicit-GEMM kernels run it (conv_igemm /
+ *     conv_igemm_rb, conv_igemm_x3 in the split modes); the 3x3 patch kernels, which stage a one-pixel halo, and every fused form of the planner are not
+ *     taken (GDT_PLAN_DILATED_CONVS, GDT_PLAN_DILATED_SPECIAL_FORMS).
+ *   desc->leaky != 0: Conv2d + bias (+ folded BatchNorm2d) + nn.LeakyReLU(slope): the convs of NLayerDiscriminator (nn.Conv2d(.., kernel_size=4,
+ *     stride=2 | 1, padding=1) .. nn.LeakyReLU(0.2, True), p2p_networks.py:533, :543-547, :557-561).  The activation is applied in the epilogue after bias
+ *     and BN.  relu, transposed and out_f32_nchw must be 0; no residual; precision modes f16 and f16x3.  k4 / pad 1 layers with cin % 64 == 0 run on
+ *     conv4x4_halo.hip (f16; none with GDT_CONV4X4_HALO=0), everything else on the generic implicit-GEMM kernels. */
+int gdt_net_conv(gdt_net* net, int in_a, int in_b, const gdt_conv_desc* desc, const gdt_conv_weights* weights, int residual_tensor, int* out_tensor);
 
-/* nn.MaxPool2d(kernel, stride, padding), floor mode */
-int gdt_net_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int* out_tensor);
-/* nn.MaxPool2d(kernel, stride, ceil_mode=True), no padding (RCF pool1-3: (2, 2), pool4: (2, 1); rcf.py:43-46): torch's output size -- ceil, then one
- * less when the last window would start outside the input; a window that hangs over the edge takes the maximum of its pixels inside.  Fused into
- * its producer's epilogue only where the result equals floor mode (2 x 2, stride 2, even sizes). */
-int gdt_net_maxpool_ceil(gdt_net* net, int in_tensor, int kernel, int stride, int* out_tensor);
+/* nn.InstanceNorm2d(affine=False, eps) (+ fused ReLU) (+ fused residual add AFTER the norm): p2p_networks.py:29,:272,:505.
+ * leaky != 0: + nn.LeakyReLU(leaky) instead, slope in (0, 1), no ReLU and no residual: norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True) of
+ * NLayerDiscriminator (p2p_networks.py:545-546, :559-560).  Always its own statistics and apply passes: neither its producer nor its consumer takes part of it. */
+int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, float leaky, int residual_tensor, int* out_tensor);
+
+/* nn.MaxPool2d(kernel, stride, padding), floor mode; ceil_mode = 1: nn.MaxPool2d(kernel, stride, ceil_mode=True), pad must be 0 (RCF pool1-3: (2, 2), pool4:
+ * (2, 1); rcf.py:43-46): torch's output size -- ceil, then one less when the last window would start outside the input; a window that hangs over the edge
+ * takes the maximum of its pixels inside.  Fused into its producer's epilogue only where the result equals floor mode (2 x 2, stride 2, even sizes). */
+int gdt_net_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int ceil_mode, int* out_tensor);
 
 /* l2n(gem(x, p, eps_gem), eps_l2): cirtorch layers/functional.py:21-22,:130-131.  External output: fp32 [N][D]
  * row-major, i.e. the memory the reference's `o.permute(1,0)` view aliases (imageretrievalnet.py:123). */
@@ -154,17 +155,21 @@ int gdt_net_gem_l2n(gdt_net* net, int in_tensor, float p, float eps_gem, float e
  *   fw / fb    the final whitening (nn.Linear) with its l2n, NULL: none.  eps_l2: the eps of every l2n (x / (||x|| + eps)).
  * levels: 1..3 (cirtorch's L = 3).  The regions of a map size are those of gdt_rpool_regions.  All regions are pooled in ONE pass over the map; the
  * number of launches depends on the layers present, never on the batch or the number of regions; the whitening layers run in fp32 in every
- * precision mode.  External output: fp32 [N][D] row-major, as gdt_net_gem_l2n. */
-int gdt_net_pool_head(gdt_net* net, int in_tensor, int kind, const float* p, int n_p, float eps, int aggregate, int levels, const float* rw,
-                      const float* rb, const float* fw, const float* fb, float eps_l2, int* out_slot);
-/* The head of CirRetrievalNetAttention.forward (mdir/components/model/network/cirnet.py:116-125): pool(x * att) -> l2n, where att is one weight per
- * position of the map.  attention 1: L2NormAttention (mdir/components/model/layers/attention.py:4-15), att = sqrt(sum_c x_c^2 + 1e-10), divided by its
- * maximum over the IMAGE when normalize_max (the reference's forward only works on a batch of one; a batch here is that forward per image).  The other
- * arguments as in gdt_net_pool_head; there is no final whitening (the reference asserts its absence), a regional pooling keeps its own.  The weights
- * are computed in one pass over the map (+ one pass over the weights when normalize_max) and folded into the one pooling pass as an fp32 multiply in
- * front of GeM's clamp and power: the head reads the map twice, whatever the batch and the number of regions (gdt_net_plan_summary counts [17], [18]). */
-int gdt_net_pool_head_attention(gdt_net* net, int in_tensor, int kind, const float* p, int n_p, float eps, int aggregate, int levels, const float* rw,
-                                const float* rb, float eps_l2, int attention, int normalize_max, int* out_slot);
+ * precision mode.  External output: fp32 [N][D] row-major, as gdt_net_gem_l2n.
+ *   attention  0: none.  1: the head of CirRetrievalNetAttention.forward (mdir/components/model/network/cirnet.py:116-125): pool(x * att) -> l2n, where att
+ * is one weight per position of the map: L2NormAttention (mdir/components/model/layers/attention.py:4-15), att = sqrt(sum_c x_c^2 + 1e-10), divided by its
+ * maximum over the IMAGE when normalize_max (0 or 1; the reference's forward only works on a batch of one; a batch here is that forward per image).  There
+ * is no final whitening then (fw must be NULL: the reference asserts its absence), a regional pooling keeps its own.  The weights are computed in one pass
+ * over the map (+ one pass over the weights when normalize_max) and folded into the one pooling pass as an fp32 multiply in front of GeM's clamp and power:
+ * the head reads the map twice, whatever the batch and the number of regions (GDT_PLAN_ATTENTION_LAUNCHES, GDT_PLAN_ATTENTION_MAP_READS). */
+typedef struct gdt_pool_head_desc {
+    int kind; const float* p; int n_p; float eps;
+    int aggregate, levels;
+    const float* rw; const float* rb; const float* fw; const float* fb;
+    float eps_l2;
+    int attention, normalize_max;
+} gdt_pool_head_desc;
+int gdt_net_pool_head(gdt_net* net, int in_tensor, const gdt_pool_head_desc* desc, int* out_slot);
 
 /* Feature tap: internal fp16 NHWC tensor -> external fp32 NCHW (+ optional per-channel bias), p2p_networks.py:316-334 */
 int gdt_net_output_nchw(gdt_net* net, int in_tensor, const float* bias, int* out_slot);
@@ -236,19 +241,39 @@ int gdt_net_levels_joined(gdt_net* net, int* level_launches);
  * the numerator of bench.py's roofline.achieved. */
 int gdt_net_flops(gdt_net* net, int n, int rh, int rw, double* flops);
 
-/* The planner's decisions for a geometry as counts (host logic only, no device call): counts[0] conv launches (a fused launch counts once), [1] whole Bottlenecks in one
- * launch, [2] 3x3 + expand launches, [3] of those with the next block's reduce conv chained in, [4] projection shortcuts folded into their expand conv, [5] InstanceNorms
- * applied by their consumer's staging, [6] max-pools written by their producer, [7] 1 if the stem reads the caller's image itself (resize = 0 only), [8] transposed convs as
- * one fused-phase launch, [9] stride-2 convs as the shift form.  n_counts >= 10; with n_counts >= 12 also [10] dilated convs (gdt_net_conv_dilated) and
- * [11] of those on any special form (a patch kernel, a fused launch): 0 -- dilation runs on the generic implicit-GEMM kernels only; with n_counts >= 14 also
- * [12] the launches of the pool-head ops (gdt_net_pool_head: fixed by the layers present, whatever the batch and the number of regions) and [13] those
- * among them that read the feature map (one per op); with n_counts >= 15 also [14] the conv launches that run on the 4x4 patch kernel (conv4x4_halo.hip;
- * none with GDT_CONV4X4_HALO=0); with n_counts >= 16 also [15] the transposed 4x4 convs (gdt_net_conv_transposed4) that run as one launch of
- * conv4x4t_halo.hip (none with GDT_CONV4X4T_HALO=0); with n_counts >= 17 also [16] the convs of a concatenation (gdt_net_conv_cat) that run as one launch of
- * conv3x3_cat_halo.hip (none with GDT_CONV3X3_CAT_HALO=0); with n_counts >= 19 also [17] the launches the attention of gdt_net_pool_head_attention adds in
- * front of the pooling (the norm pass, and the division by the maximum when normalize_max) and [18] the launches of such heads that read the feature map (two per
- * op: the norm pass and the weighted pooling pass) -- [12] and [13] count an attention head's launches behind the weights as for any head.
- * (Diagnostics / tests; no reference counterpart.) */
+/* The planner's decisions for a geometry as counts (host logic only, no device call; diagnostics / tests; no reference counterpart). */
+enum {
+    GDT_PLAN_CONV_LAUNCHES,          /* "conv_launches": launches of conv ops (a fused launch counts once)                                            */
+    GDT_PLAN_BOTTLENECKS_FUSED,      /* "bottlenecks_fused": whole Bottlenecks in one launch (conv_bneck.hip)                                         */
+    GDT_PLAN_CONV3X3_EXPAND,         /* "conv3x3_expand": 3x3 + expand launches (conv3x3_expand_rb.hip)                                               */
+    GDT_PLAN_CHAINED_REDUCE,         /* "chained_reduce": of those, with the next block's reduce conv chained in                                      */
+    GDT_PLAN_SHORTCUTS_FOLDED,       /* "shortcuts_folded": projection shortcuts folded into their expand conv (K-concatenated 1x1)                   */
+    GDT_PLAN_NORMS_FOLDED,           /* "norms_folded": InstanceNorms applied by their consumer's staging                                             */
+    GDT_PLAN_POOLS_FUSED,            /* "pools_fused": max-pools written by their producer                                                            */
+    GDT_PLAN_DIRECT_STEM,            /* "direct_stem": 1 if the stem reads the caller's image itself (resize = 0 only)                                */
+    GDT_PLAN_TRANSPOSED_FUSED,       /* "transposed_fused": transposed convs as one fused-phase launch                                                */
+    GDT_PLAN_STRIDE2_SHIFT,          /* "stride2_shift": stride-2 convs as the shift form                                                             */
+    GDT_PLAN_DILATED_CONVS,          /* "dilated_convs": convs with desc->dilation > 1                                                                */
+    GDT_PLAN_DILATED_SPECIAL_FORMS,  /* "dilated_special_forms": of those on any special form (a patch kernel, a fused launch): 0 -- dilation runs on
+                                        the generic implicit-GEMM kernels only                                                                        */
+    GDT_PLAN_HEAD_LAUNCHES,          /* "head_launches": launches of the pool-head ops (gdt_net_pool_head: fixed by the layers present, whatever the
+                                        batch and the number of regions); an attention head's launches behind the weights count as for any head      */
+    GDT_PLAN_HEAD_MAP_READS,         /* "head_map_reads": those among them that read the feature map (one per op)                                     */
+    GDT_PLAN_CONV4X4_LAUNCHES,       /* "conv4x4_launches": conv launches that run on the 4x4 patch kernel (conv4x4_halo.hip: what gdt_launch_conv
+                                        decides for the conv as its own plain launch; none with GDT_CONV4X4_HALO=0)                                  */
+    GDT_PLAN_CONV4X4T_LAUNCHES,      /* "conv4x4t_launches": transposed 4x4 convs that run as one launch of conv4x4t_halo.hip, the concatenation in
+                                        front never written (none with GDT_CONV4X4T_HALO=0 -- then four phase launches each)                         */
+    GDT_PLAN_CONV3X3_CAT_LAUNCHES,   /* "conv3x3_cat_launches": convs of a concatenation that run as one launch of conv3x3_cat_halo.hip (none with
+                                        GDT_CONV3X3_CAT_HALO=0 -- then a copy + the conv of one tensor)                                              */
+    GDT_PLAN_ATTENTION_LAUNCHES,     /* "attention_launches": launches the attention of a pool head adds in front of the pooling (the norm pass, and
+                                        the division by the maximum when normalize_max)                                                              */
+    GDT_PLAN_ATTENTION_MAP_READS,    /* "attention_map_reads": launches of such heads that read the feature map (two per op: the norm pass and the
+                                        weighted pooling pass)                                                                                        */
+    GDT_PLAN_COUNT
+};
+/* name of counter `index` (the quoted names above), NULL past the last index and for negative ones */
+const char* gdt_plan_count_name(int index);
+/* fills counts[0 .. GDT_PLAN_COUNT); n_counts >= GDT_PLAN_COUNT */
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts);
 
 /* Per-op timing for bench.py's roofline line: when enabled, gdt_net_forward records HIP events on the caller's stream

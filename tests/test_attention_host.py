@@ -222,7 +222,11 @@ def test_other_embedders_count_no_attention_and_plan_as_before():
             net.gem_l2n(f, 3.0)
         assert net.attention_launches(2, 512, 512) == (0, 0) and net.head_launches(2, 512, 512) == ((3, 1) if with_head else (0, 0))
         if not with_head:                                            # the figures tests/test_hip_descriptor_heads.py pins for the plain GeM embedder
-            assert tuple(net.plan_summary(1, 512, 512).values()) == (13, 0, 0, 0, 0, 0, 4, 1, 0, 0, 0, 0)
+            plan = net.plan_summary(1, 512, 512)
+            pinned = dict(conv_launches=13, bottlenecks_fused=0, conv3x3_expand=0, chained_reduce=0, shortcuts_folded=0, norms_folded=0, pools_fused=4,
+                          direct_stem=1, transposed_fused=0, stride2_shift=0, dilated_convs=0, dilated_special_forms=0)
+            assert {k: plan[k] for k in pinned} == pinned
+            assert all(v == 0 for k, v in plan.items() if k not in pinned), plan            # every other counter
             assert net.workspace_bytes(1, 512, 512) == 46137600
 
 
@@ -261,13 +265,14 @@ def test_builder_argument_validation():
     f = net.conv(x, sd["features.0.weight"].sum(dim=1, keepdim=True), sd["features.0.bias"], pad=1, relu=True)
     lib, out = net.lib, ctypes.c_int()
     one = (ctypes.c_float * 1)(3.0)
-    for args in ((f, 2, one, 1, 1e-6, 0, 3, None, None, 1e-6, 2, 0),       # unknown attention
-                 (f, 2, one, 1, 1e-6, 0, 3, None, None, 1e-6, 1, 2),       # normalize_max
-                 (f, 2, None, 0, 1e-6, 0, 3, None, None, 1e-6, 1, 0),      # GeM without its exponent
-                 (99, 0, None, 0, 1e-6, 0, 3, None, None, 1e-6, 1, 0)):    # tensor id
+    pone = ctypes.cast(one, ctypes.c_void_p)
+    for t, args in ((f, (2, pone, 1, 1e-6, 0, 3, None, None, None, None, 1e-6, 2, 0)),       # unknown attention
+                    (f, (2, pone, 1, 1e-6, 0, 3, None, None, None, None, 1e-6, 1, 2)),       # normalize_max
+                    (f, (2, None, 0, 1e-6, 0, 3, None, None, None, None, 1e-6, 1, 0)),       # GeM without its exponent
+                    (99, (0, None, 0, 1e-6, 0, 3, None, None, None, None, 1e-6, 1, 0))):     # tensor id
         ops = lib.gdt_net_num_ops(net.handle)
         with pytest.raises(ValueError):
-            _hip.check(lib.gdt_net_pool_head_attention(net.handle, *args, ctypes.byref(out)))
+            _hip.check(lib.gdt_net_pool_head(net.handle, t, ctypes.byref(_hip.PoolHeadDesc(*args)), ctypes.byref(out)))
         assert lib.gdt_net_num_ops(net.handle) == ops                  # a refused head leaves nothing in the graph
     bytes_ = ctypes.c_size_t()
     with pytest.raises(ValueError):

@@ -1,6 +1,6 @@
 """The normalisation U-Nets (p2p_unet, outconv_unet, inconv_p2p_unet, aligned_p2p_unet, shallow_p2p_unet) on the host: the registry and the ``mdir`` alias, the
 module trees against the reference's key lists and shapes, the CPU forward against the reference's output (tests/golden/p2p_unet.npz), the ``meta`` dicts, what
-the device path refuses before it needs a device, and the argument validation of gdt_net_conv_cat.  No GPU."""
+the device path refuses before it needs a device, and the argument validation of gdt_net_conv with two inputs.  No GPU."""
 import ctypes
 import os
 
@@ -138,8 +138,7 @@ def test_device_path_rejections_that_need_no_device():
 
 
 def test_conv_cat_validates_its_arguments_without_a_gpu():
-    """gdt_net_conv_cat: unknown tensor id, transposed / reflect-padded descriptor (the descriptor has no dilation field: a conv of a concatenation is never
-    dilated), channel mismatch with the weight -- ValueError before any HIP call; a refused layer leaves nothing in the graph"""
+    """gdt_net_conv with two inputs: unknown tensor id, transposed / reflect-padded descriptor, channel mismatch with the weight -- ValueError before any HIP call; a refused layer leaves nothing in the graph"""
     net = engine.HipNet(DEV)
     t = net.input(3)
     a = net.conv(t, synth._normal(0, "wa", (64, 3, 1, 1)))
@@ -160,10 +159,10 @@ def test_conv_cat_validates_its_arguments_without_a_gpu():
         fields.update(bad)
         d = _hip.ConvDesc(**fields)
         with pytest.raises(ValueError):
-            _hip.check(net.lib.gdt_net_conv_cat(net.handle, a, b, ctypes.byref(d), wn.ctypes.data_as(ctypes.c_void_p), None, None, None, None, None, ctypes.byref(out)))
+            _hip.check(net.lib.gdt_net_conv(net.handle, a, b, ctypes.byref(d), ctypes.byref(_hip.ConvWeights(wn.ctypes.data)), -1, ctypes.byref(out)))
     with pytest.raises(ValueError):                                              # BatchNorm vectors come all four or none
-        _hip.check(net.lib.gdt_net_conv_cat(net.handle, a, b, ctypes.byref(_hip.ConvDesc(192, 64, 3, 3, 1, 1, 0, 0, 0, 0, 0, 1e-5)),
-                                            wn.ctypes.data_as(ctypes.c_void_p), None, wn.ctypes.data_as(ctypes.c_void_p), None, None, None, ctypes.byref(out)))
+        _hip.check(net.lib.gdt_net_conv(net.handle, a, b, ctypes.byref(_hip.ConvDesc(192, 64, 3, 3, 1, 1, 0, 0, 0, 0, 0, 1e-5)),
+                                        ctypes.byref(_hip.ConvWeights(wn.ctypes.data, None, wn.ctypes.data)), -1, ctypes.byref(out)))
     ops = net.lib.gdt_net_num_ops(net.handle)
     y = net.conv_cat(a, b, w, pad=1, relu=True)
     assert net.lib.gdt_net_num_ops(net.handle) == ops + 2                        # the copy op of the generic route + the conv
@@ -216,3 +215,53 @@ def test_conv_cat_knob_is_read_at_every_query(monkeypatch):
     assert net.conv3x3_cat_launches(2, 10, 14) == 0
     assert net.workspace_bytes(2, 10, 14) == ws
     assert "GDT_CONV3X3_CAT_HALO" not in _hip.plan_knobs()
+
+
+def test_conv_refuses_what_the_routes_do_not_combine():
+    """gdt_net_conv, gdt_net_maxpool, gdt_net_pool_head: combinations of descriptor fields no route takes -- ValueError, nothing added to the graph"""
+    net = engine.HipNet(DEV)
+    t = net.input(3)
+    a = net.conv(t, synth._normal(0, "wa", (64, 3, 1, 1)))
+    b = net.conv(t, synth._normal(0, "wb", (128, 3, 1, 1)))
+    lib, out = net.lib, ctypes.c_int()
+    ones = np.ones(64 * 64, np.float32)
+    bn = [ones.ctypes.data] * 4
+
+    def conv(in_b, weight_shape, residual=-1, bn=(), **fields):
+        w = np.zeros(weight_shape, np.float32)
+        transposed = fields.get("transposed", 0)
+        d = _hip.ConvDesc(cin=w.shape[0 if transposed else 1], cout=w.shape[1 if transposed else 0], kh=w.shape[2], kw=w.shape[3], bn_eps=1e-5,
+                          **dict(dict(stride=1, pad=1), **fields))
+        return lib.gdt_net_conv(net.handle, a, in_b, ctypes.byref(d), ctypes.byref(_hip.ConvWeights(w.ctypes.data, None, *bn)), residual, ctypes.byref(out))
+
+    one = ctypes.cast((ctypes.c_float * 1)(3.0), ctypes.c_void_p)
+    white = ones.ctypes.data
+    refused = {
+        "dilation + second input": lambda: conv(b, (64, 192, 3, 3), pad=2, dilation=2),
+        "dilation + leaky": lambda: conv(-1, (64, 64, 3, 3), pad=2, dilation=2, leaky=0.2),
+        "dilation + BatchNorm": lambda: conv(-1, (64, 64, 3, 3), bn=bn, pad=2, dilation=2),
+        "dilation + residual": lambda: conv(-1, (64, 64, 3, 3), residual=a, pad=2, dilation=2),
+        "leaky + transposed": lambda: conv(-1, (64, 64, 3, 3), stride=2, transposed=1, leaky=0.2),
+        "leaky + transposed 4x4": lambda: conv(-1, (64, 64, 4, 4), stride=2, transposed=1, leaky=0.2),
+        "leaky + second input": lambda: conv(b, (64, 192, 3, 3), leaky=0.2),
+        "in_relu on a conv": lambda: conv(-1, (64, 64, 3, 3), in_relu=1),
+        "in_relu on a conv of two": lambda: conv(b, (64, 192, 3, 3), in_relu=1),
+        "in_relu on a transposed 3x3": lambda: conv(-1, (64, 64, 3, 3), stride=2, transposed=1, in_relu=1),
+        "residual + second input": lambda: conv(b, (64, 192, 3, 3), residual=a),
+        "residual + transposed 4x4 of two": lambda: conv(b, (192, 64, 4, 4), residual=a, stride=2, transposed=1),
+        "transposed 4x4: cin is not the inputs' sum": lambda: conv(b, (128, 64, 4, 4), stride=2, transposed=1),
+        "ceil pool + padding": lambda: lib.gdt_net_maxpool(net.handle, a, 3, 2, 1, 1, ctypes.byref(out)),
+        "attention + final whitening": lambda: lib.gdt_net_pool_head(net.handle, a, ctypes.byref(
+            _hip.PoolHeadDesc(2, one, 1, 1e-6, 0, 3, None, None, white, white, 1e-6, 1, 0)), ctypes.byref(out)),
+    }
+    ops = lib.gdt_net_num_ops(net.handle)
+    for what, call in refused.items():
+        with pytest.raises(ValueError):
+            _hip.check(call())
+            pytest.fail("accepted: " + what)
+        assert lib.gdt_net_num_ops(net.handle) == ops, what
+    # ... and each of them is accepted without the offending field
+    assert conv(-1, (64, 64, 3, 3), pad=2, dilation=2) == 0 and conv(-1, (64, 64, 3, 3), leaky=0.2) == 0 and conv(-1, (64, 64, 3, 3), residual=a, bn=bn) == 0
+    assert conv(b, (192, 64, 4, 4), stride=2, transposed=1, in_relu=1) == 0 and conv(b, (64, 192, 3, 3)) == 0
+    assert lib.gdt_net_maxpool(net.handle, a, 3, 2, 0, 1, ctypes.byref(out)) == 0
+    assert lib.gdt_net_pool_head(net.handle, a, ctypes.byref(_hip.PoolHeadDesc(2, one, 1, 1e-6, 0, 3, None, None, None, None, 1e-6, 1, 0)), ctypes.byref(out)) == 0

@@ -100,20 +100,22 @@ def test_c_entries_validate_arguments_without_gpu():
         _hip.check(lib.gdt_net_input(h, 3, None, None, None, ctypes.byref(out)))
         x = out.value
         w = np.zeros((64, 3, 3, 3), np.float32)
-        d = _hip.ConvDesc(3, 64, 3, 3, 1, 2, 0, 0, 1, 0, 0, 1e-5)
-        wp = w.ctypes.data_as(ctypes.c_void_p)
+        d = _hip.ConvDesc(3, 64, 3, 3, 1, 2, 0, 0, 1, 0, 0, 1e-5, dilation=2)
+        wts = _hip.ConvWeights(w.ctypes.data_as(ctypes.c_void_p))
+
+        def conv(in_tensor, desc):
+            return lib.gdt_net_conv(h, in_tensor, -1, ctypes.byref(desc), ctypes.byref(wts), -1, ctypes.byref(out))
         with pytest.raises(ValueError):
-            _hip.check(lib.gdt_net_conv_dilated(h, 99, ctypes.byref(d), 2, wp, None, ctypes.byref(out)))       # unknown tensor id
+            _hip.check(conv(99, d))                                                                             # unknown tensor id
         with pytest.raises(ValueError):
-            _hip.check(lib.gdt_net_conv_dilated(h, x, ctypes.byref(d), 0, wp, None, ctypes.byref(out)))        # dilation < 1
-        dt = _hip.ConvDesc(3, 64, 3, 3, 2, 1, 0, 1, 0, 0, 0, 1e-5)
+            _hip.check(conv(x, _hip.ConvDesc(3, 64, 3, 3, 1, 2, 0, 0, 1, 0, 0, 1e-5, dilation=0)))              # dilation < 1
         with pytest.raises(ValueError):
-            _hip.check(lib.gdt_net_conv_dilated(h, x, ctypes.byref(dt), 2, wp, None, ctypes.byref(out)))       # transposed + dilation
+            _hip.check(conv(x, _hip.ConvDesc(3, 64, 3, 3, 2, 1, 0, 1, 0, 0, 0, 1e-5, dilation=2)))              # transposed + dilation
         with pytest.raises(ValueError):
-            _hip.check(lib.gdt_net_maxpool_ceil(h, 99, 2, 2, ctypes.byref(out)))                               # unknown tensor id
+            _hip.check(lib.gdt_net_maxpool(h, 99, 2, 2, 0, 1, ctypes.byref(out)))                               # ceil mode: unknown tensor id
         with pytest.raises(ValueError):
-            _hip.check(lib.gdt_net_maxpool_ceil(h, x, 2, 0, ctypes.byref(out)))                                # stride 0
-        _hip.check(lib.gdt_net_conv_dilated(h, x, ctypes.byref(d), 2, wp, None, ctypes.byref(out)))
+            _hip.check(lib.gdt_net_maxpool(h, x, 2, 0, 0, 1, ctypes.byref(out)))                                # ceil mode: stride 0
+        _hip.check(conv(x, d))
         f = out.value
         side = np.zeros(64, np.float32)
         sw = (ctypes.c_void_p * 13)(*[side.ctypes.data] * 13)
@@ -139,6 +141,21 @@ def test_c_entries_validate_arguments_without_gpu():
         engine.build_rcf(synth.rcf_state(0), DEV, finalize=False).rcf_head([1] * 12, [0] * 12, [side] * 12, [0.0] * 5, [0.0] * 5, 0.0)   # 12 features
 
 
+def test_conv_desc_defaults_to_no_dilation():
+    """the twelve-field construction means "no dilation"; an explicit dilation of 0 reaches the library, which refuses it"""
+    from gandtr_amd import _hip
+    d = _hip.ConvDesc(3, 64, 3, 3, 1, 1, 0, 0, 1, 0, 0, 1e-5)
+    assert d.dilation == 1 and d.leaky == 0.0 and d.in_relu == 0
+    assert _hip.ConvDesc(3, 64, 3, 3, 1, 1, 0, 0, 1, 0, 0, 1e-5, dilation=0).dilation == 0
+    net = engine.HipNet(DEV)
+    x = net.input(3)
+    ops = net.lib.gdt_net_num_ops(net.handle)
+    with pytest.raises(ValueError):
+        net.conv(x, torch.zeros(64, 3, 3, 3), pad=1, dilation=0)
+    assert net.lib.gdt_net_num_ops(net.handle) == ops
+    net.conv(x, torch.zeros(64, 3, 3, 3), pad=1)
+
+
 def test_planner_keeps_dilated_convs_and_side_tensors_plain():
     """Every dilated conv runs on a generic implicit-GEMM kernel (no patch kernel stages a 2-pixel halo), and no pool is fused into its producer:
     every pre-pool tensor (conv1_2, conv2_2, conv3_3, conv4_3) also feeds the side output; HED's 4 pools are not fused for the same reason."""
@@ -156,7 +173,7 @@ def test_planner_keeps_dilated_convs_and_side_tensors_plain():
 
 
 def test_ceil_pool_shapes_follow_torch():
-    """gdt_net_maxpool_ceil: torch's ceil_mode output size, odd and even, stride 2 and 1; floor mode unchanged"""
+    """gdt_net_maxpool with ceil_mode: torch's ceil_mode output size, odd and even, stride 2 and 1; floor mode unchanged"""
     for k, s in ((2, 2), (2, 1), (3, 2)):
         for hw in ((7, 10), (8, 9), (3, 4), (33, 31)):
             net = engine.HipNet(DEV)

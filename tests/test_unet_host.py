@@ -152,15 +152,21 @@ def test_c_abi_adder_validates_without_a_device():
     _hip.check(lib.gdt_net_create(ctypes.byref(h)))
     _hip.check(lib.gdt_net_input(h, 3, None, None, None, ctypes.byref(out)))
     w = np.zeros((8, 8, 4, 4), np.float32)
+    wts = _hip.ConvWeights(w.ctypes.data)
+
+    def t4(in_b, relu, act, res):
+        d = _hip.ConvDesc(3, 8, 4, 4, 2, 1, 0, 1, relu, 0, act, 1e-5)          # cin: the channels of the input (the weight's first three rows are read)
+        return lib.gdt_net_conv(h, out.value, in_b, ctypes.byref(d), ctypes.byref(wts), -1, ctypes.byref(res))
     with pytest.raises(ValueError):               # unknown second input
-        _hip.check(lib.gdt_net_conv_transposed4(h, out.value, 7, 0, 8, w.ctypes.data, None, None, None, None, None, 1e-5, 0, 0, 0, ctypes.byref(out)))
+        _hip.check(t4(7, 0, 0, out))
     with pytest.raises(ValueError):               # an internal output takes no tanh
-        _hip.check(lib.gdt_net_conv_transposed4(h, out.value, -1, 0, 8, w.ctypes.data, None, None, None, None, None, 1e-5, 0, 0, 1, ctypes.byref(out)))
+        _hip.check(t4(-1, 0, 1, out))
     t = ctypes.c_int()
-    _hip.check(lib.gdt_net_conv_transposed4(h, out.value, -1, 0, 8, w.ctypes.data, None, None, None, None, None, 1e-5, 1, 0, 0, ctypes.byref(t)))
-    counts = (ctypes.c_int * 16)()
-    _hip.check(lib.gdt_net_plan_summary(h, 1, 8, 8, 0, counts, 16))
-    assert counts[0] == 1 and counts[15] == 0     # 8 channels: the generic route
+    _hip.check(t4(-1, 1, 0, t))
+    names = _hip.plan_count_names()
+    counts = (ctypes.c_int * len(names))()
+    _hip.check(lib.gdt_net_plan_summary(h, 1, 8, 8, 0, counts, len(names)))
+    assert counts[names.index("conv_launches")] == 1 and counts[names.index("conv4x4t_launches")] == 0     # 8 channels: the generic route
     lib.gdt_net_destroy(h)
 
 
