@@ -5,7 +5,7 @@ fallback: if the library is missing the HIP path raises -- a CUDA/HIP device req
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_void_p
 
 _LIB_PATH = os.environ.get("GANDTR_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgandtr_hip.so")
 _lib = None
@@ -138,6 +138,10 @@ SIGNATURES = {
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gdt_retrieval_diverse_anchors_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "gdt_retrieval_diverse_anchors": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gdt_retrieval_topk_workspace_bytes": (c_int, [c_long, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "gdt_retrieval_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_long, c_int, c_void_p, c_size_t,
+                                   c_void_p]),
+    "gdt_retrieval_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "gdt_tuple_loss_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
     "gdt_tuple_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_size_t, c_void_p]),

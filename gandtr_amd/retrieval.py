@@ -191,6 +191,107 @@ def sharded_topk(vecs_local, qvecs, k, group=None):
     return torch.gather(flat_s, 1, order).t(), torch.gather(flat_i, 1, order.long()).t()
 
 
+# ---- streaming top-k, query expansion and database augmentation (gandtr_amd/csrc/retrieval_topk.hip)
+
+def _on_one_device(name, *tensors):
+    if not all(torch.is_tensor(t) and t.is_cuda for t in tensors) or any(t.device != tensors[0].device for t in tensors):
+        raise ValueError("%s needs descriptors on one HIP device" % name)
+
+
+def _topk_rows(v, q, k, index_base=0, self_base=-1, slices=0):
+    """gdt_retrieval_topk on contiguous fp32 rows: v [Ndb][D], q [Nq][D] -> (scores [Nq][k] fp32, ids [Nq][k] int32).  slices = 0: the library's choice."""
+    lib = _hip.load()
+    ndb, d = v.shape
+    nq = q.shape[0]
+    need = ctypes.c_size_t()
+    _hip.check(lib.gdt_retrieval_topk_workspace_bytes(ndb, nq, d, int(k), int(slices), ctypes.byref(need)))
+    with torch.cuda.device(v.device):
+        ws = torch.empty(need.value, dtype=torch.uint8, device=v.device)
+        scores = torch.empty((nq, int(k)), dtype=torch.float32, device=v.device)
+        ids = torch.empty((nq, int(k)), dtype=torch.int32, device=v.device)
+        _hip.check(lib.gdt_retrieval_topk(v.data_ptr(), q.data_ptr(), ids.data_ptr(), scores.data_ptr(), ndb, nq, d, int(k), int(index_base),
+                                          int(self_base), int(slices), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(v.device).cuda_stream))
+    return scores, ids
+
+
+def _expand_rows(v, base, ids, scores, alpha, index_base=0):
+    """gdt_retrieval_expand on contiguous rows: v [Ndb][D], base [Nq][D] or None, ids / scores [Nq][k] -> [Nq][D] unit rows."""
+    lib = _hip.load()
+    ndb, d = v.shape
+    nq, k = ids.shape
+    ids, scores = ids.contiguous(), scores.contiguous()
+    with torch.cuda.device(v.device):
+        out = torch.empty((nq, d), dtype=torch.float32, device=v.device)
+        _hip.check(lib.gdt_retrieval_expand(v.data_ptr(), base.data_ptr() if base is not None else None, ids.data_ptr(), scores.data_ptr(),
+                                            out.data_ptr(), ndb, nq, d, k, int(index_base), float(alpha),
+                                            torch.cuda.current_stream(v.device).cuda_stream))
+    return out
+
+
+def _same_set(vecs, qvecs):
+    if vecs is qvecs:
+        return True
+    return vecs.shape == qvecs.shape and vecs.device == qvecs.device and bool(torch.equal(vecs, qvecs))
+
+
+def topk(vecs, qvecs, k, index_base=0, exclude_self=False):
+    """Per query the k best database entries without the Ndb x Nq score matrix.  vecs: D x Ndb, qvecs: D x Nq (one HIP device), any D up to
+    8192, no limit on Ndb * Nq, 1 <= k <= 256.  Returns (scores k x Nq fp32, ids k x Nq int32 = index_base + database column), per column in the
+    strict order (score descending, id ascending); with Ndb < k the tail is id -1 / score -inf.  ``exclude_self`` (vecs and qvecs are the same
+    set) leaves column j out of the answer for query j."""
+    if vecs.shape[0] != qvecs.shape[0]:
+        raise ValueError("descriptor sizes differ: %d vs %d" % (vecs.shape[0], qvecs.shape[0]))
+    if exclude_self and not _same_set(vecs, qvecs):
+        raise ValueError("exclude_self needs vecs and qvecs to be the same set")
+    _on_one_device("topk", vecs, qvecs)
+    v = _rows(vecs)
+    scores, ids = _topk_rows(v, v if vecs is qvecs else _rows(qvecs), k, index_base, 0 if exclude_self else -1)
+    return scores.t(), ids.t()
+
+
+def expand_queries(vecs, qvecs, k, alpha=3.0):
+    """alpha-weighted query expansion: every query becomes the renormalised sum of itself and its k best database vectors, each weighted by
+    max(score, 0) ** alpha (alpha = 0: the plain average, AQE).  vecs: D x Ndb, qvecs: D x Nq -> D x Nq unit columns."""
+    if vecs.shape[0] != qvecs.shape[0]:
+        raise ValueError("descriptor sizes differ: %d vs %d" % (vecs.shape[0], qvecs.shape[0]))
+    _on_one_device("expand_queries", vecs, qvecs)
+    v, q = _rows(vecs), _rows(qvecs)
+    scores, ids = _topk_rows(v, q, k)
+    return _expand_rows(v, q, ids, scores, alpha).t()
+
+
+def augment_database(vecs, k, alpha=3.0, block=8192):
+    """Database-side augmentation: every database vector becomes the weighted, renormalised sum of its own k best matches in the database
+    (itself among them, found by the search).  vecs: D x Ndb -> D x Ndb unit columns.  Runs in blocks of ``block`` query columns, so memory
+    stays O(Ndb * D + block * k); the block size does not show in the result."""
+    _on_one_device("augment_database", vecs)
+    if block < 1:
+        raise ValueError("block >= 1")
+    v = _rows(vecs)
+    out = torch.empty_like(v)
+    for b0 in range(0, v.shape[0], int(block)):
+        q = v[b0:b0 + int(block)]
+        scores, ids = _topk_rows(v, q, k)
+        out[b0:b0 + q.shape[0]] = _expand_rows(v, None, ids, scores, alpha)
+    return out.t()
+
+
+def knn_graph(vecs, k, block=8192):
+    """Each vector's k best neighbours other than itself: (scores k x N fp32, ids k x N int32).  ``topk`` with ``exclude_self`` in blocks of
+    ``block`` query columns."""
+    _on_one_device("knn_graph", vecs)
+    if block < 1:
+        raise ValueError("block >= 1")
+    v = _rows(vecs)
+    n = v.shape[0]
+    scores = torch.empty((n, int(k)), dtype=torch.float32, device=v.device)
+    ids = torch.empty((n, int(k)), dtype=torch.int32, device=v.device)
+    for b0 in range(0, n, int(block)):
+        q = v[b0:b0 + int(block)]
+        scores[b0:b0 + q.shape[0]], ids[b0:b0 + q.shape[0]] = _topk_rows(v, q, k, 0, b0)
+    return scores.t(), ids.t()
+
+
 # ---- mAP evaluation (mdir/external/cirtorch/utils/evaluate.py): average precision and precision@k per query
 
 def _id_list(x):

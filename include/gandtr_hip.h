@@ -393,6 +393,27 @@ int gdt_retrieval_average_precision(const int* ranks_t, int ndb, int nq, int nse
 int gdt_retrieval_diverse_anchors_workspace_bytes(int nq, int d, int nsel, size_t* bytes);
 int gdt_retrieval_diverse_anchors(const float* vecs, int nq, int d, const int* target_rank, int nsel, int first_idx, int* out_idx,
                                   float* out_score, void* workspace, size_t workspace_bytes, void* stream);
+/* Streaming top-k: per query the k best database rows, without the nq x ndb score matrix (gandtr_amd/csrc/retrieval_topk.hip).
+ * vecs [ndb][d], qvecs [nq][d]: row-major fp32 rows, 1 <= d <= 8192 of any value (the kernel pads, the caller copies nothing), 1 <= ndb < 2^31,
+ * nq >= 1 with no limit on ndb * nq, 1 <= k <= 256.  Scores are fp32 inner products on f32-input MFMAs (exact products, fp32 accumulation).
+ * ids int32 [nq][k] / scores fp32 [nq][k]: per query the k entries that come first in the strict total order (score descending, row ascending),
+ * in that order; ids hold index_base + row (index_base >= 0); with fewer than k rows the tail is id -1, score -inf.  self_base >= 0 excludes
+ * database row self_base + j for query j (the neighbours other than itself of a kNN graph); -1: none.  Workgroups own (query tile, database
+ * slice) pairs and keep their candidate lists in LDS; a second launch merges the `slices` lists of a query.  slices = 0 lets the library
+ * choose, 1 .. 1024 forces the number: the result is the same bits for every value.  The workspace holds slices lists of k (score, row) pairs
+ * and a count per query, and no operand copy: its size does not depend on ndb.  All buffers are device buffers; arguments are checked
+ * before anything is launched (GDT_ERR_INVALID; GDT_ERR_WORKSPACE for a workspace below gdt_retrieval_topk_workspace_bytes). */
+int gdt_retrieval_topk_workspace_bytes(long ndb, int nq, int d, int k, int slices, size_t* bytes);
+int gdt_retrieval_topk(const float* vecs, const float* qvecs, int* ids, float* scores, long ndb, int nq, int d, int k, int index_base, long self_base,
+                       int slices, void* workspace, size_t workspace_bytes, void* stream);
+/* Weighted aggregation and renormalisation on top-k results: query expansion (AQE / alpha-QE) and database-side augmentation
+ * (Radenovic et al., TPAMI 2018, section 5.3).  x = (base ? base[q] : 0) + sum_{j < k, ids[q][j] >= 0} w_j vecs[ids[q][j] - index_base] with
+ * w_j = 1 for alpha == 0, else powf(max(scores[q][j], 0), alpha);  out[q] = x / (||x||_2 + 1e-6), cirtorch's l2n.  base [nq][d] or NULL, ids /
+ * scores [nq][k] as gdt_retrieval_topk writes them (an id of -1, or one outside the database, adds nothing), out [nq][d]; 1 <= d <= 8192,
+ * 1 <= k <= 256, alpha >= 0.  fp32 sums in an order fixed by (d, k): j ascending per component, the norm by a fixed tree; no atomics, two runs
+ * give the same bits.  One workgroup per query. */
+int gdt_retrieval_expand(const float* vecs, const float* base, const int* ids, const float* scores, float* out, long ndb, int nq, int d, int k,
+                         int index_base, float alpha, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Loss of retrieval tuples (the validation of the fine-tuning scenario: decisive criterion "val/learning/loss:total")
