@@ -142,6 +142,12 @@ SIGNATURES = {
     "gdt_retrieval_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_long, c_int, c_void_p, c_size_t,
                                    c_void_p]),
     "gdt_retrieval_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "gdt_retrieval_knn_affinity": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "gdt_retrieval_diffuse_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "gdt_retrieval_diffuse": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                      c_float, c_float, c_int, c_void_p, c_size_t, c_void_p]),
+    "gdt_retrieval_rank_scores_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "gdt_retrieval_rank_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "gdt_tuple_loss_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
     "gdt_tuple_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_size_t, c_void_p]),

@@ -5,6 +5,7 @@ Reference (CPU numpy): ``scores = np.dot(vecs.T, qvecs); ranks = np.argsort(-sco
 (mdir/external/cirtorch/datasets/traindataset.py:246-279).  Same layout conventions here: descriptors are D x N (one column
 per image, views of the library's [N][D] blocks), scores are Ndb x Nq, ranks are Ndb x Nq database indices per query column.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -290,6 +291,110 @@ def knn_graph(vecs, k, block=8192):
         q = v[b0:b0 + int(block)]
         scores[b0:b0 + q.shape[0]], ids[b0:b0 + q.shape[0]] = _topk_rows(v, q, k, 0, b0)
     return scores.t(), ids.t()
+
+
+# ---- diffusion re-ranking on the mutual kNN graph (gandtr_amd/csrc/retrieval_diffusion.hip; Iscen et al., CVPR 2017)
+
+DiffusionResult = collections.namedtuple("DiffusionResult", ["scores", "iterations", "residual"])
+DiffusionResult.__doc__ = """scores N x Nq fp32 (a view of the library's [Nq][N] block), iterations int32 [Nq], residual fp32 [Nq]: the final relative
+residual ||r|| / ||y|| of the conjugate-gradient recurrence per column (above ``tol`` where ``max_iter`` ended the column)."""
+
+
+def _lists(name, a, b, dtype_b):
+    """two k x N lists on one HIP device -> contiguous [N][k] rows"""
+    if not (torch.is_tensor(a) and torch.is_tensor(b)) or a.dim() != 2 or a.shape != b.shape:
+        raise ValueError("%s: the two lists have one shape (k x N)" % name)
+    _on_one_device(name, a, b)
+    return a.t().contiguous().float(), b.t().contiguous().to(dtype_b)
+
+
+def mutual_knn_affinity(scores, ids, gamma=3.0):
+    """Normalised weights of the mutual kNN graph.  scores / ids: k x N as ``knn_graph`` returns them.  Edge (i, s) with j = ids[s, i] keeps
+    min(max(score, 0) ** gamma of i -> j, the same of j -> i) where j lists i too, else 0; the weights are scaled by 1 / sqrt(degree) on both
+    ends (isolated rows stay 0).  Returns weights k x N fp32 for the same ``ids``: symmetric bit for bit."""
+    lib = _hip.load()
+    sc, idx = _lists("mutual_knn_affinity", scores, ids, torch.int32)
+    n, k = sc.shape
+    with torch.cuda.device(sc.device):
+        w = torch.empty_like(sc)
+        rnorm = torch.empty(n, dtype=torch.float32, device=sc.device)
+        _hip.check(lib.gdt_retrieval_knn_affinity(idx.data_ptr(), sc.data_ptr(), w.data_ptr(), rnorm.data_ptr(), n, k, float(gamma),
+                                                  torch.cuda.current_stream(sc.device).cuda_stream))
+    return w.t()
+
+
+def diffuse(weights, ids, seed_ids, seed_weights, alpha=0.99, tol=1e-5, max_iter=64, block=64):
+    """Solves (I - alpha S) f = y for every query column by conjugate gradients on the device.  weights / ids: k x N (``mutual_knn_affinity``
+    and the ids it was given); seed_ids / seed_weights: kq x Nq, y[seed_ids[t, q], q] += seed_weights[t, q] (duplicates add, ids outside
+    [0, N) add nothing).  ``block`` columns (1 .. 64) are solved together; it does not show in the result.  Returns ``DiffusionResult``."""
+    lib = _hip.load()
+    if not (torch.is_tensor(seed_ids) and torch.is_tensor(seed_weights)) or seed_ids.dim() != 2 or seed_ids.shape != seed_weights.shape:
+        raise ValueError("diffuse: seed_ids and seed_weights have one shape (kq x Nq)")
+    w, idx = _lists("diffuse", weights, ids, torch.int32)
+    sw, sid = _lists("diffuse", seed_weights, seed_ids, torch.int32)
+    if sw.device != w.device:
+        raise ValueError("diffuse needs descriptors on one HIP device")
+    (n, k), (nq, kq), dev = w.shape, sw.shape, w.device
+    need = ctypes.c_size_t()
+    _hip.check(lib.gdt_retrieval_diffuse_workspace_bytes(n, nq, int(block), ctypes.byref(need)))
+    with torch.cuda.device(dev):
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        scores_t = torch.empty((nq, n), dtype=torch.float32, device=dev)
+        iterations = torch.empty(nq, dtype=torch.int32, device=dev)
+        residual = torch.empty(nq, dtype=torch.float32, device=dev)
+        _hip.check(lib.gdt_retrieval_diffuse(idx.data_ptr(), w.data_ptr(), sid.data_ptr(), sw.data_ptr(), scores_t.data_ptr(), iterations.data_ptr(),
+                                             residual.data_ptr(), n, k, nq, kq, int(block), float(alpha), float(tol), int(max_iter), ws.data_ptr(),
+                                             ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    return DiffusionResult(scores_t.t(), iterations, residual)
+
+
+def diffusion_scores(vecs, qvecs=None, k=50, kq=10, gamma=3.0, alpha=0.99, tol=1e-5, max_iter=64, graph=None):
+    """Diffusion scores of every database image for every query.  vecs: D x N; the graph is ``mutual_knn_affinity(*knn_graph(vecs, k), gamma)``
+    unless ``graph`` = (weights, ids), both k x N, is given (one graph serves many query sets).  qvecs: D x Nq -- the seeds of a query are its
+    ``topk(vecs, qvecs, kq)`` with weights max(score, 0) ** gamma.  ``qvecs=None`` is the database side: query j is database column j, seeded by
+    itself with weight 1 and by the first kq entries of its own kNN row, weighted the same way (N x N scores).  Returns ``DiffusionResult``."""
+    _on_one_device("diffusion_scores", vecs)
+    knn = None
+    if graph is None:
+        knn = knn_graph(vecs, k)
+        graph = (mutual_knn_affinity(knn[0], knn[1], gamma), knn[1])
+    weights, ids = graph
+    if qvecs is None:
+        if knn is None or kq > knn[0].shape[0]:
+            knn = knn_graph(vecs, kq)
+        own = torch.arange(vecs.shape[1], dtype=torch.int32, device=vecs.device)[None, :]
+        seed_ids = torch.cat([own, knn[1][:kq]])
+        seed_w = torch.cat([torch.ones_like(own, dtype=torch.float32), knn[0][:kq].clamp_min(0).pow(gamma)])
+    else:
+        s, seed_ids = topk(vecs, qvecs, kq)
+        seed_w = s.clamp_min(0).pow(gamma)
+    return diffuse(weights, ids, seed_ids, seed_w, alpha, tol, max_iter)
+
+
+def rank_scores(scores, index_base=0):
+    """Ranks of a given score matrix.  scores: Ndb x Nq fp32 on a HIP device -> ranks Ndb x Nq int32, per column the database indices in the strict
+    order (score descending, id ascending), -0.0 taken as 0.0: the dtype and orientation of ``scores_and_ranks``.  Ndb * Nq < 2^31."""
+    lib = _hip.load()
+    if not torch.is_tensor(scores) or scores.dim() != 2:
+        raise ValueError("rank_scores takes an Ndb x Nq matrix")
+    _on_one_device("rank_scores", scores)
+    st = scores.t().contiguous().float()
+    nq, n = st.shape
+    need = ctypes.c_size_t()
+    with torch.cuda.device(st.device):
+        _hip.check(lib.gdt_retrieval_rank_scores_workspace_bytes(n, nq, ctypes.byref(need)))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=st.device)
+        ranks_t = torch.empty((nq, n), dtype=torch.int32, device=st.device)
+        _hip.check(lib.gdt_retrieval_rank_scores(st.data_ptr(), ranks_t.data_ptr(), n, nq, int(index_base), ws.data_ptr(), ws.numel(),
+                                                 torch.cuda.current_stream(st.device).cuda_stream))
+    return ranks_t.t()
+
+
+def diffusion_ranks(vecs, qvecs=None, k=50, kq=10, gamma=3.0, alpha=0.99, tol=1e-5, max_iter=64, graph=None):
+    """``diffusion_scores`` and the ranking of its scores: (ranks Ndb x Nq int32 as ``scores_and_ranks`` returns them -- ``compute_map`` takes
+    them --, the ``DiffusionResult``)."""
+    result = diffusion_scores(vecs, qvecs, k, kq, gamma, alpha, tol, max_iter, graph)
+    return rank_scores(result.scores), result
 
 
 # ---- mAP evaluation (mdir/external/cirtorch/utils/evaluate.py): average precision and precision@k per query

@@ -414,6 +414,36 @@ int gdt_retrieval_topk(const float* vecs, const float* qvecs, int* ids, float* s
  * give the same bits.  One workgroup per query. */
 int gdt_retrieval_expand(const float* vecs, const float* base, const int* ids, const float* scores, float* out, long ndb, int nq, int d, int k,
                          int index_base, float alpha, void* stream);
+/* Diffusion re-ranking on the mutual kNN graph (Iscen et al., CVPR 2017; gandtr_amd/csrc/retrieval_diffusion.hip).  ids int32 [n][k] / scores fp32
+ * [n][k]: the kNN lists of n database vectors as gdt_retrieval_topk writes them with self_base (self excluded, id -1 = missing; an id outside
+ * [0, n) is a missing entry: no id is dereferenced unchecked).
+ *   a_is = powf(max(scores[i][s], 0), gamma);  with j = ids[i][s]:  w_is = min(a_is, a_jt) if 0 <= j < n and row j lists i at slot t (the first
+ *   such t), else 0;  deg_i = sum_s w_is (float64, s ascending);  r_i = (float)(1 / sqrt(deg_i)), 1 where deg_i == 0;  S_is = w_is * (r_i * r_j)
+ *   in fp32, the product r_i * r_j formed first: S is symmetric bit for bit.
+ * gdt_retrieval_knn_affinity writes S to weights [n][k] (same slots as ids; must not alias scores) and r to rnorm [n].  1 <= k <= 256, n >= 1,
+ * gamma >= 0.
+ * gdt_retrieval_diffuse solves (I - alpha S) f_q = y_q for nq query columns by conjugate gradients from f = 0:  y_q[seed_ids[q][t]] +=
+ * seed_w[q][t], t < kq in slot order (seed_ids int32 [nq][kq], seed_w fp32 [nq][kq]; duplicate ids add, an id outside [0, n) adds nothing).  A
+ * column stops, and its state freezes, when ||r||_2 <= tol ||y||_2 or after max_iter iterations; a column with y = 0 returns exactly 0 with 0
+ * iterations.  scores_t fp32 [nq][n] = f, iterations int32 [nq], residual fp32 [nq] = the final ||r|| / ||y|| of the recurrence (0 for y = 0).
+ * Products are fp32 fmaf chains over s ascending; every dot product is accumulated in float64 in an order fixed by n alone; no float atomics: a
+ * column's bits do not depend on the other columns, on `block` (columns solved together, 1 .. 64) or on the run.  Flags and counts stay on the
+ * device: max_iter iterations are enqueued on `stream` without a host synchronisation, those of a finished block return at once.
+ * 1 <= k, kq <= 256, n, nq >= 1, 0 < alpha < 1, tol > 0, 1 <= max_iter <= 1000.  The workspace holds four [n][block] fp32 vectors and the
+ * partial sums.
+ * gdt_retrieval_rank_scores: ranks_t int32 [nq][n] = index_base + the database indices of scores_t fp32 [nq][n] in the strict order (score
+ * descending, id ascending) -- the segmented radix sort of gdt_retrieval_scores_ranks on scores it did not compute, -0.0f taken as +0.0f;
+ * n * nq < 2^31.  scores_t is not modified.
+ * All buffers are device buffers; arguments are checked before any HIP call (GDT_ERR_INVALID; GDT_ERR_WORKSPACE for a workspace below the
+ * matching *_workspace_bytes). */
+int gdt_retrieval_knn_affinity(const int* ids, const float* scores, float* weights, float* rnorm, int n, int k, float gamma, void* stream);
+int gdt_retrieval_diffuse_workspace_bytes(int n, int nq, int block, size_t* bytes);
+int gdt_retrieval_diffuse(const int* ids, const float* weights, const int* seed_ids, const float* seed_w, float* scores_t, int* iterations,
+                          float* residual, int n, int k, int nq, int kq, int block, float alpha, float tol, int max_iter, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int gdt_retrieval_rank_scores_workspace_bytes(int n, int nq, size_t* bytes);
+int gdt_retrieval_rank_scores(const float* scores_t, int* ranks_t, int n, int nq, int index_base, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Loss of retrieval tuples (the validation of the fine-tuning scenario: decisive criterion "val/learning/loss:total")
