@@ -3,6 +3,7 @@
 Drop-in surface (mirrors the reference's own modules):
   hubconf.py / gandtr_amd.hub.model      cyclegan, hedngan, gem_vgg16_*, gem_resnet101_*
   gandtr_amd.components.model.network    MODEL_LABELS / initialize_model
+  gandtr_amd.components.model.layers     ATTENTIONS, POOLINGS (geometric-median pooling of the embedder, Weiszfeld's iteration on the device), EdgeFilter
   gandtr_amd.components.data.wrapper     WRAPPERS_LABELS / initialize_wrappers
   gandtr_amd.components.data.dataset     DATASET_LABELS / initialize_dataset_loader (the GAN scenarios' data blocks, decoded and cropped on the device)
   gandtr_amd.learning.network            NETWORKS / initialize_network / SingleNetwork / CirSequentialNetwork

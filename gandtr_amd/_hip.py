@@ -36,6 +36,11 @@ class PoolHeadDesc(ctypes.Structure):
                 ("rw", c_void_p), ("rb", c_void_p), ("fw", c_void_p), ("fb", c_void_p), ("eps_l2", c_float), ("attention", c_int), ("normalize_max", c_int)]
 
 
+class MedianHeadDesc(ctypes.Structure):
+    """struct gdt_median_head_desc (include/gandtr_hip.h)."""
+    _fields_ = [("iterations", c_int), ("fw", c_void_p), ("fb", c_void_p), ("eps_l2", c_float), ("attention", c_int), ("normalize_max", c_int)]
+
+
 class IngestItem(ctypes.Structure):
     """struct gdt_ingest_item (include/gandtr_hip.h)."""
     _fields_ = [("src", c_void_p), ("h", c_int), ("w", c_int), ("fx", c_int), ("fy", c_int), ("box", c_float * 4),
@@ -104,6 +109,7 @@ SIGNATURES = {
     "gdt_net_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, _IP]),
     "gdt_net_gem_l2n": (c_int, [c_void_p, c_int, c_float, c_float, c_float, _IP]),
     "gdt_net_pool_head": (c_int, [c_void_p, c_int, POINTER(PoolHeadDesc), _IP]),
+    "gdt_net_median_head": (c_int, [c_void_p, c_int, POINTER(MedianHeadDesc), _IP]),
     "gdt_net_input_filter": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_float, c_float]),
     "gdt_net_output_nchw": (c_int, [c_void_p, c_int, c_void_p, _IP]),
     "gdt_net_hed_head": (c_int, [c_void_p, _IP, POINTER(c_void_p), _FP, _FP, c_float, c_int, _IP]),
@@ -163,6 +169,8 @@ SIGNATURES = {
     "gdt_pool_regions_weighted": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "gdt_pixel_attention_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "gdt_pixel_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gdt_geometric_median_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "gdt_geometric_median": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gdt_pack_input_filter": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
     "gdt_mfma_only_tflops": (c_int, [c_int, POINTER(c_double), c_void_p]),
     "gdt_ingest_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),

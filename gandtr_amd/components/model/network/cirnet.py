@@ -8,6 +8,8 @@ The whole descriptor head runs on the HIP path: any of the five poolings, made r
 and the final whitening layers (engine.build_embedder, csrc/pool_head.hip); the hub configuration (mdir/hub/embedding.yml:6-10:
 plain GeM, no whitening layers) keeps its own two-launch op.  The attention net's weights are computed and folded into the pooling pass there too
 (pixel_norm_kernel, the weighted pool_regions_kernel), and the EdgeFilter of the edge-map net is evaluated by the input pack (csrc/aux_kernels.hip).
+The dict-valued pooling of init_cirnet (mdir/components/model/network/cirnet.py:61-63), ``{"type": "GeometricMedianWeiszfeld", "iterations": k,
+"intermediate_gradients": b}`` (layers/pooling.py), has a head op of its own (engine.HipNet.median_head, csrc/median_pool.hip).
 """
 import math
 
@@ -17,7 +19,7 @@ import torch.nn.functional as F
 from torch.nn.parameter import Parameter
 
 from . import backbones
-from ..layers import attention as attention_layers, preprocessing as preprocessing_layers
+from ..layers import attention as attention_layers, pooling as pooling_layers, preprocessing as preprocessing_layers
 from ._hipbacked import HipBacked, ScaledInput
 
 
@@ -225,6 +227,11 @@ class ImageRetrievalNet(HipBacked, nn.Module):
         the HIP net, so swapping ``pool`` or a whitening layer rebuilds): (pooling kind, regional, L, eps of the pooling, local whitening, final
         whitening).  None for the hub configuration (plain GeM, no whitening layers), which keeps its own op."""
         pool = self.pool
+        if type(pool) is pooling_layers.GeometricMedianWeiszfeld:
+            iterations = pool.iterations
+            if int(iterations) != iterations or not 0 <= iterations <= 64:
+                raise NotImplementedError("HIP embedder: the geometric median takes 0..64 iterations, got %r" % (iterations,))
+            return ("geometric_median", int(iterations), self.lwhiten is not None, self.whiten is not None)
         regional = isinstance(pool, Rpool)
         inner = pool.rpool if regional else pool
         kinds = {MAC: "mac", SPoC: "spoc", GeM: "gem", GeMmp: "gemmp", RMAC: "rmac"}
@@ -295,9 +302,21 @@ def init_network(params):
     if pretrained:
         raise ValueError("pretrained ImageNet trunks need a download; use pretrained=False and load a checkpoint")
     if isinstance(pooling, dict):
-        raise NotImplementedError("dict-valued pooling (the POOLINGS kinds of mdir/components/model/layers/pooling.py) is not mirrored; "
-                                  "use one of %s" % sorted(POOLING))
-    if pooling not in POOLING:
+        # The reference builds this pooling in init_cirnet, behind an init_network that skipped it (imageretrievalnet.py:228), with
+        # ``params['pooling'].pop("type")``: that empties the caller's dict AND the meta that aliases it of the type, so that a net cannot be rebuilt from its
+        # own meta.  Deviation: the dict is copied, the caller's is left alone and ``meta["pooling"]`` keeps its ``type``.
+        pooling = dict(pooling)
+        kind = pooling.get("type")
+        if kind == "HordeCascadedKOrder":
+            raise NotImplementedError("dict-valued pooling 'HordeCascadedKOrder' is not mirrored: it returns a list, which ImageRetrievalNet.forward "
+                                      "(norm(pool(o))) cannot take in the reference itself")
+        if kind not in pooling_layers.POOLINGS:
+            raise NotImplementedError("dict-valued pooling of type %r is not mirrored; the dict kinds are %s, the named ones %s"
+                                      % (kind, sorted(pooling_layers.POOLINGS), sorted(POOLING)))
+        if regional:
+            raise NotImplementedError("regional=True with a dict-valued pooling: the reference replaces the Rpool by the bare pooling and its "
+                                      "parameter_groups then fails; not mirrored")
+    elif pooling not in POOLING:
         raise KeyError(pooling)
     if regional and pooling == "rmac":
         raise NotImplementedError("regional=True with pooling='rmac' (R-MAC regions of R-MAC regions) is not mirrored; no published network uses it")
@@ -310,7 +329,10 @@ def init_network(params):
     dim = last_convs[-1].out_channels
 
     lwhiten = nn.Linear(dim, dim, bias=True) if local_whitening else None
-    pool = POOLING[pooling](mp=dim) if pooling == "gemmp" else POOLING[pooling]()
+    if isinstance(pooling, dict):           # (a missing ``iterations`` is the constructor's TypeError, as in the reference; no parameters, nothing drawn)
+        pool = pooling_layers.POOLINGS[pooling["type"]](**{k: v for k, v in pooling.items() if k != "type"})
+    else:
+        pool = POOLING[pooling](mp=dim) if pooling == "gemmp" else POOLING[pooling]()
     if regional:
         pool = Rpool(pool, nn.Linear(dim, dim, bias=True))
     whiten = None
@@ -428,7 +450,7 @@ class CirRetrievalNetAttention(CirRetrievalNet):
 
     def _hip_head(self):
         head = super()._hip_head()
-        if head is not None and (head[4] or head[5]):
+        if head is not None and (head[-2] or head[-1]):                 # (either form of the tuple ends with: local whitening, final whitening)
             raise NotImplementedError("HIP embedder: the attention net takes no local and no final whitening layer")
         return head
 

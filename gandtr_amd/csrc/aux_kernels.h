@@ -72,3 +72,15 @@ int gdt_k_region_sum(const float* v, float* y, int N, int R, int D, float eps, i
 size_t gdt_pool_head_scratch_floats(int N, int R, int D);
 int gdt_k_pool_head(const void* x, int f32, int N, int H, int W, int D, const GdtPoolHead& hd, const GdtPoolRegions& g, float* scratch, float* out,
                     hipStream_t st);
+
+// ---- geometric-median pooling (median_pool.hip) ----
+// Weiszfeld's iteration per image: y = scale * x, weights from `prior` (either may be null: ones; fp32 [N][HW]); out fp32 [N][D];
+// scratch: gdt_geometric_median_scratch_floats(N, HW, D) floats
+int gdt_geometric_median_check(int n, int h, int w, int d, int iterations);       // the argument limits, before any HIP call
+size_t gdt_geometric_median_scratch_floats(int N, long HW, int D);
+int gdt_k_geometric_median(const void* x, int f32, int N, long HW, int D, int iterations, const float* scale, const float* prior, float* out, float* scratch,
+                           hipStream_t st);
+// the head with this pooling: median -> l2n -> (whiten -> l2n); scratch: gdt_median_head_scratch_floats(N, HW, D) floats
+size_t gdt_median_head_scratch_floats(int N, long HW, int D);
+int gdt_k_median_head(const void* x, int f32, int N, long HW, int D, int iterations, const float* scale, const float* fw, const float* fb, float eps_l2,
+                      float* scratch, float* out, hipStream_t st);

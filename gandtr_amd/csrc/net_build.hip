@@ -779,6 +779,26 @@ int gdt_net_pool_head(gdt_net* net, int in_tensor, const gdt_pool_head_desc* des
     return GDT_OK;
 }
 
+int gdt_net_median_head(gdt_net* net, int in_tensor, const gdt_median_head_desc* desc, int* out_slot) {
+    GDT_REQUIRE(net && !net->finalized && desc && out_slot, "net");
+    const gdt_median_head_desc& h = *desc;
+    GDT_REQUIRE(h.iterations >= 0 && h.iterations <= GDT_MEDIAN_MAX_ITERATIONS, "median head: 0..64 iterations");
+    if (h.attention) {
+        GDT_REQUIRE(h.attention == 1, "median head attention: attention 1 = L2-norm attention");
+        GDT_REQUIRE(h.normalize_max == 0 || h.normalize_max == 1, "median head attention: normalize_max is 0 or 1");
+        GDT_REQUIRE(!h.fw && !h.fb, "median head attention: there is no final whitening");
+    }
+    GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "tensor id");
+    const int D = net->tensors[in_tensor].C;
+    GDT_REQUIRE(D % 64 == 0 && D <= 4096 && D == net->tensors[in_tensor].Creal, "median head needs channels % 64 == 0, at most 4096");
+    GDT_REQUIRE((h.fw == nullptr) == (h.fb == nullptr), "median head: a whitening layer is a weight and a bias");
+    Op o; o.kind = OP_MEDIAN_HEAD; o.in = in_tensor; o.median_iterations = h.iterations; o.eps_l2 = h.eps_l2;
+    o.att = h.attention; o.att_max = h.attention ? h.normalize_max : 0;
+    if (h.fw) { o.fw_off = net->blob_append(h.fw, (size_t)D * D * sizeof(float)); o.fb_off = net->blob_append(h.fb, (size_t)D * sizeof(float)); o.has_fw = true; }
+    *out_slot = push_op(net, std::move(o), true);
+    return GDT_OK;
+}
+
 int gdt_net_input_filter(gdt_net* net, int kind, float w, float p, float beta, float tau, float eps) {
     GDT_REQUIRE(net && !net->finalized && net->input_op >= 0, "input filter: between gdt_net_input and gdt_net_finalize");
     GDT_REQUIRE(kind == GDT_FILTER_EDGE, "input filter: kind 1 = EdgeFilter");

@@ -315,6 +315,21 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                 rc = gdt_k_pool_head(tptr(o.in), f32, n, ti.H, ti.W, ti.C, hd, g, (float*)(ws + stp.aux_off[0]), (float*)outputs[o.slot], st);
                 break;
             }
+            case OP_MEDIAN_HEAD: {
+                const Tensor& ti = T[o.in];
+                const long HW = (long)ti.H * ti.W;
+                float* scratch = (float*)(ws + stp.aux_off[0]);
+                const float* wts = nullptr;
+                if (o.att) {                // the attention weights [n][H * W] and the workgroups' maxima, behind the head's own scratch (net_plan.hip)
+                    float* a = scratch + gdt_median_head_scratch_floats(n, HW, ti.C);
+                    rc = gdt_k_pixel_attention(tptr(o.in), f32, n, HW, ti.C, o.att_max, a, a + (size_t)n * HW, st);
+                    if (rc != GDT_OK) break;
+                    wts = a;
+                }
+                rc = gdt_k_median_head(tptr(o.in), f32, n, HW, ti.C, o.median_iterations, wts, o.has_fw ? (const float*)(net->dev_blob + o.fw_off) : nullptr,
+                                       o.has_fw ? (const float*)(net->dev_blob + o.fb_off) : nullptr, o.eps_l2, scratch, (float*)outputs[o.slot], st);
+                break;
+            }
             case OP_OUT_NCHW: {
                 const Tensor& ti = T[o.in];
                 rc = gdt_k_unpack_output(tptr(o.in), f32, (float*)outputs[o.slot],

@@ -19,7 +19,7 @@ inline size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
 inline int next_pow2(int v) { int p = 8; while (p < v) p <<= 1; return p; }
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF, OP_POOL_HEAD, OP_CONCAT };
+enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF, OP_POOL_HEAD, OP_CONCAT, OP_MEDIAN_HEAD };
 
 struct PackedPhase {
     size_t w_off = 0;                 // byte offset in the device weight blob
@@ -82,6 +82,8 @@ struct Op {
     int pool_kind = 0, pool_aggregate = 0, pool_levels = 0;
     size_t pch_off = 0, rw_off = 0, rb_off = 0, fw_off = 0, fb_off = 0; bool has_rw = false, has_fw = false;
     int att = 0, att_max = 0;   // gdt_pool_head_desc::attention: 1 = L2-norm attention weights in front of the pooling, divided by the image's maximum when att_max
+    // median head (median_pool.hip): Weiszfeld iterations; eps_l2, the final whitening (fw_off / fb_off / has_fw) and att / att_max as for the pool head
+    int median_iterations = 0;
     // out_nchw
     size_t tap_bias_off = 0; bool tap_has_bias = false;
     // head ops (OP_HED, OP_RCF): the feature tensors they read -- inputs like `in` / `res` (op_inputs), kept alive until the head runs

@@ -669,8 +669,16 @@ int Planner::layout() {
                 st.aux_off[0] = arena.scratch(floats * sizeof(float));
                 break;
             }
+            case OP_MEDIAN_HEAD: {                      // the workgroups' partial sums, the previous median and three [N][D] rows (gdt_k_median_head)
+                const Tensor& ti = T[o.in];
+                const long HW = (long)ti.H * ti.W;
+                size_t floats = gdt_median_head_scratch_floats(N, HW, ti.C);
+                if (o.att) floats += (size_t)N * HW + gdt_pixel_attention_partial_floats(N, HW);      // the weights and the workgroups' maxima behind it
+                st.aux_off[0] = arena.scratch(floats * sizeof(float));
+                break;
+            }
             case OP_OUT_NCHW: break;
-            case OP_HED: case OP_RCF: {                 // one fp32 score map per feature tensor (HED) / per stage, at the stage's size (RCF)
+            case OP_HED: case OP_RCF: {               // one fp32 score map per feature tensor (HED) / per stage, at the stage's size (RCF)
                 size_t sz[5] = {0, 0, 0, 0, 0};
                 for (size_t j = 0; j < o.feats.size(); ++j) { const Tensor& tf = T[o.feats[j]]; sz[o.kind == OP_HED ? j : o.stage_of[j]] = (size_t)N * tf.H * tf.W * sizeof(float); }
                 for (int k = 0; k < 5; ++k) st.aux_off[k] = arena.alloc(sz[k]);
@@ -773,7 +781,7 @@ int gdt_net_output_shape(gdt_net* net, int slot, int n, int rh, int rw, int* dim
         case OP_CONV:
             dims[0] = n; dims[1] = o.cd.cout; dims[2] = conv_out_dim(o, ti.H, o.cd.kh); dims[3] = conv_out_dim(o, ti.W, o.cd.kw);
             *ndim = 4; break;
-        case OP_GEM: case OP_POOL_HEAD: dims[0] = n; dims[1] = ti.C; *ndim = 2; break;
+        case OP_GEM: case OP_POOL_HEAD: case OP_MEDIAN_HEAD: dims[0] = n; dims[1] = ti.C; *ndim = 2; break;
         case OP_OUT_NCHW: dims[0] = n; dims[1] = ti.C; dims[2] = ti.H; dims[3] = ti.W; *ndim = 4; break;
         case OP_HED: case OP_RCF: dims[0] = n; dims[1] = 1; dims[2] = rh; dims[3] = rw; *ndim = 4; break;     // (edge maps at the network input size)
         default: GDT_REQUIRE(false, "not an output op");
@@ -820,6 +828,14 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
             if (o.att) {                                              // the attention in front of the pooling: the norm pass (+ the division by the image's maximum)
                 counts[GDT_PLAN_ATTENTION_LAUNCHES] += 1 + (o.att_max ? 1 : 0);
                 counts[GDT_PLAN_ATTENTION_MAP_READS] += 2;            // the map is read by the norm pass and by the weighted pooling pass
+            }
+        }
+        if (o.kind == OP_MEDIAN_HEAD) { // the launches of gdt_k_median_head: a pass over the map and its finishing step per weighted mean, the l2n, the whitening and its l2n
+            counts[GDT_PLAN_HEAD_LAUNCHES] += 2 * (o.median_iterations + 1) + 1 + (o.has_fw ? 2 : 0);
+            counts[GDT_PLAN_HEAD_MAP_READS] += o.median_iterations + 1;
+            if (o.att) {                                              // the norm pass in front (+ the division by the image's maximum); it reads the map once more
+                counts[GDT_PLAN_ATTENTION_LAUNCHES] += 1 + (o.att_max ? 1 : 0);
+                counts[GDT_PLAN_ATTENTION_MAP_READS] += o.median_iterations + 2;
             }
         }
         if (o.kind != OP_CONV) continue;

@@ -207,6 +207,17 @@ class HipNet:
         image's maximum when ``normalize_max``"""
         return self._pool_head(x, kind, p, eps, aggregate, levels, rwhiten, None, eps_l2, attention=1, normalize_max=normalize_max)
 
+    def median_head(self, x, iterations, whiten=None, eps_l2=1e-6, attention=None):
+        """gdt_net_median_head: geometric median of the map's positions by ``iterations`` Weiszfeld steps -> l2n -> optional final whitening + l2n
+        (``whiten`` = (weight [D][D], bias [D]) or None).  ``attention`` ("l2norm", normalize_max): the median of the map weighted per position by its
+        L2-norm attention (CirRetrievalNetAttention with this pooling); no whitening then"""
+        if attention is not None and attention[0] != "l2norm":
+            raise NotImplementedError("attention %r: only 'l2norm' is on the HIP path" % (attention[0],))
+        arrays = [_f32(t) for t in tuple(whiten or (None, None))]
+        fw, fb = (_ptr(t) for t in arrays)                             # (the arrays stay alive until the call has returned)
+        d = _hip.MedianHeadDesc(int(iterations), fw, fb, float(eps_l2), 0 if attention is None else 1, int(bool(attention and attention[1])))
+        return self._add("median_head", x, ctypes.byref(d))
+
     def output_nchw(self, x, bias=None):
         b = _f32(bias)
         return self._add("output_nchw", x, _ptr(b))
@@ -703,6 +714,8 @@ def build_embedder(sd, device, in_affine=None, feature_tap=False, precision="f16
     ``ImageRetrievalNet._hip_head`` gives: (pooling "mac" | "spoc" | "gem" | "gemmp" | "rmac", regional, L, eps of the pooling, local whitening, final
     whitening); the layers' weights are the reference's state-dict entries (``lwhiten.*``, ``pool.p`` / ``pool.rpool.p``, ``pool.whiten.*``,
     ``whiten.*``).  The local whitening is a 1x1 conv with bias and no ReLU in front of the pool; everything behind the map is one pool_head op.
+    ``("geometric_median", iterations, local whitening, final whitening)``: the dict-valued pooling GeometricMedianWeiszfeld, on one median_head op
+    (csrc/median_pool.hip), alone or with ``attention``.
 
     ``attention`` ("l2norm", normalize_max): CirRetrievalNetAttention -- the map is weighted per position by its L2 norm (divided by the image's maximum
     when normalize_max) inside the pooling pass (pool_head_attention); no local and no final whitening, as the reference asserts.  With ``head`` None
@@ -721,6 +734,15 @@ def build_embedder(sd, device, in_affine=None, feature_tap=False, precision="f16
         raise NotImplementedError("attention %r: only 'l2norm' is on the HIP path" % (attention[0],))
     if head is None and attention is None:
         net.out_slot = net.gem_l2n(f, float(sd["pool.p"].reshape(-1)[0]))
+    elif head is not None and head[0] == "geometric_median":
+        # the dict-valued pooling GeometricMedianWeiszfeld: ("geometric_median", iterations, local whitening, final whitening); no parameters of its own
+        _, iterations, local_whitening, whitening = head
+        if attention is not None and (local_whitening or whitening):
+            raise NotImplementedError("the attention net takes no local and no final whitening (cirnet.py:117)")
+        if local_whitening:
+            w = sd["lwhiten.weight"]
+            f = net.conv(f, w.reshape(w.shape[0], w.shape[1], 1, 1), sd["lwhiten.bias"], relu=False)
+        net.out_slot = net.median_head(f, iterations, whiten=(sd["whiten.weight"], sd["whiten.bias"]) if whitening else None, attention=attention)
     else:
         kind, regional, levels, eps, local_whitening, whitening = head if head is not None else ("gem", False, 0, 1e-6, False, False)
         if attention is not None and (local_whitening or whitening):
@@ -1076,6 +1098,31 @@ def pool_regions_weighted(fmap, weights, kind, p=3.0, p_channels=None, eps=1e-6,
         _hip.check(lib.gdt_pool_regions_weighted(fmap.data_ptr(), int(fmap.dtype == torch.float32), n, h, w, d, HipNet.POOL_KINDS[kind], float(p),
                                                  pc.data_ptr() if pc is not None else None, float(eps), int(levels), weights.data_ptr(), out.data_ptr(),
                                                  _stream(fmap)))
+    return out
+
+
+def geometric_median(fmap, iterations, scale=None, prior=None):
+    """gdt_geometric_median: the geometric median of the positions of each image of an NHWC map (N x H x W x D, fp16 or fp32, D % 64 == 0) by
+    ``iterations`` Weiszfeld steps (0: the mean) -> fp32 N x D.  ``scale``: fp32 N x H x W, the map is taken as ``fmap * scale[..., None]``; ``prior``: fp32
+    N x H x W prior weights a_i (w_i = a_i / |m - y_i|); None: ones"""
+    lib = _hip.load()
+    fmap = _nhwc_map(fmap, "geometric_median")
+    n, h, w, d = fmap.shape
+    if int(iterations) != iterations or iterations < 0:
+        raise ValueError("geometric_median needs a non-negative integer number of iterations, got %r" % (iterations,))
+    for name, t in (("scale", scale), ("prior", prior)):
+        if t is not None and (not t.is_cuda or t.device != fmap.device or t.dtype != torch.float32 or tuple(t.shape) != (n, h, w)):
+            raise ValueError("geometric_median needs fp32 N x H x W %s on the map's device" % name)
+    scale = scale.contiguous() if scale is not None else None
+    prior = prior.contiguous() if prior is not None else None
+    with torch.cuda.device(fmap.device):
+        need = ctypes.c_size_t()
+        _hip.check(lib.gdt_geometric_median_workspace_bytes(n, h, w, d, ctypes.byref(need)))
+        ws = torch.empty(max(1, need.value), dtype=torch.uint8, device=fmap.device)
+        out = torch.empty((n, d), dtype=torch.float32, device=fmap.device)
+        _hip.check(lib.gdt_geometric_median(fmap.data_ptr(), int(fmap.dtype == torch.float32), n, h, w, d, int(iterations),
+                                            scale.data_ptr() if scale is not None else None, prior.data_ptr() if prior is not None else None,
+                                            out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(fmap)))
     return out
 
 

@@ -171,6 +171,25 @@ typedef struct gdt_pool_head_desc {
 } gdt_pool_head_desc;
 int gdt_net_pool_head(gdt_net* net, int in_tensor, const gdt_pool_head_desc* desc, int* out_slot);
 
+/* The head of ImageRetrievalNet.forward with the dict-valued pooling GeometricMedianWeiszfeld (mdir/components/model/layers/pooling.py:44-67, put in place
+ * by init_cirnet, mdir/components/model/network/cirnet.py:61-63): geometric median of the map's positions by `iterations` (0..64) Weiszfeld steps
+ * (gdt_geometric_median below; 0: the mean) -> l2n -> (whiten fw / fb -> l2n), the whitening in fp32 in every precision mode.  The reference's pooling only
+ * works on a batch of one; a batch here is that forward per image, and an image's descriptor does not depend on its neighbours in the batch, bit for bit.
+ *   attention  0: none.  1: the head of CirRetrievalNetAttention.forward with this pooling: the median of x * att, att the L2-norm attention of
+ * gdt_net_pool_head (divided by the image's maximum when normalize_max), computed by the same kernels and handed to the median as its `scale`; fw must be
+ * NULL then.
+ * Launches: 2 (iterations + 1) for the median, one l2n, two more with the whitening, whatever the batch; the map is read iterations + 1 times.  They are
+ * counted under GDT_PLAN_HEAD_LAUNCHES / GDT_PLAN_HEAD_MAP_READS, the attention's under GDT_PLAN_ATTENTION_LAUNCHES and, with the map reads of the median
+ * passes behind it (iterations + 2 in all), GDT_PLAN_ATTENTION_MAP_READS.  External output: fp32 [N][D] row-major, as gdt_net_pool_head. */
+#define GDT_MEDIAN_MAX_ITERATIONS 64
+typedef struct gdt_median_head_desc {
+    int iterations;
+    const float* fw; const float* fb;
+    float eps_l2;
+    int attention, normalize_max;
+} gdt_median_head_desc;
+int gdt_net_median_head(gdt_net* net, int in_tensor, const gdt_median_head_desc* desc, int* out_slot);
+
 /* Feature tap: internal fp16 NHWC tensor -> external fp32 NCHW (+ optional per-channel bias), p2p_networks.py:316-334 */
 int gdt_net_output_nchw(gdt_net* net, int in_tensor, const float* bias, int* out_slot);
 
@@ -258,7 +277,8 @@ enum {
                                         the generic implicit-GEMM kernels only                                                                        */
     GDT_PLAN_HEAD_LAUNCHES,          /* "head_launches": launches of the pool-head ops (gdt_net_pool_head: fixed by the layers present, whatever the
                                         batch and the number of regions); an attention head's launches behind the weights count as for any head      */
-    GDT_PLAN_HEAD_MAP_READS,         /* "head_map_reads": those among them that read the feature map (one per op)                                     */
+    GDT_PLAN_HEAD_MAP_READS,         /* "head_map_reads": those among them that read the feature map (one per pool head, iterations + 1 per median
+                                        head; gdt_net_median_head counts under both names)                                                           */
     GDT_PLAN_CONV4X4_LAUNCHES,       /* "conv4x4_launches": conv launches that run on the 4x4 patch kernel (conv4x4_halo.hip: what gdt_launch_conv
                                         decides for the conv as its own plain launch; none with GDT_CONV4X4_HALO=0)                                  */
     GDT_PLAN_CONV4X4T_LAUNCHES,      /* "conv4x4t_launches": transposed 4x4 convs that run as one launch of conv4x4t_halo.hip, the concatenation in
@@ -278,7 +298,7 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
 
 /* Per-op timing for bench.py's roofline line: when enabled, gdt_net_forward records HIP events on the caller's stream
  * around every op.  gdt_net_profile_read (after the forward) returns per op: kind (0 input, 1 conv, 2 instance-norm,
- * 3 maxpool, 4 gem, 5 tap, 6 hed, 7 rcf head, 8 pool head, 9 channel concatenation), the conv kernel variant (BM*1000+BN: conv_igemm_kernel<BM,BN>; 900000+BN:
+ * 3 maxpool, 4 gem, 5 tap, 6 hed, 7 rcf head, 8 pool head, 9 channel concatenation, 10 median head), the conv kernel variant (BM*1000+BN: conv_igemm_kernel<BM,BN>; 900000+BN:
  * conv3x3_halo_kernel<BN>), elapsed ms and the algorithmic FLOPs.  No reference counterpart (the reference has wall-clock StopWatch only, mdir/tools/stats.py:48-68). */
 int gdt_net_set_profiling(gdt_net* net, int enable);
 int gdt_net_profile_read(gdt_net* net, int max_ops, int* n_ops, int* kinds, int* tile_n, double* ms, double* flops);
@@ -338,6 +358,18 @@ int gdt_pool_regions_weighted(const void* fmap, int f32, int n, int h, int w, in
 int gdt_pixel_attention_workspace_bytes(int n, int h, int w, size_t* bytes);
 int gdt_pixel_attention(const void* fmap, int f32, int n, int h, int w, int d, int normalize_max, float* out, void* workspace, size_t workspace_bytes,
                         void* stream);
+
+/* GeometricMedianWeiszfeld / WeightedGeometricMedianWeiszfeld (mdir/components/model/layers/pooling.py:44-95) per image: fmap an NHWC map [n][h][w][d] on the
+ * device (f32 = 0: fp16, 1: fp32; d % 64 == 0, d <= 4096), scale and prior optional fp32 [n][h * w] on the device (NULL: ones), out fp32 [n][d].
+ *   y_i = scale_i * x_i, w_i = prior_i;  `iterations` (0..GDT_MEDIAN_MAX_ITERATIONS) times: m = sum_i w_i y_i / sum_i w_i, w_i = prior_i / sqrt(sum_c (y_ic - m_c)^2 + 1e-10);
+ *   out = sum_i w_i y_i / sum_i w_i  (0 iterations: the mean).
+ * All arithmetic in fp32; the squared distance is summed as written (never expanded), the division by sum w is a division.  The map is read
+ * iterations + 1 times, in 2 (iterations + 1) launches whatever n.  No atomics: the sums run in an order fixed by (h, w, d) alone, two runs give the same bits,
+ * and image k of a batch gives the bits it gives alone.  workspace: gdt_geometric_median_workspace_bytes(n, h, w, d) bytes on the device (the workgroups'
+ * partial sums and the previous median). */
+int gdt_geometric_median_workspace_bytes(int n, int h, int w, int d, size_t* bytes);
+int gdt_geometric_median(const void* fmap, int f32, int n, int h, int w, int d, int iterations, const float* scale, const float* prior, float* out,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* The input pack of gdt_net_input with the filter of gdt_net_input_filter on its own (no resize, permutation or affine): x fp32 [n][c][h][w] on the
  * device, c <= 8, out NHWC8 [n][h][w][8] (out_f32 = 0: fp16, 1: fp32), channels past c zero. */
