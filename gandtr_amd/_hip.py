@@ -107,6 +107,7 @@ SIGNATURES = {
     "gdt_net_conv": (c_int, [c_void_p, c_int, c_int, POINTER(ConvDesc), POINTER(ConvWeights), c_int, _IP]),
     "gdt_net_instance_norm": (c_int, [c_void_p, c_int, c_float, c_int, c_float, c_int, _IP]),
     "gdt_net_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, _IP]),
+    "gdt_net_resize": (c_int, [c_void_p, c_int, c_int, c_int, _IP]),
     "gdt_net_gem_l2n": (c_int, [c_void_p, c_int, c_float, c_float, c_float, _IP]),
     "gdt_net_pool_head": (c_int, [c_void_p, c_int, POINTER(PoolHeadDesc), _IP]),
     "gdt_net_median_head": (c_int, [c_void_p, c_int, POINTER(MedianHeadDesc), _IP]),
@@ -125,6 +126,7 @@ SIGNATURES = {
     "gdt_net_set_group_factor": (c_int, [c_void_p, c_float]),
     "gdt_plan_knob_name": (c_char_p, [c_int]),
     "gdt_plan_count_name": (c_char_p, [c_int]),
+    "gdt_plan_count_more_name": (c_char_p, [c_int]),
     "gdt_net_flops": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_double)]),
     "gdt_net_set_profiling": (c_int, [c_void_p, c_int]),
     "gdt_net_profile_read": (c_int, [c_void_p, c_int, _IP, _IP, _IP, POINTER(c_double), POINTER(c_double)]),
@@ -254,6 +256,11 @@ def plan_knobs():
 def plan_count_names():
     """Names of the counters gdt_net_plan_summary fills (gdt_plan_count_name), in index order."""
     return _names(load().gdt_plan_count_name)
+
+
+def plan_count_more_names():
+    """Names of the counters gdt_net_plan_summary fills behind those (gdt_plan_count_more_name) when the array has room for them, in index order."""
+    return _names(load().gdt_plan_count_more_name)
 
 
 def check(rc):

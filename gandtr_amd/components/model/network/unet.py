@@ -1,6 +1,12 @@
 """Learnable photometric normalisation nets -- mirror of mdir/components/model/network/unet.py: ``p2p_unet``, ``outconv_unet``, ``inconv_p2p_unet``,
-``aligned_p2p_unet`` and ``shallow_p2p_unet`` (``orig_unet`` and ``outconv_dynint_unet`` are not mirrored).  Image-to-image nets that sit in front of the
-embedder, at the embedder's image sizes.
+``aligned_p2p_unet``, ``shallow_p2p_unet``, ``orig_unet`` and ``outconv_dynint_unet``.  Image-to-image nets that sit in front of the embedder, at the
+embedder's image sizes.
+
+The last two have module trees of their own, at the end of the file: ``orig_unet`` (OrigUNet: pairs of 3x3 convs, MaxPool2d(2) down, ConvTranspose2d(k2, s2)
+up; device graph ``engine.build_orig_unet``, the transposed-2 route of gdt_net_conv) and ``outconv_dynint_unet`` (OutconvP2pUNetDynamicInterpolate: an
+F.interpolate back to the size each block received + Conv(k3) in place of every transposed conv, so it takes any image size; ``engine.build_dynint_unet``,
+gdt_net_resize).  Both are in ``CLASSES`` under their labels; the model registry (``MODEL_LABELS`` in this package's __init__) lists the first five only.
+What follows describes the first five.
 
 Every net is an ``outerblock`` nn.Sequential: a stem, ONE chain of nested skip blocks, a head.  A skip block returns ``cat([x, nested(x)], 1)``; ``nested`` goes
 down by a Conv2d(**conv_opts) (k4, s2, p1 by default) to ``inter`` channels, through the next block if there is one, and up again by a
@@ -236,3 +242,157 @@ class AlignedP2pUNet(_FamilyNet):
 
 
 CLASSES = {c.label: c for c in (P2pUNet, OutconvP2pUNet, InconvP2pUNet, AlignedP2pUNet, ShallowP2pUNet)}
+
+
+# ---- orig_unet: the classic U-Net (3x3 conv pairs, max-pool down, ConvTranspose2d(k2, s2) up) -- its own module tree, not an ``outerblock`` Sequential
+
+class OrigConvBlock(nn.Module):
+    """Conv3x3(p1) + ReLU, twice"""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_channels, out_channels, 3, padding=1)
+        self.relu1 = nn.ReLU()
+        self.conv2 = nn.Conv2d(out_channels, out_channels, 3, padding=1)
+        self.relu2 = nn.ReLU()
+
+    def forward(self, x):
+        return self.relu2(self.conv2(self.relu1(self.conv1(x))))
+
+
+class OrigSkipConnBlock(nn.Module):
+    """``x1 = downconv(x)``; ``x2 = convT(nested(pool(x1)))``; ``upconv(cat([x1, x2], 1))``"""
+
+    def __init__(self, nested, channels, in_channels=None):
+        super().__init__()
+        self.downconv = OrigConvBlock(channels // 2 if in_channels is None else in_channels, channels)
+        self.pool = nn.MaxPool2d(2)
+        self.nested = nested
+        self.convT = nn.ConvTranspose2d(2 * channels, channels, 2, stride=2)
+        self.upconv = OrigConvBlock(2 * channels, channels)
+
+    def forward(self, x):
+        x1 = self.downconv(x)
+        return self.upconv(torch.cat([x1, self.convT(self.nested(self.pool(x1)))], dim=1))
+
+
+class OrigUNet(HipBacked, nn.Module):
+    """``orig_unet``: ``nested_levels`` skip blocks of ``min_channels * 2**level`` channels around a conv block of ``min_channels * 2**nested_levels``, then
+    ``outconv = Conv2d(64, out_channels, 1)``.  The 64 is the reference's own constant: with ``min_channels != 64`` the net constructs and its forward fails at
+    ``outconv`` on the CPU, as the reference's does; on a HIP device it is refused before anything is built.  H and W must be multiples of
+    ``2**nested_levels`` (the pools halve, the transposed convs double)."""
+    hip_default_precision = "f16"
+    label = "orig_unet"
+
+    def __init__(self, in_channels, out_channels, nested_levels=4, min_channels=64):
+        nn.Module.__init__(self)
+        if nested_levels < 1:
+            raise ValueError("orig_unet needs at least one skip block, got nested_levels = %s" % (nested_levels,))
+        self.meta = {"in_channels": in_channels, "out_channels": out_channels}
+        self._cfg = dict(in_channels=in_channels, out_channels=out_channels, nested_levels=nested_levels, min_channels=min_channels)
+        block = OrigConvBlock(min_channels * 2 ** (nested_levels - 1), min_channels * 2 ** nested_levels)
+        for level in range(nested_levels - 1, 0, -1):
+            block = OrigSkipConnBlock(block, min_channels * 2 ** level)
+        self.outerblock = OrigSkipConnBlock(block, min_channels, in_channels=in_channels)
+        self.outconv = nn.Conv2d(64, out_channels, 1)
+
+    def forward(self, x):
+        if self._hip_device().type == "cuda":
+            return self._forward_hip(x)
+        return self.outconv(self.outerblock(x))
+
+    def _forward_hip(self, x):
+        from .... import engine
+        cfg = self._cfg
+        prec = self._hip_precision()
+        if prec not in ("f16", "f16x3"):
+            raise NotImplementedError("HIP orig_unet runs in 'f16' or 'f16x3'; %r is a ResnetGenerator mode" % (prec,))
+        engine.orig_unet_check(cfg)
+        div = 2 ** cfg["nested_levels"]
+        if x.dim() != 4 or x.shape[2] % div or x.shape[3] % div:
+            raise ValueError("orig_unet with nested_levels = %d needs H and W divisible by %d, got %s: pad the input with the 'reflectpad_divisible:%d' wrapper"
+                             % (cfg["nested_levels"], div, tuple(x.shape), div))
+        self._hip_check_inference()
+        net = self._hip_net(("orig_unet", prec), lambda sd, dev: engine.build_orig_unet(sd, dev, cfg, precision=prec))
+        return net.forward(x)[net.out_slot]
+
+
+CLASSES["orig_unet"] = OrigUNet
+
+
+# ---- outconv_dynint_unet: the outconv net with a resize + Conv(k3) in place of every transposed conv -- it returns maps of exactly the size it received
+
+class DynIntSkipConnBlock(nn.Module):
+    """``cat([x, up(interpolate(down(x), size of x))], 1)``; ``down`` = Conv [BatchNorm] LeakyReLU(0.2) [the nested block], ``up`` = Conv [BatchNorm] [Dropout] ReLU"""
+
+    def __init__(self, nested, outer_channels, inter_channels, conv_opts, upconv_opts, upsample, batchnorm_opts, batchnorm=True, dropout=False):
+        super().__init__()
+        self.upsample = upsample
+        down = [nn.Conv2d(outer_channels, inter_channels, **conv_opts)]
+        if batchnorm:
+            down.append(nn.BatchNorm2d(inter_channels, **batchnorm_opts))
+        down.append(nn.LeakyReLU(0.2))
+        if nested is not None:
+            down.append(nested)
+        self.down = nn.Sequential(*down)
+        up = [nn.Conv2d(inter_channels * (2 if nested is not None else 1), outer_channels, **upconv_opts)]
+        if batchnorm:
+            up.append(nn.BatchNorm2d(outer_channels, **batchnorm_opts))
+        if dropout:
+            up.append(nn.Dropout(p=dropout))
+        up.append(nn.ReLU())
+        self.up = nn.Sequential(*up)
+
+    def forward(self, x):
+        y = nn.functional.interpolate(self.down(x), size=x.shape[-2:], mode=self.upsample)
+        return torch.cat([x, self.up(y)], dim=1)
+
+
+class OutconvP2pUNetDynamicInterpolate(HipBacked, nn.Module):
+    """``outconv_dynint_unet``: Conv(k4, s2, p1) + LeakyReLU(0.2) to 64 channels, ``nested_levels`` skip blocks (64 -> 128 -> 256 -> 512 -> 512 ..), a resize to
+    the input's size, Conv(k3) to ``outconv_channels`` + ReLU, a k x k conv.  No transposed conv: every block resizes its result to the size it received, so the
+    net takes any H x W whose innermost map is not empty (no ``reflectpad_divisible`` in front)."""
+    hip_default_precision = "f16"
+    label = "outconv_dynint_unet"
+
+    def __init__(self, in_channels, out_channels, conv_opts=None, upconv_opts=None, nested_levels=7, upsample="bilinear", outconv_channels=32, outconv_kernel=3,
+                 dropout=False, batchnorm=False):
+        nn.Module.__init__(self)
+        assert outconv_kernel % 2 == 1
+        self.upsample = upsample
+        conv_opts = {"kernel_size": 4, "stride": 2, "padding": 1, **(conv_opts or {})}
+        upconv_opts = {"kernel_size": 3, "stride": 1, "padding": 1, **(upconv_opts or {})}
+        self.meta = {"in_channels": in_channels, "out_channels": out_channels}
+        self._cfg = dict(in_channels=in_channels, out_channels=out_channels, conv_opts=conv_opts, upconv_opts=upconv_opts, nested_levels=nested_levels,
+                         upsample=upsample, outconv_channels=outconv_channels, outconv_kernel=outconv_kernel, dropout=dropout, batchnorm=batchnorm)
+        widths = ([(64, 128), (128, 256), (256, 512)] + [(512, 512)] * max(0, nested_levels - 3))[:nested_levels]
+        inner = None
+        for outer, inter in reversed(widths):
+            inner = DynIntSkipConnBlock(inner, outer, inter, conv_opts, upconv_opts, upsample, {}, batchnorm=batchnorm, dropout=dropout)
+        self.down = nn.Sequential(nn.Conv2d(in_channels, 64, **conv_opts), nn.LeakyReLU(0.2), inner)
+        self.up = nn.Sequential(nn.Conv2d(128, outconv_channels, **upconv_opts), nn.ReLU(),
+                                nn.Conv2d(outconv_channels, out_channels, outconv_kernel, padding=outconv_kernel // 2))
+
+    def forward(self, x):
+        if self._hip_device().type == "cuda":
+            return self._forward_hip(x)
+        return self.up(nn.functional.interpolate(self.down(x), size=x.shape[-2:], mode=self.upsample))
+
+    def _forward_hip(self, x):
+        from .... import engine
+        cfg = self._cfg
+        if self.training and (cfg["batchnorm"] or cfg["dropout"]):
+            raise NotImplementedError("HIP outconv_dynint_unet is inference-only: call .eval() (BatchNorm uses running statistics, Dropout is the identity)")
+        prec = self._hip_precision()
+        if prec not in ("f16", "f16x3"):
+            raise NotImplementedError("HIP outconv_dynint_unet runs in 'f16' or 'f16x3'; %r is a ResnetGenerator mode" % (prec,))
+        engine.dynint_unet_check(cfg)
+        if x.dim() != 4 or min(x.shape[2:]) >> (cfg["nested_levels"] + 1) < 1:
+            raise ValueError("outconv_dynint_unet with nested_levels = %d halves the map %d times: H and W must be at least %d, got %s"
+                             % (cfg["nested_levels"], cfg["nested_levels"] + 1, 2 ** (cfg["nested_levels"] + 1), tuple(x.shape)))
+        self._hip_check_inference()
+        net = self._hip_net(("outconv_dynint_unet", prec), lambda sd, dev: engine.build_dynint_unet(sd, dev, cfg, precision=prec))
+        return net.forward(x)[net.out_slot]
+
+
+CLASSES["outconv_dynint_unet"] = OutconvP2pUNetDynamicInterpolate

@@ -20,6 +20,8 @@ int gdt_k_instance_norm_fused(const void* x, const void* res, void* y, int f32, 
 int gdt_k_instance_norm_stats(const void* x, int f32, int fused, float* partial, int tiles_per_image, int nphase, float* mean_rstd,
                               int N, int HW, int C, float eps, hipStream_t st);
 int gdt_k_maxpool(const void* x, void* y, int f32, int N, int H, int W, int C, int OH, int OW, int k, int s, int p, hipStream_t st);
+// F.interpolate(x [N][H][W][C], size=(OH, OW), mode 0 "bilinear" (align_corners=False) | 1 "nearest") -> y [N][OH][OW][C]
+int gdt_k_resize(const void* x, void* y, int f32, int N, int H, int W, int C, int OH, int OW, int mode, hipStream_t st);
 // y[.., 0 .. ca) = a (+ ReLU), y[.., ca .. ca + cb) = b, zero up to C: torch.cat along the channels of NHWC tensors with channel strides Ca / Cb
 int gdt_k_concat(const void* a, const void* b, void* y, int f32, long NP, int Ca, int ca, int Cb, int cb, int C, int relu_a, hipStream_t st);
 int gdt_k_gem_l2n(const void* x, int f32, float* pooled, float* out, int N, int HW, int D, float p, float eps_gem, float eps_l2,

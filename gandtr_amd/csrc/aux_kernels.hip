@@ -260,6 +260,55 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const T* __restrict__ x, T
     }
 }
 
+// ------------------------------------------------------------------------------------------------ resize of a feature map
+// F.interpolate(x, size=(OH, OW), mode="bilinear" (align_corners=False) | "nearest") of an NHWC tensor: the upsampling of
+// OutconvP2pUNetDynamicInterpolate.SkipConnBlock.forward (unet.py).  torch's coordinates: scale = in / out (fp32); bilinear src = max(scale * (dst + 0.5) - 0.5, 0),
+// i0 = floor(src), i1 = i0 + (i0 < in - 1), l = src - i0; nearest i = min(floor(dst * scale), in - 1).  8 channels (one 16-byte group of fp16) per lane, fp32
+// arithmetic, ONE store in the tensor's type.  Equal sizes: scale = 1, src = dst, l = 0 -- the products with 1 and 0 are exact, a bit-exact copy.
+// The bilinear coordinates are taken from the exact rational src = ((2 dst + 1) in - out) / (2 out): i0 by integer division, l = remainder / (2 out) rounded
+// ONCE.  In fp32, scale * (dst + 0.5) - 0.5 carries half an ulp of src (2^-20 at src = 18) into l, which then shows wherever the taps change sign; the
+// nearest index keeps torch's fp32 expression, so that it picks the pixel torch picks.
+// bilinear source of output index `o`: i0, i1 and the weight l of i1
+__device__ __forceinline__ void resize_source(int o, int in, int out, int& i0, int& i1, float& l) {
+    const int num = (2 * o + 1) * in - out;
+    i0 = 0; l = 0.f;
+    if (num > 0) {
+        i0 = num / (2 * out);
+        l = (float)(num - i0 * 2 * out) / (float)(2 * out);
+        if (i0 > in - 1) { i0 = in - 1; l = 0.f; }
+    }
+    i1 = i0 + (i0 < in - 1 ? 1 : 0);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void resize_kernel(const T* __restrict__ x, T* __restrict__ y, int N, int H, int W, int C, int OH, int OW, float sy, float sx,
+                                                     int mode) {
+    const int c8n = C >> 3;
+    const long total = (long)N * OH * OW * c8n;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int c8 = (int)(i % c8n);
+        long t = i / c8n;
+        const int ox = (int)(t % OW); t /= OW;
+        const int oy = (int)(t % OH), n = (int)(t / OH);
+        const T* img = x + (long)n * H * W * C + c8 * 8;
+        float v[8];
+        if (mode == 1) {
+            const int iy = min((int)floorf(oy * sy), H - 1), ix = min((int)floorf(ox * sx), W - 1);
+            load8(img + ((long)iy * W + ix) * C, v);
+        } else {
+            int y0, y1, x0, x1;
+            float ly, lx;
+            resize_source(oy, H, OH, y0, y1, ly);
+            resize_source(ox, W, OW, x0, x1, lx);
+            float v00[8], v01[8], v10[8], v11[8];
+            load8(img + ((long)y0 * W + x0) * C, v00); load8(img + ((long)y0 * W + x1) * C, v01);
+            load8(img + ((long)y1 * W + x0) * C, v10); load8(img + ((long)y1 * W + x1) * C, v11);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (1.f - ly) * ((1.f - lx) * v00[e] + lx * v01[e]) + ly * ((1.f - lx) * v10[e] + lx * v11[e]);
+        }
+        store8(y + i * 8, v);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ channel concatenation
 // torch.cat([a, b], 1) of two NHWC tensors (+ ReLU on the `a` part) into a tensor of C channels, zero behind the real ones: the skip connection of
 // UnetSkipConnectionBlock (p2p_networks.py:236) as the generic transposed-conv route reads it.  Ca / Cb: channel strides, ca / cb: channels copied
@@ -673,6 +722,18 @@ int gdt_k_maxpool(const void* x, void* y, int f32, int N, int H, int W, int C, i
     const dim3 grid(grid_for((long)N * OH * OW * (C / 8)));
     if (f32) hipLaunchKernelGGL(maxpool_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (float*)y, N, H, W, C, OH, OW, k, s, p);
     else hipLaunchKernelGGL(maxpool_kernel<f16>, grid, dim3(256), 0, st, (const f16*)x, (f16*)y, N, H, W, C, OH, OW, k, s, p);
+    GDT_CHECK_HIP(hipGetLastError());
+    return GDT_OK;
+}
+
+int gdt_k_resize(const void* x, void* y, int f32, int N, int H, int W, int C, int OH, int OW, int mode, hipStream_t st) {
+    GDT_REQUIRE(x && y && C % 8 == 0 && N >= 1 && H >= 1 && W >= 1 && OH >= 1 && OW >= 1, "resize needs C % 8 == 0 and non-empty maps");
+    GDT_REQUIRE(mode == 0 || mode == 1, "resize mode: 0 bilinear, 1 nearest");
+    GDT_REQUIRE((long)H * OH < (1L << 29) && (long)W * OW < (1L << 29), "resize: the exact coordinates need in * out < 2^29 per axis");
+    const float sy = (float)H / (float)OH, sx = (float)W / (float)OW;          // torch: area_pixel_compute_scale, align_corners=False, no scale_factor
+    const dim3 grid(grid_for((long)N * OH * OW * (C / 8)));
+    if (f32) hipLaunchKernelGGL(resize_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (float*)y, N, H, W, C, OH, OW, sy, sx, mode);
+    else hipLaunchKernelGGL(resize_kernel<f16>, grid, dim3(256), 0, st, (const f16*)x, (f16*)y, N, H, W, C, OH, OW, sy, sx, mode);
     GDT_CHECK_HIP(hipGetLastError());
     return GDT_OK;
 }

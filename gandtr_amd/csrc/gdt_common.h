@@ -265,6 +265,10 @@ inline void gdt_t4_step(int step, int& sy, int& sx, int& py, int& px) {
                 for (px = 0; px < 2; ++px)
                     if (gdt_t4_meets(sy, py) && gdt_t4_meets(sx, px) && s++ == step) return;
 }
+// convt2x2.hip: ConvTranspose2d(k2, s2, p0) as one GEMM with the depth-to-space in its stores, variant 902128.  `w` = [4 Cout][Cin] fp16 with GEMM column
+// (dy * 2 + dx) * phase_cout + cout, `bias` per column; Cout / CoutPad count GEMM columns, phase_cout the layer's output channels
+bool gdt_convt2x2_eligible(const ConvLaunch& d);
+int gdt_launch_convt2x2(const ConvLaunch& d, hipStream_t stream, int* variant);
 // conv3x3_cat_halo.hip: Conv2d(k3, s1, p1) of the channel concatenation of `in` (Cin channels) and `in2` (in2_cin channels), variant 908064; the fragment-ordered
 // weights have k = (chunk * 9 + tap) * 64 + channel, chunks counted over both inputs
 bool gdt_conv3x3_cat_halo_eligible(const ConvLaunch& d);

@@ -437,6 +437,24 @@ static void pack_ctf(ConvPack& cp) {
     o.has_ctf = true;
 }
 
+// ConvTranspose2d(k2,s2,p0), fp16: the one-launch form (Op::has_t2, convt2x2.hip).  GEMM column (dy * 2 + dx) * cout + co, k = input channel: [4 cout][cin]
+static void pack_t2(ConvPack& cp) {
+    gdt_net* net = cp.net; Op& o = cp.o;
+    const gdt_conv_desc& cd = o.cd;
+    const int ncol = 4 * cd.cout;
+    std::vector<f16> pk((size_t)ncol * cd.cin);
+    std::vector<float> b4(ncol);
+    for (int ph = 0; ph < 4; ++ph)
+        for (int co = 0; co < cd.cout; ++co) {
+            const int col = ph * cd.cout + co;
+            b4[col] = cp.shift[co];
+            for (int c = 0; c < cd.cin; ++c) pk[(size_t)col * cd.cin + c] = (f16)(cp.weight[((size_t)c * cd.cout + co) * 4 + ph] * cp.scale[co]);
+        }
+    o.t2_w_off = net->blob_append(pk.data(), pk.size() * sizeof(f16));
+    if (cp.has_shift) o.t2_bias_off = net->blob_append(b4.data(), b4.size() * sizeof(float));
+    o.has_t2 = true;
+}
+
 // the bias of a conv (BatchNorm folded): for the combine kernel of a row-split head, else padded for the GEMM epilogue
 static void pack_bias(ConvPack& cp) {
     gdt_net* net = cp.net; Op& o = cp.o;
@@ -508,7 +526,8 @@ static int add_conv(gdt_net* net, int in_a, int in_b, const gdt_conv_desc* desc,
     const float* weight = wts->weight;
     const int dil = cd.dilation, ntensors = (int)net->tensors.size();
     const bool t4 = cd.transposed && cd.kh == 4 && cd.kw == 4 && cd.stride == 2 && cd.pad == 1;       // the transposed-4 route
-    const bool cat = in_b >= 0 && !t4;                                                                   // the conv-of-a-concatenation route
+    const bool t2 = cd.transposed && cd.kh == 2 && cd.kw == 2 && cd.stride == 2 && cd.pad == 0;       // the transposed-2 route
+    const bool cat = in_b >= 0 && !t4 && !t2;                                                            // the conv-of-a-concatenation route
     GDT_REQUIRE(dil >= 1 && dil <= 16, "dilation must be 1..16");
     GDT_REQUIRE(dil == 1 || (!cd.transposed && !cd.pad_reflect && !cd.out_f32_nchw), "a dilated conv is a plain Conv2d with zero padding and an internal output");
     GDT_REQUIRE(dil == 1 || (in_b < 0 && cd.leaky == 0.f && !wts->bn_gamma && residual_tensor < 0),
@@ -523,6 +542,11 @@ static int add_conv(gdt_net* net, int in_a, int in_b, const gdt_conv_desc* desc,
     GDT_REQUIRE(!(t4 || cat) || residual_tensor < 0, "a ConvTranspose2d(k4,s2,p1) and a conv of a concatenation take no residual");
     if (t4) GDT_REQUIRE(net->precision == 0 || net->precision == 1, "ConvTranspose2d(k4,s2,p1) exists in the f16 and f16x3 modes");
     if (cat) GDT_REQUIRE(net->precision == 0 || net->precision == 1, "a Conv2d of a concatenation exists in the f16 and f16x3 modes");
+    if (t2) {
+        GDT_REQUIRE(net->precision == 0 || net->precision == 1, "ConvTranspose2d(k2,s2,p0) exists in the f16 and f16x3 modes");
+        GDT_REQUIRE(in_b < 0 && residual_tensor < 0, "ConvTranspose2d(k2,s2,p0) takes one input and no residual");
+        GDT_REQUIRE(!cd.pad_reflect && !cd.out_f32_nchw && cd.act == 0, "ConvTranspose2d(k2,s2,p0) pads nothing and has an internal output");
+    }
     GDT_REQUIRE(in_a >= 0 && in_a < ntensors && in_b >= -1 && in_b < ntensors, "input tensor id");
     GDT_REQUIRE(residual_tensor < ntensors, "residual tensor id");
     if (cat) {
@@ -548,8 +572,8 @@ static int add_conv(gdt_net* net, int in_a, int in_b, const gdt_conv_desc* desc,
         GDT_REQUIRE(cd.cin == ca + cb && ca + cb <= 4096, "the channels of the two inputs do not add up to the conv's cin");
     } else {
         GDT_REQUIRE(net->tensors[in_a].C == cin_pad && ca == cd.cin, "input tensor channel count does not match conv cin");
-        if (cd.transposed) GDT_REQUIRE(cd.kh == 3 && cd.kw == 3 && cd.stride == 2 && cd.pad == 1 && !cd.pad_reflect,
-                                       "only ConvTranspose2d(k3,s2,p1,op1) is supported");
+        if (cd.transposed) GDT_REQUIRE(t2 || (cd.kh == 3 && cd.kw == 3 && cd.stride == 2 && cd.pad == 1 && !cd.pad_reflect),
+                                       "only ConvTranspose2d(k3,s2,p1,op1), (k4,s2,p1) and (k2,s2,p0) are supported");
     }
     if (!cd.out_f32_nchw) GDT_REQUIRE(cd.cout % 8 == 0, "internal conv outputs need cout % 8 == 0");
     if (residual_tensor >= 0) GDT_REQUIRE(net->tensors[residual_tensor].C == cd.cout && !cd.out_f32_nchw, "residual channels");
@@ -583,20 +607,23 @@ static int add_conv(gdt_net* net, int in_a, int in_b, const gdt_conv_desc* desc,
     } else {
         // four sub-pixel phases.  k3: o = 2i - 1 + k.  Even outputs (parity 0): k = 1, i = y.  Odd outputs: k = 0 (i = y + 1) and k = 2 (i = y).
         // k4: 2 x 2 taps each: output parity 0 meets kernel rows 1 (input row y) and 3 (y - 1), parity 1 rows 0 (y + 1) and 2 (y); columns alike
+        // k2 (stride = kernel size): one tap each, output (2y + py, 2x + px) = input (y, x) through kernel tap (py, px)
         const int k = cd.kh;
         for (int py = 0; py < 2; ++py)
             for (int px = 0; px < 2; ++px) {
                 PackedPhase ph;
-                const int th = t4 || py ? 2 : 1, tw = t4 || px ? 2 : 1;
+                const int th = t2 ? 1 : t4 || py ? 2 : 1, tw = t2 ? 1 : t4 || px ? 2 : 1;
                 ph.ntaps = th * tw; ph.TW = tw;
-                ph.dy0 = py; ph.dys = -1; ph.dx0 = px; ph.dxs = -1;
+                ph.dy0 = t2 ? 0 : py; ph.dys = -1; ph.dx0 = t2 ? 0 : px; ph.dxs = -1;
                 ph.ooy = py; ph.oox = px;
-                auto tap = [&](int par, int t) { return par ? (t == 0 ? 0 : 2) : (t4 ? (t == 0 ? 1 : 3) : 1); };      // kernel row / column of tap t at output parity par
+                auto tap = [&](int par, int t) { return t2 ? par : par ? (t == 0 ? 0 : 2) : (t4 ? (t == 0 ? 1 : 3) : 1); };      // kernel row / column of tap t at output parity par
                 pack_phase(cp, ph, [&](int co, int c, int t) { return weight[(((size_t)c * cd.cout + co) * k + tap(py, t / tw)) * k + tap(px, t % tw)]; });
                 o.phases.push_back(ph);
             }
-        if (!t4 && net->precision == 1 && cd.cout == 64 && cin_pad % 32 == 0 && cd.cin == cin_pad && residual_tensor < 0) pack_pairs(cp);
-        if (!t4 && net->precision != 1 && cin_pad % 64 == 0 && (4 * cd.cout) % 256 == 0 && 256 % cd.cout == 0 && cd.cout >= 64 && residual_tensor < 0) pack_ctf(cp);
+        if (t2 && !net->precision && cd.cin % 64 == 0 && cd.cin == cin_pad && cd.cout % 64 == 0) pack_t2(cp);
+        const bool k3 = !t4 && !t2;                    // the fused forms of ConvTranspose2d(k3,s2,p1,op1)
+        if (k3 && net->precision == 1 && cd.cout == 64 && cin_pad % 32 == 0 && cd.cin == cin_pad && residual_tensor < 0) pack_pairs(cp);
+        if (k3 && net->precision != 1 && cin_pad % 64 == 0 && (4 * cd.cout) % 256 == 0 && 256 % cd.cout == 0 && cd.cout >= 64 && residual_tensor < 0) pack_ctf(cp);
     }
     // the patch kernels that read the sources themselves (which then live until this op: feats)
     if (t4 && !net->precision && !cd.out_f32_nchw && ca % 64 == 0 && cb % 64 == 0 && cd.cout % 64 == 0) {
@@ -732,6 +759,16 @@ int gdt_net_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad
     GDT_REQUIRE(kernel >= 1 && stride >= 1 && pad >= 0 && pad * 2 <= kernel, "maxpool geometry");
     GDT_REQUIRE(!ceil_mode || pad == 0, "ceil-mode max-pooling takes no padding");
     Op o; o.kind = OP_MAXPOOL; o.in = in_tensor; o.k = kernel; o.s = stride; o.p = pad; o.ceil = ceil_mode ? 1 : 0;
+    *out_tensor = push_op(net, std::move(o), false, net->tensors[in_tensor].C, net->tensors[in_tensor].Creal);
+    return GDT_OK;
+}
+
+int gdt_net_resize(gdt_net* net, int in_tensor, int like_tensor, int mode, int* out_tensor) {
+    GDT_REQUIRE(net && !net->finalized && out_tensor, "net");
+    const int ntensors = (int)net->tensors.size();
+    GDT_REQUIRE(in_tensor >= 0 && in_tensor < ntensors && like_tensor >= 0 && like_tensor < ntensors, "tensor id");
+    GDT_REQUIRE(mode == 0 || mode == 1, "resize mode: 0 bilinear, 1 nearest");
+    Op o; o.kind = OP_RESIZE; o.in = in_tensor; o.like = like_tensor; o.resize_mode = mode;
     *out_tensor = push_op(net, std::move(o), false, net->tensors[in_tensor].C, net->tensors[in_tensor].Creal);
     return GDT_OK;
 }

@@ -216,6 +216,15 @@ int exec_conv(const ConvStep& s) {
             return rc;
         }
     }
+    if (s.o.has_t2) {                              // ConvTranspose2d(k2,s2,p0) as one launch (convt2x2.hip) -- else the four phase launches below
+        const ConvLaunch d = conv_desc_t2(s.x, stp.op);
+        if (gdt_convt2x2_eligible(d)) {
+            int variant = 0;
+            const int rc = gdt_launch_convt2x2(d, s.st, &variant);
+            s.variant(variant);
+            return rc;
+        }
+    }
     if (conv_takes_cat_kernel(s.x, s.c.plan, stp.op)) {     // Conv2d(k3,s1,p1) from its own two inputs (conv3x3_cat_halo.hip) -- else the conv of one tensor below, over the concatenation
         int variant = 0;
         const int rc = gdt_launch_conv3x3_cat_halo(conv_desc_cc(s.x, stp.op, fold_of(net, s.c.plan, stp.op)), s.st, &variant);
@@ -280,6 +289,11 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                 const Tensor& ta = T[o.in]; const Tensor& to = T[o.out];
                 rc = gdt_k_concat(tptr(o.in), o.res >= 0 ? tptr(o.res) : nullptr, tptr(o.out), f32, (long)n * ta.H * ta.W, ta.C, ta.Creal,
                                   o.res >= 0 ? T[o.res].C : 0, o.res >= 0 ? T[o.res].Creal : 0, to.C, o.relu, st);
+                break;
+            }
+            case OP_RESIZE: {
+                const Tensor& ti = T[o.in]; const Tensor& to = T[o.out];
+                rc = gdt_k_resize(tptr(o.in), tptr(o.out), f32, n, ti.H, ti.W, ti.C, to.H, to.W, o.resize_mode, st);
                 break;
             }
             case OP_MAXPOOL: {

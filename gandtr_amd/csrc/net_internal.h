@@ -19,7 +19,7 @@ inline size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
 inline int next_pow2(int v) { int p = 8; while (p < v) p <<= 1; return p; }
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF, OP_POOL_HEAD, OP_CONCAT, OP_MEDIAN_HEAD };
+enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF, OP_POOL_HEAD, OP_CONCAT, OP_MEDIAN_HEAD, OP_RESIZE };
 
 struct PackedPhase {
     size_t w_off = 0;                 // byte offset in the device weight blob
@@ -70,8 +70,13 @@ struct Op {
     // -- conv4x4t_halo.hip when cd.transposed, else conv3x3_cat_halo.hip; the sources are then also in `feats`, so that they live until this op, and the
     // concatenation is never written
     bool has_cat_frag = false; size_t cat_frag_off = 0; int src_a = -1, src_b = -1, src_relu = 0, cat_op = -1;
+    // The transposed-2 route of gdt_net_conv -- ConvTranspose2d(k2,s2,p0): `phases` are its four 1 x 1 sub-pixel phases (the generic route); has_t2: the
+    // [4 cout][cin] matrix (columns [dy][dx][co]) and the per-column bias of the one-launch form (convt2x2.hip), a launch-time choice on the same plan
+    bool has_t2 = false; size_t t2_w_off = 0, t2_bias_off = 0;
     // concat (OP_CONCAT): in / res = the two tensors (res < 0: one), relu = ReLU on the first; cat_for = the conv op that reads the output
     int cat_for = -1;
+    // resize (OP_RESIZE, gdt_net_resize): `in` resized to the H x W of tensor `like` (read for its shape only: it need not be alive), mode 0 bilinear / 1 nearest
+    int like = -1, resize_mode = 0;
     int dil = 1;          // conv: dilation (gdt_conv_desc::dilation); the taps are (dy0 + (t / TW) * dil, ...): only the generic implicit-GEMM kernels take it
     // maxpool
     int k = 0, s = 0, p = 0; int ceil = 0;
@@ -270,6 +275,7 @@ ConvLaunch conv_desc_xexp(const DescCtx& x, int i, int chain, float group_factor
 ConvLaunch conv_desc_kcat(const DescCtx& x, int i);                                      // expand conv + its projection shortcut, K-concatenated
 ConvLaunch conv_desc_stem_direct(const DescCtx& x, int i, int pool_into);                // ResNet stem from the caller's image (+ the 3 x 3 max-pool behind it)
 ConvLaunch conv_desc_t4(const DescCtx& x, int i);                                        // ConvTranspose2d(k4,s2,p1) from its one or two inputs (Op::has_cat_frag, conv4x4t_halo.hip)
+ConvLaunch conv_desc_t2(const DescCtx& x, int i);                                        // ConvTranspose2d(k2,s2,p0) as one launch (Op::has_t2, convt2x2.hip)
 
 ConvLaunch conv_desc_cc(const DescCtx& x, int i, const ConvFold& f);                     // Conv2d(k3,s1,p1) from its two inputs (Op::has_cat_frag, conv3x3_cat_halo.hip)
 // conv op i of a planned geometry runs on conv3x3_cat_halo.hip: its own plain launch in the plan, and eligible (the knob is read here: a launch-time choice)

@@ -33,6 +33,7 @@ static void conv_geometry(const gdt_net* net, const Op& o, const PackedPhase& ph
 bool conv_fuses_stats(const Op& o, const Tensor& ti) {      // InstanceNorm partial statistics from the conv epilogue
     if (o.stats_for < 0 || o.cd.relu || o.res >= 0) return false;
     if (o.cd.transposed && o.cd.kh == 4) return false;      // (ConvTranspose2d(k4,s2,p1): its two routes are a launch-time choice on ONE plan, and conv4x4t_halo.hip delivers no statistics)
+    if (o.cd.transposed && o.cd.kh == 2) return false;      // (ConvTranspose2d(k2,s2,p0): likewise, convt2x2.hip)
     const int hwg = o.cd.transposed ? ti.H * ti.W : conv_out_dim(o, ti.H, o.cd.kh) * conv_out_dim(o, ti.W, o.cd.kw);
     return hwg % 128 == 0;
 }
@@ -226,6 +227,22 @@ ConvLaunch conv_desc_t4(const DescCtx& x, int i) {
     return d;
 }
 
+ConvLaunch conv_desc_t2(const DescCtx& x, int i) {
+    const Op& o = x.net->ops[i];
+    const auto& T = *x.T;
+    const Tensor& ti = T[o.in];
+    ConvLaunch d{};
+    d.in = x.p.act(T, o.in); d.Cin = ti.C; d.lc8 = ilog2(ti.C / 8);
+    d.N = x.n; d.H = ti.H; d.W = ti.W; d.OH = d.H * 2; d.OW = d.W * 2; d.OHg = d.H; d.OWg = d.W; d.M = x.n * d.H * d.W;
+    d.Cout = d.CoutPad = 4 * o.cd.cout; d.phase_cout = o.cd.cout; d.Kpad = ti.C; d.nk = d.Kpad / 64;
+    d.ntaps = 1; d.TW = 1; d.invTW = 65536; d.sy = d.sx = 1; d.osy = d.osx = 2; d.relu = o.cd.relu;
+    d.w = o.has_t2 ? x.p.w<const f16*>(o.t2_w_off) : nullptr;
+    d.bias = o.has_t2 && o.has_bias ? x.p.w<const float*>(o.t2_bias_off) : nullptr;
+    d.out = x.p.act(T, o.out);
+    d.zeros = x.p.w<const f16*>(x.net->zeros_off);
+    return d;
+}
+
 ConvLaunch conv_desc_cc(const DescCtx& x, int i, const ConvFold& f) {
     const Op& o = x.net->ops[i];
     const auto& T = *x.T;
@@ -300,6 +317,7 @@ int Planner::shapes() {
             case OP_MAXPOOL:
                 h = pool_out_dim(o, T[o.in].H); w = pool_out_dim(o, T[o.in].W);
                 break;
+            case OP_RESIZE: h = T[o.like].H; w = T[o.like].W; break;      // (`like` was added before this op: its shape is known)
             case OP_RCF: {                              // the reference's crop (rcf.py:95-99) and torch.cat of the five maps at the image size
                 for (int t : o.feats) GDT_REQUIRE(T[t].H > 0 && T[t].W > 0, "layer output would be empty for this input size");
                 for (size_t j = 0; j < o.feats.size(); ++j) {
@@ -656,6 +674,7 @@ int Planner::layout() {
                 break;
             }
             case OP_MAXPOOL: if (!st.skip) alloc_tensor(o.out); break;
+            case OP_RESIZE: alloc_tensor(o.out); break;
             case OP_CONCAT: alloc_tensor(o.out); break;       // (laid out on either route of its conv: which one runs is decided at launch time)
             case OP_GEM: st.aux_off[0] = arena.scratch((size_t)N * T[o.in].C * sizeof(float)); break;
             case OP_POOL_HEAD: {                        // the [N][R][D] pooled vectors and their normalised copy, two [N][D] rows (gdt_k_pool_head)
@@ -807,6 +826,9 @@ static const char* const PLAN_COUNT_NAMES[GDT_PLAN_COUNT] = {
     "stride2_shift", "dilated_convs", "dilated_special_forms", "head_launches", "head_map_reads", "conv4x4_launches", "conv4x4t_launches", "conv3x3_cat_launches",
     "attention_launches", "attention_map_reads"};
 const char* gdt_plan_count_name(int index) { return index >= 0 && index < GDT_PLAN_COUNT ? PLAN_COUNT_NAMES[index] : nullptr; }
+// ... and of the counters behind them (index from 0: counter GDT_PLAN_COUNT + index), filled when the caller's array has room for them
+static const char* const PLAN_COUNT_MORE_NAMES[GDT_PLAN_COUNT_ALL - GDT_PLAN_COUNT] = {"convt2x2_launches"};
+const char* gdt_plan_count_more_name(int index) { return index >= 0 && index < GDT_PLAN_COUNT_ALL - GDT_PLAN_COUNT ? PLAN_COUNT_MORE_NAMES[index] : nullptr; }
 
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts) {
     GDT_REQUIRE(net && counts && n_counts >= GDT_PLAN_COUNT && n >= 1 && rh >= 1 && rw >= 1, "plan summary arguments");
@@ -815,6 +837,7 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
     int rc = make_plan(net, n, rh, rw, plan, resize == 0);
     if (rc != GDT_OK) return rc;
     for (int k = 0; k < n_counts; ++k) counts[k] = 0;
+    const bool more = n_counts >= GDT_PLAN_COUNT_ALL;
     const DescCtx probe{net, &net->tensors, n, Ptrs{}};
     for (size_t i = 0; i < plan.steps.size(); ++i) {
         const Step& st = plan.steps[i];
@@ -846,6 +869,7 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
             counts[GDT_PLAN_CONV4X4_LAUNCHES] += gdt_conv4x4_halo_eligible(conv_desc_phase(probe, (int)i, o.phases[0], 0, fold_of(net, plan, (int)i)));
         if (o.has_cat_frag && o.cd.transposed && !st.skip) counts[GDT_PLAN_CONV4X4T_LAUNCHES] += gdt_conv4x4t_halo_eligible(conv_desc_t4(probe, (int)i));
         counts[GDT_PLAN_CONV3X3_CAT_LAUNCHES] += conv_takes_cat_kernel(probe, plan, (int)i);
+        if (more && o.has_t2 && !st.skip) counts[GDT_PLAN_CONVT2X2_LAUNCHES] += gdt_convt2x2_eligible(conv_desc_t2(probe, (int)i));
         if (o.dil != 1) {
             ++counts[GDT_PLAN_DILATED_CONVS];
             // what gdt_launch_conv / gdt_launch_conv_x3 would be handed for the conv as its own plain launch

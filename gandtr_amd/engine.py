@@ -167,6 +167,13 @@ class HipNet:
             raise ValueError("conv_transposed4 takes a [cin][cout][4][4] weight, got %s" % (tuple(w.shape),))
         return self._conv(a, b, w, bias, bn, stride=2, pad=1, transposed=1, relu=relu, out_f32_nchw=out_f32, act=act, in_relu=relu_a)
 
+    def conv_transposed2(self, x, weight, bias=None, bn=None, relu=False):
+        """nn.ConvTranspose2d(k2, s2, p0) of ``x`` (gdt_net_conv, transposed-2 route); ``weight`` [cin][cout][2][2]; internal output of 2H x 2W"""
+        w = _f32(weight)
+        if w.ndim != 4 or w.shape[2:] != (2, 2):
+            raise ValueError("conv_transposed2 takes a [cin][cout][2][2] weight, got %s" % (tuple(w.shape),))
+        return self._conv(x, -1, w, bias, bn, stride=2, pad=0, transposed=1, relu=relu)
+
     def conv_cat(self, a, b, weight, bias=None, bn=None, stride=1, pad=0, relu=False, out_f32=False, act=0):
         """nn.Conv2d of ``torch.cat([a, b], 1)`` (gdt_net_conv with two inputs); ``weight`` [cout][cin_a + cin_b][kh][kw], ``a``'s channels first"""
         w = _f32(weight)
@@ -184,6 +191,14 @@ class HipNet:
         if ceil and pad:
             raise ValueError("ceil-mode max-pooling takes no padding here")
         return self._add("maxpool", x, kernel, stride, pad, int(ceil))
+
+    RESIZE_MODES = {"bilinear": 0, "nearest": 1}                     # include/gandtr_hip.h, gdt_net_resize
+
+    def resize(self, x, like, mode="bilinear"):
+        """gdt_net_resize: ``F.interpolate(x, size=<the H x W of tensor like>, mode=mode)`` (bilinear: align_corners=False)"""
+        if mode not in self.RESIZE_MODES:
+            raise NotImplementedError("resize mode %r: only 'bilinear' and 'nearest' are on the HIP path" % (mode,))
+        return self._add("resize", x, like, self.RESIZE_MODES[mode])
 
     def gem_l2n(self, x, p, eps_gem=1e-6, eps_l2=1e-6):
         return self._add("gem_l2n", x, float(p), eps_gem, eps_l2)
@@ -283,9 +298,14 @@ class HipNet:
 
     def plan_summary(self, n, rh, rw, resize=False):
         """the planner's decisions for a geometry as a dict of named counts (GDT_PLAN_* in include/gandtr_hip.h): host logic, no device call"""
-        c = (ctypes.c_int * len(self.PLAN_KEYS))()
+        keys = self.PLAN_KEYS + _hip.plan_count_more_names()
+        c = (ctypes.c_int * len(keys))()
         _hip.check(self.lib.gdt_net_plan_summary(self.handle, n, rh, rw, int(bool(resize)), c, len(c)))
-        return dict(zip(self.PLAN_KEYS, c))
+        return dict(zip(keys, c))
+
+    def convt2x2_launches(self, n, rh, rw):
+        """transposed 2x2 convs of a geometry that run as one launch of convt2x2.hip (GDT_CONVT2X2=0: none) -- the planner's count"""
+        return self.plan_summary(n, rh, rw)["convt2x2_launches"]
 
     def conv4x4_launches(self, n, rh, rw):
         """conv launches of a geometry that run on the 4x4 patch kernel (conv4x4_halo.hip; GDT_CONV4X4_HALO=0: none) -- the planner's count"""
@@ -1009,6 +1029,110 @@ def build_p2p_unet(label, sd, device, cfg, precision="f16", pre_act=False, final
         return value
 
     net.out_slot = walk(layers, "outerblock.", x, True)
+    if finalize:
+        net.finalize()
+    return net
+
+
+def orig_unet_check(cfg):
+    """what the device path of ``orig_unet`` (components/model/network/unet.py, OrigUNet) does not do, refused before anything is built"""
+    if cfg["min_channels"] != 64:
+        raise NotImplementedError("HIP orig_unet needs min_channels = 64: its outconv is Conv2d(64, out_channels, 1) whatever min_channels is, so the forward "
+                                  "of min_channels = %d fails in torch as well" % cfg["min_channels"])
+    if cfg["in_channels"] > 8:
+        raise NotImplementedError("HIP orig_unet takes at most 8 input channels (the input pack kernel), got %d" % cfg["in_channels"])
+
+
+def build_orig_unet(sd, device, cfg, precision="f16", finalize=True):
+    """``orig_unet`` (unet.py, OrigUNet) as a HIP graph.  Per skip block: the two 3x3 convs of ``downconv`` with fused ReLU -> x1; MaxPool2d(2) of x1 as its own
+    op (x1 has a second reader, the skip, so the planner does not fold the pool into conv2's epilogue); the nested block; ``convT`` on the transposed-2 route
+    (conv_transposed2) -> x2; ``upconv.conv1`` as the conv of the pair (x1, x2) (conv_cat: the concatenation is never written where conv3x3_cat_halo.hip takes
+    the layer), ``upconv.conv2``.  ``outconv`` (1x1) writes the external fp32 NCHW output."""
+    if precision not in ("f16", "f16x3"):
+        raise NotImplementedError("orig_unet runs in 'f16' or 'f16x3'; %r is a ResnetGenerator mode" % (precision,))
+    orig_unet_check(cfg)
+    net, x = _open(device, precision, cfg["in_channels"])
+
+    def conv_block(value, prefix, pair=None):
+        w1, b1 = sd[prefix + "conv1.weight"], sd[prefix + "conv1.bias"]
+        if pair is None:
+            value = net.conv(value, w1, b1, pad=1, relu=True)
+        else:
+            value = net.conv_cat(pair[0], pair[1], w1, bias=b1, pad=1, relu=True)
+        return net.conv(value, sd[prefix + "conv2.weight"], sd[prefix + "conv2.bias"], pad=1, relu=True)
+
+    def block(value, prefix, level):
+        if level == cfg["nested_levels"]:                      # the innermost conv block
+            return conv_block(value, prefix)
+        x1 = conv_block(value, prefix + "downconv.")
+        inner = block(net.maxpool(x1, 2, 2, 0), prefix + "nested.", level + 1)
+        x2 = net.conv_transposed2(inner, sd[prefix + "convT.weight"], sd[prefix + "convT.bias"])
+        return conv_block(None, prefix + "upconv.", pair=(x1, x2))
+
+    y = block(x, "outerblock.", 0)
+    net.out_slot = net.conv(y, sd["outconv.weight"], sd["outconv.bias"], out_f32=True)
+    if finalize:
+        net.finalize()
+    return net
+
+
+DYNINT_CONV_OPTS = {"kernel_size": 4, "stride": 2, "padding": 1}
+DYNINT_UPCONV_OPTS = {"kernel_size": 3, "stride": 1, "padding": 1}
+
+
+def dynint_unet_check(cfg):
+    """what the device path of ``outconv_dynint_unet`` (unet.py, OutconvP2pUNetDynamicInterpolate) does not do, refused before anything is built"""
+    if cfg["upsample"] not in HipNet.RESIZE_MODES:
+        raise NotImplementedError("HIP outconv_dynint_unet resizes with 'bilinear' or 'nearest'; upsample = %r has no device form" % (cfg["upsample"],))
+    if cfg["conv_opts"] != DYNINT_CONV_OPTS:
+        raise NotImplementedError("HIP outconv_dynint_unet runs the reference's down convs, kernel_size 4, stride 2, padding 1; conv_opts %r has no device form" % (cfg["conv_opts"],))
+    if cfg["upconv_opts"] != DYNINT_UPCONV_OPTS:
+        raise NotImplementedError("HIP outconv_dynint_unet runs the reference's up convs, kernel_size 3, stride 1, padding 1; upconv_opts %r has no device form" % (cfg["upconv_opts"],))
+    if cfg["in_channels"] > 8:
+        raise NotImplementedError("HIP outconv_dynint_unet takes at most 8 input channels (the input pack kernel), got %d" % cfg["in_channels"])
+    if cfg["outconv_channels"] % 8:
+        raise NotImplementedError("HIP outconv_dynint_unet needs outconv_channels %% 8 == 0 (an internal tensor), got %d" % cfg["outconv_channels"])
+    if cfg["nested_levels"] < 1:
+        raise NotImplementedError("HIP outconv_dynint_unet needs at least one skip block (its last up conv reads 128 channels)")
+
+
+def build_dynint_unet(sd, device, cfg, precision="f16", finalize=True):
+    """``outconv_dynint_unet`` (unet.py, OutconvP2pUNetDynamicInterpolate) as a HIP graph; takes ANY image size: every map is floor(H / 2) of the one above and
+    is resized back to exactly the size its block received.  Per block: Conv(k4, s2, p1) [+ folded BatchNorm] + LeakyReLU(0.2) in the conv epilogue; the
+    nested block; a resize (gdt_net_resize) to the block input's size; Conv(k3, s1, p1) [+ BatchNorm] + ReLU (Dropout is the identity).  A block's value is the
+    PAIR (what it received, its up conv's result).  Bilinear and nearest resizing act per channel, so the two tensors of a pair are resized separately and the
+    conv behind them reads the pair through conv_cat: no concatenation is written where conv3x3_cat_halo.hip takes the layer."""
+    if precision not in ("f16", "f16x3"):
+        raise NotImplementedError("outconv_dynint_unet runs in 'f16' or 'f16x3'; %r is a ResnetGenerator mode" % (precision,))
+    dynint_unet_check(cfg)
+    mode = cfg["upsample"]
+    net, x = _open(device, precision, cfg["in_channels"])
+
+    def norm(key):
+        if key is None or not cfg["batchnorm"]:              # (the net's own last up conv has no BatchNorm)
+            return None
+        if key + ".running_mean" not in sd:
+            raise NotImplementedError("BatchNorm without running statistics (track_running_stats=False) has no inference form on the HIP path")
+        return _bn(sd, key)
+
+    def up(value, like, prefix, bn_key, out_f32=False):
+        """the conv at ``prefix`` + "0" (+ BatchNorm + ReLU) of ``value`` (a tensor or a pair) resized to the size of ``like``"""
+        w, b = sd[prefix + "0.weight"], sd.get(prefix + "0.bias")
+        if isinstance(value, tuple):
+            return net.conv_cat(net.resize(value[0], like, mode), net.resize(value[1], like, mode), w, bias=b, bn=norm(bn_key), pad=1, relu=True)
+        return net.conv(net.resize(value, like, mode), w, b, bn=norm(bn_key), pad=1, relu=True)
+
+    def block(value, prefix, level):
+        d = net.conv(value, sd[prefix + "down.0.weight"], sd.get(prefix + "down.0.bias"), bn=norm(prefix + "down.1"), stride=2, pad=1, leaky=0.2)
+        inner = d
+        if level + 1 < cfg["nested_levels"]:
+            inner = block(d, "%sdown.%d." % (prefix, 3 if cfg["batchnorm"] else 2), level + 1)
+        return value, up(inner, value, prefix + "up.", prefix + "up.1")
+
+    d0 = net.conv(x, sd["down.0.weight"], sd.get("down.0.bias"), stride=2, pad=1, leaky=0.2)
+    y = up(block(d0, "down.2.", 0), x, "up.", None)
+    k = cfg["outconv_kernel"]
+    net.out_slot = net.conv(y, sd["up.2.weight"], sd.get("up.2.bias"), pad=k // 2, out_f32=True)
     if finalize:
         net.finalize()
     return net

@@ -169,6 +169,59 @@ def p2p_unet_state(label, seed=0, in_channels=3, out_channels=3, out_gain=1.0, *
     return sd
 
 
+def orig_unet_state(seed=0, in_channels=3, out_channels=3, nested_levels=4, min_channels=64, out_gain=1.0):
+    """State dict of ``orig_unet`` (components/model/network/unet.py, OrigUNet), keys in the module's order: kaiming-scaled 3x3 conv weights, the
+    ConvTranspose2d(k2, s2) counted with the fan-in that meets one output pixel (cin: one tap), N(0, 0.1) biases everywhere; ``outconv`` is
+    N(0, out_gain * sqrt(2 / 64)), which leaves the output map O(1) behind ReLU layers of unit scale."""
+    sd = {}
+
+    def conv_block(prefix, cin, cout):
+        _conv(sd, seed, prefix + "conv1", cout, cin, 3, True)
+        _conv(sd, seed, prefix + "conv2", cout, cout, 3, True)
+
+    def block(prefix, level, cin):
+        c = min_channels * 2 ** level
+        if level == nested_levels:
+            conv_block(prefix, cin, c)
+            return
+        conv_block(prefix + "downconv.", cin, c)
+        block(prefix + "nested.", level + 1, c)
+        _conv(sd, seed, prefix + "convT", c, 2 * c, 2, True, math.sqrt(2.0 / (2 * c)), transposed=True)
+        conv_block(prefix + "upconv.", 2 * c, c)
+
+    block("outerblock.", 0, in_channels)
+    _conv(sd, seed, "outconv", out_channels, 64, 1, True, out_gain * math.sqrt(2.0 / 64))
+    return sd
+
+
+def dynint_unet_state(seed=0, in_channels=3, out_channels=3, nested_levels=7, outconv_channels=32, outconv_kernel=3, batchnorm=False, out_gain=1.0):
+    """State dict of ``outconv_dynint_unet`` (components/model/network/unet.py, OutconvP2pUNetDynamicInterpolate) with the reference's default conv options,
+    keys in the module's order (a block's ``down`` Sequential -- conv, [BatchNorm], LeakyReLU, [the nested block] -- in front of its ``up``): kaiming-scaled conv
+    weights, N(0, 0.1) biases, non-trivial BatchNorm statistics and affine parameters; the last conv is N(0, out_gain * sqrt(2 / fan_in))."""
+    sd = {}
+    widths = ([(64, 128), (128, 256), (256, 512)] + [(512, 512)] * max(0, nested_levels - 3))[:nested_levels]
+
+    def block(prefix, level):
+        outer, inter = widths[level]
+        last = level + 1 == nested_levels
+        _conv(sd, seed, prefix + "down.0", inter, outer, 4, True)
+        if batchnorm:
+            _bn(sd, seed, prefix + "down.1", inter)
+        if not last:
+            block("%sdown.%d." % (prefix, 3 if batchnorm else 2), level + 1)
+        _conv(sd, seed, prefix + "up.0", outer, inter * (1 if last else 2), 3, True)
+        if batchnorm:
+            _bn(sd, seed, prefix + "up.1", outer)
+
+    _conv(sd, seed, "down.0", 64, in_channels, 4, True)
+    if nested_levels:
+        block("down.2.", 0)
+    _conv(sd, seed, "up.0", outconv_channels, 128, 3, True)
+    k = outconv_kernel
+    _conv(sd, seed, "up.2", out_channels, outconv_channels, k, True, out_gain * math.sqrt(2.0 / (outconv_channels * k * k)))
+    return sd
+
+
 def patchsample_state(seed=0, channels=(128, 256, 256, 256), nc=256, gain=1.0):
     """PatchSampleF state dict (p2p_networks.py:628-636): per feature map i of ``channels[i]`` channels ``mlp_<i>.0`` Linear(channels[i], nc) and
     ``mlp_<i>.2`` Linear(nc, nc), N(0, gain * sqrt(2 / fan_in)) weights and N(0, 0.1) biases: on O(1) features the hidden and the output rows are O(1)"""

@@ -80,7 +80,8 @@ typedef struct gdt_conv_desc {
     int pad;              /* padding on every side                                                                 */
     int pad_reflect;      /* 0: zeros (Conv2d padding=p), 1: nn.ReflectionPad2d(p) in front of the conv            */
     int transposed;       /* 1: nn.ConvTranspose2d(k3, s2, p1, output_padding 1)  (p2p_networks.py:295-298), or
-                             nn.ConvTranspose2d(k4, s2, p1): the transposed-4 route below                         */
+                             nn.ConvTranspose2d(k4, s2, p1): the transposed-4 route below, or
+                             nn.ConvTranspose2d(k2, s2, p0): the transposed-2 route below                         */
     int relu;             /* fuse nn.ReLU after bias (+BN) (+residual)                                             */
     int out_f32_nchw;     /* 1: result is an EXTERNAL fp32 NCHW output (generator head), 0: internal fp16 tensor   */
     int act;              /* external output only: 0 none, 1 tanh (p2p_networks.py:311), 2 sigmoid                 */
@@ -100,7 +101,7 @@ typedef struct gdt_conv_weights {
 
 /* Conv2d / ConvTranspose2d of in_a, or of the channel concatenation torch.cat([in_a, in_b], 1) (in_b = -1: one input).  residual_tensor >= 0 adds that tensor
  * before the ReLU (ResnetBlock.forward p2p_networks.py:505; torchvision Bottleneck).  out_tensor receives the new tensor id, or the external output slot
- * index when out_f32_nchw = 1.  A refused layer leaves nothing in the graph.  The descriptor selects one of three routes:
+ * index when out_f32_nchw = 1.  A refused layer leaves nothing in the graph.  The descriptor selects one of four routes:
  *
  * Transposed-4 (desc->transposed, 4x4 kernel, stride 2, pad 1): [nn.ReLU] nn.ConvTranspose2d(cin_a + cin_b, cout, kernel_size=4, stride=2, padding=1)
  *   (+ folded BatchNorm2d) (+ ReLU: desc->relu): the up-convolutions of UnetSkipConnectionBlock (p2p_networks.py:205-221, :236).  in_b = -1: one input (the
@@ -109,6 +110,14 @@ typedef struct gdt_conv_weights {
  *   residual, no LeakyReLU, no dilation.  In f16, layers with cin_a % 64 == 0, cin_b % 64 == 0, cout % 64 == 0 and an internal output run as ONE launch of
  *   conv4x4t_halo.hip, which reads both inputs itself; everything else (and everything with GDT_CONV4X4T_HALO=0) runs as a copy that writes the
  *   concatenation (+ ReLU) once and the four sub-pixel phases of 2 x 2 taps on the generic implicit-GEMM kernels (GDT_PLAN_CONV4X4T_LAUNCHES).
+ *
+ * Transposed-2 (desc->transposed, 2x2 kernel, stride 2, pad 0): nn.ConvTranspose2d(cin, cout, 2, stride=2) (+ folded BatchNorm2d) (+ ReLU: desc->relu): the
+ *   up-convolution of OrigUNet.SkipConnBlock (unet.py, convT).  Kernel size = stride: output pixel (2y + dy, 2x + dx) = bias + in(y, x) . W[:, :, dy, dx], one
+ *   source pixel each.  in_b must be -1; weight [cin][cout][2][2]; internal output tensor of 2H x 2W (cout % 8 == 0; out_f32_nchw and act must be 0).
+ *   Precision modes f16 and f16x3; no residual, no LeakyReLU, no dilation, no reflection padding.  In f16, layers with cin % 64 == 0 and cout % 64 == 0 run
+ *   as ONE launch of convt2x2.hip -- a GEMM over [4 cout][cin] weights with columns ordered [dy][dx][co], whose stores are the depth-to-space; everything
+ *   else (and everything with GDT_CONVT2X2=0) runs as four sub-pixel phase launches of one 1 x 1 tap each on the generic implicit-GEMM kernels
+ *   (GDT_PLAN_CONVT2X2_LAUNCHES).
  *
  * Conv of a concatenation (in_b >= 0 otherwise): nn.Conv2d(cin_a + cin_b, cout, k, stride, padding) (+ folded BatchNorm2d) (+ ReLU): the
  *   nn.Conv2d(128, 64, 3, padding=1) that AlignedP2pUNet applies to the output [x, nested(x)] of its inner SkipConnBlock (unet.py, AlignedP2pUNet.__init__ /
@@ -140,6 +149,13 @@ int gdt_net_instance_norm(gdt_net* net, int in_tensor, float eps, int relu, floa
  * (2, 1); rcf.py:43-46): torch's output size -- ceil, then one less when the last window would start outside the input; a window that hangs over the edge
  * takes the maximum of its pixels inside.  Fused into its producer's epilogue only where the result equals floor mode (2 x 2, stride 2, even sizes). */
 int gdt_net_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad, int ceil_mode, int* out_tensor);
+
+/* F.interpolate(in_tensor, size = the H x W of like_tensor, mode = "bilinear" (0; align_corners=False) | "nearest" (1)): the upsampling of
+ * OutconvP2pUNetDynamicInterpolate (unet.py), which resizes a block's result back to the size the block received, whatever that size is.  The output has
+ * in_tensor's channels and like_tensor's size, resolved per geometry at shape inference; like_tensor is read for its shape only.  torch's coordinates:
+ * scale = in / out; bilinear src = max(scale (dst + 0.5) - 0.5, 0), i0 = floor(src), i1 = i0 + (i0 < in - 1), lambda = src - i0; nearest
+ * i = min(floor(dst scale), in - 1).  fp32 arithmetic, one store in the tensor's type; equal sizes are a bit-exact copy.  All precision modes. */
+int gdt_net_resize(gdt_net* net, int in_tensor, int like_tensor, int mode, int* out_tensor);
 
 /* l2n(gem(x, p, eps_gem), eps_l2): cirtorch layers/functional.py:21-22,:130-131.  External output: fp32 [N][D]
  * row-major, i.e. the memory the reference's `o.permute(1,0)` view aliases (imageretrievalnet.py:123). */
@@ -289,16 +305,22 @@ enum {
                                         the division by the maximum when normalize_max)                                                              */
     GDT_PLAN_ATTENTION_MAP_READS,    /* "attention_map_reads": launches of such heads that read the feature map (two per op: the norm pass and the
                                         weighted pooling pass)                                                                                        */
-    GDT_PLAN_COUNT
+    GDT_PLAN_COUNT,                  /* the counters gdt_plan_count_name names and every caller's array holds (a fixed set)                          */
+    GDT_PLAN_CONVT2X2_LAUNCHES = GDT_PLAN_COUNT,
+                                     /* "convt2x2_launches": transposed 2x2 convs that run as one launch of convt2x2.hip (none with GDT_CONVT2X2=0 --
+                                        then four phase launches each)                                                                                */
+    GDT_PLAN_COUNT_ALL
 };
-/* name of counter `index` (the quoted names above), NULL past the last index and for negative ones */
+/* name of counter `index` (the quoted names above), NULL past the last index (GDT_PLAN_COUNT - 1) and for negative ones */
 const char* gdt_plan_count_name(int index);
-/* fills counts[0 .. GDT_PLAN_COUNT); n_counts >= GDT_PLAN_COUNT */
+/* name of counter GDT_PLAN_COUNT + `index`: the counters added behind the fixed set; NULL past the last one and for negative indices */
+const char* gdt_plan_count_more_name(int index);
+/* fills counts[0 .. GDT_PLAN_COUNT), and counts[GDT_PLAN_COUNT .. GDT_PLAN_COUNT_ALL) as well when n_counts >= GDT_PLAN_COUNT_ALL; n_counts >= GDT_PLAN_COUNT */
 int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* counts, int n_counts);
 
 /* Per-op timing for bench.py's roofline line: when enabled, gdt_net_forward records HIP events on the caller's stream
  * around every op.  gdt_net_profile_read (after the forward) returns per op: kind (0 input, 1 conv, 2 instance-norm,
- * 3 maxpool, 4 gem, 5 tap, 6 hed, 7 rcf head, 8 pool head, 9 channel concatenation, 10 median head), the conv kernel variant (BM*1000+BN: conv_igemm_kernel<BM,BN>; 900000+BN:
+ * 3 maxpool, 4 gem, 5 tap, 6 hed, 7 rcf head, 8 pool head, 9 channel concatenation, 10 median head, 11 resize), the conv kernel variant (BM*1000+BN: conv_igemm_kernel<BM,BN>; 900000+BN:
  * conv3x3_halo_kernel<BN>), elapsed ms and the algorithmic FLOPs.  No reference counterpart (the reference has wall-clock StopWatch only, mdir/tools/stats.py:48-68). */
 int gdt_net_set_profiling(gdt_net* net, int enable);
 int gdt_net_profile_read(gdt_net* net, int max_ops, int* n_ops, int* kinds, int* tile_n, double* ms, double* flops);
