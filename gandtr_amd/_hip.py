@@ -209,6 +209,16 @@ SIGNATURES = {
     "gdt_clahe_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "gdt_clahe_lab_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), POINTER(c_float),
                                   POINTER(c_float), c_double, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "gdt_photometric_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "gdt_lab_lightness_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_void_p]),
+    "gdt_rgb2lab_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_void_p]),
+    "gdt_hist256_f32": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p]),
+    "gdt_match_channel_f32": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gdt_match_histogram_lab_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), POINTER(c_float),
+                                            POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gdt_gamma_channel_f32": (c_int, [c_void_p, c_void_p, c_int, c_long, c_double, c_void_p, c_void_p, c_void_p]),
+    "gdt_gamma_equalize_lab_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), POINTER(c_float),
+                                           POINTER(c_float), c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

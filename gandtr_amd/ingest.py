@@ -220,13 +220,16 @@ class DeviceTransform:
     H x W x 3 tensors on the device and returns the fp32 3 x h x w tensors the network expects.  Supported steps: pil2np, apply_clahe[:clip[:grid[:lab]]],
     totensor, normalize and the geometric steps scalecrop:W_H[:lo_hi], centerscalecrop:W_H[:s], downscale:N, center_crop:W_H, square_crop, mirror[:p]
     (augmentation_transforms.py:24-164) in the chain shape ``crops / mirrors, at most one resampling step, mirrors``; apply_clahe comes after them.
+    With ``photometric=True`` a chain may hold, in apply_clahe's place, ONE of ``match_histogram:NAME[:lab]`` or ``gamma_equalize:T[:lab]``
+    (photometric_transforms.py:56-104; gandtr_amd/photometric.py); without it those names raise KeyError like every unknown step.
 
     ``__call__(img, imsize=None)`` serves chains without geometric steps (the hub's).  A chain with them runs as ``plan`` (host, draws the random numbers
     the reference draws) + ``apply_many`` (device, one crop-resize launch for a whole batch)."""
 
-    def __init__(self, augmentations, mean_std):
+    def __init__(self, augmentations, mean_std, photometric=False):
         self.mean, self.std = [float(v) for v in mean_std[0]], [float(v) for v in mean_std[1]]
         self.clahe_clip, self.clahe_grid, self.normalize = None, 8, False
+        self.photometric = None                                            # ("match_histogram", name) or ("gamma_equalize", target), with photometric=True
         self.spec = augmentations
         self.geometric = []                                                # (name, host transform): the one statement of each step's geometry
         resampled = False
@@ -237,13 +240,31 @@ class DeviceTransform:
             if name == "normalize":
                 self.normalize = True
             elif name == "apply_clahe":
+                if self.photometric is not None:
+                    raise NotImplementedError("one of apply_clahe, match_histogram, gamma_equalize per chain on the HIP path: '%s'" % augmentations)
                 self.clahe_clip = float(args[0]) if args else 4.0          # ApplyClahe defaults (photometric_transforms.py:31)
                 self.clahe_grid = int(args[1]) if len(args) > 1 else 8
                 if len(args) > 2 and args[2].lower() != "lab":
                     raise NotImplementedError("Colorspace %s is not supported on the HIP path" % args[2])
+            elif photometric and name in ("match_histogram", "gamma_equalize"):
+                # (photometric_transforms.py:56-104) one of them, in the position apply_clahe may take; it normalises the result itself
+                if self.photometric is not None or self.clahe_clip is not None:
+                    raise NotImplementedError("one of apply_clahe, match_histogram, gamma_equalize per chain on the HIP path: '%s'" % augmentations)
+                if not args:
+                    raise TypeError("%s needs its %s" % (name, "histogram" if name == "match_histogram" else "target"))
+                if len(args) > 1 and args[1].lower() != "lab":
+                    raise NotImplementedError("Colorspace %s is not supported on the HIP path" % args[1])
+                if name == "gamma_equalize":
+                    target = float(args[0])
+                    assert target > 0 and target < 1, target
+                    self.photometric = (name, target)
+                else:
+                    self.photometric = (name, args[0])
             elif name in _RESAMPLERS + _CROPS + ("mirror",):
                 if self.clahe_clip is not None:
                     raise NotImplementedError("apply_clahe before a geometric step is not supported on the HIP path: '%s'" % augmentations)
+                if self.photometric is not None:
+                    raise NotImplementedError("%s before a geometric step is not supported on the HIP path: '%s'" % (self.photometric[0], augmentations))
                 if resampled and name != "mirror":
                     raise NotImplementedError("only mirrors may follow a resampling step on the HIP path: '%s'" % augmentations)
                 resampled = resampled or name in _RESAMPLERS
@@ -258,7 +279,17 @@ class DeviceTransform:
         if self.geometric:
             raise NotImplementedError("a chain with geometric steps runs through plan() + apply_many(): '%s'" % self.spec)
         mean, std = self._mean_std()
+        if self.photometric is not None:
+            return self._photometric(ingest(img, imsize, [0.0] * 3, [1.0] * 3)[None])[0]
         return ingest(img, imsize, mean, std, self.clahe_clip, self.clahe_grid)
+
+    def _photometric(self, unit):
+        """the chain's match_histogram / gamma_equalize step on a batch of unit images N x 3 x h x w, normalised on the way out"""
+        from . import photometric
+        kind, arg = self.photometric
+        if kind == "match_histogram":
+            return photometric.match_histogram(unit, arg, None, self._mean_std())
+        return photometric.gamma_equalize(unit, arg, None, self._mean_std())
 
     def plan(self, shapes, rng=random):
         """One ``Geometry`` per pic of ONE item (``shapes``: their decoded (h, w)).  Pure host code; draws from ``rng`` exactly what the reference's
@@ -294,7 +325,8 @@ class DeviceTransform:
         on decoded 8-bit data).  Items that end with different sizes raise RuntimeError, as ``default_collate`` does."""
         n, ncols = len(decoded_items), len(decoded_items[0])
         dev = decoded_items[0][0].device
-        mean_std = self._mean_std() if self.clahe_clip is None else None         # (CLAHE takes the unit image and normalises itself)
+        own_norm = self.clahe_clip is not None or self.photometric is not None
+        mean_std = None if own_norm else self._mean_std()                        # (CLAHE and the photometric steps take the unit image and normalise themselves)
         columns = []
         for c in range(ncols):
             sizes = [plans[i][c].out for i in range(n)]
@@ -324,6 +356,8 @@ class DeviceTransform:
         if self.clahe_clip is not None:
             from . import clahe
             columns = [clahe.clahe_lab(col, self.clahe_clip, self.clahe_grid, None, self._mean_std()) for col in columns]
+        if self.photometric is not None:
+            columns = [self._photometric(col) for col in columns]
         return columns
 
     def __repr__(self):

@@ -610,6 +610,41 @@ int gdt_clahe_lab_f32(const float* x, float* y, int n, int h, int w, const float
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Photometric normalisation of the lightness channel: histogram equalisation / matching and gamma equalisation
+ * Replaces the per-image numpy / cv2 / scipy path of
+ *   channel_histogram_matching, channel2channel_histogram_matching   mdir/components/data/transform/functional.py:96-109
+ *   channel_gamma_matching (scipy.optimize.newton, secant form)       functional.py:116-130
+ *   image_histogram_matching / image_gamma_matching                   functional.py:103-104 / :132-133 (apply_lightness_transform :81-85)
+ *   rgb2normspace "lab" (ToColorspace, AddIntensityFromRgb, AddClaheFromRgb)   functional.py:28-36, channel_transforms.py:67-89,
+ *                                                                              photometric_transforms.py:10-25
+ * All buffers are device buffers unless stated; planes are fp32 [n][count], images fp32 [n][3][h][w] RGB with the affines of gdt_clahe_lab_f32
+ * (host float[3], NULL = identity).  `grid`: 513 device doubles computed by the HOST with numpy -- the 257 histogram edges
+ * np.linspace(-1/510, 1 + 1/510, 257) followed by the 256 centres np.linspace(0, 1, 256) (functional.py:92-93).
+ * gdt_lab_lightness_f32: lightness [n][h][w] = L / 100.    gdt_rgb2lab_f32: lab [n][3][h][w] = (L / 100, (a + 128) / 255, (b + 128) / 255).
+ * gdt_hist256_f32: hist [n][256] uint32 = np.histogram(plane, edges)[0] (the call clears it first).
+ * mode: 0 "eq", 1 target_cdf (256 device doubles: np.cumsum of the target histogram), 2 the second planes chan1 [n][count1] (channel form only).
+ * gdt_match_channel_f32: out = float32(np.interp(chan, centres, table)), table = cdf0 * centres[255] | np.interp(cdf0, target_cdf | cdf1, centres).
+ * gdt_match_histogram_lab_f32: RGB -> Lab, the same on L / 100, Lab -> RGB, y = (rgb - out_mean) / out_std.
+ * gdt_gamma_channel_f32 / gdt_gamma_equalize_lab_f32: per plane / image gamma with mean(L^gamma) = target (0 < target < 1) by the secant iteration of
+ *   scipy.optimize.newton (tol 1e-4, 50 iterations, the reference's fall-back 0.1 | 10 and clip to [0.1, 10]), solved on the device in one launch, one
+ *   workgroup per image; out = L^gamma.  gamma [n] device doubles (written), evaluations [n] device ints or NULL (function evaluations of each solve).
+ * workspace: device scratch of gdt_photometric_workspace_bytes(n, h, w) (histograms, tables, the fp32 lightness plane); planes pass h = 1, w = count.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int gdt_photometric_workspace_bytes(int n, int h, int w, size_t* bytes);
+int gdt_lab_lightness_f32(const float* x, float* lightness, int n, int h, int w, const float* in_scale, const float* in_shift, void* stream);
+int gdt_rgb2lab_f32(const float* x, float* lab, int n, int h, int w, const float* in_scale, const float* in_shift, void* stream);
+int gdt_hist256_f32(const float* chan, int n, long count, const double* grid, unsigned* hist, void* stream);
+int gdt_match_channel_f32(const float* chan, float* out, int n, long count, int mode, const double* target_cdf, const float* chan1, long count1,
+                          const double* grid, void* workspace, size_t workspace_bytes, void* stream);
+int gdt_match_histogram_lab_f32(const float* x, float* y, int n, int h, int w, const float* in_scale, const float* in_shift, const float* out_mean,
+                                const float* out_std, int mode, const double* target_cdf, const double* grid, void* workspace, size_t workspace_bytes,
+                                void* stream);
+int gdt_gamma_channel_f32(const float* chan, float* out, int n, long count, double target, double* gamma, int* evaluations, void* stream);
+int gdt_gamma_equalize_lab_f32(const float* x, float* y, int n, int h, int w, const float* in_scale, const float* in_shift, const float* out_mean,
+                               const float* out_std, double target, double* gamma, int* evaluations, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Image ingest after decoding ("next" row of SURVEY.md section 8f, rank 3)
  * Replaces  img.thumbnail((s, s), LANCZOS)  (mdir/external/cirtorch/datasets/datahelpers.py:75-82, genericdataset.py:66-102)
  * and  pil2np | totensor | normalize  (mdir/components/data/transform/core_transforms.py:35-100) for a decoded image that
