@@ -63,8 +63,8 @@ enum GdtLiveKnob { GDT_LIVE_KNOBS(GDT_LIVE_KNOB_ID) GDT_LIVE_KNOB_COUNT };
 #define GDT_KNOB_LATCHED(fn, name, dflt) [[maybe_unused]] static int fn() { static const int v = gdt_env_int(name, dflt); return v; }
 #define GDT_KNOB_LATCHED_SET(fn, name) [[maybe_unused]] static bool fn() { static const bool v = gdt_env_set(name); return v; }      // presence, whatever the value
 #define GDT_KNOB_LIVE(fn, id, dflt) [[maybe_unused]] static int fn() { return gdt_env_int(GDT_LIVE_KNOB_NAMES[GDT_LIVE_##id], dflt); }
-// LAUNCH knobs are read whenever a launcher chooses between two kernels that compute the same layer on the same plan (same tensors, same workspace): one
-// process can A/B them, and nothing that caches a plan needs to know them.
+// LAUNCH knobs are read whenever a geometry is planned (every forward plans its own) or a launcher picks a kernel: they choose between kernels that compute the
+// same layer on the same LAYOUT (same tensors, same workspace).  One process can A/B them, and nothing that caches a layout needs to know them.
 #define GDT_KNOB_LAUNCH(fn, name, dflt) [[maybe_unused]] static int fn() { return gdt_env_int(name, dflt); }
 
 // ---- a kernel's launcher: its dynamic-LDS set-up PER DEVICE, its cached CU figure, its launch ----

@@ -32,6 +32,8 @@ struct ConvStep {
     f16* tptr(int t) const { return (f16*)(c.ws + c.T[t].off); }
     double tbytes(int t) const { return (double)c.n * c.T[t].H * c.T[t].W * c.T[t].C * (double)net->esize(); }
     void variant(int v) const { if (net->profiling) net->last_variant[stp.op] = v; }
+    // a launcher that names the kernel variant it took
+    int launch(int (*launcher)(const ConvLaunch&, hipStream_t, int*), const ConvLaunch& d) const { int v = 0; const int rc = launcher(d, st, &v); variant(v); return rc; }
 };
 
 // weights and channel counts of a fused Bottleneck step (the same for every geometry)
@@ -140,10 +142,7 @@ int exec_s2(const ConvStep& s, const ConvFold& f) {
     const ConvLaunch d = conv_desc_s2(s.x, s.stp.op, f);
     if (s.net->precision == 1) {
         GDT_REQUIRE(gdt_conv_halo_x3_taps_eligible(d), "planned stride-2 shift launch (f16x3) is not eligible at run time");
-        int variant = 0;
-        const int rc = gdt_launch_conv_x3(d, s.st, &variant);
-        s.variant(variant);
-        return rc;
+        return s.launch(gdt_launch_conv_x3, d);
     }
     GDT_REQUIRE(gdt_conv_halo_c_s2_eligible(d), "planned stride-2 shift launch is not eligible at run time");
     s.variant(990256);
@@ -155,10 +154,7 @@ int exec_pairs(const ConvStep& s, const ConvFold& f) {
     for (size_t p = 0; p < s.o.pairs.size(); ++p) {
         const ConvLaunch d = conv_desc_pair(s.x, s.stp.op, (int)p, f);
         GDT_REQUIRE(gdt_conv_halo_x3_taps_eligible(d), "planned paired-phase launch is not eligible at run time");
-        int variant = 0;
-        const int rc = gdt_launch_conv_x3(d, s.st, &variant);
-        s.variant(variant);
-        if (rc != GDT_OK) return rc;
+        GDT_CHECK(s.launch(gdt_launch_conv_x3, d));
     }
     return GDT_OK;
 }
@@ -194,54 +190,54 @@ int exec_phases(const ConvStep& s, const ConvFold& f) {
                                   o.cd.pad_reflect, o.cd.act, s.st);
 }
 
+// The convs that read their sources themselves: ConvTranspose2d(k4,s2,p1) of one or two tensors (conv4x4t_halo.hip), ConvTranspose2d(k2,s2,p0) as one launch
+// (convt2x2.hip), Conv2d(k3,s1,p1) of two tensors (conv3x3_cat_halo.hip).  Bytes: the concatenation (where the graph has one) is neither written nor read; its sources are read once
+void book_unwritten_concat(const ConvStep& s) {
+    if (!s.net->profiling || !s.book || s.o.cat_op < 0) return;
+    const Op& oc = s.net->ops[s.o.cat_op];
+    s.net->last_bytes[s.stp.op] += s.tbytes(oc.in) + (oc.res >= 0 ? s.tbytes(oc.res) : 0.0) - s.tbytes(s.o.in);
+}
+
+int exec_t4(const ConvStep& s) {
+    const ConvLaunch d = conv_desc_t4(s.x, s.stp.op);
+    GDT_REQUIRE(gdt_conv4x4t_halo_eligible(d), "planned transposed 4x4 launch is not eligible at run time");
+    book_unwritten_concat(s);
+    return s.launch(gdt_launch_conv4x4t_halo, d);
+}
+
+int exec_t2(const ConvStep& s) {
+    const ConvLaunch d = conv_desc_t2(s.x, s.stp.op);
+    GDT_REQUIRE(gdt_convt2x2_eligible(d), "planned transposed 2x2 launch is not eligible at run time");
+    return s.launch(gdt_launch_convt2x2, d);
+}
+
+int exec_cat(const ConvStep& s, const ConvFold& f) {
+    const ConvLaunch d = conv_desc_cc(s.x, s.stp.op, f);
+    GDT_REQUIRE(gdt_conv3x3_cat_halo_eligible(d), "planned launch of a conv of a concatenation is not eligible at run time");
+    book_unwritten_concat(s);
+    return s.launch(gdt_launch_conv3x3_cat_halo, d);
+}
+
 int exec_conv(const ConvStep& s) {
-    gdt_net* net = s.net;
-    const Step& stp = s.stp;
-    if (stp.skip) return GDT_OK;           // second / third conv of a fused Bottleneck
-    if (stp.bneck) return exec_bneck(s);
-    if (stp.direct) return exec_stem_direct(s);
-    if (stp.xexp) return exec_xexp(s);
-    if (stp.kcat) return exec_kcat(s);
-    if (s.o.has_cat_frag && s.o.cd.transposed) {   // ConvTranspose2d(k4,s2,p1) from its own inputs (conv4x4t_halo.hip) -- else the phase launches below, over the concatenation
-        const ConvLaunch d = conv_desc_t4(s.x, stp.op);
-        if (gdt_conv4x4t_halo_eligible(d)) {
-            int variant = 0;
-            const int rc = gdt_launch_conv4x4t_halo(d, s.st, &variant);
-            s.variant(variant);
-            if (net->profiling && s.book && s.o.cat_op >= 0) {      // bytes: the concatenation is neither written nor read; its two sources are read once
-                const Op& oc = net->ops[s.o.cat_op];
-                const double src = s.tbytes(oc.in) + (oc.res >= 0 ? s.tbytes(oc.res) : 0.0);
-                net->last_bytes[stp.op] += src - s.tbytes(s.o.in);
-            }
-            return rc;
-        }
+    const ConvFold f = fold_of(s.net, s.c.plan, s.stp.op);      // InstanceNorm(+ReLU) of the producer applied while staging the input, statistics, pool
+    // bytes the folded form must move on top of the conv's own: the residual tensor read, the normalised tensor written back (a norm is folded into the last four
+    // routes only: no other pass takes a conv that has one, and conv3x3_cat_halo.hip refuses it)
+    if (f.norm >= 0 && s.net->profiling) s.net->last_bytes[s.stp.op] += s.tbytes(s.net->ops[f.norm].in) * ((f.res ? 1.0 : 0.0) + (f.wb ? 1.0 : 0.0));
+    switch (s.stp.route) {
+        case ROUTE_SKIP: return GDT_OK;    // done by another conv's launch
+        case ROUTE_BNECK: return exec_bneck(s);
+        case ROUTE_DIRECT: return exec_stem_direct(s);
+        case ROUTE_XEXP: return exec_xexp(s);
+        case ROUTE_KCAT: return exec_kcat(s);
+        case ROUTE_T4: return exec_t4(s);
+        case ROUTE_T2: return exec_t2(s);
+        case ROUTE_CAT: return exec_cat(s, f);
+        case ROUTE_CTF: return exec_ctf(s, f);
+        case ROUTE_S2: return exec_s2(s, f);
+        case ROUTE_PAIRS: return exec_pairs(s, f);
+        case ROUTE_OWN: return exec_phases(s, f);
     }
-    if (s.o.has_t2) {                              // ConvTranspose2d(k2,s2,p0) as one launch (convt2x2.hip) -- else the four phase launches below
-        const ConvLaunch d = conv_desc_t2(s.x, stp.op);
-        if (gdt_convt2x2_eligible(d)) {
-            int variant = 0;
-            const int rc = gdt_launch_convt2x2(d, s.st, &variant);
-            s.variant(variant);
-            return rc;
-        }
-    }
-    if (conv_takes_cat_kernel(s.x, s.c.plan, stp.op)) {     // Conv2d(k3,s1,p1) from its own two inputs (conv3x3_cat_halo.hip) -- else the conv of one tensor below, over the concatenation
-        int variant = 0;
-        const int rc = gdt_launch_conv3x3_cat_halo(conv_desc_cc(s.x, stp.op, fold_of(net, s.c.plan, stp.op)), s.st, &variant);
-        s.variant(variant);
-        if (net->profiling && s.book) {                     // bytes: the concatenation is neither written nor read; its two sources are read once
-            const Op& oc = net->ops[s.o.cat_op];
-            net->last_bytes[stp.op] += s.tbytes(oc.in) + s.tbytes(oc.res) - s.tbytes(s.o.in);
-        }
-        return rc;
-    }
-    const ConvFold f = fold_of(net, s.c.plan, stp.op);      // InstanceNorm(+ReLU) of the producer applied while staging the input, statistics, pool
-    if (f.norm >= 0 && net->profiling)        // bytes the folded form must move on top of the conv's own: the residual tensor read, the normalised tensor written back
-        net->last_bytes[stp.op] += s.tbytes(net->ops[f.norm].in) * ((f.res ? 1.0 : 0.0) + (f.wb ? 1.0 : 0.0));
-    if (stp.ctf) return exec_ctf(s, f);
-    if (stp.s2) return exec_s2(s, f);
-    if (stp.ctp) return exec_pairs(s, f);
-    return exec_phases(s, f);
+    GDT_REQUIRE(false, "conv step without a route");
 }
 
 // One op of the graph on one geometry (`defer`, `book`: see ConvStep)
@@ -255,17 +251,15 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
     const int f32 = net->precision ? 1 : 0;      // activation element type handed to the helper kernels: fp32 in both split modes
     const Op& o = net->ops[stp.op];
     int rc = GDT_OK;
+    // nothing to launch: the input the stem conv reads itself, a conv or max-pool done by another conv's launch, a concatenation whose conv reads the sources
+    if (stp.route == ROUTE_SKIP) return rc;
         switch (o.kind) {
             case OP_INPUT: {
                 const int resize = (rh != h || rw != w) ? 1 : 0;
-                if (stp.direct) break;                       // the stem conv reads x itself (planned only for calls that do not resize)
-                rc = gdt_k_pack_input(c.x, tptr(o.out), stp.aug ? 2 : f32, n, o.in_c, h, w, rh, rw, c.rscale, resize, o.perm, o.scale, o.shift, st,
-                                      o.filter.kind ? &o.filter : nullptr);
-                break;
+                return gdt_k_pack_input(c.x, tptr(o.out), stp.aug ? 2 : f32, n, o.in_c, h, w, rh, rw, c.rscale, resize, o.perm, o.scale, o.shift, st,
+                                        o.filter.kind ? &o.filter : nullptr);
             }
-            case OP_CONV:
-                rc = exec_conv(ConvStep{net, c, stp, o, st, defer, book, DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}});
-                break;
+            case OP_CONV: return exec_conv(ConvStep{net, c, stp, o, st, defer, book, DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}});
             case OP_INORM: {
                 const Tensor& ti = T[o.in];
                 if (stp.norm_into >= 0)     // the consuming conv applies it: only mean / rstd are produced here
@@ -283,30 +277,22 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                 break;
             }
             case OP_CONCAT: {
-                const Op& oc = net->ops[o.cat_for];
-                if (oc.has_cat_frag && oc.cd.transposed && gdt_conv4x4t_halo_eligible(conv_desc_t4(DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}, o.cat_for))) break;   // the conv reads the sources itself
-                if (conv_takes_cat_kernel(DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}, plan, o.cat_for)) break;           // (likewise, conv3x3_cat_halo.hip)
                 const Tensor& ta = T[o.in]; const Tensor& to = T[o.out];
-                rc = gdt_k_concat(tptr(o.in), o.res >= 0 ? tptr(o.res) : nullptr, tptr(o.out), f32, (long)n * ta.H * ta.W, ta.C, ta.Creal,
-                                  o.res >= 0 ? T[o.res].C : 0, o.res >= 0 ? T[o.res].Creal : 0, to.C, o.relu, st);
-                break;
+                return gdt_k_concat(tptr(o.in), o.res >= 0 ? tptr(o.res) : nullptr, tptr(o.out), f32, (long)n * ta.H * ta.W, ta.C, ta.Creal,
+                                    o.res >= 0 ? T[o.res].C : 0, o.res >= 0 ? T[o.res].Creal : 0, to.C, o.relu, st);
             }
             case OP_RESIZE: {
                 const Tensor& ti = T[o.in]; const Tensor& to = T[o.out];
-                rc = gdt_k_resize(tptr(o.in), tptr(o.out), f32, n, ti.H, ti.W, ti.C, to.H, to.W, o.resize_mode, st);
-                break;
+                return gdt_k_resize(tptr(o.in), tptr(o.out), f32, n, ti.H, ti.W, ti.C, to.H, to.W, o.resize_mode, st);
             }
             case OP_MAXPOOL: {
-                if (stp.skip) break;                  // done by the producing conv's epilogue
                 const Tensor& ti = T[o.in]; const Tensor& to = T[o.out];
-                rc = gdt_k_maxpool(tptr(o.in), tptr(o.out), f32, n, ti.H, ti.W, ti.C, to.H, to.W, o.k, o.s, o.p, st);
-                break;
+                return gdt_k_maxpool(tptr(o.in), tptr(o.out), f32, n, ti.H, ti.W, ti.C, to.H, to.W, o.k, o.s, o.p, st);
             }
             case OP_GEM: {
                 const Tensor& ti = T[o.in];
-                rc = gdt_k_gem_l2n(tptr(o.in), f32, (float*)(ws + stp.aux_off[0]), (float*)outputs[o.slot], n, ti.H * ti.W, ti.C, o.gem_p,
-                                   o.eps_gem, o.eps_l2, st);
-                break;
+                return gdt_k_gem_l2n(tptr(o.in), f32, (float*)(ws + stp.aux_off[0]), (float*)outputs[o.slot], n, ti.H * ti.W, ti.C, o.gem_p,
+                                     o.eps_gem, o.eps_l2, st);
             }
             case OP_POOL_HEAD: {
                 const Tensor& ti = T[o.in];
@@ -346,9 +332,8 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
             }
             case OP_OUT_NCHW: {
                 const Tensor& ti = T[o.in];
-                rc = gdt_k_unpack_output(tptr(o.in), f32, (float*)outputs[o.slot],
-                                         o.tap_has_bias ? (const float*)(net->dev_blob + o.tap_bias_off) : nullptr, n, ti.H * ti.W, ti.C, st);
-                break;
+                return gdt_k_unpack_output(tptr(o.in), f32, (float*)outputs[o.slot],
+                                           o.tap_has_bias ? (const float*)(net->dev_blob + o.tap_bias_off) : nullptr, n, ti.H * ti.W, ti.C, st);
             }
             case OP_HED: {
                 const float* sc[5]; int hh[5], wwv[5];

@@ -67,11 +67,11 @@ struct Op {
     // The two-input routes of gdt_net_conv -- ConvTranspose2d(k4,s2,p1) (cd.transposed) and Conv2d of a concatenation: `in` is what the generic launches (four
     // phases / the conv of one tensor) read -- the first input itself, or the output of the OP_CONCAT op `cat_op` (channel concatenation of src_a and src_b,
     // ReLU on the src_a part when src_relu).  has_cat_frag: the fragment-ordered weights (cat_frag_off) of the patch kernel that reads src_a / src_b itself
-    // -- conv4x4t_halo.hip when cd.transposed, else conv3x3_cat_halo.hip; the sources are then also in `feats`, so that they live until this op, and the
-    // concatenation is never written
+    // -- conv4x4t_halo.hip when cd.transposed, else conv3x3_cat_halo.hip; the sources are then also in `feats`, so that they live until this op.  Which route a
+    // geometry takes is the plan's decision (ROUTE_T4 / ROUTE_CAT, with the OP_CONCAT step skipped: the concatenation is laid out but never written)
     bool has_cat_frag = false; size_t cat_frag_off = 0; int src_a = -1, src_b = -1, src_relu = 0, cat_op = -1;
     // The transposed-2 route of gdt_net_conv -- ConvTranspose2d(k2,s2,p0): `phases` are its four 1 x 1 sub-pixel phases (the generic route); has_t2: the
-    // [4 cout][cin] matrix (columns [dy][dx][co]) and the per-column bias of the one-launch form (convt2x2.hip), a launch-time choice on the same plan
+    // [4 cout][cin] matrix (columns [dy][dx][co]) and the per-column bias of the one-launch form (convt2x2.hip), the plan's decision per geometry (ROUTE_T2) on the same layout
     bool has_t2 = false; size_t t2_w_off = 0, t2_bias_off = 0;
     // concat (OP_CONCAT): in / res = the two tensors (res < 0: one), relu = ReLU on the first; cat_for = the conv op that reads the output
     int cat_for = -1;
@@ -197,24 +197,36 @@ struct gdt_net {
 
 namespace gdtn {
 
+// How a step runs: ONE route per step.  A planner pass gives a route only to steps that have none yet (ROUTE_OWN); the executor switches on it and asserts the
+// kernel's eligibility again; gdt_net_plan_summary counts it.  The forms exclude one another today (the builder packs no conv for two of them).  Should two ever
+// take the same conv, the one listed first below wins: skipped, Bottleneck, direct stem, 3x3 + expand, K-concatenated shortcut, transposed-4, transposed-2, conv of
+// a concatenation, fused-phase transposed, stride-2 shift, paired phases, own launches -- run the pass of the form that ranks higher first.
+enum Route {
+    ROUTE_OWN = 0,     // the op's own launch(es); for a conv the phase launches, kernel by the launcher's choice
+    ROUTE_SKIP,        // nothing to launch.  MAXPOOL / CONV: done by another conv's launch.  INPUT: the stem conv reads the caller's image.  CONCAT: its conv reads the sources
+    ROUTE_BNECK,       // CONV: first conv of a Bottleneck that runs as ONE launch (conv_bneck.hip): ops i, i + 1, i + 2 (identity shortcut), or see bneck_ds
+    ROUTE_DIRECT,      // CONV: the ResNet stem, the INPUT op's only consumer, from the caller's image (conv_stem_pair_kernel)
+    ROUTE_XEXP,        // CONV (3x3): the block's expand conv (op i + 1: 1x1 + residual + ReLU) runs in the same launch on the LDS-resident tile (conv3x3_expand_rb.hip)
+    ROUTE_KCAT,        // CONV: expand conv that also computes its projection shortcut (Op::kcat_ds, whose own step is skipped)
+    ROUTE_T4,          // CONV: ConvTranspose2d(k4,s2,p1) from its one or two inputs in one launch (conv4x4t_halo.hip) instead of four phase launches over the concatenation
+    ROUTE_T2,          // CONV: ConvTranspose2d(k2,s2,p0) as one launch (convt2x2.hip) instead of four phase launches
+    ROUTE_CAT,         // CONV: Conv2d(k3,s1,p1) from its two inputs (conv3x3_cat_halo.hip) instead of the conv of one tensor over the concatenation
+    ROUTE_CTF,         // CONV (transposed): the single fused-phase launch
+    ROUTE_S2,          // CONV (stride 2, f16c / f16x3): the shift form over the virtual space-to-depth input
+    ROUTE_PAIRS,       // CONV (transposed, f16x3, 64 output channels): two paired-phase launches (Op::pairs) instead of four phase launches
+};
+
 struct Step {
     int op = 0; size_t aux_off[8] = {}; bool fused_stats = false; int tiles_per_image = 0;
+    Route route = ROUTE_OWN;     // ... and what rides along with it:
     int norm_into = -1;      // INORM: index of the conv op that applies this normalisation while staging its input (-1: own apply pass)
     int norm_from = -1;      // CONV: index of the INORM op folded into the input staging (-1: none)
     bool wb = false;         // INORM folded into a conv that also writes the normalised tensor out (residual / further consumers)
-    bool ctf = false;        // CONV (transposed): runs as the single fused-phase launch
     bool aug = false;        // INPUT / CONV (f16c): the image is packed as augmented fp16 pixel words for the stem kernel's f16c form
-    bool s2 = false;         // CONV (stride 2, f16c): runs as the shift form over the virtual space-to-depth input
-    bool ctp = false;        // CONV (transposed, f16x3, 64 output channels): two paired-phase launches (Op::pairs) instead of four phase launches
-    int pool_into = -1;      // CONV: index of the MAXPOOL(2,2) op whose output this conv writes directly (-1: none)
-    bool skip = false;       // MAXPOOL fused into its producer; CONV: second / third conv of a fused Bottleneck (done by the first one's launch)
-    bool bneck = false;      // CONV: first conv of a Bottleneck that runs as ONE launch (conv_bneck.hip): ops i, i + 1, i + 2 (identity shortcut) ...
-    int bneck_ds = -1;       // ... or {reduce, 1x1 projection shortcut} in either order at i, i + 1 (bneck_a / bneck_ds), i + 2 (3x3), i + 3 (expand + shortcut); -1: identity form
+    int pool_into = -1;      // CONV: index of the MAXPOOL op whose output this conv writes directly (-1: none)
+    int bneck_ds = -1;       // ROUTE_BNECK: {reduce, 1x1 projection shortcut} in either order at i, i + 1 (bneck_a / bneck_ds), i + 2 (3x3), i + 3 (expand + shortcut); -1: identity form
     int bneck_a = 0;         // index of the block's reduce conv (identity form: the step itself)
-    bool xexp = false;       // CONV (3x3): the block's expand conv (op i + 1: 1x1 + residual + ReLU) runs in the same launch on the LDS-resident tile (conv3x3_expand_rb.hip)
-    int xchain = -1;         // ... and the NEXT block's reduce conv (op index; -1: none -- 1x1, C -> 256, ReLU, reading the expand's output) as a third phase of that launch
-    bool kcat = false;       // CONV: expand conv that also computes its projection shortcut (Op::kcat_ds, whose own step is skipped)
-    bool direct = false;     // INPUT + its only consumer, the ResNet stem conv: the conv reads the caller's fp32 NCHW image itself when no resize is asked (conv_stem_pair_kernel)
+    int xchain = -1;         // ROUTE_XEXP: the NEXT block's reduce conv (op index; -1: none -- 1x1, C -> 256, ReLU, reading the expand's output) as a third phase of that launch
     int stats_sets = 1;      // CONV with fused statistics: record sets the INORM finalize sums (phase launches, or N tiles of the fused form)
 };
 struct Plan { std::vector<Step> steps; size_t peak = 0; };
@@ -246,7 +258,7 @@ double op_flops(const gdt_net* net, const Op& o, int n, int rh, int rw);
 double op_bytes(const gdt_net* net, const Op& o, int n);
 
 // ONE descriptor for probe and launch.  The conv_desc_* functions below fill the ConvLaunch of one launch form of one conv op; the planner hands the result to
-// the gdt_*_eligible predicates, the executor to the launchers (after asking the same predicate again).  Where the pointers come from is the resolver's business:
+// the gdt_*_eligible predicates, the executor to the launchers (after asking the same predicate again: an assertion, the decision is the plan's).  Where the pointers come from is the resolver's business:
 struct Ptrs {
     const char* blob = nullptr; char* ws = nullptr; void* const* outputs = nullptr;     // all null = the planner's probe
     // The probe hands out ONE non-null marker for whatever the forward would find at (blob + off) / (ws + off) / outputs[slot]: present or absent is decided
@@ -276,9 +288,6 @@ ConvLaunch conv_desc_kcat(const DescCtx& x, int i);                             
 ConvLaunch conv_desc_stem_direct(const DescCtx& x, int i, int pool_into);                // ResNet stem from the caller's image (+ the 3 x 3 max-pool behind it)
 ConvLaunch conv_desc_t4(const DescCtx& x, int i);                                        // ConvTranspose2d(k4,s2,p1) from its one or two inputs (Op::has_cat_frag, conv4x4t_halo.hip)
 ConvLaunch conv_desc_t2(const DescCtx& x, int i);                                        // ConvTranspose2d(k2,s2,p0) as one launch (Op::has_t2, convt2x2.hip)
-
 ConvLaunch conv_desc_cc(const DescCtx& x, int i, const ConvFold& f);                     // Conv2d(k3,s1,p1) from its two inputs (Op::has_cat_frag, conv3x3_cat_halo.hip)
-// conv op i of a planned geometry runs on conv3x3_cat_halo.hip: its own plain launch in the plan, and eligible (the knob is read here: a launch-time choice)
-bool conv_takes_cat_kernel(const DescCtx& x, const Plan& plan, int i);
 
 }  // namespace gdtn

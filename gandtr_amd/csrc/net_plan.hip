@@ -32,7 +32,7 @@ static void conv_geometry(const gdt_net* net, const Op& o, const PackedPhase& ph
 
 bool conv_fuses_stats(const Op& o, const Tensor& ti) {      // InstanceNorm partial statistics from the conv epilogue
     if (o.stats_for < 0 || o.cd.relu || o.res >= 0) return false;
-    if (o.cd.transposed && o.cd.kh == 4) return false;      // (ConvTranspose2d(k4,s2,p1): its two routes are a launch-time choice on ONE plan, and conv4x4t_halo.hip delivers no statistics)
+    if (o.cd.transposed && o.cd.kh == 4) return false;      // (ConvTranspose2d(k4,s2,p1): its two routes share ONE layout, and conv4x4t_halo.hip delivers no statistics)
     if (o.cd.transposed && o.cd.kh == 2) return false;      // (ConvTranspose2d(k2,s2,p0): likewise, convt2x2.hip)
     const int hwg = o.cd.transposed ? ti.H * ti.W : conv_out_dim(o, ti.H, o.cd.kh) * conv_out_dim(o, ti.W, o.cd.kw);
     return hwg % 128 == 0;
@@ -255,13 +255,6 @@ ConvLaunch conv_desc_cc(const DescCtx& x, int i, const ConvFold& f) {
     return d;
 }
 
-bool conv_takes_cat_kernel(const DescCtx& x, const Plan& plan, int i) {
-    const Op& o = x.net->ops[i];
-    const Step& st = plan.steps[i];
-    if (o.kind != OP_CONV || !o.has_cat_frag || o.cd.transposed || st.skip || st.bneck || st.direct || st.xexp || st.kcat || st.ctf || st.s2 || st.ctp || st.aug) return false;
-    return gdt_conv3x3_cat_halo_eligible(conv_desc_cc(x, i, fold_of(x.net, plan, i)));
-}
-
 // ---- make_plan, pass by pass ------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -279,7 +272,8 @@ struct Planner {
         ConvFold f; f.norm = norm; f.res = res; f.wb = wb; f.stats = conv_fuses_stats(ops[i], T[ops[i].in]); return f;
     }
     void fold_norm(int j, int k, bool wb) { plan.steps[j].norm_into = k; plan.steps[k].norm_from = j; plan.steps[j].wb = wb; }
-    bool taken(int k) const { const Step& s = plan.steps[k]; return s.norm_from >= 0 || s.pool_into >= 0 || s.skip || s.bneck; }    // step k is part of a fusion already
+    Route& route(int k) { return plan.steps[k].route; }
+    bool taken(int k) const { const Step& s = plan.steps[k]; return s.norm_from >= 0 || s.pool_into >= 0 || s.route != ROUTE_OWN; }    // step k is part of a fusion already
 
     int shapes();
     void transposed_forms();
@@ -292,6 +286,7 @@ struct Planner {
     void kcat_folds();
     void direct_stem();
     int layout();
+    void source_routes();
 };
 
 // ---- pass 1: shapes
@@ -350,7 +345,7 @@ void Planner::transposed_forms() {
         if (!o.cd.transposed || !o.has_ctf || o.cd.out_f32_nchw) continue;
         const ConvLaunch d = conv_desc_ctf(probe, i, fold(i));
         if (net->precision == 2) {                 // f16c: the compensated LDS-resident form whenever eligible
-            if (gdt_conv_halo_c_ct_eligible(d)) { plan.steps[i].ctf = true; plan.steps[i].stats_sets = 1; }
+            if (gdt_conv_halo_c_ct_eligible(d)) { route(i) = ROUTE_CTF; plan.steps[i].stats_sets = 1; }
             continue;
         }
         // GDT_CONV_CTF: 0 never, 1 (default) the LDS-resident kernel whenever eligible and the generic persistent GEMM only where
@@ -368,7 +363,7 @@ void Planner::transposed_forms() {
                 }
         }
         // record sets the finalize kernel sums: one per phase pair
-        if (want && (gdt_conv_igemm_rb_eligible(d) || gdt_conv_halo_ct_eligible(d))) { plan.steps[i].ctf = true; plan.steps[i].stats_sets = 2; }
+        if (want && (gdt_conv_igemm_rb_eligible(d) || gdt_conv_halo_ct_eligible(d))) { route(i) = ROUTE_CTF; plan.steps[i].stats_sets = 2; }
     }
 }
 
@@ -388,14 +383,14 @@ void Planner::split_mode_forms() {
     for (int i = 0; i < nops; ++i) {
         if (ops[i].kind != OP_CONV || !ops[i].has_s2) continue;
         const ConvLaunch d = conv_desc_s2(probe, i, fold(i));
-        if (net->precision == 1 ? gdt_conv_halo_x3_taps_eligible(d) : gdt_conv_halo_c_s2_eligible(d)) plan.steps[i].s2 = true;
+        if (net->precision == 1 ? gdt_conv_halo_x3_taps_eligible(d) : gdt_conv_halo_c_s2_eligible(d)) route(i) = ROUTE_S2;
     }
     for (int i = 0; i < nops && net->precision == 1; ++i) {
         const Op& o = ops[i];
-        if (o.kind != OP_CONV || !o.has_pairs) continue;
+        if (o.kind != OP_CONV || !o.has_pairs || route(i) != ROUTE_OWN) continue;       // (a conv that transposed_forms has put on the fused-phase launch stays there)
         bool all = true;
         for (size_t p = 0; p < o.pairs.size(); ++p) all = all && gdt_conv_halo_x3_taps_eligible(conv_desc_pair(probe, i, (int)p, fold(i)));
-        plan.steps[i].ctp = all;
+        if (all) route(i) = ROUTE_PAIRS;
     }
 }
 
@@ -425,7 +420,7 @@ void Planner::norm_folds() {
         }
         const Op& ok = ops[k];
         if (ok.kind != OP_CONV || ok.in != oj.out || ok.res == oj.out || ok.leaky != 0.f) continue;     // (a LeakyReLU conv is a plain launch: gdt_launch_conv)
-        if (ok.cd.transposed && !plan.steps[k].ctf) {
+        if (ok.cd.transposed && route(k) != ROUTE_CTF) {
             // f16x3: the four sub-pixel phase launches of a transposed conv read the same input; each applies the norm while it stages (conv_igemm_x3.hip)
             bool all = net->precision == 1 && x3_fold >= 2 && !wb && !res && !ok.phases.empty();
             for (size_t p = 0; p < ok.phases.size() && all; ++p) all = gdt_conv_x3_norm_eligible(conv_desc_phase(probe, k, ok.phases[p], (int)p, fold(k, j)));
@@ -433,11 +428,11 @@ void Planner::norm_folds() {
             continue;
         }
         if (ok.cd.out_f32_nchw && !ok.rowsplit) continue;
-        if (plan.steps[k].ctf && net->precision == 2) {
+        if (route(k) == ROUTE_CTF && net->precision == 2) {
             if (consumers[oj.out] == 1 && gdt_conv_halo_c_ct_eligible(conv_desc_ctf(probe, k, fold(k, j, res)))) fold_norm(j, k, false);
             continue;
         }
-        if (plan.steps[k].s2) {
+        if (route(k) == ROUTE_S2) {
             if (res) continue;
             const ConvLaunch d = conv_desc_s2(probe, k, fold(k, j, false, wb));
             if (net->precision == 1) {         // conv3x3_halo_x3.hip FORM 2: plain norm (+ReLU)
@@ -455,7 +450,7 @@ void Planner::norm_folds() {
             if (ok.phases[0].has_mx && gdt_conv_halo_c_eligible(conv_desc_phase(probe, k, ok.phases[0], 0, fold(k, j, res, wb)))) fold_norm(j, k, wb);
             continue;
         }
-        if (plan.steps[k].ctf) {
+        if (route(k) == ROUTE_CTF) {
             // (a residual without further consumers needs no write-back: the LDS-resident form adds it while staging)
             const ConvLaunch dn = conv_desc_ctf(probe, k, fold(k, j, res));
             if (consumers[oj.out] == 1 && (gdt_conv_halo_ct_eligible(dn) || (!res && gdt_conv_igemm_rb_eligible(dn)))) fold_norm(j, k, false);
@@ -476,7 +471,7 @@ void Planner::norm_folds() {
 void Planner::stats_sets() {
     for (int i = 0; i < nops; ++i) {
         const Op& o = ops[i];
-        if (o.kind != OP_CONV || plan.steps[i].ctf || o.cd.transposed || o.rowsplit || o.cd.out_f32_nchw || net->precision) continue;
+        if (o.kind != OP_CONV || route(i) == ROUTE_CTF || o.cd.transposed || o.rowsplit || o.cd.out_f32_nchw || net->precision) continue;
         if (!conv_fuses_stats(o, T[o.in])) continue;
         if (plan.steps[i].norm_from >= 0 && plan.steps[plan.steps[i].norm_from].wb) continue;                      // (patch kernels)
         const ConvLaunch d = conv_desc_phase(probe, i, o.phases[0], 0, fold(i, plan.steps[i].norm_from));
@@ -496,7 +491,7 @@ void Planner::pool_folds() {
         if (i < 0 || ops[i].cd.transposed || ops[i].cd.out_f32_nchw || ops[i].res >= 0 || ops[i].dil != 1 || ops[i].leaky != 0.f) continue;
         if (plan.steps[i].norm_from >= 0 && plan.steps[plan.steps[i].norm_from].wb) continue;
         // (asked of the launch as it is without the pool: pool2 = 0)
-        if (gdt_conv_pool2_eligible(conv_desc_phase(probe, i, ops[i].phases[0], 0, fold(i, plan.steps[i].norm_from)))) { plan.steps[i].pool_into = j; plan.steps[j].skip = true; }
+        if (gdt_conv_pool2_eligible(conv_desc_phase(probe, i, ops[i].phases[0], 0, fold(i, plan.steps[i].norm_from)))) { plan.steps[i].pool_into = j; route(j) = ROUTE_SKIP; }
     }
 }
 
@@ -514,12 +509,11 @@ void Planner::bottlenecks() {
         if (!is_3x3_relu(b) || b.in != a.out) continue;
         if (!is_1x1(c) || !c.cd.relu || c.in != b.out || c.res != a.in) continue;
         if (consumers[a.out] != 1 || consumers[b.out] != 1) continue;
-        if (plan.steps[i].norm_from >= 0 || plan.steps[i + 1].norm_from >= 0 || plan.steps[i + 2].norm_from >= 0) continue;
-        if (plan.steps[i].pool_into >= 0 || plan.steps[i + 1].pool_into >= 0 || plan.steps[i + 2].pool_into >= 0) continue;
+        if (taken(i) || taken(i + 1) || taken(i + 2)) continue;
         const int C = a.cd.cin, mid = a.cd.cout;
         if (a.cin_pad != C || a.cout_pad != mid || b.cd.cin != mid || b.cd.cout != mid || b.cout_pad != mid || c.cd.cin != mid || c.cd.cout != C || c.cout_pad != C) continue;
         if (!gdt_bneck_eligible(C, C, mid, N, T[a.in].H, T[a.in].W)) continue;
-        plan.steps[i].bneck = true; plan.steps[i + 1].skip = true; plan.steps[i + 2].skip = true;
+        route(i) = ROUTE_BNECK; route(i + 1) = route(i + 2) = ROUTE_SKIP;
     }
     // ... and the projection-shortcut form (first block of a stage at stride 1): conv 1x1 (CIN -> MID, ReLU), conv 1x1 (CIN -> C, no ReLU: the shortcut,
     // same input), conv 3x3, conv 1x1 (MID -> C) + shortcut, ReLU
@@ -539,8 +533,8 @@ void Planner::bottlenecks() {
         if (a.cin_pad != cin || a.cout_pad != mid || ds.cd.cin != cin || ds.cin_pad != cin || ds.cd.cout != C || ds.cout_pad != C || b.cd.cin != mid || b.cd.cout != mid ||
             b.cout_pad != mid || c.cd.cin != mid || c.cout_pad != C || cin == C) continue;
         if (!gdt_bneck_eligible(cin, C, mid, N, T[a.in].H, T[a.in].W)) continue;
-        plan.steps[i].bneck = true; plan.steps[i].bneck_ds = ids; plan.steps[i].bneck_a = ia;
-        plan.steps[i + 1].skip = true; plan.steps[i + 2].skip = true; plan.steps[i + 3].skip = true;
+        route(i) = ROUTE_BNECK; plan.steps[i].bneck_ds = ids; plan.steps[i].bneck_a = ia;
+        route(i + 1) = route(i + 2) = route(i + 3) = ROUTE_SKIP;
     }
 }
 
@@ -558,7 +552,7 @@ void Planner::expand_folds() {
         if (b.cd.cin != 256 || b.cin_pad != 256 || b.cd.cout != 256 || b.cout_pad != 256 || c.cd.cin != 256 || c.cout_pad != c.cd.cout) continue;
         const ConvLaunch d = conv_desc_xexp(probe, i, -1, net->group_factor);
         if (!gdt_conv3x3_expand_eligible(d)) continue;
-        plan.steps[i].xexp = true; plan.steps[i + 1].skip = true;
+        route(i) = ROUTE_XEXP; route(i + 1) = ROUTE_SKIP;
         // ... chained with the next block's reduce conv (torchvision Bottleneck.conv1 of the following block): 1x1, stride 1, C -> 256, bias, ReLU, no residual,
         // reading the tensor this launch writes; its own launch (and its read of that tensor from HBM) goes away
         int j2 = i + 2;
@@ -567,8 +561,8 @@ void Planner::expand_folds() {
             const Op& a2 = ops[j2];
             const bool ok = plain_s1(a2) && is_1x1(a2) && a2.cd.relu && a2.res < 0 && a2.in == c.out &&
                             a2.cd.cin == c.cd.cout && a2.cin_pad == a2.cd.cin && a2.cd.cout == 256 && a2.cout_pad == 256 && a2.kcat_ds < 0 && a2.out >= 0 &&
-                            !taken(j2) && !plan.steps[j2].kcat;
-            if (ok && gdt_conv3x3_expand_chain_eligible(d)) { plan.steps[i].xchain = j2; plan.steps[j2].skip = true; }
+                            !taken(j2);
+            if (ok && gdt_conv3x3_expand_chain_eligible(d)) { plan.steps[i].xchain = j2; route(j2) = ROUTE_SKIP; }
         }
     }
 }
@@ -579,10 +573,9 @@ void Planner::kcat_folds() {
         const Op& c = ops[i];
         if (c.kind != OP_CONV || c.kcat_ds < 0) continue;
         const int ids = c.kcat_ds;
-        if (plan.steps[i].skip || plan.steps[i].bneck || plan.steps[ids].skip || plan.steps[ids].bneck) continue;
-        if (plan.steps[i].norm_from >= 0 || plan.steps[ids].norm_from >= 0 || plan.steps[i].pool_into >= 0 || consumers[ops[ids].out] != 1) continue;
+        if (taken(i) || taken(ids) || consumers[ops[ids].out] != 1) continue;
         if (!gdt_conv_1x1_cat_eligible(conv_desc_kcat(probe, i))) continue;
-        plan.steps[i].kcat = true; plan.steps[ids].skip = true;
+        route(i) = ROUTE_KCAT; route(ids) = ROUTE_SKIP;
     }
 }
 
@@ -593,12 +586,12 @@ void Planner::direct_stem() {
     const Op& o = ops[j];
     if (o.kind != OP_CONV || o.in != ops[0].out || o.res >= 0 || o.leaky != 0.f || o.phases.size() != 1 || !o.phases[0].has_pair || plan.steps[j].aug || o.stats_for >= 0 || taken(j)) return;
     if (!gdt_conv_stem_pair_eligible(conv_desc_stem_direct(probe, j, -1))) return;
-    plan.steps[0].direct = true; plan.steps[j].direct = true;
+    route(0) = ROUTE_SKIP; route(j) = ROUTE_DIRECT;
     // ... and the MaxPool2d(3, 2, 1) behind it, when it is the stem's only consumer: the stem launch writes the pooled tensor
     const bool pool_ok = knob_stem_pool() != 0;
     const int jp = consumers[o.out] == 1 ? consumer_op[o.out] : -1;
     if (pool_ok && jp >= 0 && ops[jp].kind == OP_MAXPOOL && ops[jp].k == 3 && ops[jp].s == 2 && ops[jp].p == 1 && !ops[jp].ceil && o.cd.relu && o.slot < 0) {
-        plan.steps[j].pool_into = jp; plan.steps[jp].skip = true;
+        plan.steps[j].pool_into = jp; route(jp) = ROUTE_SKIP;
     }
 }
 
@@ -610,7 +603,7 @@ int Planner::layout() {
         const int in = o.kind == OP_CONV ? conv_input(i) : o.in;
         if (in >= 0) T[in].last_use = i;
         if (o.res >= 0) T[o.res].last_use = i;
-        if (o.kind == OP_CONV && plan.steps[i].kcat) T[ops[o.kcat_ds].in].last_use = i;      // the expand conv reads the projection's input itself
+        if (o.kind == OP_CONV && plan.steps[i].route == ROUTE_KCAT) T[ops[o.kcat_ds].in].last_use = i;      // the expand conv reads the projection's input itself
         if (o.kind == OP_CONV && plan.steps[i].norm_from >= 0) {
             const Op& nj = ops[plan.steps[i].norm_from];          // the conv reads the residual and (wb) writes the norm's output tensor
             if (nj.res >= 0) T[nj.res].last_use = std::max(T[nj.res].last_use, i);
@@ -629,16 +622,13 @@ int Planner::layout() {
         const Op& o = ops[i];
         Step& st = plan.steps[i];
         switch (o.kind) {
-            case OP_INPUT: if (!st.direct) alloc_tensor(o.out); break;      // (direct: the stem conv reads the caller's image, the packed tensor never exists)
+            case OP_INPUT: if (st.route != ROUTE_SKIP) alloc_tensor(o.out); break;      // (direct: the stem conv reads the caller's image, the packed tensor never exists)
             case OP_CONV: {
                 const Tensor& ti = T[o.in];       // same size as the raw tensor when the norm is folded
                 const int oh = conv_out_dim(o, ti.H, o.cd.kh);
-                if (st.skip) break;                           // (fused Bottleneck: done by the block's first conv)
-                if (st.bneck) {                               // the launch writes the block output; r and t (and the projected shortcut) never exist
-                    alloc_tensor(ops[i + (st.bneck_ds >= 0 ? 3 : 2)].out);
-                    break;
-                }
-                if (st.xexp) {                                // the launch writes the expand conv's output; the 3x3's own output never exists
+                if (st.route == ROUTE_SKIP) break;                           // (fused Bottleneck: done by the block's first conv)
+                if (st.route == ROUTE_BNECK) { alloc_tensor(ops[i + (st.bneck_ds >= 0 ? 3 : 2)].out); break; }     // the launch writes the block output; r and t (and the projected shortcut) never exist
+                if (st.route == ROUTE_XEXP) {                                // the launch writes the expand conv's output; the 3x3's own output never exists
                     alloc_tensor(ops[i + 1].out);
                     if (st.xchain >= 0) alloc_tensor(ops[st.xchain].out);     // ... and the next block's reduce output
                     break;
@@ -673,9 +663,9 @@ int Planner::layout() {
                 else arena.release(st.aux_off[1], mr_bytes);
                 break;
             }
-            case OP_MAXPOOL: if (!st.skip) alloc_tensor(o.out); break;
+            case OP_MAXPOOL: if (st.route != ROUTE_SKIP) alloc_tensor(o.out); break;
             case OP_RESIZE: alloc_tensor(o.out); break;
-            case OP_CONCAT: alloc_tensor(o.out); break;       // (laid out on either route of its conv: which one runs is decided at launch time)
+            case OP_CONCAT: alloc_tensor(o.out); break;       // (laid out on either route of its conv: the layout does not depend on the route knobs)
             case OP_GEM: st.aux_off[0] = arena.scratch((size_t)N * T[o.in].C * sizeof(float)); break;
             case OP_POOL_HEAD: {                        // the [N][R][D] pooled vectors and their normalised copy, two [N][D] rows (gdt_k_pool_head)
                 const Tensor& ti = T[o.in];
@@ -710,7 +700,7 @@ int Planner::layout() {
             if (t >= 0 && T[t].last_use == i && T[t].bytes) { arena.release(T[t].off, T[t].bytes); T[t].last_use = -2; }
         };
         maybe_free(o.kind == OP_CONV ? conv_input(i) : o.in); maybe_free(o.res);
-        if (o.kind == OP_CONV && st.kcat) maybe_free(ops[o.kcat_ds].in);
+        if (o.kind == OP_CONV && st.route == ROUTE_KCAT) maybe_free(ops[o.kcat_ds].in);
         for (int t : o.feats) maybe_free(t);
         if (o.kind == OP_CONV && st.norm_from >= 0) { maybe_free(ops[st.norm_from].res); maybe_free(ops[st.norm_from].out); }
         if (o.out >= 0 && T[o.out].last_use == -1 && T[o.out].bytes) arena.release(T[o.out].off, T[o.out].bytes);   // never consumed
@@ -718,6 +708,20 @@ int Planner::layout() {
     }
     plan.peak = arena.peak;
     return GDT_OK;
+}
+
+// ---- pass 4: ConvTranspose2d(k4,s2,p1), ConvTranspose2d(k2,s2,p0) and Conv2d(k3,s1,p1) of a concatenation on the kernels that read the sources themselves, where
+// the builder packed their weights and the kernel takes the geometry (its knob is read inside the predicate: at every planning); the copy op of a concatenation
+// nobody reads is skipped with it.  After the layout, which is the same on either route: the kernel is asked with all that the finished plan folds around the conv
+void Planner::source_routes() {
+    auto take = [&](int i, Route r) { route(i) = r; if (ops[i].cat_op >= 0) route(ops[i].cat_op) = ROUTE_SKIP; };
+    for (int i = 0; i < nops; ++i) {
+        const Op& o = ops[i];
+        if (o.kind != OP_CONV || route(i) != ROUTE_OWN) continue;
+        if (o.has_cat_frag && o.cd.transposed) { if (gdt_conv4x4t_halo_eligible(conv_desc_t4(probe, i))) take(i, ROUTE_T4); }
+        else if (o.has_t2) { if (gdt_convt2x2_eligible(conv_desc_t2(probe, i))) take(i, ROUTE_T2); }
+        else if (o.has_cat_frag && !plan.steps[i].aug && gdt_conv3x3_cat_halo_eligible(conv_desc_cc(probe, i, fold_of(net, plan, i)))) take(i, ROUTE_CAT);
+    }
 }
 
 }  // namespace
@@ -740,7 +744,9 @@ int make_plan(gdt_net* net, int N, int RH, int RW, Plan& plan, bool direct_ok) {
     p.expand_folds();
     p.kcat_folds();
     p.direct_stem();
-    return p.layout();
+    GDT_CHECK(p.layout());
+    p.source_routes();
+    return GDT_OK;
 }
 
 double op_flops(const gdt_net* net, const Op& o, int n, int rh, int rw) {
@@ -843,8 +849,8 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
         const Step& st = plan.steps[i];
         const Op& o = net->ops[i];
         if (o.kind == OP_INORM) counts[GDT_PLAN_NORMS_FOLDED] += st.norm_into >= 0;
-        if (o.kind == OP_MAXPOOL) counts[GDT_PLAN_POOLS_FUSED] += st.skip;
-        if (o.kind == OP_INPUT) counts[GDT_PLAN_DIRECT_STEM] += st.direct;
+        if (o.kind == OP_MAXPOOL) counts[GDT_PLAN_POOLS_FUSED] += st.route == ROUTE_SKIP;
+        if (o.kind == OP_INPUT) counts[GDT_PLAN_DIRECT_STEM] += st.route == ROUTE_SKIP;
         if (o.kind == OP_POOL_HEAD) {   // the launches of gdt_k_pool_head: fixed by the layers present, whatever the batch and the number of regions
             counts[GDT_PLAN_HEAD_LAUNCHES] += 1 + (o.pool_aggregate ? 2 + (o.has_rw ? 2 : 0) + (o.pool_aggregate == 2 ? 1 : 0) : 1) + (o.has_fw ? 2 : 0);
             counts[GDT_PLAN_HEAD_MAP_READS] += 1;                     // ... of which read the feature map: the pooling pass
@@ -862,19 +868,19 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
             }
         }
         if (o.kind != OP_CONV) continue;
-        counts[GDT_PLAN_CONV_LAUNCHES] += !st.skip;
-        counts[GDT_PLAN_BOTTLENECKS_FUSED] += st.bneck; counts[GDT_PLAN_CONV3X3_EXPAND] += st.xexp; counts[GDT_PLAN_CHAINED_REDUCE] += st.xchain >= 0;
-        counts[GDT_PLAN_SHORTCUTS_FOLDED] += st.kcat; counts[GDT_PLAN_TRANSPOSED_FUSED] += st.ctf; counts[GDT_PLAN_STRIDE2_SHIFT] += st.s2;
-        if (!net->precision && o.phases.size() == 1 && !o.rowsplit && !(st.skip || st.bneck || st.xexp || st.kcat || st.direct || st.ctf || st.s2 || st.ctp || st.aug))
+        counts[GDT_PLAN_CONV_LAUNCHES] += st.route != ROUTE_SKIP;
+        counts[GDT_PLAN_BOTTLENECKS_FUSED] += st.route == ROUTE_BNECK; counts[GDT_PLAN_CONV3X3_EXPAND] += st.route == ROUTE_XEXP; counts[GDT_PLAN_CHAINED_REDUCE] += st.xchain >= 0;
+        counts[GDT_PLAN_SHORTCUTS_FOLDED] += st.route == ROUTE_KCAT; counts[GDT_PLAN_TRANSPOSED_FUSED] += st.route == ROUTE_CTF; counts[GDT_PLAN_STRIDE2_SHIFT] += st.route == ROUTE_S2;
+        counts[GDT_PLAN_CONV4X4T_LAUNCHES] += st.route == ROUTE_T4; counts[GDT_PLAN_CONV3X3_CAT_LAUNCHES] += st.route == ROUTE_CAT;
+        if (more) counts[GDT_PLAN_CONVT2X2_LAUNCHES] += st.route == ROUTE_T2;
+        const bool own = st.route == ROUTE_OWN && !st.aug;       // the conv's own plain launch(es)
+        if (!net->precision && o.phases.size() == 1 && !o.rowsplit && own)
             counts[GDT_PLAN_CONV4X4_LAUNCHES] += gdt_conv4x4_halo_eligible(conv_desc_phase(probe, (int)i, o.phases[0], 0, fold_of(net, plan, (int)i)));
-        if (o.has_cat_frag && o.cd.transposed && !st.skip) counts[GDT_PLAN_CONV4X4T_LAUNCHES] += gdt_conv4x4t_halo_eligible(conv_desc_t4(probe, (int)i));
-        counts[GDT_PLAN_CONV3X3_CAT_LAUNCHES] += conv_takes_cat_kernel(probe, plan, (int)i);
-        if (more && o.has_t2 && !st.skip) counts[GDT_PLAN_CONVT2X2_LAUNCHES] += gdt_convt2x2_eligible(conv_desc_t2(probe, (int)i));
         if (o.dil != 1) {
             ++counts[GDT_PLAN_DILATED_CONVS];
             // what gdt_launch_conv / gdt_launch_conv_x3 would be handed for the conv as its own plain launch
             const ConvLaunch d = conv_desc_phase(probe, (int)i, o.phases[0], 0, ConvFold{});
-            counts[GDT_PLAN_DILATED_SPECIAL_FORMS] += st.skip || st.bneck || st.xexp || st.pool_into >= 0 || st.s2 || st.aug || st.direct || gdt_conv_halo_eligible(d) ||
+            counts[GDT_PLAN_DILATED_SPECIAL_FORMS] += !own || st.pool_into >= 0 || gdt_conv_halo_eligible(d) ||
                           gdt_conv_halo_rb_eligible(d) || gdt_conv_halo_x3_eligible(d) || gdt_conv_halo_x3_taps_eligible(d) || gdt_conv_halo_c_eligible(d) ||
                           gdt_conv_stem_eligible(d) || gdt_conv_stem_c_eligible(d) || gdt_conv_1x1_rb_eligible(d);
         }

@@ -297,18 +297,20 @@ enum {
                                         head; gdt_net_median_head counts under both names)                                                           */
     GDT_PLAN_CONV4X4_LAUNCHES,       /* "conv4x4_launches": conv launches that run on the 4x4 patch kernel (conv4x4_halo.hip: what gdt_launch_conv
                                         decides for the conv as its own plain launch; none with GDT_CONV4X4_HALO=0)                                  */
-    GDT_PLAN_CONV4X4T_LAUNCHES,      /* "conv4x4t_launches": transposed 4x4 convs that run as one launch of conv4x4t_halo.hip, the concatenation in
-                                        front never written (none with GDT_CONV4X4T_HALO=0 -- then four phase launches each)                         */
-    GDT_PLAN_CONV3X3_CAT_LAUNCHES,   /* "conv3x3_cat_launches": convs of a concatenation that run as one launch of conv3x3_cat_halo.hip (none with
-                                        GDT_CONV3X3_CAT_HALO=0 -- then a copy + the conv of one tensor)                                              */
+    GDT_PLAN_CONV4X4T_LAUNCHES,      /* "conv4x4t_launches": transposed 4x4 convs the plan puts on one launch of conv4x4t_halo.hip, the concatenation
+                                        in front never written (none with GDT_CONV4X4T_HALO=0 -- then four phase launches each).  This and the two
+                                        counters of convt2x2.hip and conv3x3_cat_halo.hip count the route recorded in the plan, which the forward
+                                        follows; their knobs are read whenever a geometry is planned and change no tensor and no workspace size      */
+    GDT_PLAN_CONV3X3_CAT_LAUNCHES,   /* "conv3x3_cat_launches": convs of a concatenation the plan puts on one launch of conv3x3_cat_halo.hip (none
+                                        with GDT_CONV3X3_CAT_HALO=0 -- then a copy + the conv of one tensor)                                         */
     GDT_PLAN_ATTENTION_LAUNCHES,     /* "attention_launches": launches the attention of a pool head adds in front of the pooling (the norm pass, and
                                         the division by the maximum when normalize_max)                                                              */
     GDT_PLAN_ATTENTION_MAP_READS,    /* "attention_map_reads": launches of such heads that read the feature map (two per op: the norm pass and the
                                         weighted pooling pass)                                                                                        */
     GDT_PLAN_COUNT,                  /* the counters gdt_plan_count_name names and every caller's array holds (a fixed set)                          */
     GDT_PLAN_CONVT2X2_LAUNCHES = GDT_PLAN_COUNT,
-                                     /* "convt2x2_launches": transposed 2x2 convs that run as one launch of convt2x2.hip (none with GDT_CONVT2X2=0 --
-                                        then four phase launches each)                                                                                */
+                                     /* "convt2x2_launches": transposed 2x2 convs the plan puts on one launch of convt2x2.hip (none with
+                                        GDT_CONVT2X2=0 -- then four phase launches each)                                                              */
     GDT_PLAN_COUNT_ALL
 };
 /* name of counter `index` (the quoted names above), NULL past the last index (GDT_PLAN_COUNT - 1) and for negative ones */

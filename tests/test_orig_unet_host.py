@@ -114,7 +114,7 @@ def test_graph_plans_without_a_device(monkeypatch, i):
     ws = net.workspace_bytes(n, h, w)
     monkeypatch.setenv(KNOB, "0")
     assert net.convt2x2_launches(n, h, w) == 0
-    assert net.workspace_bytes(n, h, w) == ws                         # a launch knob: the same plan either way
+    assert net.workspace_bytes(n, h, w) == ws                         # a launch knob: the same layout either way
     assert KNOB not in _hip.plan_knobs()
 
 

@@ -206,7 +206,7 @@ def test_conv_cat_routing_rule(monkeypatch):
 
 
 def test_conv_cat_knob_is_read_at_every_query(monkeypatch):
-    """GDT_CONV3X3_CAT_HALO is a launch knob: 0 -> the generic route, inside one process; it is no plan knob (the plan is the same either way)"""
+    """GDT_CONV3X3_CAT_HALO is a launch knob: 0 -> the generic route, inside one process; it is no plan knob (the layout is the same either way)"""
     net = _graph("aligned_p2p_unet", nested_levels=1)
     monkeypatch.delenv("GDT_CONV3X3_CAT_HALO", raising=False)
     assert net.conv3x3_cat_launches(2, 10, 14) == 1
