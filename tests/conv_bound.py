@@ -101,9 +101,9 @@ def products(w, transposed=False):
     return w.shape[1] * w.shape[2] * w.shape[3]
 
 
-def norm_input(x, relu=False, residual=None, eps=1e-5, err_r=STAT_ERR_R, err_m=STAT_ERR_M):
-    """(a, da): the float64 input InstanceNorm(x) (+ ReLU, + residual) of a conv that folds the norm into its staging, and the bound on what the kernel stages instead
-    (see the docstring); ``x`` the tapped fp16 tensor"""
+def norm_value(x, relu=False, residual=None, eps=1e-5, err_r=STAT_ERR_R, err_m=STAT_ERR_M):
+    """(a, dz): norm_input's float64 value and its error BEFORE the rounding of the store; ``err_r`` / ``err_m`` are numbers or tensors that broadcast against
+    [N, C, 1, 1] (aux_bound.py derives them per channel for the separate statistics pass)"""
     x = x.double()
     mean = x.mean(dim=(2, 3), keepdim=True)
     rstd = 1.0 / torch.sqrt(x.var(dim=(2, 3), unbiased=False, keepdim=True) + eps)
@@ -113,6 +113,13 @@ def norm_input(x, relu=False, residual=None, eps=1e-5, err_r=STAT_ERR_R, err_m=S
     if residual is not None:
         a = a + residual.double()
         dz = dz + U32 * a.abs()
+    return a, dz
+
+
+def norm_input(x, relu=False, residual=None, eps=1e-5, err_r=STAT_ERR_R, err_m=STAT_ERR_M):
+    """(a, da): the float64 input InstanceNorm(x) (+ ReLU, + residual) of a conv that folds the norm into its staging, and the bound on what the kernel stages instead
+    (see the docstring); ``x`` the tapped fp16 tensor"""
+    a, dz = norm_value(x, relu, residual, eps, err_r, err_m)
     return a, dz + U16 * a.abs() + SUB16
 
 
