@@ -108,6 +108,7 @@ SIGNATURES = {
     "gdt_net_instance_norm": (c_int, [c_void_p, c_int, c_float, c_int, c_float, c_int, _IP]),
     "gdt_net_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, _IP]),
     "gdt_net_resize": (c_int, [c_void_p, c_int, c_int, c_int, _IP]),
+    "gdt_net_blur_resample": (c_int, [c_void_p, c_int, c_int, _IP]),
     "gdt_net_gem_l2n": (c_int, [c_void_p, c_int, c_float, c_float, c_float, _IP]),
     "gdt_net_pool_head": (c_int, [c_void_p, c_int, POINTER(PoolHeadDesc), _IP]),
     "gdt_net_median_head": (c_int, [c_void_p, c_int, POINTER(MedianHeadDesc), _IP]),
@@ -133,6 +134,7 @@ SIGNATURES = {
     "gdt_net_profile_read_bytes": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_double)]),
     "gdt_net_num_ops": (c_int, [c_void_p]),
     "gdt_net_plan_summary": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _IP, c_int]),
+    "gdt_net_blur_summary": (c_int, [c_void_p, c_int, c_int, c_int, _IP, _IP]),
     "gdt_ms_aggregate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "gdt_whiten": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gdt_whiten_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -11,6 +11,7 @@ import functools
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from ._hipbacked import HipBacked
 
@@ -58,10 +59,47 @@ class ResnetBlock(nn.Module):
         return x + self.conv_block(x)
 
 
+def _binomial_filter(size):
+    """the normalised outer product of the binomial row of ``size`` taps: [1, 2, 1] (3) or [1, 3, 3, 1] (4)"""
+    row = torch.tensor({3: [1., 2., 1.], 4: [1., 3., 3., 1.]}[size])
+    filt = row[:, None] * row[None, :]
+    return filt / filt.sum()
+
+
+class Downsample(nn.Module):
+    """CUT's anti-aliased down-sampling: reflection pad by 1, then a depthwise 3x3 conv at stride 2 with the weights outer([1, 2, 1], [1, 2, 1]) / 16;
+    ceil(H / 2) x ceil(W / 2), H and W at least 2.  ``filt`` is a buffer [C, 1, 3, 3], as in the reference's state dicts.  On the HIP path:
+    gdt_net_blur_resample, mode 0."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.channels = channels
+        self.register_buffer("filt", _binomial_filter(3)[None, None].repeat(channels, 1, 1, 1))
+
+    def forward(self, x):
+        return F.conv2d(F.pad(x, (1, 1, 1, 1), mode="reflect"), self.filt, stride=2, groups=x.shape[1])
+
+
+class Upsample(nn.Module):
+    """CUT's anti-aliased up-sampling: replicate pad by 1, a depthwise transposed 4x4 conv at stride 2 with the weights outer([1, 3, 3, 1], [1, 3, 3, 1]) / 16
+    and a crop to 2H x 2W -- the function F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) computes.  ``filt`` is a buffer
+    [C, 1, 4, 4], as in the reference's state dicts.  On the HIP path: gdt_net_blur_resample, mode 1."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.channels = channels
+        self.register_buffer("filt", (_binomial_filter(4) * 4)[None, None].repeat(channels, 1, 1, 1))
+
+    def forward(self, x):
+        y = F.conv_transpose2d(F.pad(x, (1, 1, 1, 1), mode="replicate"), self.filt, stride=2, padding=2, groups=x.shape[1])
+        return y[:, :, 1:-1, 1:-1]
+
+
 class ResnetGenerator(HipBacked, nn.Module):
-    """ResNet generator: 7x7 stem, two stride-2 down convs, n_blocks ResnetBlocks, two ConvTranspose up layers, 7x7
-    head + tanh.  Only the hub configuration (no_antialias / no_antialias_up, reflect padding, no dropout) is on the
-    HIP hot path; other configurations are rejected with NotImplementedError on a cuda device."""
+    """ResNet generator: 7x7 stem, two down layers, n_blocks ResnetBlocks, two up layers, 7x7 head + tanh.  A down layer is a stride-2 conv
+    (``no_antialias``, the hub configuration) or a stride-1 conv + norm + ReLU + Downsample (CUT's default); an up layer is a ConvTranspose
+    (``no_antialias_up``) or Upsample + stride-1 conv + norm + ReLU.  Reflect padding without dropout is on the HIP hot path, in all four combinations
+    of the two flags; other configurations are rejected with NotImplementedError on a cuda device."""
 
     #: the generators meet north_star's 1e-3 in the compensated mode only (DESIGN.md section 5)
     hip_default_precision = "f16c"
@@ -72,11 +110,9 @@ class ResnetGenerator(HipBacked, nn.Module):
                  padding_type="reflect", no_antialias=True, no_antialias_up=True, track_running_stats=True):
         assert n_blocks >= 0
         super().__init__()
-        if not (no_antialias and no_antialias_up):
-            raise NotImplementedError("anti-aliased down/up-sampling (CUT) is outside the gandtr hot path")
         self.meta = {"in_channels": input_nc, "out_channels": output_nc}
         self._cfg = dict(norm=norm_layer if isinstance(norm_layer, str) else None, n_blocks=n_blocks,
-                         padding_type=padding_type, use_dropout=use_dropout)
+                         padding_type=padding_type, use_dropout=use_dropout, no_antialias=no_antialias, no_antialias_up=no_antialias_up)
         norm_layer = get_norm_layer(norm_layer, track_running_stats)
         base = norm_layer.func if isinstance(norm_layer, functools.partial) else norm_layer
         use_bias = base == nn.InstanceNorm2d
@@ -85,14 +121,19 @@ class ResnetGenerator(HipBacked, nn.Module):
                nn.ReLU(True)]
         ch = ngf
         for _ in range(2):
-            seq += [nn.Conv2d(ch, ch * 2, kernel_size=3, stride=2, padding=1, bias=use_bias), norm_layer(ch * 2), nn.ReLU(True)]
+            seq += [nn.Conv2d(ch, ch * 2, kernel_size=3, stride=2 if no_antialias else 1, padding=1, bias=use_bias), norm_layer(ch * 2), nn.ReLU(True)]
+            if not no_antialias:
+                seq.append(Downsample(ch * 2))
             ch *= 2
         for _ in range(n_blocks):
             seq.append(ResnetBlock(ch, padding_type=padding_type, norm_layer=norm_layer, use_dropout=use_dropout,
                                    use_bias=use_bias))
         for _ in range(2):
-            seq += [nn.ConvTranspose2d(ch, ch // 2, kernel_size=3, stride=2, padding=1, output_padding=1, bias=use_bias),
-                    norm_layer(ch // 2), nn.ReLU(True)]
+            if no_antialias_up:
+                seq += [nn.ConvTranspose2d(ch, ch // 2, kernel_size=3, stride=2, padding=1, output_padding=1, bias=use_bias)]
+            else:
+                seq += [Upsample(ch), nn.Conv2d(ch, ch // 2, kernel_size=3, stride=1, padding=1, bias=use_bias)]
+            seq += [norm_layer(ch // 2), nn.ReLU(True)]
             ch //= 2
         seq += [nn.ReflectionPad2d(3), nn.Conv2d(ngf, output_nc, kernel_size=7, padding=0), nn.Tanh()]
         self.model = nn.Sequential(*seq)
@@ -310,10 +351,14 @@ class Normalize(nn.Module):
 UNAVAILABLE_TAPS = "feature taps %s (reflection-padded tensors) are not materialised on the HIP path"
 
 
-def generator_tap_channels(layers, ngf=64, n_blocks=9, input_nc=3, output_nc=3):
+def generator_tap_channels(layers, ngf=64, n_blocks=9, input_nc=3, output_nc=3, no_antialias=True, no_antialias_up=True):
     """channel counts of the taps ``layers`` (nn.Sequential indices) of a ResnetGenerator, from its layout alone: no forward.  The two reflection-padded
-    tensors (index 0 and the pad before the head) are refused like ResnetGenerator refuses them on the HIP path."""
-    widths = [input_nc] + [ngf] * 3 + [2 * ngf] * 3 + [4 * ngf] * 3 + [4 * ngf] * n_blocks + [2 * ngf] * 3 + [ngf] * 3 + [ngf] + [output_nc] * 2
+    tensors (index 0 and the pad before the head) are refused like ResnetGenerator refuses them on the HIP path.  ``no_antialias`` False: a Downsample
+    behind each down layer; ``no_antialias_up`` False: an Upsample (of the incoming width) in front of each up conv."""
+    down = 3 if no_antialias else 4
+    up = lambda cin: [cin // 2] * 3 if no_antialias_up else [cin] + [cin // 2] * 3
+    widths = ([input_nc] + [ngf] * 3 + [2 * ngf] * down + [4 * ngf] * down + [4 * ngf] * n_blocks + up(4 * ngf) + up(2 * ngf) + [ngf] +
+              [output_nc] * 2)
     last = len(widths) - 1
     bad = [l for l in layers if l in (0, last - 2)]
     if bad:

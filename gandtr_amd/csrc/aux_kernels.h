@@ -6,6 +6,28 @@
 
 #include "gdt_common.h"
 
+// ---- device side, shared by the helper kernels (aux_kernels.hip, blur_resample.hip)
+// activation element access: 8 consecutive channels as fp32, for fp16 (default) and fp32 ("f16x3" precision mode) tensors
+__device__ __forceinline__ void load8(const f16* p, float (&v)[8]) {
+    const f16x8 t = *(const f16x8*)p;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
+}
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+    const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+__device__ __forceinline__ void store8(f16* p, const float (&v)[8]) {
+    f16x8 t;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) t[e] = (f16)v[e];
+    *(f16x8*)p = t;
+}
+__device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
+    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+    *(float4*)(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+
 // A per-pixel function of the input pack, applied in fp32 behind resize, permutation and affine and in front of the rounding to fp16.  kind 1 = EdgeFilter
 // (mdir/components/model/layers/preprocessing.py:18-25): w * max(x, eps)^p / (exp(min(-beta * (x - tau), 50)) + 1); tau is clamped by whoever fills this.
 struct GdtInputFilter { int kind = 0; float w = 0.f, p = 0.f, beta = 0.f, tau = 0.f, eps = 0.f; };
@@ -22,6 +44,10 @@ int gdt_k_instance_norm_stats(const void* x, int f32, int fused, float* partial,
 int gdt_k_maxpool(const void* x, void* y, int f32, int N, int H, int W, int C, int OH, int OW, int k, int s, int p, hipStream_t st);
 // F.interpolate(x [N][H][W][C], size=(OH, OW), mode 0 "bilinear" (align_corners=False) | 1 "nearest") -> y [N][OH][OW][C]
 int gdt_k_resize(const void* x, void* y, int f32, int N, int H, int W, int C, int OH, int OW, int mode, hipStream_t st);
+// The anti-aliased sampling of gdt_net_blur_resample (blur_resample.hip): x [N][H][W][C] -> y [N][ceil(H/2)][ceil(W/2)][C] (down; H, W >= 2) / [N][2H][2W][C] (up).
+// mean_rstd == null: the plain form.  Else the norm-folded form: (x - mean) * rstd of the InstanceNorm's [N][C][2] slab, then the ReLU when `relu`, on every tap as it is read.
+int gdt_k_blur_down(const void* x, void* y, int f32, int N, int H, int W, int C, const float* mean_rstd, int relu, hipStream_t st);
+int gdt_k_blur_up(const void* x, void* y, int f32, int N, int H, int W, int C, const float* mean_rstd, int relu, hipStream_t st);
 // y[.., 0 .. ca) = a (+ ReLU), y[.., ca .. ca + cb) = b, zero up to C: torch.cat along the channels of NHWC tensors with channel strides Ca / Cb
 int gdt_k_concat(const void* a, const void* b, void* y, int f32, long NP, int Ca, int ca, int Cb, int cb, int C, int relu_a, hipStream_t st);
 int gdt_k_gem_l2n(const void* x, int f32, float* pooled, float* out, int N, int HW, int D, float p, float eps_gem, float eps_l2,

@@ -20,27 +20,6 @@
 
 namespace {
 
-// activation element access: 8 consecutive channels as fp32, for fp16 (default) and fp32 ("f16x3" precision mode) tensors
-__device__ __forceinline__ void load8(const f16* p, float (&v)[8]) {
-    const f16x8 t = *(const f16x8*)p;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
-}
-__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
-    const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void store8(f16* p, const float (&v)[8]) {
-    f16x8 t;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) t[e] = (f16)v[e];
-    *(f16x8*)p = t;
-}
-__device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
-    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
-    *(float4*)(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-}
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

@@ -773,6 +773,15 @@ int gdt_net_resize(gdt_net* net, int in_tensor, int like_tensor, int mode, int* 
     return GDT_OK;
 }
 
+int gdt_net_blur_resample(gdt_net* net, int in_tensor, int mode, int* out_tensor) {
+    GDT_REQUIRE(net && !net->finalized && out_tensor, "net");
+    GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "tensor id");
+    GDT_REQUIRE(mode == 0 || mode == 1, "blur-resample mode: 0 down, 1 up");
+    Op o; o.kind = OP_BLUR; o.in = in_tensor; o.blur_up = mode;
+    *out_tensor = push_op(net, std::move(o), false, net->tensors[in_tensor].C, net->tensors[in_tensor].Creal);
+    return GDT_OK;
+}
+
 int gdt_net_gem_l2n(gdt_net* net, int in_tensor, float p, float eps_gem, float eps_l2, int* out_slot) {
     GDT_REQUIRE(net && !net->finalized && out_slot, "net");
     GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "tensor id");

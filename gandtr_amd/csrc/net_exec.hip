@@ -285,6 +285,16 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                 const Tensor& ti = T[o.in]; const Tensor& to = T[o.out];
                 return gdt_k_resize(tptr(o.in), tptr(o.out), f32, n, ti.H, ti.W, ti.C, to.H, to.W, o.resize_mode, st);
             }
+            case OP_BLUR: {                 // (a folded norm: this op reads the norm's raw input and its mean / rstd slab, the normalised tensor does not exist)
+                const Op* nj = stp.norm_from >= 0 ? &net->ops[stp.norm_from] : nullptr;
+                const int src = nj ? nj->in : o.in;
+                const Tensor& ti = T[src]; const Tensor& to = T[o.out];
+                const float* mr = nj ? (const float*)(ws + plan.steps[stp.norm_from].aux_off[1]) : nullptr;
+                if (net->profiling && book)     // the input once, the output once (and the slab)
+                    net->last_bytes[stp.op] = ((double)ti.H * ti.W + (double)to.H * to.W) * n * ti.C * (double)net->esize() + (nj ? (double)n * ti.C * 8.0 : 0.0);
+                return o.blur_up ? gdt_k_blur_up(tptr(src), tptr(o.out), f32, n, ti.H, ti.W, ti.C, mr, nj ? nj->relu : 0, st)
+                                 : gdt_k_blur_down(tptr(src), tptr(o.out), f32, n, ti.H, ti.W, ti.C, mr, nj ? nj->relu : 0, st);
+            }
             case OP_MAXPOOL: {
                 const Tensor& ti = T[o.in]; const Tensor& to = T[o.out];
                 return gdt_k_maxpool(tptr(o.in), tptr(o.out), f32, n, ti.H, ti.W, ti.C, to.H, to.W, o.k, o.s, o.p, st);
@@ -527,6 +537,7 @@ int gdt_net_levels_joined(gdt_net* net, int* level_launches) {
 int gdt_net_forward_levels(gdt_net* net, const gdt_level* levels, int n_levels, void* stream) {
     GDT_REQUIRE(net && net->finalized, "net must be finalized");
     GDT_REQUIRE(levels && n_levels >= 1 && n_levels <= GDT_MAX_LEVELS, "1..4 geometries per call");
+    if (n_levels > 1) for (const Op& o : net->ops) GDT_REQUIRE(o.kind != OP_BLUR, "a graph with a blur-resample op runs one geometry per call");
     std::vector<LevelCtx> cx(n_levels);
     double group_px = 0.0;
     for (int l = 0; l < n_levels; ++l) group_px += (double)levels[l].n * levels[l].rh * levels[l].rw;

@@ -19,7 +19,7 @@ inline size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
 inline int next_pow2(int v) { int p = 8; while (p < v) p <<= 1; return p; }
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF, OP_POOL_HEAD, OP_CONCAT, OP_MEDIAN_HEAD, OP_RESIZE };
+enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF, OP_POOL_HEAD, OP_CONCAT, OP_MEDIAN_HEAD, OP_RESIZE, OP_BLUR };
 
 struct PackedPhase {
     size_t w_off = 0;                 // byte offset in the device weight blob
@@ -77,6 +77,9 @@ struct Op {
     int cat_for = -1;
     // resize (OP_RESIZE, gdt_net_resize): `in` resized to the H x W of tensor `like` (read for its shape only: it need not be alive), mode 0 bilinear / 1 nearest
     int like = -1, resize_mode = 0;
+    // blur-resample (OP_BLUR, gdt_net_blur_resample): 0 = Downsample (reflect, [1,2,1] x [1,2,1] / 16, stride 2), 1 = Upsample (bilinear x 2).  A folded producer
+    // norm is the plan's decision (Step::norm_from of this step, Step::norm_into of the INORM step)
+    int blur_up = 0;
     int dil = 1;          // conv: dilation (gdt_conv_desc::dilation); the taps are (dy0 + (t / TW) * dil, ...): only the generic implicit-GEMM kernels take it
     // maxpool
     int k = 0, s = 0, p = 0; int ceil = 0;
@@ -219,8 +222,8 @@ enum Route {
 struct Step {
     int op = 0; size_t aux_off[8] = {}; bool fused_stats = false; int tiles_per_image = 0;
     Route route = ROUTE_OWN;     // ... and what rides along with it:
-    int norm_into = -1;      // INORM: index of the conv op that applies this normalisation while staging its input (-1: own apply pass)
-    int norm_from = -1;      // CONV: index of the INORM op folded into the input staging (-1: none)
+    int norm_into = -1;      // INORM: index of the conv (or blur-resample) op that applies this normalisation while staging its input (-1: own apply pass)
+    int norm_from = -1;      // CONV / BLUR: index of the INORM op folded into the input staging (-1: none)
     bool wb = false;         // INORM folded into a conv that also writes the normalised tensor out (residual / further consumers)
     bool aug = false;        // INPUT / CONV (f16c): the image is packed as augmented fp16 pixel words for the stem kernel's f16c form
     int pool_into = -1;      // CONV: index of the MAXPOOL op whose output this conv writes directly (-1: none)

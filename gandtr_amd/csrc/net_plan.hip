@@ -313,6 +313,18 @@ int Planner::shapes() {
                 h = pool_out_dim(o, T[o.in].H); w = pool_out_dim(o, T[o.in].W);
                 break;
             case OP_RESIZE: h = T[o.like].H; w = T[o.like].W; break;      // (`like` was added before this op: its shape is known)
+            case OP_BLUR: {                             // Downsample: ceil(H/2) x ceil(W/2), refused below 2 x 2 (the reflection); Upsample: 2H x 2W
+                const Tensor& ti = T[o.in];
+                if (o.blur_up) {
+                    GDT_REQUIRE(ti.H < (1 << 30) && ti.W < (1 << 30) && gdt_offsets_fit(N, 2 * ti.H, 2 * ti.W, ti.C), "anti-aliased Upsample: N * 2H * 2W * C must stay below 2^32");
+                    h = 2 * ti.H; w = 2 * ti.W;
+                } else {
+                    GDT_REQUIRE(ti.H >= 2 && ti.W >= 2, "the anti-aliased Downsample needs a map of at least 2 x 2 (reflection padding)");
+                    GDT_REQUIRE(gdt_offsets_fit(N, ti.H, ti.W, ti.C), "anti-aliased Downsample: N * H * W * C must stay below 2^32");
+                    h = (ti.H + 1) / 2; w = (ti.W + 1) / 2;
+                }
+                break;
+            }
             case OP_RCF: {                              // the reference's crop (rcf.py:95-99) and torch.cat of the five maps at the image size
                 for (int t : o.feats) GDT_REQUIRE(T[t].H > 0 && T[t].W > 0, "layer output would be empty for this input size");
                 for (size_t j = 0; j < o.feats.size(); ++j) {
@@ -402,6 +414,12 @@ void Planner::norm_folds() {
         // f16x3: the patch kernel folds InstanceNorm (+ReLU, + residual, + write-back) while it stages; GDT_X3_NORM_FOLD=0 switches that off, 1 keeps it to the plain
         // norm (+ReLU) without residual / write-back (the round-5 first form)
         const int x3_fold = knob_x3_norm_fold();
+        // a blur-resample op that is the norm's only consumer applies it to every tap it reads (blur_resample.hip): plain norm (+ReLU) in every precision mode; a
+        // tapped norm has a second consumer and keeps its own apply pass
+        if (oj.kind == OP_INORM && oj.leaky == 0.f && oj.res < 0 && consumers[oj.out] == 1 && ops[consumer_op[oj.out]].kind == OP_BLUR) {
+            fold_norm(j, consumer_op[oj.out], false);
+            continue;
+        }
         if (oj.kind != OP_INORM || (net->precision == 1 && !x3_fold) || oj.leaky != 0.f) continue;      // (the staging passes apply ReLU only)
         // plain norm(+ReLU): exactly one consumer.  norm + residual (ResnetBlock output): the tensor itself is still needed
         // later (as the next block's residual), so the consuming conv also writes it out -- every other consumer must come
@@ -598,9 +616,10 @@ void Planner::direct_stem() {
 // ---- pass 3: liveness + first-fit layout
 int Planner::layout() {
     auto conv_input = [&](int i) { return plan.steps[i].norm_from >= 0 ? ops[plan.steps[i].norm_from].in : ops[i].in; };
+    auto folds = [&](const Op& o) { return o.kind == OP_CONV || o.kind == OP_BLUR; };      // the ops a norm can be folded into: they read the norm's input
     for (int i = 0; i < nops; ++i) {
         const Op& o = ops[i];
-        const int in = o.kind == OP_CONV ? conv_input(i) : o.in;
+        const int in = folds(o) ? conv_input(i) : o.in;
         if (in >= 0) T[in].last_use = i;
         if (o.res >= 0) T[o.res].last_use = i;
         if (o.kind == OP_CONV && plan.steps[i].route == ROUTE_KCAT) T[ops[o.kcat_ds].in].last_use = i;      // the expand conv reads the projection's input itself
@@ -665,6 +684,7 @@ int Planner::layout() {
             }
             case OP_MAXPOOL: if (st.route != ROUTE_SKIP) alloc_tensor(o.out); break;
             case OP_RESIZE: alloc_tensor(o.out); break;
+            case OP_BLUR: alloc_tensor(o.out); break;
             case OP_CONCAT: alloc_tensor(o.out); break;       // (laid out on either route of its conv: the layout does not depend on the route knobs)
             case OP_GEM: st.aux_off[0] = arena.scratch((size_t)N * T[o.in].C * sizeof(float)); break;
             case OP_POOL_HEAD: {                        // the [N][R][D] pooled vectors and their normalised copy, two [N][D] rows (gdt_k_pool_head)
@@ -699,7 +719,7 @@ int Planner::layout() {
         auto maybe_free = [&](int t) {
             if (t >= 0 && T[t].last_use == i && T[t].bytes) { arena.release(T[t].off, T[t].bytes); T[t].last_use = -2; }
         };
-        maybe_free(o.kind == OP_CONV ? conv_input(i) : o.in); maybe_free(o.res);
+        maybe_free(folds(o) ? conv_input(i) : o.in); maybe_free(o.res);
         if (o.kind == OP_CONV && st.route == ROUTE_KCAT) maybe_free(ops[o.kcat_ds].in);
         for (int t : o.feats) maybe_free(t);
         if (o.kind == OP_CONV && st.norm_from >= 0) { maybe_free(ops[st.norm_from].res); maybe_free(ops[st.norm_from].out); }
@@ -884,6 +904,20 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
                           gdt_conv_halo_rb_eligible(d) || gdt_conv_halo_x3_eligible(d) || gdt_conv_halo_x3_taps_eligible(d) || gdt_conv_halo_c_eligible(d) ||
                           gdt_conv_stem_eligible(d) || gdt_conv_stem_c_eligible(d) || gdt_conv_1x1_rb_eligible(d);
         }
+    }
+    return GDT_OK;
+}
+
+int gdt_net_blur_summary(gdt_net* net, int n, int rh, int rw, int* launches, int* folded) {
+    GDT_REQUIRE(net && launches && folded && n >= 1 && rh >= 1 && rw >= 1, "blur summary arguments");
+    Plan plan;
+    int rc = make_plan(net, n, rh, rw, plan);
+    if (rc != GDT_OK) return rc;
+    *launches = *folded = 0;
+    for (size_t i = 0; i < plan.steps.size(); ++i) {
+        if (net->ops[i].kind != OP_BLUR) continue;
+        ++*launches;
+        *folded += plan.steps[i].norm_from >= 0;
     }
     return GDT_OK;
 }

@@ -200,6 +200,11 @@ class HipNet:
             raise NotImplementedError("resize mode %r: only 'bilinear' and 'nearest' are on the HIP path" % (mode,))
         return self._add("resize", x, like, self.RESIZE_MODES[mode])
 
+    def blur_resample(self, x, up=False):
+        """gdt_net_blur_resample: the anti-aliased Downsample (reflect pad, [1, 2, 1] x [1, 2, 1] / 16 at stride 2) or, ``up``, Upsample (bilinear x 2) of
+        CUT's ResnetGenerator.  An InstanceNorm (+ReLU) whose only consumer is this op is applied by it (``blur_summary``)."""
+        return self._add("blur_resample", x, int(bool(up)))
+
     def gem_l2n(self, x, p, eps_gem=1e-6, eps_l2=1e-6):
         return self._add("gem_l2n", x, float(p), eps_gem, eps_l2)
 
@@ -302,6 +307,13 @@ class HipNet:
         c = (ctypes.c_int * len(keys))()
         _hip.check(self.lib.gdt_net_plan_summary(self.handle, n, rh, rw, int(bool(resize)), c, len(c)))
         return dict(zip(keys, c))
+
+    def blur_summary(self, n, rh, rw):
+        """the planner's decisions about the net's blur-resample ops for a geometry: {"launches": their launches, "folded": those that apply their
+        producer's InstanceNorm themselves} (gdt_net_blur_summary): host logic, no device call"""
+        launches, folded = ctypes.c_int(), ctypes.c_int()
+        _hip.check(self.lib.gdt_net_blur_summary(self.handle, n, rh, rw, ctypes.byref(launches), ctypes.byref(folded)))
+        return {"launches": launches.value, "folded": folded.value}
 
     def convt2x2_launches(self, n, rh, rw):
         """transposed 2x2 convs of a geometry that run as one launch of convt2x2.hip (GDT_CONVT2X2=0: none) -- the planner's count"""
@@ -598,13 +610,23 @@ def _open(device, precision, channels=3, perm=None, in_affine=None):
     return net, net.input(channels, perm=perm, scale=scale, shift=shift)
 
 
+def generator_antialias(sd):
+    """(no_antialias, no_antialias_up) of a ResnetGenerator state dict: CUT's sampling layers carry a ``filt`` buffer -- a Downsample at index 7 (behind
+    the first down layer's conv, norm, ReLU), an Upsample right behind the blocks"""
+    no_antialias = "model.7.filt" not in sd
+    n_blocks = sum(1 for k in sd if k.endswith(".conv_block.1.weight"))
+    first_up = (10 if no_antialias else 12) + n_blocks
+    return no_antialias, "model.%d.filt" % first_up not in sd
+
+
 def generator_layout(sd):
     """(norm, ngf, n_blocks, in_nc, out_nc) recovered from state-dict keys: BatchNorm iff ``model.2.running_mean`` is
-    present (use_bias rule p2p_networks.py:264-267)."""
+    present (use_bias rule p2p_networks.py:264-267).  The head's index follows from the sampling layers present (generator_antialias)."""
     norm = "batch" if "model.2.running_mean" in sd else "instance"
     n_blocks = sum(1 for k in sd if k.endswith(".conv_block.1.weight"))
     w0 = sd["model.1.weight"]
-    last = 10 + n_blocks + 6 + 1
+    no_antialias, no_antialias_up = generator_antialias(sd)
+    last = (10 if no_antialias else 12) + n_blocks + (6 if no_antialias_up else 8) + 1
     return norm, w0.shape[0], n_blocks, w0.shape[1], sd["model.%d.weight" % last].shape[0]
 
 
@@ -613,6 +635,10 @@ def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precisi
     order).  Taps follow the reference's nn.Sequential indices (p2p_networks.py:316-334); a norm-layer tap aliases the
     post-ReLU tensor because the reference's ReLUs are in-place (:272).  Tap 0 / the second reflection pad are not
     materialised on the device (padding is resolved inside the conv loader) and are not available.
+
+    The layout follows the state dict (``generator_antialias``): with CUT's anti-aliased sampling a down layer is a stride-1 conv + norm + ReLU and a
+    ``blur_resample`` op (Downsample), an up layer a ``blur_resample(up=True)`` op (Upsample) and a stride-1 conv + norm + ReLU; a tap on a sampling
+    layer's index is the op's output.  The planner folds the InstanceNorm in front of a sampling op into it unless that norm (or its ReLU) is tapped.
 
     ``stop_after_taps``: the encoder-only graph (``forward(.., encode_only=True)``, p2p_networks.py:328-329) -- the graph ends with the op that
     materialises the last requested tap; there is no generator output (``out_slot`` is None).  A tapped tensor is written by its own op before any later
@@ -654,13 +680,20 @@ def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precisi
     tap(2, h); tap(3, h)
     if encoded():
         return close(None)
+    no_antialias, no_antialias_up = generator_antialias(sd)
     i = 4
     for _ in range(2):
-        h = conv_norm_relu(h, "model.%d" % i, "model.%d" % (i + 1), i, stride=2, pad=1)
+        h = conv_norm_relu(h, "model.%d" % i, "model.%d" % (i + 1), i, stride=2 if no_antialias else 1, pad=1)
         tap(i + 1, h); tap(i + 2, h)
         if encoded():
             return close(None)
         i += 3
+        if not no_antialias:      # Downsample: applies the norm in front of it itself unless that norm is tapped (Planner::norm_folds)
+            h = net.blur_resample(h)
+            tap(i, h)
+            if encoded():
+                return close(None)
+            i += 1
     for _ in range(n_blocks):
         p = "model.%d.conv_block." % i
         r = conv_norm_relu(h, p + "1", p + "2", None, pad=1, reflect=True)
@@ -670,7 +703,15 @@ def build_generator(sd, device, taps=(), pre_tanh=False, in_affine=None, precisi
             return close(None)
         i += 1
     for _ in range(2):
-        h = conv_norm_relu(h, "model.%d" % i, "model.%d" % (i + 1), i, transposed=True, stride=2, pad=1)
+        if no_antialias_up:
+            h = conv_norm_relu(h, "model.%d" % i, "model.%d" % (i + 1), i, transposed=True, stride=2, pad=1)
+        else:                     # Upsample, then a stride-1 conv
+            h = net.blur_resample(h, up=True)
+            tap(i, h)
+            if encoded():
+                return close(None)
+            i += 1
+            h = conv_norm_relu(h, "model.%d" % i, "model.%d" % (i + 1), i, pad=1)
         tap(i + 1, h); tap(i + 2, h)
         if encoded():
             return close(None)

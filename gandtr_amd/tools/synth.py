@@ -58,10 +58,18 @@ def _bn(sd, seed, name, c, gamma_scale=1.0):
     sd[name + ".num_batches_tracked"] = torch.tensor(1, dtype=torch.long)
 
 
-def generator_state(seed=0, norm="instance", ngf=64, n_blocks=9, in_nc=3, out_nc=3, gain=0.02):
+def _blur_filt(c, size):
+    """the ``filt`` buffer of a Downsample (size 3: outer([1, 2, 1]) / 16) or an Upsample (size 4: outer([1, 3, 3, 1]) / 16): [c, 1, size, size]"""
+    row = torch.tensor([1., 2., 1.] if size == 3 else [1., 3., 3., 1.])
+    return (row[:, None] * row[None, :] / 16.0)[None, None].repeat(c, 1, 1, 1)
+
+
+def generator_state(seed=0, norm="instance", ngf=64, n_blocks=9, in_nc=3, out_nc=3, gain=0.02, no_antialias=True, no_antialias_up=True):
     """ResnetGenerator state dict (p2p_networks.py:269-313).  ``norm='instance'``: N(0, gain) conv weights with
     biases (use_bias, :264-267); ``norm='batch'``: kaiming conv weights, no conv bias, non-trivial BN running
-    statistics (last BN of every ResnetBlock scaled by 0.5 so nine residual blocks stay O(1))."""
+    statistics (last BN of every ResnetBlock scaled by 0.5 so nine residual blocks stay O(1)).  ``no_antialias`` False: CUT's down layers -- the conv
+    (stride 1, same weight shape), norm, ReLU and a Downsample whose ``filt`` buffer sits at the next index; ``no_antialias_up`` False: CUT's up layers
+    -- an Upsample's ``filt`` buffer, then a Conv2d (weights [cout, cin, 3, 3]) in place of the ConvTranspose2d."""
     sd = {}
     inorm = norm == "instance"
     g = gain if inorm else None
@@ -77,6 +85,9 @@ def generator_state(seed=0, norm="instance", ngf=64, n_blocks=9, in_nc=3, out_nc
         _conv(sd, seed, "model.%d" % i, 2 * c, c, 3, inorm, g)
         norm_at("model.%d" % (i + 1), 2 * c)
         i, c = i + 3, 2 * c
+        if not no_antialias:
+            sd["model.%d.filt" % i] = _blur_filt(c, 3)
+            i += 1
     for _ in range(n_blocks):
         p = "model.%d.conv_block." % i
         _conv(sd, seed, p + "1", c, c, 3, inorm, g)
@@ -85,7 +96,10 @@ def generator_state(seed=0, norm="instance", ngf=64, n_blocks=9, in_nc=3, out_nc
         norm_at(p + "6", c, 0.5)
         i += 1
     for _ in range(2):
-        _conv(sd, seed, "model.%d" % i, c // 2, c, 3, inorm, g, transposed=True)
+        if not no_antialias_up:
+            sd["model.%d.filt" % i] = _blur_filt(c, 4)
+            i += 1
+        _conv(sd, seed, "model.%d" % i, c // 2, c, 3, inorm, g, transposed=no_antialias_up)
         norm_at("model.%d" % (i + 1), c // 2)
         i, c = i + 3, c // 2
     _conv(sd, seed, "model.%d" % (i + 1), out_nc, c, 7, True, g)

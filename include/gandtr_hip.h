@@ -157,6 +157,21 @@ int gdt_net_maxpool(gdt_net* net, int in_tensor, int kernel, int stride, int pad
  * i = min(floor(dst scale), in - 1).  fp32 arithmetic, one store in the tensor's type; equal sizes are a bit-exact copy.  All precision modes. */
 int gdt_net_resize(gdt_net* net, int in_tensor, int like_tensor, int mode, int* out_tensor);
 
+/* The anti-aliased sampling layers of ResnetGenerator(no_antialias=False / no_antialias_up=False), CUT's defaults (p2p_networks.py Downsample / Upsample).
+ * mode 0, Downsample(C): ReflectionPad2d(1), then a depthwise 3 x 3 conv at stride 2 with the weights outer([1,2,1],[1,2,1]) / 16 (all dyadic: exact in fp16
+ * and fp32): out[oy][ox] = sum_ij w_ij in[r(2 oy - 1 + i)][r(2 ox - 1 + j)], r = reflection without the edge pixel; output ceil(H/2) x ceil(W/2).  It needs
+ * H >= 2 and W >= 2: a smaller map is refused when the geometry is planned (the forward, the size queries and the summaries return the error; nothing launches).
+ * mode 1, Upsample(C): replicate pad, depthwise transposed 4 x 4 conv at stride 2 and crop -- the same function as F.interpolate(scale_factor=2, "bilinear",
+ * align_corners=False): per axis out[2 i] = 0.25 in[max(i - 1, 0)] + 0.75 in[i], out[2 i + 1] = 0.75 in[i] + 0.25 in[min(i + 1, last)]; output 2H x 2W, H, W >= 1.
+ * fp32 arithmetic, one store in the tensor's type.  All precision modes.  An InstanceNorm (plain or with ReLU; no residual, no LeakyReLU) whose ONLY consumer is
+ * this op is folded into it (GDT_NORM_FUSION=0: never): the norm step produces mean / rstd only, and the op applies (x - mean) rstd and the ReLU in fp32 to every
+ * tap as it reads it -- the normalised full-resolution tensor is neither written nor read.  Such a fold counts in "norms_folded".  gdt_net_forward_levels with
+ * more than one geometry refuses a graph with this op. */
+int gdt_net_blur_resample(gdt_net* net, int in_tensor, int mode /* 0 down, 1 up */, int* out_tensor);
+/* What the plan of a geometry decides for these ops (host logic only, like gdt_net_plan_summary): *launches = their kernel launches, *folded = how many of them
+ * apply their producer's InstanceNorm themselves. */
+int gdt_net_blur_summary(gdt_net* net, int n, int rh, int rw, int* launches, int* folded);
+
 /* l2n(gem(x, p, eps_gem), eps_l2): cirtorch layers/functional.py:21-22,:130-131.  External output: fp32 [N][D]
  * row-major, i.e. the memory the reference's `o.permute(1,0)` view aliases (imageretrievalnet.py:123). */
 int gdt_net_gem_l2n(gdt_net* net, int in_tensor, float p, float eps_gem, float eps_l2, int* out_slot);
@@ -322,12 +337,12 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
 
 /* Per-op timing for bench.py's roofline line: when enabled, gdt_net_forward records HIP events on the caller's stream
  * around every op.  gdt_net_profile_read (after the forward) returns per op: kind (0 input, 1 conv, 2 instance-norm,
- * 3 maxpool, 4 gem, 5 tap, 6 hed, 7 rcf head, 8 pool head, 9 channel concatenation, 10 median head, 11 resize), the conv kernel variant (BM*1000+BN: conv_igemm_kernel<BM,BN>; 900000+BN:
+ * 3 maxpool, 4 gem, 5 tap, 6 hed, 7 rcf head, 8 pool head, 9 channel concatenation, 10 median head, 11 resize, 12 blur-resample), the conv kernel variant (BM*1000+BN: conv_igemm_kernel<BM,BN>; 900000+BN:
  * conv3x3_halo_kernel<BN>), elapsed ms and the algorithmic FLOPs.  No reference counterpart (the reference has wall-clock StopWatch only, mdir/tools/stats.py:48-68). */
 int gdt_net_set_profiling(gdt_net* net, int enable);
 int gdt_net_profile_read(gdt_net* net, int max_ops, int* n_ops, int* kinds, int* tile_n, double* ms, double* flops);
 /* ... and the ALGORITHMIC HBM bytes of each op of that forward (conv ops: input once -- a strided 1x1 conv only the pixels it samples --,
- * output once, residual once, fp16 weights once; a fused launch is booked on its first op without the tensors that never exist; a conv that
+ * output once, residual once, fp16 weights once; a blur-resample op: input once, output once, the statistics slab of a folded norm; a fused launch is booked on its first op without the tensors that never exist; a conv that
  * applies its producer's InstanceNorm while staging also counts the block residual it adds and the normalised tensor it writes back):
  * the numerator of bench.py's HBM view of the Bottleneck 1x1 convs (SURVEY.md section 8d "compulsory bytes"). */
 int gdt_net_profile_read_bytes(gdt_net* net, int max_ops, int* n_ops, double* bytes);
