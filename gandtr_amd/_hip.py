@@ -135,6 +135,7 @@ SIGNATURES = {
     "gdt_net_num_ops": (c_int, [c_void_p]),
     "gdt_net_plan_summary": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _IP, c_int]),
     "gdt_net_blur_summary": (c_int, [c_void_p, c_int, c_int, c_int, _IP, _IP]),
+    "gdt_net_basic_summary": (c_int, [c_void_p, c_int, c_int, c_int, _IP]),
     "gdt_ms_aggregate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "gdt_whiten": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gdt_whiten_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

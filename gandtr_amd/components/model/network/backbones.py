@@ -1,10 +1,13 @@
-"""VGG16 and ResNet-50/101/152 module graphs.
+"""VGG16, ResNet-18/34 and ResNet-50/101/152 module graphs.
 
 The reference obtains these from ``torchvision.models.<arch>(pretrained=False)`` (mdir/external/cirtorch/networks/
 imageretrievalnet.py:174-180) and keeps ``features.children()[:-1]`` (VGG) / ``children()[:-2]`` (ResNet), :185-190.
 torchvision is neither vendored by the reference nor installed here, so the published architectures are restated with
 torchvision's module names (checkpoint keys ``features.<i>...`` must match): VGG cfg "D"; ResNet v1.5 Bottleneck
-(stride on the 3x3 conv, expansion 4).  Parity of this layer graph is pinned by no reference test.
+(stride on the 3x3 conv, expansion 4); BasicBlock (two 3x3 convs, stride on the first, expansion 1) for the
+ResNet-18/34 the reference's cirtorch lists with output dimension 512 (imageretrievalnet.py:76-77).  Parity of this
+layer graph is pinned by no reference test; tests/test_resnet_basic_host.py holds the BasicBlock nets to
+torchvision's parameter counts and key names.
 """
 import torch
 import torch.nn as nn
@@ -31,6 +34,26 @@ class VGG(nn.Module):
         return self.classifier(torch.flatten(self.avgpool(self.features(x)), 1))
 
 
+class BasicBlock(nn.Module):
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):
+        idt = x if self.downsample is None else self.downsample(x)
+        o = self.relu(self.bn1(self.conv1(x)))
+        o = self.bn2(self.conv2(o))
+        return self.relu(o + idt)
+
+
 class Bottleneck(nn.Module):
     expansion = 4
 
@@ -55,8 +78,9 @@ class Bottleneck(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, blocks, num_classes=1000):
+    def __init__(self, blocks, num_classes=1000, block=Bottleneck):
         super().__init__()
+        self.block = block
         self.inplanes = 64
         self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -67,7 +91,7 @@ class ResNet(nn.Module):
         self.layer3 = self._make_layer(256, blocks[2], 2)
         self.layer4 = self._make_layer(512, blocks[3], 2)
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
-        self.fc = nn.Linear(2048, num_classes)
+        self.fc = nn.Linear(512 * block.expansion, num_classes)
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
@@ -76,13 +100,14 @@ class ResNet(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
     def _make_layer(self, planes, n, stride):
-        down = None
-        if stride != 1 or self.inplanes != planes * 4:
-            down = nn.Sequential(nn.Conv2d(self.inplanes, planes * 4, kernel_size=1, stride=stride, bias=False),
-                                 nn.BatchNorm2d(planes * 4))
-        layers = [Bottleneck(self.inplanes, planes, stride, down)]
-        self.inplanes = planes * 4
-        layers += [Bottleneck(self.inplanes, planes) for _ in range(1, n)]
+        block, down = self.block, None
+        width = planes * block.expansion
+        if stride != 1 or self.inplanes != width:
+            down = nn.Sequential(nn.Conv2d(self.inplanes, width, kernel_size=1, stride=stride, bias=False),
+                                 nn.BatchNorm2d(width))
+        layers = [block(self.inplanes, planes, stride, down)]
+        self.inplanes = width
+        layers += [block(self.inplanes, planes) for _ in range(1, n)]
         return nn.Sequential(*layers)
 
     def forward(self, x):
@@ -101,6 +126,16 @@ def vgg16(pretrained=False):
     return VGG(VGG16_CFG)
 
 
+def resnet18(pretrained=False):
+    _no_pretrained(pretrained)
+    return ResNet((2, 2, 2, 2), block=BasicBlock)
+
+
+def resnet34(pretrained=False):
+    _no_pretrained(pretrained)
+    return ResNet((3, 4, 6, 3), block=BasicBlock)
+
+
 def resnet50(pretrained=False):
     _no_pretrained(pretrained)
     return ResNet((3, 4, 6, 3))
@@ -116,4 +151,4 @@ def resnet152(pretrained=False):
     return ResNet((3, 8, 36, 3))
 
 
-ARCHITECTURES = {"vgg16": vgg16, "resnet50": resnet50, "resnet101": resnet101, "resnet152": resnet152}
+ARCHITECTURES = {"vgg16": vgg16, "resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "resnet101": resnet101, "resnet152": resnet152}

@@ -180,7 +180,7 @@ class Rpool(nn.Module):
 POOLING = {"mac": MAC, "spoc": SPoC, "gem": GeM, "gemmp": GeMmp, "rmac": RMAC}
 
 
-OUTPUT_DIM = {"vgg16": 512, "resnet50": 2048, "resnet101": 2048, "resnet152": 2048}
+OUTPUT_DIM = {"vgg16": 512, "resnet18": 512, "resnet34": 512, "resnet50": 2048, "resnet101": 2048, "resnet152": 2048}
 
 
 class ImageRetrievalNet(HipBacked, nn.Module):
@@ -220,7 +220,7 @@ class ImageRetrievalNet(HipBacked, nn.Module):
             o = self.norm(self.whiten(o))
         return o.permute(1, 0)
 
-    HIP_TRUNKS = ("vgg16", "resnet50", "resnet101", "resnet152")
+    HIP_TRUNKS = ("vgg16", "resnet18", "resnet34", "resnet50", "resnet101", "resnet152")
 
     def _hip_head(self):
         """What engine.build_embedder needs to know about the head beyond the state dict, as a hashable tuple (it is part of the cache key of
@@ -252,7 +252,7 @@ class ImageRetrievalNet(HipBacked, nn.Module):
     def _hip_embedder(self):
         from .... import engine
         if self.meta.get("architecture") not in self.HIP_TRUNKS:
-            raise NotImplementedError("HIP embedder supports vgg16 / resnet50 / resnet101 / resnet152 trunks")
+            raise NotImplementedError("HIP embedder supports vgg16 / resnet18 / resnet34 / resnet50 / resnet101 / resnet152 trunks")
         head = self._hip_head()
         variant = self._hip_variant()
         self._hip_check_inference()

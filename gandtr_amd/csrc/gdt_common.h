@@ -334,4 +334,9 @@ int gdt_launch_bneck(const f16* x, f16* y, const f16* wr, const f16* w3, const f
                      const f16* wd, const float* bd, int cin, int C, int mid, int N, int H, int W, hipStream_t stream);   // wd / bd: 1x1 projection shortcut (cin != C), else null
 int gdt_launch_bneck_levels(const f16* const* x, f16* const* y, const f16* wr, const f16* w3, const f16* we, const float* br, const float* b3, const float* be,
                             const f16* wd, const float* bd, int cin, int C, int mid, const int* N, const int* H, const int* W, int L, hipStream_t stream);   // ... on L geometries in one launch
+// conv3x3_basic.hip: identity BasicBlock (3x3 + ReLU -> 3x3 + residual + ReLU, 64 -> 64 channels) as one launch (variant 936064); w1 / w2 in fragment order,
+// b1 / b2 the folded shifts.  Knob GDT_CONV_BASIC: 0 never, 1 with at least GDT_BASIC_MIN_TILES patches, 2 whatever the patch count
+bool gdt_basic_eligible(int C, int N, int H, int W);
+int gdt_launch_basic_levels(const f16* const* x, f16* const* y, const f16* w1, const f16* w2, const float* b1, const float* b2, const int* N, const int* H,
+                            const int* W, int L, hipStream_t stream);   // L = 1: the plain launch; else L geometries in one launch
 int gdt_conv_bn(int Cout);    // N tile used for a given Cout (CoutPad must be a multiple of it)

@@ -15,13 +15,13 @@ struct LevelCtx {
     Plan plan; std::vector<Tensor> T;
     float group_factor = 1.f;                    // the planner hint this geometry was planned with (gdt_net_set_group_factor)
 };
-enum { DEFER_NONE = 0, DEFER_CONV = 1, DEFER_BNECK = 2 };
+enum { DEFER_NONE = 0, DEFER_CONV = 1, DEFER_BNECK = 2, DEFER_BASIC = 3 };
 // a launch a step WOULD make, handed back instead of issued: the lock-step driver (several geometries per forward) joins the levels' launches of one op
 struct Deferred {
     int kind = DEFER_NONE;
     bool kcat = false;
     ConvLaunch d;                                // DEFER_CONV: the descriptor gdt_launch_conv / gdt_launch_conv_1x1_rb (kcat) would get
-    const f16* bx = nullptr; f16* by = nullptr; int bn = 0, bh = 0, bw = 0;      // DEFER_BNECK: block input / output and geometry (the weights are the op's)
+    const f16* bx = nullptr; f16* by = nullptr; int bn = 0, bh = 0, bw = 0;      // DEFER_BNECK / DEFER_BASIC: block input / output and geometry (the weights are the op's)
 };
 
 // One conv op of the graph on one geometry, as exec_step sees it.  `defer` != null: launches that can share a launch with the other geometries' are handed back
@@ -65,6 +65,38 @@ int exec_bneck(const ConvStep& s) {
         for (const Op* w : {b.oa, b.ob, b.oc, b.od}) if (w) by += (double)w->cd.cin * w->cd.cout * w->cd.kh * w->cd.kw * sizeof(f16);
         for (int k = 0; k <= nskip; ++k) net->last_bytes[stp.op + k] = 0.0;
         net->last_bytes[stp.op] = by;
+    }
+    return rc;
+}
+
+// weights of a fused BasicBlock step (the step of the block's second conv; the first is the op in front of it)
+struct BasicArgs { const f16 *w1, *w2; const float *b1, *b2; const Op *oa, *ob; };
+BasicArgs basic_args(const gdt_net* net, const Step& stp) {
+    const Op &oa = net->ops[stp.op - 1], &ob = net->ops[stp.op];
+    auto wf = [&](const Op& o) { return (const f16*)(net->dev_blob + o.phases[0].w_frag_off); };
+    auto bs = [&](const Op& o) { return (const float*)(net->dev_blob + o.bias_off); };
+    return {wf(oa), wf(ob), bs(oa), bs(ob), &oa, &ob};
+}
+
+// the whole identity BasicBlock in one launch (conv3x3_basic.hip)
+int exec_basic(const ConvStep& s) {
+    gdt_net* net = s.net;
+    const Step& stp = s.stp;
+    const BasicArgs b = basic_args(net, stp);
+    const int in = b.oa->in, H = s.c.T[in].H, W = s.c.T[in].W;
+    GDT_REQUIRE(b.ob->res == in && gdt_basic_eligible(b.oa->cd.cin, s.c.n, H, W), "planned BasicBlock launch is not eligible at run time");
+    int rc = GDT_OK;
+    if (s.defer) { s.defer->kind = DEFER_BASIC; s.defer->bx = s.tptr(in); s.defer->by = s.tptr(b.ob->out); s.defer->bn = s.c.n; s.defer->bh = H; s.defer->bw = W; }
+    else {
+        const f16* x = s.tptr(in); f16* y = s.tptr(b.ob->out); const int n = s.c.n;
+        rc = gdt_launch_basic_levels(&x, &y, b.w1, b.w2, b.b1, b.b2, &n, &H, &W, 1, s.st);
+    }
+    if (net->profiling && s.book) {      // the block's FLOPs, bytes and time are booked on its second conv
+        net->last_variant[stp.op] = 936064;
+        net->last_flops[stp.op] += net->last_flops[stp.op - 1]; net->last_flops[stp.op - 1] = 0.0;
+        // bytes: the block-boundary tensors (x once -- it is also the residual --, y once) and both weight matrices once
+        net->last_bytes[stp.op - 1] = 0.0;
+        net->last_bytes[stp.op] = s.tbytes(in) + s.tbytes(b.ob->out) + 2.0 * 64 * 64 * 9 * sizeof(f16);
     }
     return rc;
 }
@@ -232,6 +264,7 @@ int exec_conv(const ConvStep& s) {
         case ROUTE_T4: return exec_t4(s);
         case ROUTE_T2: return exec_t2(s);
         case ROUTE_CAT: return exec_cat(s, f);
+        case ROUTE_BASIC: return exec_basic(s);
         case ROUTE_CTF: return exec_ctf(s, f);
         case ROUTE_S2: return exec_s2(s, f);
         case ROUTE_PAIRS: return exec_pairs(s, f);
@@ -388,8 +421,15 @@ int launch_bneck_levels(gdt_net* net, const Step& stp, const Deferred* df, int L
     return gdt_launch_bneck_levels(xs, ys, b.wr, b.w3, b.we, b.br, b.b3, b.be, b.wd, b.bd, b.cin, b.C, b.mid, ns, hs, wsz, L, st);
 }
 
+int launch_basic_levels(gdt_net* net, const Step& stp, const Deferred* df, int L, hipStream_t st) {
+    const BasicArgs b = basic_args(net, stp);
+    const f16* xs[GDT_MAX_LEVELS]; f16* ys[GDT_MAX_LEVELS]; int ns[GDT_MAX_LEVELS], hs[GDT_MAX_LEVELS], wsz[GDT_MAX_LEVELS];
+    for (int l = 0; l < L; ++l) { xs[l] = df[l].bx; ys[l] = df[l].by; ns[l] = df[l].bn; hs[l] = df[l].bh; wsz[l] = df[l].bw; }
+    return gdt_launch_basic_levels(xs, ys, b.w1, b.w2, b.b1, b.b2, ns, hs, wsz, L, st);
+}
+
 // The forward on L independent geometries in lock-step: op by op, every geometry's launch of the op -- joined into ONE launch where the kernel has a
-// multi-geometry entry and the levels select the same kernel family (conv1x1_rb.hip, conv3x3_halo_rb.hip, conv_bneck.hip), else issued one after the other
+// multi-geometry entry and the levels select the same kernel family (conv1x1_rb.hip, conv3x3_halo_rb.hip, conv_bneck.hip, conv3x3_basic.hip), else issued one after the other
 int forward_levels(gdt_net* net, LevelCtx* cx, int L, hipStream_t st) {
     const int nops = (int)net->ops.size();
     net->last_joined = 0; net->last_level_launches = 0;
@@ -411,15 +451,17 @@ int forward_levels(gdt_net* net, LevelCtx* cx, int L, hipStream_t st) {
         if (L == 1) rc = exec_step(net, cx[0], cx[0].plan.steps[i], st, nullptr, true);
         else {
             Deferred df[GDT_MAX_LEVELS];
-            int nconv = 0, nbneck = 0, nkcat = 0;
+            int nconv = 0, nbneck = 0, nkcat = 0, nbasic = 0;
             for (int l = 0; l < L && rc == GDT_OK; ++l) {
                 rc = exec_step(net, cx[l], cx[l].plan.steps[i], st, &df[l], l == 0);
                 nconv += df[l].kind == DEFER_CONV; nbneck += df[l].kind == DEFER_BNECK; nkcat += df[l].kind == DEFER_CONV && df[l].kcat;
+                nbasic += df[l].kind == DEFER_BASIC;
             }
             if (rc != GDT_OK) return rc;
-            net->last_level_launches += nconv + nbneck;
+            net->last_level_launches += nconv + nbneck + nbasic;
             bool joined = false;
             if (nbneck == L) { rc = launch_bneck_levels(net, cx[0].plan.steps[i], df, L, st); joined = true; }
+            else if (nbasic == L) { rc = launch_basic_levels(net, cx[0].plan.steps[i], df, L, st); joined = true; }
             else if (nconv == L && (nkcat == 0 || nkcat == L)) {
                 ConvLaunch dl[GDT_MAX_LEVELS];
                 int fam = nkcat ? 1 : gdt_conv_family(df[0].d);
@@ -428,11 +470,11 @@ int forward_levels(gdt_net* net, LevelCtx* cx, int L, hipStream_t st) {
                 else if (fam == 2 && gdt_conv_halo_rb_levels_ok(dl, L)) { rc = gdt_launch_conv_halo_rb_levels(dl, L, st); joined = true; if (net->profiling) net->last_variant[i] = 910256; }
             }
             if (joined) ++net->last_joined;
-            if (knob_levels_debug() && (nconv || nbneck)) {
+            if (knob_levels_debug() && (nconv || nbneck || nbasic)) {
                 fprintf(stderr, "[levels] op %d joined %d:", i, (int)joined);
                 for (int l = 0; l < L; ++l) {
                     if (df[l].kind == DEFER_CONV) fprintf(stderr, " [conv%s fam %d M %d Cin %d Cout %d taps %d s%d]", df[l].kcat ? " kcat" : "", gdt_conv_family(df[l].d), df[l].d.M, df[l].d.Cin, df[l].d.Cout, df[l].d.ntaps, df[l].d.sy);
-                    else if (df[l].kind == DEFER_BNECK) fprintf(stderr, " [bneck %dx%dx%d]", df[l].bn, df[l].bh, df[l].bw);
+                    else if (df[l].kind == DEFER_BNECK || df[l].kind == DEFER_BASIC) fprintf(stderr, " [%s %dx%dx%d]", df[l].kind == DEFER_BNECK ? "bneck" : "basic", df[l].bn, df[l].bh, df[l].bw);
                     else fprintf(stderr, " [-]");
                 }
                 fprintf(stderr, "\n");
@@ -440,6 +482,7 @@ int forward_levels(gdt_net* net, LevelCtx* cx, int L, hipStream_t st) {
             if (!joined) {                    // one by one (levels whose step was not handed back have launched already)
                 for (int l = 0; l < L && rc == GDT_OK; ++l) {
                     if (df[l].kind == DEFER_BNECK) rc = launch_bneck_levels(net, cx[l].plan.steps[i], &df[l], 1, st);
+                    else if (df[l].kind == DEFER_BASIC) rc = launch_basic_levels(net, cx[l].plan.steps[i], &df[l], 1, st);
                     else if (df[l].kind == DEFER_CONV && df[l].kcat) rc = gdt_launch_conv_1x1_rb(df[l].d, st);
                     else if (df[l].kind == DEFER_CONV) { int variant = 0; rc = gdt_launch_conv(df[l].d, st, &variant); if (net->profiling && l == 0) net->last_variant[i] = variant; }
                 }

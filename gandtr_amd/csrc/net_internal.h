@@ -214,6 +214,8 @@ enum Route {
     ROUTE_T4,          // CONV: ConvTranspose2d(k4,s2,p1) from its one or two inputs in one launch (conv4x4t_halo.hip) instead of four phase launches over the concatenation
     ROUTE_T2,          // CONV: ConvTranspose2d(k2,s2,p0) as one launch (convt2x2.hip) instead of four phase launches
     ROUTE_CAT,         // CONV: Conv2d(k3,s1,p1) from its two inputs (conv3x3_cat_halo.hip) instead of the conv of one tensor over the concatenation
+    ROUTE_BASIC,       // CONV: SECOND conv of an identity BasicBlock (3x3 + ReLU at op i - 1, whose step is skipped; this one 3x3 + residual + ReLU) that runs as ONE launch
+                       //       (conv3x3_basic.hip); the tensor between the two is laid out but never written
     ROUTE_CTF,         // CONV (transposed): the single fused-phase launch
     ROUTE_S2,          // CONV (stride 2, f16c / f16x3): the shift form over the virtual space-to-depth input
     ROUTE_PAIRS,       // CONV (transposed, f16x3, 64 output channels): two paired-phase launches (Op::pairs) instead of four phase launches

@@ -742,6 +742,20 @@ void Planner::source_routes() {
         else if (o.has_t2) { if (gdt_convt2x2_eligible(conv_desc_t2(probe, i))) take(i, ROUTE_T2); }
         else if (o.has_cat_frag && !plan.steps[i].aug && gdt_conv3x3_cat_halo_eligible(conv_desc_cc(probe, i, fold_of(net, plan, i)))) take(i, ROUTE_CAT);
     }
+    // ... and (fp16 mode) identity BasicBlocks as one launch (conv3x3_basic.hip): conv 3x3 s1 zero-pad 1 (64 -> 64, ReLU) -> conv 3x3 s1 zero-pad 1 (64 -> 64) + residual
+    // = the first conv's input, ReLU; the tensor between them has no other consumer (a tap counts as one).  Reflect padding, a block without the final ReLU,
+    // LeakyReLU, InstanceNorm statistics or a folded norm are not this form (plain_conv, is_3x3_relu, taken).  The launch is the SECOND conv's step: its input,
+    // residual and output are alive there on either route, and the tensor between the convs is laid out but never written.
+    for (int i = 0; i + 1 < nops && !net->precision; ++i) {
+        const Op &a = ops[i], &b = ops[i + 1];
+        if (!plain_s1(a) || !plain_s1(b) || !is_3x3_relu(a)) continue;
+        if (b.cd.kh != 3 || b.cd.kw != 3 || b.cd.pad != 1 || b.cd.pad_reflect || !b.cd.relu || b.in != a.out || b.res != a.in || b.out < 0) continue;
+        if (consumers[a.out] != 1 || route(i) != ROUTE_OWN || route(i + 1) != ROUTE_OWN || taken(i) || taken(i + 1)) continue;
+        auto c64 = [](const Op& o) { return o.cd.cin == 64 && o.cin_pad == 64 && o.cd.cout == 64 && o.cout_pad == 64 && o.phases[0].ntaps == 9 && o.phases[0].Kpad == 576; };
+        if (!c64(a) || !c64(b)) continue;
+        if (!gdt_basic_eligible(64, N, T[a.in].H, T[a.in].W)) continue;
+        route(i) = ROUTE_SKIP; route(i + 1) = ROUTE_BASIC;
+    }
 }
 
 }  // namespace
@@ -919,6 +933,16 @@ int gdt_net_blur_summary(gdt_net* net, int n, int rh, int rw, int* launches, int
         ++*launches;
         *folded += plan.steps[i].norm_from >= 0;
     }
+    return GDT_OK;
+}
+
+int gdt_net_basic_summary(gdt_net* net, int n, int rh, int rw, int* fused) {
+    GDT_REQUIRE(net && fused && n >= 1 && rh >= 1 && rw >= 1, "basic summary arguments");
+    Plan plan;
+    int rc = make_plan(net, n, rh, rw, plan);
+    if (rc != GDT_OK) return rc;
+    *fused = 0;
+    for (const Step& st : plan.steps) *fused += st.route == ROUTE_BASIC;
     return GDT_OK;
 }
 

@@ -315,6 +315,13 @@ class HipNet:
         _hip.check(self.lib.gdt_net_blur_summary(self.handle, n, rh, rw, ctypes.byref(launches), ctypes.byref(folded)))
         return {"launches": launches.value, "folded": folded.value}
 
+    def basic_blocks_fused(self, n, rh, rw):
+        """identity BasicBlocks of a geometry that run as one launch of conv3x3_basic.hip (gdt_net_basic_summary; GDT_CONV_BASIC: unset = the measured
+        default, off; 0 never; 1 with enough patches; 2 wherever the shapes fit): host logic, no device call"""
+        fused = ctypes.c_int()
+        _hip.check(self.lib.gdt_net_basic_summary(self.handle, n, rh, rw, ctypes.byref(fused)))
+        return fused.value
+
     def convt2x2_launches(self, n, rh, rw):
         """transposed 2x2 convs of a geometry that run as one launch of convt2x2.hip (GDT_CONVT2X2=0: none) -- the planner's count"""
         return self.plan_summary(n, rh, rw)["convt2x2_launches"]
@@ -754,8 +761,12 @@ def _resnet_trunk(net, x, sd, prefix="features."):
             p = "%s%d.%d." % (prefix, 4 + li, b)
             stride = 2 if (b == 0 and li > 0) else 1
             idt = x
-            if b == 0:
+            if p + "downsample.0.weight" in sd:              # (every first block of a Bottleneck stage; of a BasicBlock stage only where stride or width change)
                 idt = net.conv(x, sd[p + "downsample.0.weight"], None, bn=_bn(sd, p + "downsample.1"), stride=stride)
+            if p + "conv3.weight" not in sd:                 # BasicBlock (resnet18 / 34): two 3x3 convs, the stride on the first
+                o = net.conv(x, sd[p + "conv1.weight"], None, bn=_bn(sd, p + "bn1"), stride=stride, pad=1, relu=True)
+                x = net.conv(o, sd[p + "conv2.weight"], None, bn=_bn(sd, p + "bn2"), pad=1, relu=True, residual=idt)
+                continue
             o = net.conv(x, sd[p + "conv1.weight"], None, bn=_bn(sd, p + "bn1"), relu=True)
             o = net.conv(o, sd[p + "conv2.weight"], None, bn=_bn(sd, p + "bn2"), stride=stride, pad=1, relu=True)
             x = net.conv(o, sd[p + "conv3.weight"], None, bn=_bn(sd, p + "bn3"), relu=True, residual=idt)

@@ -298,6 +298,31 @@ def resnet101_state(seed=0, p=3.0, blocks=(3, 4, 23, 3), width_div=1):
     return sd
 
 
+def resnet_basic_state(seed=0, p=3.0, blocks=(2, 2, 2, 2), width_div=1):
+    """GeM-ResNet-18 (blocks (2, 2, 2, 2)) / -34 ((3, 4, 6, 3)) embedder state dict: ``features.0`` conv1, ``features.1`` bn1,
+    ``features.{4..7}.<b>.*`` BasicBlocks -- two 3x3 convs, a ``downsample`` only where stride or width change, so not in
+    ``features.4.0`` -- (bn2 gamma x0.25 so the residual stream stays O(1) without calibrated statistics) + ``pool.p``."""
+    sd = {}
+    base = 64 // width_div
+    _conv(sd, seed, "features.0", base, 3, 7, False)
+    _bn(sd, seed, "features.1", base)
+    inpl = base
+    for li, nb in enumerate(blocks):
+        planes = base * (2 ** li)
+        for b in range(nb):
+            q = "features.%d.%d." % (4 + li, b)
+            _conv(sd, seed, q + "conv1", planes, inpl, 3, False)
+            _bn(sd, seed, q + "bn1", planes)
+            _conv(sd, seed, q + "conv2", planes, planes, 3, False)
+            _bn(sd, seed, q + "bn2", planes, 0.25)
+            if b == 0 and (li > 0 or inpl != planes):
+                _conv(sd, seed, q + "downsample.0", planes, inpl, 1, False)
+                _bn(sd, seed, q + "downsample.1", planes)
+            inpl = planes
+    sd["pool.p"] = torch.ones(1) * p
+    return sd
+
+
 HED_BLOCKS = ((64, 64), (128, 128), (256, 256, 256), (512, 512, 512), (512, 512, 512))
 
 

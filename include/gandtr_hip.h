@@ -171,6 +171,12 @@ int gdt_net_blur_resample(gdt_net* net, int in_tensor, int mode /* 0 down, 1 up 
 /* What the plan of a geometry decides for these ops (host logic only, like gdt_net_plan_summary): *launches = their kernel launches, *folded = how many of them
  * apply their producer's InstanceNorm themselves. */
 int gdt_net_blur_summary(gdt_net* net, int n, int rh, int rw, int* launches, int* folded);
+/* Identity BasicBlocks (torchvision BasicBlock without `downsample`: conv 3x3 s1 p1 + ReLU -> conv 3x3 s1 p1 + residual = the first conv's input + ReLU, 64 -> 64
+ * channels, folded BatchNorm or plain bias, precision "f16") that the plan of a geometry runs as ONE launch of conv3x3_basic.hip (the tensor between the two
+ * convs stays in LDS): *fused = their number.  Host logic only, like gdt_net_plan_summary.  Knob GDT_CONV_BASIC, read at every planning: unset = the measured
+ * default (off: DESIGN.md section 4), 0 = never, 1 = wherever the shape conditions hold and the geometry has at least GDT_BASIC_MIN_TILES (256) patches,
+ * 2 = wherever the shape conditions hold.  The layout of a geometry is the same on either route. */
+int gdt_net_basic_summary(gdt_net* net, int n, int rh, int rw, int* fused);
 
 /* l2n(gem(x, p, eps_gem), eps_l2): cirtorch layers/functional.py:21-22,:130-131.  External output: fp32 [N][D]
  * row-major, i.e. the memory the reference's `o.permute(1,0)` view aliases (imageretrievalnet.py:123). */
