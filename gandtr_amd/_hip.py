@@ -153,6 +153,13 @@ SIGNATURES = {
     "gdt_retrieval_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_long, c_int, c_void_p, c_size_t,
                                    c_void_p]),
     "gdt_retrieval_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "gdt_codebook_nearest_workspace_bytes": (c_int, [c_long, c_long, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "gdt_codebook_nearest": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "gdt_codebook_aggregate_workspace_bytes": (c_int, [c_long, c_long, c_int, c_int, POINTER(c_size_t)]),
+    "gdt_codebook_aggregate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_int,
+                                       c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
+    "gdt_kmeans_update_workspace_bytes": (c_int, [c_long, c_long, POINTER(c_size_t)]),
+    "gdt_kmeans_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_size_t, c_void_p]),
     "gdt_retrieval_knn_affinity": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "gdt_retrieval_diffuse_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "gdt_retrieval_diffuse": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
@@ -172,6 +179,9 @@ SIGNATURES = {
     "gdt_rpool_regions": (c_int, [c_int, c_int, c_int, _IP, c_int, _IP]),
     "gdt_pool_regions": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_float, c_int, c_void_p, c_void_p]),
     "gdt_pool_regions_weighted": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "gdt_local_descriptors_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "gdt_local_descriptors": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gdt_net_local_head": (c_int, [c_void_p, c_int, c_float, c_int, _IP]),
     "gdt_pixel_attention_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "gdt_pixel_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gdt_geometric_median_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),

@@ -1,3 +1,3 @@
 """Layers of the reference's mdir/components/model/layers that the retrieval embedders use: attention (L2NormAttention), pooling
-(GeometricMedianWeiszfeld) and preprocessing (EdgeFilter)."""
-from . import attention, pooling, preprocessing  # noqa: F401
+(GeometricMedianWeiszfeld), preprocessing (EdgeFilter), and the grouping of local descriptors over codebooks (grouping, functional)."""
+from . import attention, functional, grouping, pooling, preprocessing  # noqa: F401

@@ -468,3 +468,84 @@ def init_cirnet_attention(attention, **params):
     model = init_cirnet(**params)
     layer = attention_layers.ATTENTIONS[attention.pop("type")](**attention)
     return CirRetrievalNetAttention(layer, model.features, model.lwhiten, model.pool, model.whiten, model.meta)
+
+
+# ---- local descriptors (mdir/external/cirtorch/networks/imageretrievalnet.py:396-427) --------------------------------------------------------
+
+def local_forward(net, x, normalize_max=False):
+    """(descriptors N x D x h x w, attention N x h x w) of a batch: ``net.norm(net.features(x))`` -- every position's L2-normalised descriptor --
+    and the positions' L2NormAttention value sqrt(sum_c x^2 + 1e-10), divided by the image's maximum when ``normalize_max``.  On a HIP device
+    both come from one launch behind the trunk (engine.HipNet.local_head); on the CPU from torch ops.  No gradients on the HIP path."""
+    if net._hip_device().type == "cuda":
+        from .... import engine
+        if net.meta.get("architecture") not in net.HIP_TRUNKS:
+            raise NotImplementedError("HIP embedder supports vgg16 / resnet18 / resnet34 / resnet50 / resnet101 / resnet152 trunks")
+        if net.lwhiten is not None:
+            raise NotImplementedError("local descriptors are taken from the trunk's map: no local whitening")
+        variant = net._hip_variant()
+        net._hip_check_inference()
+        prec = net._hip_precision()
+        head = ("local", float(net.norm.eps), bool(normalize_max))
+        in_c = int(net.features[0].weight.shape[1])
+        hip = net._hip_net(("embed", prec, head) + ((in_c,) + variant if variant or in_c != 3 else ()),
+                           lambda sd, dev: engine.build_embedder(sd, dev, precision=prec, head=head, **dict(variant)))
+        outs = hip.forward(x)
+        return outs[hip.out_slot], outs[hip.attention_slot]
+    o = net.features(net._preprocess(x))
+    att = (o.pow(2).sum(dim=1) + 1e-10).sqrt()
+    if normalize_max:
+        att = att / att.flatten(1).max(dim=1)[0].view(-1, 1, 1)
+    return net.norm(o), att
+
+
+def extract_ssl(net, input):
+    """D x (h w) local descriptors of one image (imageretrievalnet.py:426-427); the tensor stays on the device"""
+    return local_forward(net, input)[0].squeeze(0).reshape(net.meta["out_channels"], -1).detach()
+
+
+def _local_items(images, image_size, transform, bbxs, device):
+    if all(torch.is_tensor(im) for im in images):
+        return [im.unsqueeze(0) if im.dim() == 3 else im for im in images]
+    from ....datasets import ImagesFromList
+    data = ImagesFromList(root="", images=images, imsize=image_size, bbxs=bbxs, transform=transform, device=device)
+    return [t.unsqueeze(0) for t in data.batch(range(len(data)))]
+
+
+def _local_batches(net, items, normalize_max=False, max_batch=32):
+    """per item (descriptors D x h x w, attention h x w); items of equal size go through the network as one batch, as stages.validate.extract_vectors
+    batches them (the trunk and the local head treat every image of a batch on its own)"""
+    device = net._hip_device()
+    groups, out = {}, [None] * len(items)
+    for i, x in enumerate(items):
+        groups.setdefault(tuple(x.shape[1:]), []).append(i)
+    with torch.no_grad():
+        for idx in groups.values():
+            for lo in range(0, len(idx), max_batch):
+                part = idx[lo:lo + max_batch]
+                desc, att = local_forward(net, torch.cat([items[i].to(device) for i in part], 0), normalize_max)
+                for j, i in enumerate(part):
+                    out[i] = (desc[j], att[j])
+    return out
+
+
+def extract_local_vectors(net, images, image_size, transform, bbxs=None, ms=[1], msp=1, print_freq=10):
+    """per image the D x (h w) matrix of ``extract_ssl`` (imageretrievalnet.py:396-424).  ``images``: image tensors (C x H x W or 1 x C x H x W,
+    already transformed) or file names, which ``datasets.ImagesFromList`` loads on the device as the reference's loader does.  More than one scale
+    raises NotImplementedError, like the reference.  Tensors stay on the device; images of equal size are batched."""
+    if len(ms) != 1:
+        raise NotImplementedError("multi-scale local descriptors are not implemented (nor in the reference)")
+    net.eval()
+    items = _local_items(list(images), image_size, transform, bbxs, net._hip_device())
+    return [desc.reshape(desc.shape[0], -1) for desc, _ in _local_batches(net, items)]
+
+
+def extract_local_features(net, images, image_size, transform, scales=(1,), normalize_max=False):
+    """per image ([D x h x w per scale], [h x w attention per scale]): the structure ``layers.grouping.Grouping.forward`` consumes.  A scale other
+    than 1 resizes the image bilinearly (``F.interpolate(scale_factor=s, align_corners=False)``, as extract_ms does) in front of the network."""
+    net.eval()
+    items = _local_items(list(images), image_size, transform, None, net._hip_device())
+    per_scale = []
+    for s in scales:
+        scaled = items if s == 1 else [F.interpolate(x, scale_factor=s, mode="bilinear", align_corners=False) for x in items]
+        per_scale.append(_local_batches(net, scaled, normalize_max))
+    return [([lv[i][0] for lv in per_scale], [lv[i][1] for lv in per_scale]) for i in range(len(items))]

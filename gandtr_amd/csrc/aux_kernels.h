@@ -95,6 +95,10 @@ int gdt_k_pool_regions(const void* x, int f32, float* out, int N, int H, int W, 
 // normalize_max; `partial`: gdt_pixel_attention_partial_floats(N, HW) floats (the workgroups' maxima), unused without normalize_max
 size_t gdt_pixel_attention_partial_floats(int N, long HW);
 int gdt_k_pixel_attention(const void* x, int f32, int N, long HW, int D, int normalize_max, float* out, float* partial, hipStream_t st);
+// The local head (local_head.hip): desc [N][D][HW] = x / (||x||_2 + eps) per position, transposed through LDS; att [N][HW] = sqrt(sum x^2 + 1e-10), divided by the
+// image's maximum when normalize_max; `partial`: gdt_local_head_partial_floats floats (the workgroups' maxima), unused without normalize_max.  One read of the map
+size_t gdt_local_head_partial_floats(int N, long HW, int D, int f32);
+int gdt_k_local_descriptors(const void* x, int f32, int N, long HW, int D, float eps, int normalize_max, float* desc, float* att, float* partial, hipStream_t st);
 int gdt_k_linear_rows(const float* a, const float* w, const float* bias, float* out, int rows, int K, int Dout, hipStream_t st);
 int gdt_k_region_sum(const float* v, float* y, int N, int R, int D, float eps, int l2n, hipStream_t st);
 size_t gdt_pool_head_scratch_floats(int N, int R, int D);

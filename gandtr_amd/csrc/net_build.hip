@@ -845,6 +845,20 @@ int gdt_net_median_head(gdt_net* net, int in_tensor, const gdt_median_head_desc*
     return GDT_OK;
 }
 
+int gdt_net_local_head(gdt_net* net, int in_tensor, float eps, int normalize_max, int* out_slot) {
+    GDT_REQUIRE(net && !net->finalized && out_slot, "net");
+    GDT_REQUIRE(in_tensor >= 0 && in_tensor < (int)net->tensors.size(), "tensor id");
+    const int D = net->tensors[in_tensor].C;
+    GDT_REQUIRE(D % 64 == 0 && D <= 8192 && D == net->tensors[in_tensor].Creal, "local head needs channels % 64 == 0, at most 8192");
+    GDT_REQUIRE(eps >= 0.f && (normalize_max == 0 || normalize_max == 1), "local head: eps >= 0, normalize_max is 0 or 1");
+    Op o; o.kind = OP_LOCAL_HEAD; o.in = in_tensor; o.eps_l2 = eps; o.att_max = normalize_max;
+    o.slot2 = (int)net->out_ops.size() + 1;                     // the attention's slot follows the descriptors'
+    const int op_index = (int)net->ops.size();
+    *out_slot = push_op(net, std::move(o), true);
+    net->out_ops.push_back(op_index);
+    return GDT_OK;
+}
+
 int gdt_net_input_filter(gdt_net* net, int kind, float w, float p, float beta, float tau, float eps) {
     GDT_REQUIRE(net && !net->finalized && net->input_op >= 0, "input filter: between gdt_net_input and gdt_net_finalize");
     GDT_REQUIRE(kind == GDT_FILTER_EDGE, "input filter: kind 1 = EdgeFilter");

@@ -373,6 +373,11 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                                        o.has_fw ? (const float*)(net->dev_blob + o.fb_off) : nullptr, o.eps_l2, scratch, (float*)outputs[o.slot], st);
                 break;
             }
+            case OP_LOCAL_HEAD: {
+                const Tensor& ti = T[o.in];
+                return gdt_k_local_descriptors(tptr(o.in), f32, n, (long)ti.H * ti.W, ti.C, o.eps_l2, o.att_max, (float*)outputs[o.slot], (float*)outputs[o.slot2],
+                                               (float*)(ws + stp.aux_off[0]), st);
+            }
             case OP_OUT_NCHW: {
                 const Tensor& ti = T[o.in];
                 return gdt_k_unpack_output(tptr(o.in), f32, (float*)outputs[o.slot],

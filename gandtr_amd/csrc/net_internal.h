@@ -19,7 +19,7 @@ inline size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
 inline int next_pow2(int v) { int p = 8; while (p < v) p <<= 1; return p; }
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF, OP_POOL_HEAD, OP_CONCAT, OP_MEDIAN_HEAD, OP_RESIZE, OP_BLUR };
+enum OpKind { OP_INPUT, OP_CONV, OP_INORM, OP_MAXPOOL, OP_GEM, OP_OUT_NCHW, OP_HED, OP_RCF, OP_POOL_HEAD, OP_CONCAT, OP_MEDIAN_HEAD, OP_RESIZE, OP_BLUR, OP_LOCAL_HEAD };
 
 struct PackedPhase {
     size_t w_off = 0;                 // byte offset in the device weight blob
@@ -92,6 +92,8 @@ struct Op {
     int att = 0, att_max = 0;   // gdt_pool_head_desc::attention: 1 = L2-norm attention weights in front of the pooling, divided by the image's maximum when att_max
     // median head (median_pool.hip): Weiszfeld iterations; eps_l2, the final whitening (fw_off / fb_off / has_fw) and att / att_max as for the pool head
     int median_iterations = 0;
+    // local head (local_head.hip, OP_LOCAL_HEAD): TWO external outputs -- `slot` the descriptors [N][D][H W], `slot2` the attention [N][H W]; eps in eps_l2, att_max as above
+    int slot2 = -1;
     // out_nchw
     size_t tap_bias_off = 0; bool tap_has_bias = false;
     // head ops (OP_HED, OP_RCF): the feature tensors they read -- inputs like `in` / `res` (op_inputs), kept alive until the head runs

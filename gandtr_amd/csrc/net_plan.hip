@@ -706,6 +706,9 @@ int Planner::layout() {
                 st.aux_off[0] = arena.scratch(floats * sizeof(float));
                 break;
             }
+            case OP_LOCAL_HEAD:                         // the workgroups' maxima of the attention (gdt_k_local_descriptors)
+                st.aux_off[0] = arena.scratch(std::max<size_t>(gdt_local_head_partial_floats(N, (long)T[o.in].H * T[o.in].W, T[o.in].C, net->precision ? 1 : 0), 1) * sizeof(float));
+                break;
             case OP_OUT_NCHW: break;
             case OP_HED: case OP_RCF: {               // one fp32 score map per feature tensor (HED) / per stage, at the stage's size (RCF)
                 size_t sz[5] = {0, 0, 0, 0, 0};
@@ -842,6 +845,10 @@ int gdt_net_output_shape(gdt_net* net, int slot, int n, int rh, int rw, int* dim
             *ndim = 4; break;
         case OP_GEM: case OP_POOL_HEAD: case OP_MEDIAN_HEAD: dims[0] = n; dims[1] = ti.C; *ndim = 2; break;
         case OP_OUT_NCHW: dims[0] = n; dims[1] = ti.C; dims[2] = ti.H; dims[3] = ti.W; *ndim = 4; break;
+        case OP_LOCAL_HEAD:                                            // the descriptors [n][D][h][w] (= [n][D][h w]), then the attention [n][h][w]
+            if (slot == o.slot) { dims[0] = n; dims[1] = ti.C; dims[2] = ti.H; dims[3] = ti.W; *ndim = 4; }
+            else { dims[0] = n; dims[1] = ti.H; dims[2] = ti.W; *ndim = 3; }
+            break;
         case OP_HED: case OP_RCF: dims[0] = n; dims[1] = 1; dims[2] = rh; dims[3] = rw; *ndim = 4; break;     // (edge maps at the network input size)
         default: GDT_REQUIRE(false, "not an output op");
     }
@@ -892,6 +899,10 @@ int gdt_net_plan_summary(gdt_net* net, int n, int rh, int rw, int resize, int* c
                 counts[GDT_PLAN_ATTENTION_LAUNCHES] += 1 + (o.att_max ? 1 : 0);
                 counts[GDT_PLAN_ATTENTION_MAP_READS] += 2;            // the map is read by the norm pass and by the weighted pooling pass
             }
+        }
+        if (o.kind == OP_LOCAL_HEAD) {  // one pass over the map (+ the division by the image's maximum)
+            counts[GDT_PLAN_HEAD_LAUNCHES] += 1 + (o.att_max ? 1 : 0);
+            counts[GDT_PLAN_HEAD_MAP_READS] += 1;
         }
         if (o.kind == OP_MEDIAN_HEAD) { // the launches of gdt_k_median_head: a pass over the map and its finishing step per weighted mean, the l2n, the whitening and its l2n
             counts[GDT_PLAN_HEAD_LAUNCHES] += 2 * (o.median_iterations + 1) + 1 + (o.has_fw ? 2 : 0);

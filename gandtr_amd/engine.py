@@ -97,6 +97,7 @@ class HipNet:
         self.out_slot = None                       # external output of the model's result (set by the build_* functions)
         self.tap_slots = {}                        # generator: tap index -> external output
         self.feature_slot = None                   # embedder: external output of the feature map, if tapped
+        self.attention_slot = None                 # embedder with the local head: external output of the positions' attention
         self._finalized = False                    # finalize() ran: weights are on the device, forwards allowed, geometries cached
         self._profiling = False                    # set_profiling: per-op events; profiled forwards run eagerly, level by level
         self._group_factor = 1.0                   # the planner hint the handle holds (set_group_factor)
@@ -237,6 +238,11 @@ class HipNet:
         fw, fb = (_ptr(t) for t in arrays)                             # (the arrays stay alive until the call has returned)
         d = _hip.MedianHeadDesc(int(iterations), fw, fb, float(eps_l2), 0 if attention is None else 1, int(bool(attention and attention[1])))
         return self._add("median_head", x, ctypes.byref(d))
+
+    def local_head(self, x, eps=1e-6, normalize_max=False):
+        """gdt_net_local_head: the map's positions as L2-normalised descriptors [N][D][H W] (returned slot) and their L2-norm attention [N][H W]
+        (returned slot + 1), divided by the image's maximum when ``normalize_max``"""
+        return self._add("local_head", x, float(eps), int(bool(normalize_max)))
 
     def output_nchw(self, x, bias=None):
         b = _f32(bias)
@@ -804,7 +810,13 @@ def build_embedder(sd, device, in_affine=None, feature_tap=False, precision="f16
     f = _resnet_trunk(net, x, sd) if embedder_arch(sd) == "resnet" else _vgg16_trunk(net, x, sd)
     if attention is not None and attention[0] != "l2norm":
         raise NotImplementedError("attention %r: only 'l2norm' is on the HIP path" % (attention[0],))
-    if head is None and attention is None:
+    if head is not None and head[0] == "local":
+        # ("local", eps of the L2N layer, normalize_max): no pooling -- the local head's two outputs (descriptors, attention slot = out_slot + 1)
+        if attention is not None:
+            raise NotImplementedError("the local head computes the L2-norm attention itself")
+        net.out_slot = net.local_head(f, head[1], head[2])
+        net.attention_slot = net.out_slot + 1
+    elif head is None and attention is None:
         net.out_slot = net.gem_l2n(f, float(sd["pool.p"].reshape(-1)[0]))
     elif head is not None and head[0] == "geometric_median":
         # the dict-valued pooling GeometricMedianWeiszfeld: ("geometric_median", iterations, local whitening, final whitening); no parameters of its own
@@ -1255,6 +1267,26 @@ def pixel_attention(fmap, normalize_max=False):
         _hip.check(lib.gdt_pixel_attention(fmap.data_ptr(), int(fmap.dtype == torch.float32), n, h, w, d, int(bool(normalize_max)), out.data_ptr(),
                                            ws.data_ptr(), ws.numel(), _stream(fmap)))
     return out
+
+
+def local_descriptors(fmap, eps=1e-6, normalize_max=False):
+    """gdt_local_descriptors, the local head's kernel on its own: NHWC map (fp16 or fp32, D % 64 == 0) -> (fp32 N x D x H x W descriptors
+    x / (||x||_2 + eps) per position, fp32 N x H x W attention sqrt(sum x^2 + 1e-10), divided by the image's maximum when ``normalize_max``)"""
+    lib = _hip.load()
+    if not (fmap.is_cuda and fmap.dim() == 4 and fmap.dtype in (torch.float16, torch.float32)):
+        raise ValueError("local_descriptors takes an N x H x W x D fp16 or fp32 map on a HIP device")
+    fmap = fmap.contiguous()
+    n, h, w, d = fmap.shape
+    f32 = int(fmap.dtype == torch.float32)
+    need = ctypes.c_size_t()
+    _hip.check(lib.gdt_local_descriptors_workspace_bytes(n, h, w, d, f32, ctypes.byref(need)))
+    with torch.cuda.device(fmap.device):
+        desc = torch.empty((n, d, h, w), dtype=torch.float32, device=fmap.device)
+        att = torch.empty((n, h, w), dtype=torch.float32, device=fmap.device)
+        ws = torch.empty(max(need.value, 4), dtype=torch.uint8, device=fmap.device)
+        _hip.check(lib.gdt_local_descriptors(fmap.data_ptr(), f32, n, h, w, d, float(eps), int(bool(normalize_max)), desc.data_ptr(), att.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), _stream(fmap)))
+    return desc, att
 
 
 def pool_regions_weighted(fmap, weights, kind, p=3.0, p_channels=None, eps=1e-6, levels=0):

@@ -227,6 +227,13 @@ typedef struct gdt_median_head_desc {
 } gdt_median_head_desc;
 int gdt_net_median_head(gdt_net* net, int in_tensor, const gdt_median_head_desc* desc, int* out_slot);
 
+/* The local head (local_head.hip; extract_ssl, imageretrievalnet.py:426-427, and the L2NormAttention value of every position): TWO external outputs,
+ * *out_slot = fp32 [N][D][H][W] = x / (||x||_2 + eps) per position (the reference's layout: net.norm(net.features(x)), .view(D, -1) per image) and
+ * *out_slot + 1 = fp32 [N][H][W] = sqrt(sum x^2 + 1e-10), divided by the image's maximum when normalize_max.  The map needs channels % 64 == 0 (at most
+ * 8192).  One launch that reads the map once (+ the division by the maximum), counted under GDT_PLAN_HEAD_LAUNCHES / GDT_PLAN_HEAD_MAP_READS.  The
+ * kernel on its own: gdt_local_descriptors. */
+int gdt_net_local_head(gdt_net* net, int in_tensor, float eps, int normalize_max, int* out_slot);
+
 /* Feature tap: internal fp16 NHWC tensor -> external fp32 NCHW (+ optional per-channel bias), p2p_networks.py:316-334 */
 int gdt_net_output_nchw(gdt_net* net, int in_tensor, const float* bias, int* out_slot);
 
@@ -395,6 +402,14 @@ int gdt_pool_regions(const void* fmap, int f32, int n, int h, int w, int d, int 
  * Weights of 1 give gdt_pool_regions bit for bit. */
 int gdt_pool_regions_weighted(const void* fmap, int f32, int n, int h, int w, int d, int kind, float p, const float* p_channels, float eps, int levels,
                               const float* weights, float* out, void* stream);
+/* The local head on its own (gandtr_amd/csrc/local_head.hip): fmap = an NHWC map [n][h][w][d], fp16 or fp32 (f32), 16-byte aligned, d % 64 == 0, d <= 8192.
+ *   desc fp32 [n][d][h * w] = x / (||x||_2 + eps) per position: net.norm(net.features(x)).view(D, -1), the reference's layout (extract_ssl), transposed through
+ *   LDS with coalesced stores;  att fp32 [n][h * w] = sqrt(sum x^2 + 1e-10), the L2NormAttention value (the bits of gdt_pixel_attention), divided by the
+ *   image's maximum when normalize_max (workspace: gdt_local_descriptors_workspace_bytes; unused, may be NULL, otherwise).  One read of the map; sums in an
+ *   order fixed by d alone. */
+int gdt_local_descriptors_workspace_bytes(int n, int h, int w, int d, int f32, size_t* bytes);
+int gdt_local_descriptors(const void* fmap, int f32, int n, int h, int w, int d, float eps, int normalize_max, float* desc, float* att, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* L2NormAttention on its own (mdir/components/model/layers/attention.py:10-15): fmap an NHWC map [n][h][w][d] on the device (f32 = 0: fp16, 1: fp32;
  * d % 64 == 0), out fp32 [n][h * w]: sqrt(sum_c x_c^2 + 1e-10), summed in fp32 in an order fixed by d, divided (not multiplied by a reciprocal) by the
@@ -491,6 +506,36 @@ int gdt_retrieval_topk(const float* vecs, const float* qvecs, int* ids, float* s
  * give the same bits.  One workgroup per query. */
 int gdt_retrieval_expand(const float* vecs, const float* base, const int* ids, const float* scores, float* out, long ndb, int nq, int d, int k,
                          int index_base, float alpha, void* stream);
+/* Codebooks (gandtr_amd/csrc/codebook.hip): the nearest centroids of local descriptors, their aggregation per image and the k-means update.
+ *
+ * gdt_codebook_nearest: x fp32 [F][D], c fp32 [K][D], 1 <= ma <= 8, any 1 <= D <= 8192 (no padded copy), 1 <= F, K < 2^31.
+ *   d2(i, j) = max(0, fmaf(-2, x_i . c_j, xx_i + cc_j)): x_i . c_j accumulated in fp32 in k order on v_mfma_f32_32x32x2_f32 (exact products, the
+ *   arithmetic of gdt_retrieval_topk); xx, cc summed once into the workspace in an order fixed by D alone.  ids int32 [F][ma] / dists fp32 [F][ma]
+ *   = sqrtf(d2): per feature the ma entries that come first in the strict order (d2 ascending, centroid id ascending), in that order; with K < ma
+ *   the tail is id -1, distance +inf.  A centroid whose row holds a NaN (or lies at infinite distance) is never chosen.  The F x K matrix is never
+ *   written.  slices as in gdt_retrieval_topk (0: the library's choice, 1 .. 1024 forced); the result is the same bits for every value.
+ * gdt_codebook_aggregate: per image i (features image_offsets[i] .. image_offsets[i + 1] - 1; int64 [n_images + 1] on the device, ascending, an image
+ *   may be empty) and centroid k:  d = sum over the members (f, s) with ids[f][s] == k, in (f, s) order, of assign[f][s] * feature(x_f, att_f, c_k);
+ *   grouped fp32 [n_images][K][D] = descriptor(d).  att [F] or NULL (ones), assign [F][ma] or NULL (ones); an id outside [0, K) adds nothing.
+ *   feature_fn: 0 iden x, 1 att att*x, 2 res x-c, 3 resatt att*(x-c), 4 normres n(x-c), 5 normresatt att*n(x-c), 6 normresatt2 att^2*n(x-c), with
+ *   n(v) = v / (||v|| + 1e-6).  descriptor_fn: 0 l2norm d/(||d||+1e-6), 1 normsign sign(d)/sqrt(D), 2 sigmoid 2*sigmoid(descriptor_param*d)-1.
+ *   stats fp32 [7][n_images][K]: member count, max and sum of assign, max and sum of assign*att, sum of assign*att^2, ||d||; maxima start at 0 (a
+ *   centroid without members: zeros everywhere, and descriptor(0) = 0 in `grouped`).  Members are ordered by a counting sort on the device and every
+ *   (image, centroid) row is summed in member order by one workgroup and written exactly once; no float atomics, two runs give the same bits, an
+ *   image's rows do not depend on the other images.  Cost beyond the output: the rank pass is quadratic in the members of one (image, centroid) row.
+ * gdt_kmeans_update: c[k] = mean of the points x[f] with ids[f] == k (summed in f order), in place; a cluster without members keeps its centroid and
+ *   sets bit 0 of the device word *status (the caller clears it).
+ * All buffers are device buffers; arguments are checked before any launch (GDT_ERR_INVALID; GDT_ERR_WORKSPACE for a workspace below the matching
+ * *_workspace_bytes).  No synchronisation. */
+int gdt_codebook_nearest_workspace_bytes(long F, long K, int D, int ma, int slices, size_t* bytes);
+int gdt_codebook_nearest(const float* x, const float* c, int* ids, float* dists, long F, long K, int D, int ma, int slices, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int gdt_codebook_aggregate_workspace_bytes(long F, long K, int ma, int n_images, size_t* bytes);
+int gdt_codebook_aggregate(const float* x, const float* att, const float* c, const int* ids, const float* assign, const long long* image_offsets,
+                           float* grouped, float* stats, long F, long K, int D, int ma, int n_images, int feature_fn, int descriptor_fn,
+                           float descriptor_param, void* workspace, size_t workspace_bytes, void* stream);
+int gdt_kmeans_update_workspace_bytes(long F, long K, size_t* bytes);
+int gdt_kmeans_update(const float* x, const int* ids, float* c, int* status, long F, long K, int D, void* workspace, size_t workspace_bytes, void* stream);
 /* Diffusion re-ranking on the mutual kNN graph (Iscen et al., CVPR 2017; gandtr_amd/csrc/retrieval_diffusion.hip).  ids int32 [n][k] / scores fp32
  * [n][k]: the kNN lists of n database vectors as gdt_retrieval_topk writes them with self_base (self excluded, id -1 = missing; an id outside
  * [0, n) is a missing entry: no id is dereferenced unchecked).

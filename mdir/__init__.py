@@ -4,6 +4,7 @@
     mdir.components.model.network          -> gandtr_amd.components.model.network   (MODEL_LABELS, initialize_model)
     mdir.components.model.network.unet     -> gandtr_amd.components.model.network.unet (P2pUNet, OutconvP2pUNet, InconvP2pUNet, AlignedP2pUNet, ShallowP2pUNet)
     mdir.components.model.layers(.attention|.pooling|.preprocessing) -> gandtr_amd.components.model.layers (ATTENTIONS, L2NormAttention, POOLINGS, GeometricMedianWeiszfeld, EdgeFilter)
+    mdir.components.model.layers(.grouping|.functional) -> gandtr_amd.components.model.layers (GROUPINGS, BatchClustering, LoadedCodebook, iterate_kmeans, ..)
     mdir.components.data.wrapper           -> gandtr_amd.components.data.wrapper    (WRAPPERS_LABELS, initialize_wrappers)
     mdir.components.data.transform         -> gandtr_amd.components.data.transform  (initialize_transforms)
     mdir.components.data.dataset           -> gandtr_amd.components.data.dataset    (DATASET_LABELS, initialize_dataset_loader: the GAN scenarios' data)
@@ -36,6 +37,8 @@ _ALIASES = {
     "mdir.components.model.layers.attention": "gandtr_amd.components.model.layers.attention",
     "mdir.components.model.layers.pooling": "gandtr_amd.components.model.layers.pooling",
     "mdir.components.model.layers.preprocessing": "gandtr_amd.components.model.layers.preprocessing",
+    "mdir.components.model.layers.grouping": "gandtr_amd.components.model.layers.grouping",
+    "mdir.components.model.layers.functional": "gandtr_amd.components.model.layers.functional",
     "mdir.components.model.network.single_layer": "gandtr_amd.components.model.network.single_layer",
     "mdir.components.model.network.p2p_networks": "gandtr_amd.components.model.network.p2p_networks",
     "mdir.components.model.network.cirnet": "gandtr_amd.components.model.network.cirnet",
