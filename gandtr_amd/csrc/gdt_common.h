@@ -55,7 +55,7 @@ void gdt_set_error(const std::string& msg);
 // only as entries of GDT_LIVE_KNOBS, which is also what gdt_plan_knob_name() (include/gandtr_hip.h) hands to such a cache.
 inline int gdt_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 inline bool gdt_env_set(const char* name) { return getenv(name) != nullptr; }
-#define GDT_LIVE_KNOBS(X) X(CONV_XEXP) X(XEXP_CHAIN) X(CONV_BNECK) X(CONV_HALO_X3) X(CONV_HALO_X3_FORMS) X(X3_NORM_FOLD)
+#define GDT_LIVE_KNOBS(X) X(CONV_XEXP) X(XEXP_CHAIN) X(CONV_BNECK) X(CONV_HALO_X3) X(CONV_HALO_X3_FORMS) X(X3_NORM_FOLD) X(PLAN_NO_REUSE)
 #define GDT_LIVE_KNOB_NAME(id) "GDT_" #id,
 constexpr const char* GDT_LIVE_KNOB_NAMES[] = { GDT_LIVE_KNOBS(GDT_LIVE_KNOB_NAME) };
 #define GDT_LIVE_KNOB_ID(id) GDT_LIVE_##id,

@@ -125,11 +125,13 @@ constexpr int GDT_RCF_FEATURES = 13;          // conv1_1 .. conv5_3
 
 struct Tensor { int C = 0; int Creal = 0; int H = 0, W = 0; int last_use = -1; size_t off = 0, bytes = 0; };   // C: padded, Creal: logical
 
-// first-fit allocator with coalescing free list; "top" grows when nothing fits
+// first-fit allocator with coalescing free list; "top" grows when nothing fits.  no_reuse (GDT_PLAN_NO_REUSE, the reference layout): nothing is ever
+// released, so every tensor, slab and scratch block of the plan has bytes of its own
 struct Arena {
     struct Blk { size_t off, size; };
     std::vector<Blk> free_;
     size_t top = 0, peak = 0;
+    bool no_reuse = false;
     size_t alloc(size_t bytes) {
         bytes = align_up(bytes);
         for (size_t i = 0; i < free_.size(); ++i)
@@ -151,6 +153,7 @@ struct Arena {
         return off;
     }
     void release(size_t off, size_t bytes) {
+        if (no_reuse) return;
         bytes = align_up(bytes);
         free_.push_back({off, bytes});
         std::sort(free_.begin(), free_.end(), [](const Blk& a, const Blk& b) { return a.off < b.off; });

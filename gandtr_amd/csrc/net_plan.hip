@@ -8,6 +8,7 @@ GDT_KNOB_LATCHED(knob_ctf, "GDT_CONV_CTF", 1)                // transposed convs
 GDT_KNOB_LATCHED(knob_norm_fusion, "GDT_NORM_FUSION", 1)     // 0: no InstanceNorm is folded into its consumer
 GDT_KNOB_LIVE(knob_x3_norm_fold, X3_NORM_FOLD, 2)            // f16x3: 0 no folded norms, 1 the plain norm (+ReLU) only, 2 also residual / write-back and the generic GEMM
 GDT_KNOB_LIVE(knob_xexp, CONV_XEXP, 1)                       // 0: no 3x3 + expand fusion (conv3x3_expand_rb.hip)
+GDT_KNOB_LIVE(knob_no_reuse, PLAN_NO_REUSE, 0)               // 1: the reference layout -- the arena never hands out a byte twice within a plan (Planner::layout); decisions unchanged
 GDT_KNOB_LATCHED(knob_stem_pool, "GDT_CONV_STEM_POOL", 1)    // 0: the max pool behind the direct stem stays its own launch
 GDT_KNOB_LATCHED_SET(knob_plan_debug, "GDT_PLAN_DEBUG")      // set: the norm-fold decisions are printed
 
@@ -631,6 +632,7 @@ int Planner::layout() {
         for (int t : o.feats) T[t].last_use = i;
     }
     Arena arena;
+    arena.no_reuse = knob_no_reuse() != 0;      // (read here, once per plan)
     std::vector<size_t> slab_off(nops, 0), slab_bytes(nops, 0);
     std::vector<std::vector<std::pair<size_t, size_t>>> deferred(nops);      // releases to perform after op i
     auto alloc_tensor = [&](int t) {

@@ -274,6 +274,11 @@ int gdt_net_workspace_bytes(gdt_net* net, int n, int rh, int rw, size_t* bytes);
 /* Threading: host calls on one handle must be serialised (each call plans its geometry into the handle before it enqueues its launches); all
  * per-forward DEVICE state lives in the caller's workspace, so forwards of one handle may overlap on the device when each is given its own
  * workspace and stream (HipNet.forward_many does that for the levels of the multi-scale pyramid). */
+/* Workspace: `workspace` is 256-byte aligned scratch of at least gdt_net_workspace_bytes() bytes for the geometry, with ANY prior content -- the result does
+ * not depend on it (no launch reads a byte that no launch of this forward has written); no byte outside [workspace, workspace + workspace_bytes) is written; and
+ * every element of every output is written.  It holds fp16 / fp32 tensors and fp32 statistics and scratch only: no index, no pointer.  The layout is the
+ * planner's liveness-based first fit; GDT_PLAN_NO_REUSE=1 (read at every plan) selects the reference layout in which no byte is handed out twice -- the same
+ * launches, bit for bit the same outputs, a larger workspace (tests/test_hip_workspace.py pins all of this; gdt_net_forward_levels: the same per level). */
 int gdt_net_forward(gdt_net* net, const float* x, int n, int h, int w, int rh, int rw, float rscale,
                     void* const* outputs, int n_outputs, void* workspace, size_t workspace_bytes, void* stream);
 

@@ -154,11 +154,11 @@ def test_planner_fusion_decisions_at_the_benchmarked_geometries(monkeypatch):
     monkeypatch.delenv("GDT_X3_NORM_FOLD")
 
 
-LIVE_KNOBS = ("GDT_CONV_XEXP", "GDT_XEXP_CHAIN", "GDT_CONV_BNECK", "GDT_CONV_HALO_X3", "GDT_CONV_HALO_X3_FORMS", "GDT_X3_NORM_FOLD")
+LIVE_KNOBS = ("GDT_CONV_XEXP", "GDT_XEXP_CHAIN", "GDT_CONV_BNECK", "GDT_CONV_HALO_X3", "GDT_CONV_HALO_X3_FORMS", "GDT_X3_NORM_FOLD", "GDT_PLAN_NO_REUSE")
 
 
 def test_library_names_its_live_knobs():
-    """the knobs read at every plan are exactly these six, and the geometry cache of HipNet is keyed on the library's own list"""
+    """the knobs read at every plan are exactly these seven, and the geometry cache of HipNet is keyed on the library's own list"""
     from gandtr_amd import _hip
     assert _hip.plan_knobs() == LIVE_KNOBS
     lib = _hip.load()
