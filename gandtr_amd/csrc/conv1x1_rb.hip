@@ -42,7 +42,7 @@ struct Pend { f16x8 v[4]; };
 // then feeds four MFMAs: with two, the weight stream alone asks the full 64 B/clk of the CU's L1 at MFMA rate
 // CAT: K-concatenated second operand (ConvLaunch::in2): K-steps [0, Cin / 64) read `in`, the rest read `in2` at the stride-in2_stride pixel of
 // the output pixel (the row -> (n, oy, ox) split is done once per tile of the staging cursor)
-// (the body takes its workgroup index and grid size as arguments: the multi-geometry entry below runs it per level, gdt_common.h MultiConv)
+// (the body takes its workgroup index and grid size as arguments: the kernel below hands it blockIdx.x and gridDim.x)
 template <bool RES, int DEPTH, int TM, bool CAT = false>
 __device__ __forceinline__ void conv1x1_rb_body(const ConvLaunch& d, const int vblocks, const int bid, const int gdim) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -262,11 +262,6 @@ template <bool RES, int DEPTH, int TM, bool CAT = false>
 __global__ __launch_bounds__(NT, 2) void conv1x1_rb_kernel(const ConvLaunch d, const int vblocks) {
     conv1x1_rb_body<RES, DEPTH, TM, CAT>(d, vblocks, blockIdx.x, gridDim.x);
 }
-template <bool RES, int DEPTH, int TM, bool CAT = false>
-__global__ __launch_bounds__(NT, 2) void conv1x1_rb_multi_kernel(const MultiConv m) {
-    const int l = gdt_multi_level(m.nlev, m.prefix, blockIdx.x);
-    conv1x1_rb_body<RES, DEPTH, TM, CAT>(m.lev[l], m.vblocks[l], blockIdx.x - m.prefix[l], m.prefix[l + 1] - m.prefix[l]);
-}
 
 GDT_KNOB_LATCHED(knob_mode, "GDT_CONV_1X1", 1)               // 0 off, 2 force
 GDT_KNOB_LATCHED(knob_min_tiles, "GDT_CONV_1X1_MIN_TILES", 64)   // (batch 2-4 @1024^2: +7 % over 512; multi-scale config +3 %)
@@ -278,11 +273,9 @@ GDT_KNOB_LATCHED(knob_wide, "GDT_CONV_1X1_WIDE", 1)          // 0: no 128 x 256 
 GDT_KNOB_LATCHED(knob_wide_min, "GDT_CONV_1X1_WIDE_MIN", 256)
 
 template <bool RES, int DEPTH, int TM, bool CAT = false>
-int launch_1x1(const ConvLaunch* dl, int L, hipStream_t stream) {
-    const ConvLaunch& d = dl[0];
+int launch_1x1(const ConvLaunch& d, hipStream_t stream) {
     using K = GdtKernel<conv1x1_rb_kernel<RES, DEPTH, TM, CAT>, (int)LDS_BYTES>;
-    using KM = GdtKernel<conv1x1_rb_multi_kernel<RES, DEPTH, TM, CAT>, (int)LDS_BYTES>;
-    int slots = 0;           // the figure cached with the single-geometry kernel: workgroup slots of the chip
+    int slots = 0;           // the figure cached with the kernel: workgroup slots of the chip
     GDT_CHECK(K::figure(slots, [](int cus, int& v) {
         int per_cu = 0;
         GDT_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv1x1_rb_kernel<RES, DEPTH, TM, CAT>, NT, LDS_BYTES));
@@ -291,14 +284,6 @@ int launch_1x1(const ConvLaunch* dl, int L, hipStream_t stream) {
         v = cus / 8 * 8 * per_cu;                 // a multiple of 8: a workgroup's tiles stay on its XCD
         return GDT_OK;
     }));
-    if (L > 1) {
-        int unused = 0;
-        GDT_CHECK(KM::figure(unused));
-        MultiConv m;
-        m.nlev = L;
-        for (int l = 0; l < L; ++l) { m.lev[l] = dl[l]; m.vblocks[l] = gdt_grid_for_tiles((dl[l].M + BM - 1) / BM, dl[l].CoutPad / (TM == 4 ? 256 : 128)); }
-        return KM::launch(gdt_multi_partition(m.prefix, m.vblocks, L, slots), NT, stream, m);
-    }
     const int vblocks = gdt_grid_for_tiles((d.M + BM - 1) / BM, d.CoutPad / (TM == 4 ? 256 : 128));
     return K::launch(vblocks < slots ? vblocks : slots, NT, stream, d, vblocks);
 }
@@ -334,31 +319,20 @@ bool gdt_conv_1x1_cat_eligible(const ConvLaunch& d) {
     return gdt_enough_tiles((d.M + BM - 1) / BM, d.CoutPad / 128, 64);
 }
 
-// `dl[0 .. L)`: the same conv on L independent geometries (the levels of a pyramid) as ONE launch; the instantiation is chosen for the levels together
-int gdt_launch_conv_1x1_rb_levels(const ConvLaunch* dl_in, int L, hipStream_t stream) {
+int gdt_launch_conv_1x1_rb(const ConvLaunch& d_in, hipStream_t stream) {
     // Row order: the reduce convs walk their rows from the END.  Their input is what the expand conv of the previous block has just
     // written front to back, so the rows written last -- the ones still in the 256 MB Infinity Cache -- are read first (and the 3x3
     // conv that follows, front to back, starts on the rows THIS launch wrote last).  ResNet-101 batch 32: 1860 -> 1882 descriptors/s;
     // reversing the expand convs instead gives the same, reversing both nothing (GDT_CONV_1X1_REV: 1 reduce, 2 expand, 3 both, 0 none).
     const int rev = knob_rev();
-    GDT_REQUIRE(L >= 1 && L <= GDT_MAX_LEVELS, "1..4 geometries per launch");
-    ConvLaunch dl[GDT_MAX_LEVELS];
-    long wide_tiles = 0;
-    for (int l = 0; l < L; ++l) {
-        dl[l] = dl_in[l];
-        dl[l].dbg = ((rev & 1) && !dl[l].res) || ((rev & 2) && dl[l].res) ? 2 : 0;
-        GDT_REQUIRE(dl[l].Kpad == dl[0].Kpad && dl[l].CoutPad == dl[0].CoutPad && (dl[l].res != nullptr) == (dl[0].res != nullptr) && (dl[l].in2 != nullptr) == (dl[0].in2 != nullptr),
-                    "the geometries of one launch run the same conv");
-        wide_tiles += (long)((dl[l].M + BM - 1) / BM) * (dl[l].CoutPad / 256);
-    }
-    const ConvLaunch& d = dl[0];
-    if (d.in2) return launch_1x1<false, 2, 4, true>(dl, L, stream);
+    ConvLaunch d = d_in;
+    d.dbg = ((rev & 1) && !d.res) || ((rev & 2) && d.res) ? 2 : 0;
+    if (d.in2) return launch_1x1<false, 2, 4, true>(d, stream);
     const int nk = d.Kpad / 64;
-    if (d.res) return nk > 1 ? launch_1x1<true, 2, 2>(dl, L, stream) : launch_1x1<true, 1, 2>(dl, L, stream);
+    if (d.res) return nk > 1 ? launch_1x1<true, 2, 2>(d, stream) : launch_1x1<true, 1, 2>(d, stream);
     // (the 128 x 256 tile halves the weight stream per MFMA but also the number of workgroups: below ~one per CU the 128 x 128 tile fills the chip better)
-    if (knob_wide() && nk > 1 && d.CoutPad % 256 == 0 && wide_tiles >= knob_wide_min()) return launch_1x1<false, 2, 4>(dl, L, stream);
-    if (nk % 4 == 0 && knob_max_depth() >= 4) return launch_1x1<false, 4, 2>(dl, L, stream);
-    return nk > 1 ? launch_1x1<false, 2, 2>(dl, L, stream) : launch_1x1<false, 1, 2>(dl, L, stream);
+    const long wide_tiles = (long)((d.M + BM - 1) / BM) * (d.CoutPad / 256);
+    if (knob_wide() && nk > 1 && d.CoutPad % 256 == 0 && wide_tiles >= knob_wide_min()) return launch_1x1<false, 2, 4>(d, stream);
+    if (nk % 4 == 0 && knob_max_depth() >= 4) return launch_1x1<false, 4, 2>(d, stream);
+    return nk > 1 ? launch_1x1<false, 2, 2>(d, stream) : launch_1x1<false, 1, 2>(d, stream);
 }
-
-int gdt_launch_conv_1x1_rb(const ConvLaunch& d, hipStream_t stream) { return gdt_launch_conv_1x1_rb_levels(&d, 1, stream); }

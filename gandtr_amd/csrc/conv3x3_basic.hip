@@ -53,15 +53,8 @@ struct BasicLaunch {
     const float* b1; const float* b2;     // folded BatchNorm shifts (or the plain biases)
     int N, H, W;
 };
-// several independent geometries (the levels of a pyramid) in one launch: gdt_common.h MultiConv, with this kernel's own descriptor
-struct MultiBasic {
-    int nlev;
-    int prefix[GDT_MAX_LEVELS + 1];
-    int ntiles[GDT_MAX_LEVELS];
-    BasicLaunch lev[GDT_MAX_LEVELS];
-};
 
-// (the body takes its workgroup index and grid size as arguments: the multi-geometry entry runs it per level)
+// (the body takes its workgroup index and grid size as arguments: the kernel below hands it blockIdx.x and gridDim.x)
 __device__ __forceinline__ void conv3x3_basic_body(const BasicLaunch& d, const int ntiles, const int bid, const int gdim) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const xbuf = smem;
@@ -286,10 +279,6 @@ __device__ __forceinline__ void conv3x3_basic_body(const BasicLaunch& d, const i
 __global__ __launch_bounds__(NT) void conv3x3_basic_kernel(const BasicLaunch d, const int ntiles) {
     conv3x3_basic_body(d, ntiles, blockIdx.x, gridDim.x);
 }
-__global__ __launch_bounds__(NT) void conv3x3_basic_multi_kernel(const MultiBasic m) {
-    const int l = gdt_multi_level(m.nlev, m.prefix, blockIdx.x);
-    conv3x3_basic_body(m.lev[l], m.ntiles[l], blockIdx.x - m.prefix[l], m.prefix[l + 1] - m.prefix[l]);
-}
 
 // Read whenever a geometry is planned.  The fused and the layer-by-layer route use the same layout (the tensor between the two convs is laid out on both).
 // Default 0: the measured default -- the whole forwards of GeM-ResNet-18 / 34 tie or lose with the fused route (profiles/resnet_basic_1gpu.json)
@@ -309,27 +298,12 @@ bool gdt_basic_eligible(int C_, int N, int H, int W) {
     return gdt_enough_tiles(gdt_patches(N, H, W, PH, PW), 1, knob_min_tiles());
 }
 
-int gdt_launch_basic_levels(const f16* const* x, f16* const* y, const f16* w1, const f16* w2, const float* b1, const float* b2, const int* N, const int* H,
-                            const int* W, int L, hipStream_t stream) {
-    GDT_REQUIRE(L >= 1 && L <= GDT_MAX_LEVELS && x && y && w1 && w2 && b1 && b2, "1..4 geometries per launch");
-    for (int l = 0; l < L; ++l) GDT_REQUIRE(x[l] && y[l] && N[l] >= 1 && H[l] >= 1 && W[l] >= 1 && gdt_offsets_fit(N[l], H[l], W[l], C, 31), "BasicBlock geometry");
+int gdt_launch_basic(const f16* x, f16* y, const f16* w1, const f16* w2, const float* b1, const float* b2, int N, int H, int W, hipStream_t stream) {
+    GDT_REQUIRE(x && y && w1 && w2 && b1 && b2 && N >= 1 && H >= 1 && W >= 1 && gdt_offsets_fit(N, H, W, C, 31), "BasicBlock geometry");
+    using K = GdtKernel<conv3x3_basic_kernel, LDS>;
     int cus = 0;
-    if (L == 1) {
-        using K = GdtKernel<conv3x3_basic_kernel, LDS>;
-        GDT_CHECK(K::figure(cus));
-        const BasicLaunch d{x[0], y[0], w1, w2, b1, b2, N[0], H[0], W[0]};
-        const int ntiles = (int)gdt_patches(N[0], H[0], W[0], PH, PW);
-        return K::launch(std::min(cus, (ntiles + 7) / 8 * 8), NT, stream, d, ntiles);
-    }
-    using K = GdtKernel<conv3x3_basic_multi_kernel, LDS>;
     GDT_CHECK(K::figure(cus));
-    MultiBasic m;
-    m.nlev = L;
-    int want[GDT_MAX_LEVELS];
-    for (int l = 0; l < L; ++l) {
-        m.lev[l] = BasicLaunch{x[l], y[l], w1, w2, b1, b2, N[l], H[l], W[l]};
-        m.ntiles[l] = (int)gdt_patches(N[l], H[l], W[l], PH, PW);
-        want[l] = (m.ntiles[l] + 7) / 8 * 8;
-    }
-    return K::launch(gdt_multi_partition(m.prefix, want, L, cus), NT, stream, m);
+    const BasicLaunch d{x, y, w1, w2, b1, b2, N, H, W};
+    const int ntiles = (int)gdt_patches(N, H, W, PH, PW);
+    return K::launch(std::min(cus, (ntiles + 7) / 8 * 8), NT, stream, d, ntiles);
 }

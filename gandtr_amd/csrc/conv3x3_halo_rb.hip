@@ -60,7 +60,7 @@ constexpr size_t rb_lds_bytes() {
 // and a wave skips the (shift, phase) blocks that are all zero; the epilogue scatters column blocks to output pixels
 // (2y + py, 2x + px).  MODE 3 (norm + residual, no write-back) exists for this form: y9 = y8 + IN(.) feeds only the first
 // transposed conv.
-// (the body takes its workgroup index and grid size as arguments: the multi-geometry entry below runs it per level, gdt_common.h MultiConv)
+// (the body takes its workgroup index and grid size as arguments: the kernel below hands it blockIdx.x and gridDim.x)
 template <int BN, int WGM, int WGN, int MODE, bool CT = false, int PHT = 16, bool SINGLE = false>
 __device__ __forceinline__ void conv3x3_halo_rb_body(const ConvLaunch& d, const int vblocks, const int bid, const int gdim) {
     constexpr int PH = PHT, BM = PHT * 16;                              // (shadow the 16-row constants of the file scope)
@@ -430,12 +430,6 @@ template <int BN, int WGM, int WGN, int MODE, bool CT = false, int PHT = 16, boo
 __global__ __launch_bounds__(WGM * WGN * 64, SINGLE ? 2 : 1) void conv3x3_halo_rb_kernel(const ConvLaunch d, const int vblocks) {
     conv3x3_halo_rb_body<BN, WGM, WGN, MODE, CT, PHT, SINGLE>(d, vblocks, blockIdx.x, gridDim.x);
 }
-// plain 3x3 convs only (MODE 0, no transposed / single-stage forms): what the embedders' pyramids run
-template <int BN, int WGM, int WGN>
-__global__ __launch_bounds__(WGM * WGN * 64, 1) void conv3x3_halo_rb_multi_kernel(const MultiConv m) {
-    const int l = gdt_multi_level(m.nlev, m.prefix, blockIdx.x);
-    conv3x3_halo_rb_body<BN, WGM, WGN, 0, false, 16, false>(m.lev[l], m.vblocks[l], blockIdx.x - m.prefix[l], m.prefix[l + 1] - m.prefix[l]);
-}
 
 GDT_KNOB_LATCHED(knob_mode, "GDT_CONV_RB", 1)                // 0 off
 GDT_KNOB_LATCHED(knob_narrow, "GDT_CONV_RB128", 1)           // 0: no 128- / 64-column four-wave forms
@@ -446,21 +440,6 @@ GDT_KNOB_LATCHED(knob_cu_limit, "GDT_CU_LIMIT", 0)           // dev: persistent 
 GDT_KNOB_LATCHED(knob_dbg, "GDT_RB_DBG", 0)                  // timing-only ablation
 GDT_KNOB_LATCHED(knob_ct_mode, "GDT_CONV_HALO_CT", 1)        // 0 off
 GDT_KNOB_LATCHED(knob_ct_min_tiles, "GDT_CONV_MIN_TILES", 128)   // (batch-1 sweeps: 64-128 best; 512 loses 25 % on a 1024^2 image)
-
-template <int BN, int WGM, int WGN>
-int launch_rb_multi(const ConvLaunch* dl, int L, hipStream_t stream) {
-    using K = GdtKernel<conv3x3_halo_rb_multi_kernel<BN, WGM, WGN>, (int)rb_lds_bytes<BN, 16, false>()>;
-    int cus = 0;
-    GDT_CHECK(K::figure(cus));
-    MultiConv m;
-    m.nlev = L;
-    for (int l = 0; l < L; ++l) {
-        m.lev[l] = dl[l]; m.lev[l].dbg = knob_dbg();
-        m.vblocks[l] = gdt_grid_for_tiles((int)gdt_patches(dl[l].N, dl[l].H, dl[l].W), dl[l].CoutPad / BN);
-    }
-    const int grid = gdt_multi_partition(m.prefix, m.vblocks, L, cus);
-    return K::launch(grid, WGM * WGN * 64, stream, m);
-}
 
 template <int BN, int WGM, int WGN, int MODE, bool CT = false, int PHT = 16, bool SINGLE = false>
 int launch_rb(const ConvLaunch& d, hipStream_t stream) {
@@ -529,27 +508,6 @@ int gdt_launch_conv_halo_rb(const ConvLaunch& d_in, hipStream_t stream) {
         if (knob_narrow() && (tiles256 < knob_split_below() || tail) && !d.in_res && !d.in_out && !d.stats) return launch_rb<128, 2, 2, 0>(d, stream);
     }
     return launch_rb_fold<false>(d, stream);
-}
-
-// The same plain 3x3 conv (no folded norm, no fused pool, no statistics, 256 output channels per tile) on L independent geometries as ONE launch; false when the
-// levels cannot share a launch (the caller then launches them one by one)
-bool gdt_conv_halo_rb_levels_ok(const ConvLaunch* dl, int L) {
-    if (L < 2 || L > GDT_MAX_LEVELS) return false;
-    for (int l = 0; l < L; ++l) {
-        const ConvLaunch& d = dl[l];
-        if (!gdt_conv_halo_rb_eligible(d) || d.in_norm || d.in_res || d.in_out || d.stats || d.pool2 || d.phase_cout || d.CoutPad % 256 != 0) return false;
-        if (d.CoutPad != dl[0].CoutPad || d.Cin != dl[0].Cin) return false;
-    }
-    return true;
-}
-
-int gdt_launch_conv_halo_rb_levels(const ConvLaunch* dl, int L, hipStream_t stream) {
-    GDT_REQUIRE(gdt_conv_halo_rb_levels_ok(dl, L), "geometries that cannot share a launch");
-    // the tile shape for the levels together (gdt_launch_conv_halo_rb's rule on the summed patch count)
-    long tiles256 = 0;
-    for (int l = 0; l < L; ++l) tiles256 += gdt_patches(dl[l].N, dl[l].H, dl[l].W) * (dl[l].CoutPad / 256);
-    if (knob_narrow() && tiles256 < knob_split_below()) return launch_rb_multi<128, 2, 2>(dl, L, stream);
-    return launch_rb_multi<256, 2, 4>(dl, L, stream);
 }
 
 // Transposed form (CT): fused ConvTranspose2d(k3,s2,p1,op1) launch (phase_cout > 0, weights of Op::ctf), 64 or 128 channels per

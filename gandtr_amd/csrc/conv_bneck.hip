@@ -84,15 +84,7 @@ struct BneckLaunch {
 
 // RAGGED: maps the patches do not tile exactly (real images: H, W arbitrary) -- the last patch row / column hangs over the image: its x loads are clamped, r is
 // zeroed there (as at every image border), residual fetches are clamped and the stores of pixels outside the image are masked off
-// several independent geometries (the levels of a pyramid) in one launch: gdt_common.h MultiConv, here with this kernel's own descriptor
-struct MultiBneck {
-    int nlev;
-    int prefix[GDT_MAX_LEVELS + 1];
-    int ntiles[GDT_MAX_LEVELS];
-    BneckLaunch lev[GDT_MAX_LEVELS];
-};
-
-// (the body takes its workgroup index and grid size as arguments: the multi-geometry entry runs it per level)
+// (the body takes its workgroup index and grid size as arguments: the kernel below hands it blockIdx.x and gridDim.x)
 template <int C, int MID, int PH, int CIN = C, bool DS = false, bool RAGGED = false>
 __device__ __forceinline__ void conv_bneck_body(const BneckLaunch& d, const int ntiles, const int bid, const int gdim) {
     using G = Geo<C, MID, PH, CIN, DS>;
@@ -465,27 +457,6 @@ template <int C, int MID, int PH, int CIN = C, bool DS = false, bool RAGGED = fa
 __global__ __launch_bounds__(NT) void conv_bneck_kernel(const BneckLaunch d, const int ntiles) {
     conv_bneck_body<C, MID, PH, CIN, DS, RAGGED>(d, ntiles, blockIdx.x, gridDim.x);
 }
-template <int C, int MID, int PH, int CIN = C, bool DS = false, bool RAGGED = false>
-__global__ __launch_bounds__(NT) void conv_bneck_multi_kernel(const MultiBneck m) {
-    const int l = gdt_multi_level(m.nlev, m.prefix, blockIdx.x);
-    conv_bneck_body<C, MID, PH, CIN, DS, RAGGED>(m.lev[l], m.ntiles[l], blockIdx.x - m.prefix[l], m.prefix[l + 1] - m.prefix[l]);
-}
-
-template <int C, int MID, int PH, int CIN = C, bool DS = false, bool RAGGED = false>
-int launch_multi(const BneckLaunch* dl, int L, hipStream_t stream) {
-    using K = GdtKernel<conv_bneck_multi_kernel<C, MID, PH, CIN, DS, RAGGED>, Geo<C, MID, PH, CIN, DS>::LDS>;
-    int cus = 0;
-    GDT_CHECK(K::figure(cus));
-    MultiBneck m;
-    m.nlev = L;
-    int want[GDT_MAX_LEVELS];
-    for (int l = 0; l < L; ++l) {
-        m.lev[l] = dl[l];
-        m.ntiles[l] = (int)gdt_patches(dl[l].N, dl[l].H, dl[l].W, PH, PW);
-        want[l] = (m.ntiles[l] + 7) / 8 * 8;
-    }
-    return K::launch(gdt_multi_partition(m.prefix, want, L, cus), NT, stream, m);
-}
 
 template <int C, int MID, int PH, int CIN = C, bool DS = false, bool RAGGED = false>
 int launch(const BneckLaunch& d, hipStream_t stream) {
@@ -542,25 +513,5 @@ int gdt_launch_bneck(const f16* x, f16* y, const f16* wr, const f16* w3, const f
     if (cin == 512 && C == 512 && mid == 128 && !wd) return (H % 8 || W % PW) ? launch<512, 128, 8, 512, false, true>(d, stream) : launch<512, 128, 8>(d, stream);
     if (cin == 64 && C == 256 && mid == 64 && wd && bd) return (H % 16 || W % PW) ? launch<256, 64, 16, 64, true, true>(d, stream) : launch<256, 64, 16, 64, true>(d, stream);
     gdt_set_error("gdt_launch_bneck: unsupported shape");
-    return GDT_ERR_INVALID;
-}
-
-// The same Bottleneck on L independent geometries (the levels of a pyramid) in ONE launch: every level its own x / y pointers and (N, H, W); the RAGGED
-// instantiation when any level needs it (it is the general form: same results on maps the patches tile exactly)
-int gdt_launch_bneck_levels(const f16* const* x, f16* const* y, const f16* wr, const f16* w3, const f16* we, const float* br, const float* b3, const float* be,
-                            const f16* wd, const float* bd, int cin, int C, int mid, const int* N, const int* H, const int* W, int L, hipStream_t stream) {
-    GDT_REQUIRE(L >= 1 && L <= GDT_MAX_LEVELS, "1..4 geometries per launch");
-    if (L == 1) return gdt_launch_bneck(x[0], y[0], wr, w3, we, br, b3, be, wd, bd, cin, C, mid, N[0], H[0], W[0], stream);
-    BneckLaunch dl[GDT_MAX_LEVELS];
-    const int ph = (C == 512) ? 8 : 16;
-    bool ragged = false;
-    for (int l = 0; l < L; ++l) {
-        dl[l] = BneckLaunch{nullptr, x[l], y[l], wr, w3, we, br, b3, be, wd, bd, N[l], H[l], W[l]};
-        ragged = ragged || (H[l] % ph) || (W[l] % PW);
-    }
-    if (cin == 256 && C == 256 && mid == 64 && !wd) return ragged ? launch_multi<256, 64, 16, 256, false, true>(dl, L, stream) : launch_multi<256, 64, 16>(dl, L, stream);
-    if (cin == 512 && C == 512 && mid == 128 && !wd) return ragged ? launch_multi<512, 128, 8, 512, false, true>(dl, L, stream) : launch_multi<512, 128, 8>(dl, L, stream);
-    if (cin == 64 && C == 256 && mid == 64 && wd && bd) return ragged ? launch_multi<256, 64, 16, 64, true, true>(dl, L, stream) : launch_multi<256, 64, 16, 64, true>(dl, L, stream);
-    gdt_set_error("gdt_launch_bneck_levels: unsupported shape");
     return GDT_ERR_INVALID;
 }

@@ -48,13 +48,6 @@ __device__ __forceinline__ bool gdt_tile_of_block(int b, int ntm, int ntn, int& 
     tile_m = xcd * mchunk + lm;
     return lm < mchunk && tile_m < ntm;
 }
-// the level of workgroup b in a multi-geometry launch (MultiConv::prefix)
-__device__ __forceinline__ int gdt_multi_level(const int nlev, const int* prefix, const int b) {
-    int l = 0;
-#pragma unroll
-    for (int k = 1; k < GDT_MAX_LEVELS; ++k) l += (k < nlev && b >= prefix[k]) ? 1 : 0;
-    return l;
-}
 // Virtual block vb of a persistent kernel's tile walk (vb = workgroup, + grid size, ...; `vblocks` of them): its tile, or valid = false
 // with tile (0, 0) -- the walk goes on fetching for a "next tile" that does not exist, so that its loads stay unconditional.
 struct GdtTile { int tile_m, tile_n; bool valid; };

@@ -1,10 +1,8 @@
-// Executor of the graph engine: the forward on one geometry or on several in lock-step, the profiling entry points and the thin free-standing wrappers of
-// the C ABI.  What to launch is the plan's business (net_plan.hip); every conv launch descriptor comes from the conv_desc_* functions the planner probed with.
+// Executor of the graph engine: the forward on one geometry, the profiling entry points and the thin free-standing wrappers of the C ABI.
+// What to launch is the plan's business (net_plan.hip); every conv launch descriptor comes from the conv_desc_* functions the planner probed with.
 #include "net_internal.h"
 
 using namespace gdtn;
-
-GDT_KNOB_LATCHED_SET(knob_levels_debug, "GDT_LEVELS_DEBUG")  // set: what every op of gdt_net_forward_levels handed to the lock-step driver is printed
 
 namespace {
 
@@ -15,19 +13,10 @@ struct LevelCtx {
     Plan plan; std::vector<Tensor> T;
     float group_factor = 1.f;                    // the planner hint this geometry was planned with (gdt_net_set_group_factor)
 };
-enum { DEFER_NONE = 0, DEFER_CONV = 1, DEFER_BNECK = 2, DEFER_BASIC = 3 };
-// a launch a step WOULD make, handed back instead of issued: the lock-step driver (several geometries per forward) joins the levels' launches of one op
-struct Deferred {
-    int kind = DEFER_NONE;
-    bool kcat = false;
-    ConvLaunch d;                                // DEFER_CONV: the descriptor gdt_launch_conv / gdt_launch_conv_1x1_rb (kcat) would get
-    const f16* bx = nullptr; f16* by = nullptr; int bn = 0, bh = 0, bw = 0;      // DEFER_BNECK / DEFER_BASIC: block input / output and geometry (the weights are the op's)
-};
 
-// One conv op of the graph on one geometry, as exec_step sees it.  `defer` != null: launches that can share a launch with the other geometries' are handed back
-// (kind != DEFER_NONE) instead of issued.  `book`: per-op profile bookkeeping of fused launches (once per forward).
+// One conv op of the graph on one geometry, as exec_step sees it
 struct ConvStep {
-    gdt_net* net; LevelCtx& c; const Step& stp; const Op& o; hipStream_t st; Deferred* defer; bool book;
+    gdt_net* net; LevelCtx& c; const Step& stp; const Op& o; hipStream_t st;
     DescCtx x;                                   // descriptors with the forward's pointers
     f16* tptr(int t) const { return (f16*)(c.ws + c.T[t].off); }
     double tbytes(int t) const { return (double)c.n * c.T[t].H * c.T[t].W * c.T[t].C * (double)net->esize(); }
@@ -36,7 +25,7 @@ struct ConvStep {
     int launch(int (*launcher)(const ConvLaunch&, hipStream_t, int*), const ConvLaunch& d) const { int v = 0; const int rc = launcher(d, st, &v); variant(v); return rc; }
 };
 
-// weights and channel counts of a fused Bottleneck step (the same for every geometry)
+// weights and channel counts of a fused Bottleneck step
 struct BneckArgs { const f16 *wr, *w3, *we, *wd; const float *br, *b3, *be, *bd; int cin, C, mid; const Op *oa, *ob, *oc, *od; };
 BneckArgs bneck_args(const gdt_net* net, const Step& stp) {
     const bool dsf = stp.bneck_ds >= 0;
@@ -54,10 +43,8 @@ int exec_bneck(const ConvStep& s) {
     const BneckArgs b = bneck_args(net, stp);
     const int nskip = b.od ? 3 : 2, in = b.oa->in, H = s.c.T[in].H, W = s.c.T[in].W;
     GDT_REQUIRE(gdt_bneck_eligible(b.cin, b.C, b.mid, s.c.n, H, W), "planned Bottleneck launch is not eligible at run time");
-    int rc = GDT_OK;
-    if (s.defer) { s.defer->kind = DEFER_BNECK; s.defer->bx = s.tptr(in); s.defer->by = s.tptr(b.oc->out); s.defer->bn = s.c.n; s.defer->bh = H; s.defer->bw = W; }
-    else rc = gdt_launch_bneck(s.tptr(in), s.tptr(b.oc->out), b.wr, b.w3, b.we, b.br, b.b3, b.be, b.wd, b.bd, b.cin, b.C, b.mid, s.c.n, H, W, s.st);
-    if (net->profiling && s.book) {      // the block's FLOPs and time are booked on its first conv
+    const int rc = gdt_launch_bneck(s.tptr(in), s.tptr(b.oc->out), b.wr, b.w3, b.we, b.br, b.b3, b.be, b.wd, b.bd, b.cin, b.C, b.mid, s.c.n, H, W, s.st);
+    if (net->profiling) {      // the block's FLOPs and time are booked on its first conv
         net->last_variant[stp.op] = 935000 + b.C + (b.od ? 1 : 0);
         for (int k = 1; k <= nskip; ++k) { net->last_flops[stp.op] += net->last_flops[stp.op + k]; net->last_flops[stp.op + k] = 0.0; }
         // bytes: the block-boundary tensors (x once -- it is also the residual --, y once) and every weight matrix once
@@ -85,13 +72,8 @@ int exec_basic(const ConvStep& s) {
     const BasicArgs b = basic_args(net, stp);
     const int in = b.oa->in, H = s.c.T[in].H, W = s.c.T[in].W;
     GDT_REQUIRE(b.ob->res == in && gdt_basic_eligible(b.oa->cd.cin, s.c.n, H, W), "planned BasicBlock launch is not eligible at run time");
-    int rc = GDT_OK;
-    if (s.defer) { s.defer->kind = DEFER_BASIC; s.defer->bx = s.tptr(in); s.defer->by = s.tptr(b.ob->out); s.defer->bn = s.c.n; s.defer->bh = H; s.defer->bw = W; }
-    else {
-        const f16* x = s.tptr(in); f16* y = s.tptr(b.ob->out); const int n = s.c.n;
-        rc = gdt_launch_basic_levels(&x, &y, b.w1, b.w2, b.b1, b.b2, &n, &H, &W, 1, s.st);
-    }
-    if (net->profiling && s.book) {      // the block's FLOPs, bytes and time are booked on its second conv
+    const int rc = gdt_launch_basic(s.tptr(in), s.tptr(b.ob->out), b.w1, b.w2, b.b1, b.b2, s.c.n, H, W, s.st);
+    if (net->profiling) {      // the block's FLOPs, bytes and time are booked on its second conv
         net->last_variant[stp.op] = 936064;
         net->last_flops[stp.op] += net->last_flops[stp.op - 1]; net->last_flops[stp.op - 1] = 0.0;
         // bytes: the block-boundary tensors (x once -- it is also the residual --, y once) and both weight matrices once
@@ -121,7 +103,7 @@ int exec_xexp(const ConvStep& s) {
     GDT_REQUIRE(gdt_conv3x3_expand_eligible(d), "planned 3x3 + expand launch is not eligible at run time");
     if (stp.xchain >= 0) GDT_REQUIRE(gdt_conv3x3_expand_chain_eligible(d), "planned 3x3 + expand + reduce launch is not eligible at run time");
     const int rc = gdt_launch_conv3x3_expand(d, s.st);
-    if (net->profiling && s.book) {
+    if (net->profiling) {
         net->last_variant[stp.op] = (stp.xchain >= 0 ? 938000 : 939000) + oc.cd.cout / 8;
         net->last_flops[stp.op] += net->last_flops[stp.op + 1]; net->last_flops[stp.op + 1] = 0.0;
         // bytes: the 256-channel tensor between the two convs is neither written nor read
@@ -141,10 +123,8 @@ int exec_kcat(const ConvStep& s) {
     const int ids = s.o.kcat_ds;
     const ConvLaunch d = conv_desc_kcat(s.x, stp.op);
     GDT_REQUIRE(gdt_conv_1x1_cat_eligible(d), "planned K-concatenated 1x1 launch is not eligible at run time");
-    int rc = GDT_OK;
-    if (s.defer) { s.defer->kind = DEFER_CONV; s.defer->kcat = true; s.defer->d = d; }
-    else rc = gdt_launch_conv_1x1_rb(d, s.st);
-    if (net->profiling && s.book) {
+    const int rc = gdt_launch_conv_1x1_rb(d, s.st);
+    if (net->profiling) {
         net->last_variant[stp.op] = 946128;
         net->last_flops[stp.op] += net->last_flops[ids]; net->last_flops[ids] = 0.0;
         // bytes: the projected tensor is neither written (projection op) nor read back as the residual (expand op)
@@ -212,7 +192,6 @@ int exec_phases(const ConvStep& s, const ConvFold& f) {
         }
         else if (net->precision == 2 && gdt_conv_halo_c16_eligible(d)) { variant = 971256; rc = gdt_launch_conv_halo_c16(d, s.st); }
         else if (net->precision == 2 && gdt_conv_halo_c_eligible(d)) { variant = 970000 + gdt_conv_halo_c_columns(d); rc = gdt_launch_conv_halo_c(d, s.st); }
-        else if (s.defer && !f32 && o.phases.size() == 1 && !o.rowsplit && !o.cd.out_f32_nchw) { s.defer->kind = DEFER_CONV; s.defer->kcat = false; s.defer->d = d; }
         else rc = f32 ? gdt_launch_conv_x3(d, s.st, &variant) : gdt_launch_conv(d, s.st, &variant);
         s.variant(variant);
         if (rc != GDT_OK) return rc;
@@ -225,7 +204,7 @@ int exec_phases(const ConvStep& s, const ConvFold& f) {
 // The convs that read their sources themselves: ConvTranspose2d(k4,s2,p1) of one or two tensors (conv4x4t_halo.hip), ConvTranspose2d(k2,s2,p0) as one launch
 // (convt2x2.hip), Conv2d(k3,s1,p1) of two tensors (conv3x3_cat_halo.hip).  Bytes: the concatenation (where the graph has one) is neither written nor read; its sources are read once
 void book_unwritten_concat(const ConvStep& s) {
-    if (!s.net->profiling || !s.book || s.o.cat_op < 0) return;
+    if (!s.net->profiling || s.o.cat_op < 0) return;
     const Op& oc = s.net->ops[s.o.cat_op];
     s.net->last_bytes[s.stp.op] += s.tbytes(oc.in) + (oc.res >= 0 ? s.tbytes(oc.res) : 0.0) - s.tbytes(s.o.in);
 }
@@ -273,8 +252,8 @@ int exec_conv(const ConvStep& s) {
     GDT_REQUIRE(false, "conv step without a route");
 }
 
-// One op of the graph on one geometry (`defer`, `book`: see ConvStep)
-int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferred* defer, bool book) {
+// One op of the graph on one geometry
+int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st) {
     const int n = c.n, h = c.h, w = c.w, rh = c.rh, rw = c.rw;
     void* const* outputs = c.outputs;
     char* ws = c.ws;
@@ -292,7 +271,7 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                 return gdt_k_pack_input(c.x, tptr(o.out), stp.aug ? 2 : f32, n, o.in_c, h, w, rh, rw, c.rscale, resize, o.perm, o.scale, o.shift, st,
                                         o.filter.kind ? &o.filter : nullptr);
             }
-            case OP_CONV: return exec_conv(ConvStep{net, c, stp, o, st, defer, book, DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}});
+            case OP_CONV: return exec_conv(ConvStep{net, c, stp, o, st, DescCtx{net, &c.T, n, Ptrs{net->dev_blob, ws, outputs}}});
             case OP_INORM: {
                 const Tensor& ti = T[o.in];
                 if (stp.norm_into >= 0)     // the consuming conv applies it: only mean / rstd are produced here
@@ -323,7 +302,7 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
                 const int src = nj ? nj->in : o.in;
                 const Tensor& ti = T[src]; const Tensor& to = T[o.out];
                 const float* mr = nj ? (const float*)(ws + plan.steps[stp.norm_from].aux_off[1]) : nullptr;
-                if (net->profiling && book)     // the input once, the output once (and the slab)
+                if (net->profiling)     // the input once, the output once (and the slab)
                     net->last_bytes[stp.op] = ((double)ti.H * ti.W + (double)to.H * to.W) * n * ti.C * (double)net->esize() + (nj ? (double)n * ti.C * 8.0 : 0.0);
                 return o.blur_up ? gdt_k_blur_up(tptr(src), tptr(o.out), f32, n, ti.H, ti.W, ti.C, mr, nj ? nj->relu : 0, st)
                                  : gdt_k_blur_down(tptr(src), tptr(o.out), f32, n, ti.H, ti.W, ti.C, mr, nj ? nj->relu : 0, st);
@@ -418,81 +397,22 @@ int exec_step(gdt_net* net, LevelCtx& c, const Step& stp, hipStream_t st, Deferr
     return rc;
 }
 
-
-int launch_bneck_levels(gdt_net* net, const Step& stp, const Deferred* df, int L, hipStream_t st) {
-    const BneckArgs b = bneck_args(net, stp);
-    const f16* xs[GDT_MAX_LEVELS]; f16* ys[GDT_MAX_LEVELS]; int ns[GDT_MAX_LEVELS], hs[GDT_MAX_LEVELS], wsz[GDT_MAX_LEVELS];
-    for (int l = 0; l < L; ++l) { xs[l] = df[l].bx; ys[l] = df[l].by; ns[l] = df[l].bn; hs[l] = df[l].bh; wsz[l] = df[l].bw; }
-    return gdt_launch_bneck_levels(xs, ys, b.wr, b.w3, b.we, b.br, b.b3, b.be, b.wd, b.bd, b.cin, b.C, b.mid, ns, hs, wsz, L, st);
-}
-
-int launch_basic_levels(gdt_net* net, const Step& stp, const Deferred* df, int L, hipStream_t st) {
-    const BasicArgs b = basic_args(net, stp);
-    const f16* xs[GDT_MAX_LEVELS]; f16* ys[GDT_MAX_LEVELS]; int ns[GDT_MAX_LEVELS], hs[GDT_MAX_LEVELS], wsz[GDT_MAX_LEVELS];
-    for (int l = 0; l < L; ++l) { xs[l] = df[l].bx; ys[l] = df[l].by; ns[l] = df[l].bn; hs[l] = df[l].bh; wsz[l] = df[l].bw; }
-    return gdt_launch_basic_levels(xs, ys, b.w1, b.w2, b.b1, b.b2, ns, hs, wsz, L, st);
-}
-
-// The forward on L independent geometries in lock-step: op by op, every geometry's launch of the op -- joined into ONE launch where the kernel has a
-// multi-geometry entry and the levels select the same kernel family (conv1x1_rb.hip, conv3x3_halo_rb.hip, conv_bneck.hip, conv3x3_basic.hip), else issued one after the other
-int forward_levels(gdt_net* net, LevelCtx* cx, int L, hipStream_t st) {
+// The forward on one geometry: the profiled handle's per-op books and events around it, then op by op in graph order
+int run_ops(gdt_net* net, LevelCtx& c, hipStream_t st) {
     const int nops = (int)net->ops.size();
-    net->last_joined = 0; net->last_level_launches = 0;
     if (net->profiling) {
-        net->last_flops.assign(nops, 0.0);
+        net->last_flops.resize(nops);
         net->last_variant.assign(nops, 0);
-        net->last_bytes.assign(nops, 0.0);
-        for (int l = 0; l < L; ++l) {
-            net->tensors = cx[l].T;                    // (op_flops / op_bytes read the planned shapes from the net's table)
-            for (int i = 0; i < nops; ++i) {
-                net->last_flops[i] += op_flops(net, net->ops[i], cx[l].n, cx[l].rh, cx[l].rw);
-                net->last_bytes[i] += op_bytes(net, net->ops[i], cx[l].n);
-            }
+        net->last_bytes.resize(nops);
+        net->tensors = c.T;                        // (op_flops / op_bytes read the planned shapes from the net's table)
+        for (int i = 0; i < nops; ++i) {
+            net->last_flops[i] = op_flops(net, net->ops[i], c.n, c.rh, c.rw);
+            net->last_bytes[i] = op_bytes(net, net->ops[i], c.n);
         }
     }
     for (int i = 0; i < nops; ++i) {
         if (net->profiling) GDT_CHECK_HIP(hipEventRecord(net->events[2 * i], st));
-        int rc = GDT_OK;
-        if (L == 1) rc = exec_step(net, cx[0], cx[0].plan.steps[i], st, nullptr, true);
-        else {
-            Deferred df[GDT_MAX_LEVELS];
-            int nconv = 0, nbneck = 0, nkcat = 0, nbasic = 0;
-            for (int l = 0; l < L && rc == GDT_OK; ++l) {
-                rc = exec_step(net, cx[l], cx[l].plan.steps[i], st, &df[l], l == 0);
-                nconv += df[l].kind == DEFER_CONV; nbneck += df[l].kind == DEFER_BNECK; nkcat += df[l].kind == DEFER_CONV && df[l].kcat;
-                nbasic += df[l].kind == DEFER_BASIC;
-            }
-            if (rc != GDT_OK) return rc;
-            net->last_level_launches += nconv + nbneck + nbasic;
-            bool joined = false;
-            if (nbneck == L) { rc = launch_bneck_levels(net, cx[0].plan.steps[i], df, L, st); joined = true; }
-            else if (nbasic == L) { rc = launch_basic_levels(net, cx[0].plan.steps[i], df, L, st); joined = true; }
-            else if (nconv == L && (nkcat == 0 || nkcat == L)) {
-                ConvLaunch dl[GDT_MAX_LEVELS];
-                int fam = nkcat ? 1 : gdt_conv_family(df[0].d);
-                for (int l = 0; l < L; ++l) { dl[l] = df[l].d; if (!nkcat && gdt_conv_family(df[l].d) != fam) fam = 0; }
-                if (fam == 1) { rc = gdt_launch_conv_1x1_rb_levels(dl, L, st); joined = true; if (net->profiling && !nkcat) net->last_variant[i] = 945128; }
-                else if (fam == 2 && gdt_conv_halo_rb_levels_ok(dl, L)) { rc = gdt_launch_conv_halo_rb_levels(dl, L, st); joined = true; if (net->profiling) net->last_variant[i] = 910256; }
-            }
-            if (joined) ++net->last_joined;
-            if (knob_levels_debug() && (nconv || nbneck || nbasic)) {
-                fprintf(stderr, "[levels] op %d joined %d:", i, (int)joined);
-                for (int l = 0; l < L; ++l) {
-                    if (df[l].kind == DEFER_CONV) fprintf(stderr, " [conv%s fam %d M %d Cin %d Cout %d taps %d s%d]", df[l].kcat ? " kcat" : "", gdt_conv_family(df[l].d), df[l].d.M, df[l].d.Cin, df[l].d.Cout, df[l].d.ntaps, df[l].d.sy);
-                    else if (df[l].kind == DEFER_BNECK || df[l].kind == DEFER_BASIC) fprintf(stderr, " [%s %dx%dx%d]", df[l].kind == DEFER_BNECK ? "bneck" : "basic", df[l].bn, df[l].bh, df[l].bw);
-                    else fprintf(stderr, " [-]");
-                }
-                fprintf(stderr, "\n");
-            }
-            if (!joined) {                    // one by one (levels whose step was not handed back have launched already)
-                for (int l = 0; l < L && rc == GDT_OK; ++l) {
-                    if (df[l].kind == DEFER_BNECK) rc = launch_bneck_levels(net, cx[l].plan.steps[i], &df[l], 1, st);
-                    else if (df[l].kind == DEFER_BASIC) rc = launch_basic_levels(net, cx[l].plan.steps[i], &df[l], 1, st);
-                    else if (df[l].kind == DEFER_CONV && df[l].kcat) rc = gdt_launch_conv_1x1_rb(df[l].d, st);
-                    else if (df[l].kind == DEFER_CONV) { int variant = 0; rc = gdt_launch_conv(df[l].d, st, &variant); if (net->profiling && l == 0) net->last_variant[i] = variant; }
-                }
-            }
-        }
+        const int rc = exec_step(net, c, c.plan.steps[i], st);
         if (rc != GDT_OK) return rc;
         if (net->profiling) GDT_CHECK_HIP(hipEventRecord(net->events[2 * i + 1], st));
     }
@@ -567,47 +487,13 @@ int gdt_net_forward(gdt_net* net, const float* x, int n, int h, int w, int rh, i
     c.x = x; c.n = n; c.h = h; c.w = w; c.rh = rh; c.rw = rw; c.rscale = rscale; c.outputs = outputs;
     int rc = plan_level(net, c, workspace, workspace_bytes);
     if (rc != GDT_OK) return rc;
-    return forward_levels(net, &c, 1, (hipStream_t)stream);
+    return run_ops(net, c, (hipStream_t)stream);
 }
 
 int gdt_net_set_group_factor(gdt_net* net, float factor) {
     GDT_REQUIRE(net && factor >= 1.f && factor < 1e6f, "group factor >= 1");
     net->group_factor = factor;
     return GDT_OK;
-}
-
-int gdt_net_levels_joined(gdt_net* net, int* level_launches) {
-    if (!net) return 0;
-    if (level_launches) *level_launches = net->last_level_launches;
-    return net->last_joined;
-}
-
-int gdt_net_forward_levels(gdt_net* net, const gdt_level* levels, int n_levels, void* stream) {
-    GDT_REQUIRE(net && net->finalized, "net must be finalized");
-    GDT_REQUIRE(levels && n_levels >= 1 && n_levels <= GDT_MAX_LEVELS, "1..4 geometries per call");
-    if (n_levels > 1) for (const Op& o : net->ops) GDT_REQUIRE(o.kind != OP_BLUR, "a graph with a blur-resample op runs one geometry per call");
-    std::vector<LevelCtx> cx(n_levels);
-    double group_px = 0.0;
-    for (int l = 0; l < n_levels; ++l) group_px += (double)levels[l].n * levels[l].rh * levels[l].rw;
-    const float saved_factor = net->group_factor;
-    struct Restore { gdt_net* n; float f; ~Restore() { n->group_factor = f; } } restore{net, saved_factor};
-    for (int l = 0; l < n_levels; ++l) {
-        const gdt_level& g = levels[l];
-        if (n_levels > 1 && g.n >= 1 && g.rh >= 1 && g.rw >= 1) net->group_factor = (float)(group_px / ((double)g.n * g.rh * g.rw));
-        GDT_REQUIRE(g.x && g.n >= 1 && g.h >= 1 && g.w >= 1 && g.rh >= 1 && g.rw >= 1, "input geometry");
-        GDT_REQUIRE(g.n_outputs == (int)net->out_ops.size() && (g.outputs || g.n_outputs == 0), "output count");
-        GDT_REQUIRE((long)g.n * g.rh * g.rw < (1l << 31) && (long)g.n * g.h * g.w < (1l << 31), "N*H*W must stay below 2^31");
-        for (int i = 0; i < g.n_outputs; ++i) GDT_REQUIRE(g.outputs[i] != nullptr, "null output buffer");
-        for (int k = 0; k < l; ++k) {      // every geometry its own scratch memory
-            const char *a0 = (const char*)levels[k].workspace, *a1 = a0 + levels[k].workspace_bytes, *b0 = (const char*)g.workspace, *b1 = b0 + g.workspace_bytes;
-            GDT_REQUIRE(a1 <= b0 || b1 <= a0, "the geometries of one call need disjoint workspaces");
-        }
-        LevelCtx& c = cx[l];
-        c.x = g.x; c.n = g.n; c.h = g.h; c.w = g.w; c.rh = g.rh; c.rw = g.rw; c.rscale = g.rscale; c.outputs = g.outputs;
-        const int rc = plan_level(net, c, g.workspace, g.workspace_bytes);
-        if (rc != GDT_OK) return rc;
-    }
-    return forward_levels(net, cx.data(), n_levels, (hipStream_t)stream);
 }
 
 int gdt_ms_aggregate(const float* x, float* y, int scales, int n, int d, float msp, void* stream) {

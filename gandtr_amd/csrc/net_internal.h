@@ -191,7 +191,6 @@ struct gdt_net {
     std::vector<double> last_bytes;         // algorithmic HBM bytes per op (op_bytes), merged like last_flops when ops are fused
     std::vector<int> last_variant;          // kernel variant per conv op (see gdt_launch_conv)
     float group_factor = 1.f;               // planner hint (gdt_net_set_group_factor): the geometry planned next runs concurrently with others; (their pixels + its own) / its own
-    int last_joined = 0, last_level_launches = 0;   // gdt_net_forward_levels: ops whose levels shared ONE launch / launches handed back by the levels in total
 
     size_t blob_append(const void* data, size_t bytes) {
         const size_t off = gdtn::align_up(host_blob.size());

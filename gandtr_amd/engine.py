@@ -105,11 +105,6 @@ class HipNet:
         self._ws = [None]                          # scratch buffer of forward() (one slot, see _grow)
         self._side = {"streams": [], "ws": []}     # per level of forward_many: side stream and scratch buffer
         self.side_workspace_cap = 8 << 30          # bytes of side scratch kept between forward_many calls
-        # hipGraph replay of whole forwards (launch-bound small batches: the reference's own operating point is batch 1)
-        self.use_graphs = os.environ.get("GANDTR_HIP_GRAPHS", "0") == "1"   # measured: no gain (kernels, not launches, bound batch 1)
-        self.graph_max_workspace = 2 << 30         # geometries needing more scratch than this run eagerly
-        self._graphs = collections.OrderedDict()   # key -> dict(graph, x, outs, ws) ; LRU of 8
-        self._seen = {}                            # key -> eager forwards so far (negative: capture failed, stay eager)
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -418,71 +413,18 @@ class HipNet:
             raise RuntimeError("HipNet.forward before finalize()")
         lv = self._level(x, scale)
         with torch.cuda.device(self.device):
-            outs = self._replayed(lv)
-            if outs is None:
-                ws, outs = self._buffers(self._ws, 0, lv)
-                self._launch(*lv, ws, outs)
+            ws, outs = self._buffers(self._ws, 0, lv)
+            self._launch(*lv, ws, outs)
         return outs
 
-    # hipGraph replay (opt-in: use_graphs).  A geometry seen for the second time is captured into a hipGraph (static input / output / scratch buffers) and replayed
-    # from then on: one graph launch instead of ~100 kernel launches, which is what bounds small batches.
-    def _replayed(self, lv):
-        """the outputs of ``lv`` from a replayed (or just captured) graph, or None: the caller launches eagerly, which is counted as a sighting of the geometry"""
-        key = lv[1:]
-        if self.use_graphs and not self._profiling:      # (a profiled forward runs eagerly: events per op)
-            entry = self._graphs.get(key)
-            if entry is not None:
-                self._graphs.move_to_end(key)
-                entry["x"].copy_(lv.x)
-                entry["graph"].replay()
-            elif self._seen.get(key, 0) >= 1 and not torch.cuda.is_current_stream_capturing():
-                need, shapes = self._geometry(lv.n, lv.rh, lv.rw)
-                if need <= self.graph_max_workspace:
-                    entry = self._capture(lv, need, shapes)
-            if entry is not None:
-                return [o.clone() for o in entry["outs"]]
-        self._seen[key] = self._seen.get(key, 0) + 1
-        if len(self._seen) > 256:
-            self._seen.clear()
-        return None
-
-    def _capture(self, lv, need, shapes):
-        dev, geo = self.device, lv[1:]
-        try:
-            sx = lv.x.clone()
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            outs = self._alloc_outputs(shapes)
-            side = side_stream(dev, 0)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):           # warm-up outside capture (lazy function attributes etc.)
-                self._launch(sx, *geo, ws, outs)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._launch(sx, *geo, ws, outs)
-            g.replay()
-        except Exception:               # capture is an optimisation only: fall back to eager launches for this geometry
-            self._seen[geo] = -(1 << 30)
-            return None
-        entry = {"graph": g, "x": sx, "outs": outs, "ws": ws}
-        self._graphs[geo] = entry
-        while len(self._graphs) > 8:
-            self._graphs.popitem(last=False)
-        return entry
-
     # ---- several levels in flight --------------------------------------------------------------------------------
-    MAX_LEVELS = 4          # GDT_MAX_LEVELS (csrc/gdt_common.h): geometries per gdt_net_forward_levels call
-
     def _group_px(self, inputs):
         """resized pixels of a group of levels (what is not an image is refused later, level by level)"""
         return float(sum(x.shape[0] * math.prod(self.resized_size(x.shape[2], x.shape[3], s)) for x, s in inputs if x.dim() == 4))
 
-    def _set_level_factor(self, group_px, lv, joint, alone=False):
+    def _set_level_factor(self, group_px, lv):
         """Tell the planner that ``lv`` runs together with its group: fusion thresholds count the group's patches."""
-        # The two paths differ, and are kept apart on purpose -- the factor feeds planner thresholds and the geometry-cache key, so unifying them would change
-        # plans: the side-stream path rounds to three decimals; the joint path does not round, and a group of one is alone (1.0).
-        f = group_px / float(lv.n * lv.rh * lv.rw)
-        self.set_group_factor((1.0 if alone else f) if joint else round(f, 3))
+        self.set_group_factor(round(group_px / float(lv.n * lv.rh * lv.rw), 3))
 
     def _side_pools(self, count):
         streams, slots = self._side["streams"], self._side["ws"]
@@ -525,73 +467,26 @@ class HipNet:
         ``side_workspace_cap`` bytes in total (default 8 GiB); beyond it they are released when the call returns."""
         if not self._finalized:
             raise RuntimeError("HipNet.forward_many before finalize()")
-        if len(inputs) == 1 or os.environ.get("GANDTR_HIP_CONCURRENT_LEVELS", "1") == "0":
+        if len(inputs) == 1 or self._profiling or os.environ.get("GANDTR_HIP_CONCURRENT_LEVELS", "1") == "0":
             return [self.forward(x, scale=s) for x, s in inputs]
-        if os.environ.get("GANDTR_HIP_JOINT_LEVELS", "0") == "1":           # (opt-in: measured 5-12 % slower than the side streams, csrc/gdt_common.h MultiConv)
-            return self._forward_levels(inputs)
-        if self._profiling:
-            return [self.forward(x, scale=s) for x, s in inputs]
-        # GANDTR_HIP_FIRST_ON_CURRENT=1 (experiment, off): the first input on the CALLER's stream, issued last, the others on side streams issued first -- one
-        # stream fewer, so that the default stream, two side streams and a collective's stream have a hardware queue each (the runtime has four).  Measured:
-        # 8 x 1024^2 6.68 -> 6.80 ms, 1 x 1024^2 2.87 -> 2.78 ms, one sharded rank 1127 -> 1100 descriptors/s: no
-        first_on_cur = os.environ.get("GANDTR_HIP_FIRST_ON_CURRENT", "0") == "1"
         # (the order in which the host enqueues the levels -- as given, smallest first, largest first -- makes no difference: hub scales at 8 x 1024^2 6.36 / 6.56 /
         # 6.43 ms, {1, 1/sqrt 2, sqrt 2} 13.68 / 13.64 / 13.67 ms)
-        order = (list(range(1, len(inputs))) + [0]) if first_on_cur else list(range(len(inputs)))
-        side = [k for k in range(len(inputs)) if not (first_on_cur and k == 0)]      # the levels that run on a side stream
         results = [None] * len(inputs)
         group_px = self._group_px(inputs)
         with self._level_group(len(inputs)) as cur:
-            for k in order:
+            streams = self._side["streams"]
+            for k in range(len(inputs)):
                 lv = self._level(*inputs[k])
-                self._set_level_factor(group_px, lv, joint=False)
-                st = self._side["streams"][k] if k in side else cur
-                if k in side:
-                    st.wait_stream(cur)
-                with torch.cuda.stream(st):
+                self._set_level_factor(group_px, lv)
+                streams[k].wait_stream(cur)
+                with torch.cuda.stream(streams[k]):
                     ws, results[k] = self._buffers(self._side["ws"], k, lv)
                     self._launch(*lv, ws, results[k])
-                    if k in side:
-                        lv.x.record_stream(st)
-            for k in side:
-                cur.wait_stream(self._side["streams"][k])
+                    lv.x.record_stream(streams[k])
+            for k in range(len(inputs)):
+                cur.wait_stream(streams[k])
                 for o in results[k]:
                     o.record_stream(cur)
-        return results
-
-    def levels_joined(self):
-        """(ops whose levels shared one launch, launches the levels handed to the lock-step driver) of the last forward_many group"""
-        n = ctypes.c_int()
-        j = int(self.lib.gdt_net_levels_joined(self.handle, ctypes.byref(n)))
-        return j, n.value
-
-    def _forward_levels(self, inputs):
-        """``inputs`` in groups of at most four geometries, each group ONE ``gdt_net_forward_levels`` call on the caller's stream: the ops run in lock-step and the
-        levels' launches of an op are one launch wherever the kernel has a multi-geometry entry (1x1 convs, 3x3 patch convs, fused Bottlenecks; round 5).  OPT-IN
-        (GANDTR_HIP_JOINT_LEVELS=1): 120 launches instead of 300 for a three-level ResNet-101 pyramid, but 5-12 % slower than one side stream per level
-        (csrc/gdt_common.h, MultiConv: measurements).  Every level has its own scratch buffer (kept between calls up to ``side_workspace_cap`` bytes in total); results are those of
-        ``forward`` level by level, bit for bit (tests/test_hip_models.py::test_pyramid_levels_share_launches_bitwise)."""
-        results = []
-        with self._level_group(min(len(inputs), self.MAX_LEVELS)) as cur:
-            for lo in range(0, len(inputs), self.MAX_LEVELS):
-                group = inputs[lo:lo + self.MAX_LEVELS]
-                levels = (_hip.Level * len(group))()
-                keep = []                   # what the struct array points into, alive until the call has returned
-                group_px = self._group_px(group)
-                for k, (x, scale) in enumerate(group):
-                    lv = self._level(x, scale)
-                    self._set_level_factor(group_px, lv, joint=True, alone=len(group) == 1)      # (gdt_net_forward_levels plans each level with the same factor)
-                    ws, outs = self._buffers(self._side["ws"], k, lv)
-                    optrs = _out_ptrs(outs)
-                    c = levels[k]
-                    c.x, c.n, c.h, c.w, c.rh, c.rw, c.rscale = lv.x.data_ptr(), lv.n, lv.h, lv.w, lv.rh, lv.rw, lv.rscale
-                    c.outputs, c.n_outputs = optrs, len(outs)
-                    c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel()
-                    keep.append((lv.x, optrs))
-                    results.append(outs)
-                self.set_group_factor(1.0)
-                _hip.check(self.lib.gdt_net_forward_levels(self.handle, levels, len(group), cur.cuda_stream))
-                del keep
         return results
 
 # ======================================================================================================= builders

@@ -165,8 +165,7 @@ int gdt_net_resize(gdt_net* net, int in_tensor, int like_tensor, int mode, int* 
  * align_corners=False): per axis out[2 i] = 0.25 in[max(i - 1, 0)] + 0.75 in[i], out[2 i + 1] = 0.75 in[i] + 0.25 in[min(i + 1, last)]; output 2H x 2W, H, W >= 1.
  * fp32 arithmetic, one store in the tensor's type.  All precision modes.  An InstanceNorm (plain or with ReLU; no residual, no LeakyReLU) whose ONLY consumer is
  * this op is folded into it (GDT_NORM_FUSION=0: never): the norm step produces mean / rstd only, and the op applies (x - mean) rstd and the ReLU in fp32 to every
- * tap as it reads it -- the normalised full-resolution tensor is neither written nor read.  Such a fold counts in "norms_folded".  gdt_net_forward_levels with
- * more than one geometry refuses a graph with this op. */
+ * tap as it reads it -- the normalised full-resolution tensor is neither written nor read.  Such a fold counts in "norms_folded". */
 int gdt_net_blur_resample(gdt_net* net, int in_tensor, int mode /* 0 down, 1 up */, int* out_tensor);
 /* What the plan of a geometry decides for these ops (host logic only, like gdt_net_plan_summary): *launches = their kernel launches, *folded = how many of them
  * apply their producer's InstanceNorm themselves. */
@@ -278,32 +277,18 @@ int gdt_net_workspace_bytes(gdt_net* net, int n, int rh, int rw, size_t* bytes);
  * not depend on it (no launch reads a byte that no launch of this forward has written); no byte outside [workspace, workspace + workspace_bytes) is written; and
  * every element of every output is written.  It holds fp16 / fp32 tensors and fp32 statistics and scratch only: no index, no pointer.  The layout is the
  * planner's liveness-based first fit; GDT_PLAN_NO_REUSE=1 (read at every plan) selects the reference layout in which no byte is handed out twice -- the same
- * launches, bit for bit the same outputs, a larger workspace (tests/test_hip_workspace.py pins all of this; gdt_net_forward_levels: the same per level). */
+ * launches, bit for bit the same outputs, a larger workspace (tests/test_hip_workspace.py pins all of this). */
 int gdt_net_forward(gdt_net* net, const float* x, int n, int h, int w, int rh, int rw, float rscale,
                     void* const* outputs, int n_outputs, void* workspace, size_t workspace_bytes, void* stream);
 
-/* The forward on several independent geometries at once -- the levels of a multi-scale pyramid (CirMultiscaleAggregation.preprocess, mdir/components/data/wrapper.py:221-233,
- * whose levels the reference runs one after the other, mdir/learning/network.py:139-140), or equal-shaped groups of a list of images.  Every level has its own input,
- * (resized) size, outputs and DISJOINT workspace (sized by gdt_net_workspace_bytes for its geometry).  The ops run in lock-step; where the kernel has a
- * multi-geometry entry (1x1 convs, 3x3 patch convs, fused Bottlenecks) the levels' launches of an op are ONE launch, whose workgroups are dealt out to the levels.
- * Results are those of gdt_net_forward called level by level, bit for bit. */
-typedef struct gdt_level {
-    const float* x; int n, h, w, rh, rw; float rscale;      /* as the arguments of gdt_net_forward */
-    void* const* outputs; int n_outputs;
-    void* workspace; size_t workspace_bytes;
-} gdt_level;
-int gdt_net_forward_levels(gdt_net* net, const gdt_level* levels, int n_levels, void* stream);
 /* Planner hint for geometries that run CONCURRENTLY on one device (the levels of a pyramid issued on side streams): factor = (pixels of all geometries in flight) /
  * (pixels of the geometry planned next), >= 1; 1 = alone (the default).  Fusions whose tile thresholds mean "enough patches to fill the chip" then count the
- * group's patches.  It applies to every later plan (gdt_net_workspace_bytes, gdt_net_output_shape, gdt_net_plan_summary, gdt_net_forward) until set again;
- * gdt_net_forward_levels sets it per level itself.  Host calls on one handle are serialised (see the threading note above). */
+ * group's patches.  It applies to every later plan (gdt_net_workspace_bytes, gdt_net_output_shape, gdt_net_plan_summary, gdt_net_forward) until set again:
+ * whoever issues the levels sets it in front of each and resets it to 1 behind the last.  Host calls on one handle are serialised (see the threading note above). */
 int gdt_net_set_group_factor(gdt_net* net, float factor);
 /* The environment knobs that a net reads EVERY time it plans a geometry (all others are read once per process): name of knob `index` (0, 1, ..), NULL past the
  * last.  Whoever caches something derived from a plan (workspace sizes, output shapes) keys the cache on the values of these. */
 const char* gdt_plan_knob_name(int index);
-/* diagnostics of the last gdt_net_forward_levels call: returns the number of ops whose levels ran as ONE launch; *level_launches = launches the levels handed
- * to the lock-step driver in total (joined or not) */
-int gdt_net_levels_joined(gdt_net* net, int* level_launches);
 
 /* Algorithmic conv FLOPs (2*MACs, real channel counts, bias/norm/activation excluded) of one forward at this geometry:
  * the numerator of bench.py's roofline.achieved. */

@@ -118,12 +118,3 @@ def test_up_op_equals_the_bilinear_resize(cuda_device, precision):
     q = float((d / (r_up.bound + r_rs.bound)).max())
     print("up op against resize %s: max |d| = %.3e, max |d| / (bound + bound) = %.3f" % (precision, float(d.max()), q))
     assert q <= 1.0
-
-
-def test_forward_levels_refuses_a_graph_with_the_op(cuda_device):
-    """the op does not join launches across pyramid levels: more than one geometry per call is refused cleanly, one geometry through the same entry runs"""
-    net, slots = _net(cuda_device, "f16", (1, 8, 6, 6), False, [None])
-    xs = [br.producer_input((1, 8, 6, 6)).to(cuda_device), br.producer_input((1, 8, 8, 10)).to(cuda_device)]
-    with pytest.raises(ValueError, match="one geometry per call"):
-        net._forward_levels([(x, None) for x in xs])
-    assert tuple(net.forward(xs[1])[slots[None]].shape) == (1, 8, 4, 5)

@@ -2,7 +2,6 @@
 tests/conv_bound.py (float64 reference on the fp16 tensors the layer consumed), and an unprofiled forward equals the profiled one bit for bit.  Shapes are the smallest
 that default knobs send to the kernel named, one ragged and one whole-tile case per family.  The ratios max |d| / bound are printed per case (DESIGN.md lists them)."""
 import math
-import os
 
 import pytest
 import torch
@@ -188,36 +187,6 @@ GENERIC = [
 @pytest.mark.parametrize("case", GENERIC, ids=_id)
 def test_generic_implicit_gemm_tiles(cuda_device, case):
     _run(cuda_device, variant=case[1], label=case[0], **case[2])
-
-
-# ---- conv3x3_halo_rb.hip, levels joined (910256) ------------------------------------------------------------------------------------------------------------------------
-def test_conv3x3_halo_rb_levels_joined(cuda_device):
-    """two geometries of one 256 -> 256 conv as ONE launch (gdt_launch_conv_halo_rb_levels), each level bounded on its own"""
-    from gandtr_amd.engine import HipNet
-    net = HipNet(cuda_device)
-    t = net.input(3)
-    a = net.conv(t, synth._normal(0, "w0", (256, 3, 1, 1), 0.7))
-    tap_in = net.output_nchw(a)
-    wt, bias = synth._normal(0, "w", (256, 256, 3, 3), math.sqrt(2.0 / 2304)), synth._normal(0, "b", (256,), 0.2)
-    tap = net.output_nchw(net.conv(a, wt, bias, pad=1, relu=True))
-    net.finalize()
-    levels = [(synth.synth_input(1, (2, 3, 44, 60)).to(cuda_device), None), (synth.synth_input(2, (3, 3, 32, 48)).to(cuda_device), None)]
-    want = [[o.clone() for o in net.forward(x)] for x, s in levels]
-    net.set_profiling(True)
-    os.environ["GANDTR_HIP_JOINT_LEVELS"] = "1"
-    try:
-        got = net.forward_many(levels)
-        torch.cuda.synchronize()
-    finally:
-        del os.environ["GANDTR_HIP_JOINT_LEVELS"]
-    variants = _conv_variants(net)
-    joined, handed = net.levels_joined()
-    net.set_profiling(False)
-    wp, shift = cb.fold(wt, bias)
-    for l, outs in enumerate(got):
-        cb.assert_layer(outs[tap].cpu(), outs[tap_in].cpu(), wp, shift, "910256 joined level %d" % l, pad=1, act="relu")
-        assert all(torch.equal(p, q) for p, q in zip(outs, want[l]))
-    assert variants[1] == 910256 and joined >= 1, (variants, joined, handed)
 
 
 # ---- conv_stem.hip (950049 / 950009): reflect stems and a resized stride-2 stem -----------------------------------------------------------------------------------------

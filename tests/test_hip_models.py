@@ -382,53 +382,32 @@ def test_forward_many_equals_level_by_level_forward(cuda_device):
         assert all(torch.equal(a, b) for a, b in zip(w, g))
 
 
-def test_pyramid_levels_share_launches_bitwise(cuda_device):
-    """Round 5: the levels of a pyramid in lock-step, ONE launch per op across the levels where the kernel has a multi-geometry entry (gdt_net_forward_levels:
-    1x1 convs, 3x3 patch convs, fused Bottlenecks) -- at BASELINE config 4's per-rank geometry scaled down (8 images, hub-default scales {1, 1/sqrt2, 1/2},
-    wrapper.py:207-208).  Same bits as forward called level by level, and as the default path (one side stream per level).  Opt-in (GANDTR_HIP_JOINT_LEVELS=1):
-    measured slower than the streams (csrc/gdt_common.h, MultiConv)."""
-    import os
+def test_pyramid_levels_on_side_streams_bitwise(cuda_device):
+    """The levels of a pyramid through forward_many (one side stream per level) -- at BASELINE config 4's per-rank geometry scaled down (8 images, hub-default
+    scales {1, 1/sqrt2, 1/2}, wrapper.py:207-208), for ResNet-101 and for VGG16.  Same bits as forward called level by level."""
     from gandtr_amd import engine
     for arch, sd, size in (("resnet101", synth.resnet101_state(0), 512), ("vgg16", synth.vgg16_state(0), 384)):
         net = engine.build_embedder(sd, cuda_device)
         x = synth.synth_input(91, (8, 3, size, size)).to(cuda_device)
         levels = [(x, 1.0), (x, 2 ** -0.5), (x, 0.5)]
         want = [[o.clone() for o in net.forward(xx, scale=s)] for xx, s in levels]
-        os.environ["GANDTR_HIP_JOINT_LEVELS"] = "1"
-        try:
-            got = net.forward_many(levels)
-            torch.cuda.synchronize()
-        finally:
-            del os.environ["GANDTR_HIP_JOINT_LEVELS"]
-        joined, handed = net.levels_joined()
-        print("%s 8 x %d^2, 3 levels: %d ops ran as one launch for all levels (%d launches handed in by the levels)" % (arch, size, joined, handed))
-        for w, g in zip(want, got):
-            assert len(w) == len(g) and all(torch.equal(a, b) for a, b in zip(w, g))
-        if arch == "resnet101":
-            assert joined >= 20, (joined, handed)                          # (at 8 x 1024^2: 82 of 88; the small levels of this test pick other kernel families; VGG16's
-                                                                            #  convs -- fused max-pools, 64 / 128 output channels -- have no multi-geometry entry: none joined)
-        got2 = net.forward_many(levels)                                     # the default: one side stream per level
+        got = net.forward_many(levels)
         torch.cuda.synchronize()
-        for w, g in zip(want, got2):
-            assert all(torch.equal(a, b) for a, b in zip(w, g))
+        for w, g in zip(want, got):
+            assert len(w) == len(g) and all(torch.equal(a, b) for a, b in zip(w, g)), arch
         del net
 
 
 def test_refused_level_group_leaves_the_handle_planning_alone(cuda_device):
-    """A group of levels that is refused half-way (gdt_net_forward_levels path: the planner's group factor is set per level) must leave the handle at factor 1: the
+    """A group of levels that is refused half-way (forward_many sets the planner's group factor per level) must leave the handle at factor 1: the
     next single forward plans -- and computes -- what a fresh handle does."""
-    import os
     from gandtr_amd import engine
     sd = synth.resnet101_state(0)
     net, fresh = engine.build_embedder(sd, cuda_device), engine.build_embedder(sd, cuda_device)
     x = synth.synth_input(92, (2, 3, 128, 128)).to(cuda_device)
     bad = torch.zeros(2, 1, 128, 128, device=cuda_device)                      # wrong channel count: refused after the first level set its factor (2.0)
-    os.environ["GANDTR_HIP_JOINT_LEVELS"] = "1"
-    try:
-        with pytest.raises(ValueError):
-            net.forward_many([(x, 1.0), (bad, 1.0)])
-    finally:
-        del os.environ["GANDTR_HIP_JOINT_LEVELS"]
+    with pytest.raises(ValueError):
+        net.forward_many([(x, 1.0), (bad, 1.0)])
     # 8 x 1024^2 has 128 layer3 patches: fused 3x3 + expand launches only with a group factor >= 1.5 (tests/test_planner_cpu.py)
     assert fresh.plan_summary(8, 1024, 1024)["conv3x3_expand"] == 0
     assert net.plan_summary(8, 1024, 1024) == fresh.plan_summary(8, 1024, 1024)
@@ -436,31 +415,6 @@ def test_refused_level_group_leaves_the_handle_planning_alone(cuda_device):
     got, want = net.forward(x), fresh.forward(x)
     torch.cuda.synchronize()
     assert all(torch.equal(a, b) for a, b in zip(got, want))
-
-
-def test_hipgraph_replay_equals_eager_launches(cuda_device):
-    """opt-in hipGraph replay of whole forwards (GANDTR_HIP_GRAPHS=1 / HipNet.use_graphs): from the second call of a geometry on the forward is captured once and
-    replayed -- same kernels, same results bit for bit, for the generator (f16c) and the embedder; another geometry falls back to eager launches"""
-    from gandtr_amd import engine
-    gen = engine.build_generator(synth.generator_state(0, "instance"), cuda_device, pre_tanh=True)
-    emb = engine.build_embedder(synth.resnet101_state(0), cuda_device)
-    for net, shape in ((gen, (4, 3, 128, 128)), (emb, (2, 3, 256, 320))):
-        x = synth.synth_input(77, shape, 1.0).to(cuda_device)
-        eager = net.forward(x)[net.out_slot].clone()
-        net.use_graphs = True
-        outs = [net.forward(x)[net.out_slot].clone() for _ in range(3)]         # eager (first sighting was above), capture + replay, replay
-        assert len(net._graphs) == 1
-        for o in outs:
-            assert torch.equal(o, eager)
-        x2 = synth.synth_input(78, shape, 1.0).to(cuda_device)
-        want = None
-        net.use_graphs = False
-        want = net.forward(x2)[net.out_slot].clone()
-        net.use_graphs = True
-        assert torch.equal(net.forward(x2)[net.out_slot], want)                    # replay with new input data
-        other = synth.synth_input(79, (1,) + shape[1:], 1.0).to(cuda_device)
-        assert net.forward(other)[net.out_slot].shape[0] == 1                      # new geometry: eager again
-        net.use_graphs = False
 
 
 def _r101_three_levels(cuda_device):
@@ -476,20 +430,6 @@ def _r101_three_levels(cuda_device):
 def _same_levels(got, want):
     torch.cuda.synchronize()
     return len(got) == len(want) and all(len(g) == len(w) and all(torch.equal(a, b) for a, b in zip(g, w)) for g, w in zip(got, want))
-
-
-def test_first_level_on_the_callers_stream_equals_level_by_level(cuda_device):
-    """GANDTR_HIP_FIRST_ON_CURRENT=1 (the first level on the caller's stream, issued last): same bits as forward level by level, also on the second call (scratch
-    buffers reused), and a plain forward afterwards is undisturbed"""
-    import os
-    net, x, levels, want = _r101_three_levels(cuda_device)
-    os.environ["GANDTR_HIP_FIRST_ON_CURRENT"] = "1"
-    try:
-        for _ in range(2):
-            assert _same_levels(net.forward_many(levels), want)
-    finally:
-        del os.environ["GANDTR_HIP_FIRST_ON_CURRENT"]
-    assert torch.equal(net.forward(x)[net.out_slot], want[0][net.out_slot])
 
 
 def test_level_by_level_modes_of_forward_many_hold_no_side_workspace(cuda_device):

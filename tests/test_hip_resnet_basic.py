@@ -1,7 +1,7 @@
 """GeM-ResNet-18 / -34 (BasicBlock trunks) on the device against the repository's own host module on the CPU in fp32 (init_network with the synthetic state
 dict loaded strictly; the oracle has no BasicBlock): the graph of build_embedder in f16 -- layer by layer, with the fused BasicBlock kernel forced
 (GDT_CONV_BASIC=2, variant 936064) and with it off -- and in f16x3, the module path (init_cirnet(...).to(cuda)), forward_many over a three-level pyramid on
-side streams and as joint launches, and the refusal of an unlisted trunk.
+side streams, and the refusal of an unlisted trunk.
 
 Gates: the project's descriptor gates in f16 (|d|_inf < 1e-3, cosine > 0.9999 per image; tests/test_hip_golden.py), 2e-5 in f16x3 (test_embedder_f16x3).
 
@@ -10,7 +10,6 @@ MEASURED (MI355X), worst over the three inputs (max |d|, min cosine):
     resnet34 f16   knob unset / 0: 1.44e-04, 0.9999998   GDT_CONV_BASIC=2: 1.39e-04, 0.9999998
     resnet18 f16x3 4.47e-08 (1 - cosine 2.8e-14)         resnet34 f16x3 5.32e-08 (1 - cosine 3.6e-14)
     init_cirnet resnet18, gem + whitening, module path f16: 3.81e-05, 1.0000000
-    three-level pyramid as joint launches: 2 ops joined (the two fused blocks) of 54 launches handed in
 """
 import pytest
 import torch
@@ -100,22 +99,15 @@ def test_module_path_equals_its_cpu_forward(cuda_device, monkeypatch):
     assert err < GATE_ABS and cos > GATE_COS, (err, cos)
 
 
-@pytest.mark.parametrize("joint", [False, True], ids=["side-streams", "joint-launches"])
-def test_forward_many_equals_the_levels_one_by_one(cuda_device, joint, monkeypatch):
-    """a three-level pyramid: forward_many (one side stream per level; or GANDTR_HIP_JOINT_LEVELS=1, the levels' launches of an op joined -- the fused
-    BasicBlocks through the kernel's multi-geometry entry) against forward level by level, bit for bit"""
+def test_forward_many_equals_the_levels_one_by_one(cuda_device, monkeypatch):
+    """a three-level pyramid with the fused BasicBlocks: forward_many (one side stream per level) against forward level by level, bit for bit"""
     monkeypatch.setenv("GDT_CONV_BASIC", "2")
-    monkeypatch.setenv("GANDTR_HIP_JOINT_LEVELS", "1" if joint else "0")
     net = engine.build_embedder(synth.resnet_basic_state(0), cuda_device)
     x = _input(0).to(cuda_device)
     levels = [(x, None), (x, 2 ** -0.5), (x, 0.5)]
     assert [net.basic_blocks_fused(2, *net.resized_size(160, 192, s)) for _, s in levels] == [2, 2, 2]
     many = net.forward_many(levels)
     torch.cuda.synchronize()
-    if joint:
-        joined, handed = net.levels_joined()
-        print("three levels, joint launches: %d ops joined, %d launches handed in" % (joined, handed))
-        assert joined >= 2                                          # at least the two fused blocks
     single = [net.forward(xx, scale=s) for xx, s in levels]
     torch.cuda.synchronize()
     for a, b in zip(many, single):

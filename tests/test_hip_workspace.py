@@ -102,10 +102,9 @@ def test_forward_is_independent_of_the_workspace_content(cuda_device, label):
 PYRAMID = ((None, 2 ** -0.5, 0.5), (2, 160, 224))
 
 
-@pytest.mark.parametrize("joint", [False, True], ids=["side-streams", "joint-launches"])
-def test_forward_many_is_independent_of_the_side_workspaces(cuda_device, joint):
-    """a three-level pyramid of the ResNet-101 embedder through forward_many -- one side stream per level, or the levels' launches joined (GANDTR_HIP_JOINT_LEVELS=1)
-    -- on side workspaces that hold each fill before the call: the level-by-level forward's bits, under either layout"""
+def test_forward_many_is_independent_of_the_side_workspaces(cuda_device):
+    """a three-level pyramid of the ResNet-101 embedder through forward_many -- one side stream per level -- on side workspaces that hold each fill before the
+    call: the level-by-level forward's bits, under either layout"""
     scales, (n, h, w) = PYRAMID
     net = wp.built(wp.R101, cuda_device, True)
     x = _input(net, n, h, w, cuda_device)
@@ -113,7 +112,7 @@ def test_forward_many_is_independent_of_the_side_workspaces(cuda_device, joint):
     for apart in ({wp.NO_REUSE: "1"}, {}):
         with wp.knobs(apart):
             want = [[o.cpu() for o in net.forward(x, scale=s)] for s in scales]
-        with wp.knobs(dict(apart, GANDTR_HIP_JOINT_LEVELS="1" if joint else "0")):
+        with wp.knobs(apart):
             # (a level's plan, and with it its size, may follow the group: four times the largest level's own need is kept by _grow whatever the group plans)
             keep = 4 * max(net.workspace_bytes(n, *net.resized_size(h, w, s)) for s in scales)
             for fill in wp.FILLS:
@@ -126,6 +125,6 @@ def test_forward_many_is_independent_of_the_side_workspaces(cuda_device, joint):
                 assert [b.data_ptr() for b in net._side["ws"]] == seeded, "a side workspace was replaced: the fill was not what the levels ran on"
                 for k, (g, r) in enumerate(zip(got, want)):
                     g = [o.cpu() for o in g]
-                    assert all(bool(torch.isfinite(o).all()) for o in g), (joint, apart, fill, k)
-                    assert _first_difference(g, r) is None, (joint, apart, fill, k, _first_difference(g, r))
+                    assert all(bool(torch.isfinite(o).all()) for o in g), (apart, fill, k)
+                    assert _first_difference(g, r) is None, (apart, fill, k, _first_difference(g, r))
     net._side["ws"] = [None] * len(net._side["ws"])

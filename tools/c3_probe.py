@@ -1,6 +1,6 @@
 """dev: where BASELINE config 4's per-rank workload (8 x 3 x 1024^2, hub-default pyramid, GeM-ResNet-101 + whitening) spends its time: each pyramid level alone
-(device time of its forward, and its wall time per call = host launch time when that is larger), the three levels one after the other / concurrent, the per-op
-table of each level, and the same with the levels' forwards replayed from hipGraphs"""
+(device time of its forward, and its wall time per call = host launch time when that is larger), the three levels one after the other / concurrent, and the per-op
+table of each level"""
 import os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -31,7 +31,6 @@ def host_only(fn, k=6):
 with torch.no_grad():
     sd = synth.resnet101_state(0)
     net = engine.build_embedder(sd, dev)
-    net.use_graphs = False
     x = synth.synth_input(5, (n, 3, 1024, 1024)).to(dev)
     scales = [1.0, 2 ** -0.5, 0.5]
     tot = 0.0
@@ -51,11 +50,6 @@ with torch.no_grad():
     print("levels one by one: %.2f ms = %.0f desc/s" % (tot, n / tot * 1e3))
     t = wall(lambda: net.forward_many([(x, s) for s in scales]))
     print("forward_many (side streams): %.2f ms = %.0f desc/s" % (t, n / t * 1e3))
-    net.use_graphs = True
-    for s in scales:
-        for _ in range(3): net.forward(x, scale=s)
-    t = wall(lambda: [net.forward(x, scale=s) for s in scales])
-    print("levels one by one, hipGraph replay: %.2f ms = %.0f desc/s" % (t, n / t * 1e3))
 with tempfile.TemporaryDirectory() as tmp, torch.no_grad():
     hub = _c3_network(dev, True, tmp)
     t = wall(lambda: hub(x))
